@@ -19,10 +19,17 @@ GPU, starts N fresh child processes of this file with RANK / LOCAL_RANK / WORLD_
 relays rank 0's JSON line and exits with the worst child's code. Under a launcher (torchrun) it is one rank, as before.
 `n_gpus` in the JSON is the communicator's size (pt_comm_world), never the flag.
 
-Prints ONE JSON line on rank 0. `roofline` is measured live with HIP events on the launch stream
-(pt_render's profile mode); `cpu_baseline` times the CPU oracle (kind "port": the faithful f64
-restatement with the platform libm; the Rust reference itself cannot be built here) on a bounded
-sample of the same workload, on rank 0 at N=1 only.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs DIR is given and prints that line: `value` (Msamples/s) and `ms_per_step` come from the timed steps alone.
+--full adds what the headline does not need: `roofline` is measured live with HIP events on the launch stream (pt_render's
+profile mode, on for the timed steps of a --full run only); `frame_check` checks the last frame (finiteness, block means
+against the reference's demo image); `cpu_baseline` times the CPU oracle (kind "port": the faithful f64 restatement with
+the platform libm; this project does not build the Rust reference itself) on a bounded sample of the same workload, on
+rank 0 at N=1 only.
+
+--dump-outputs DIR (rank 0, after the timed steps): DIR/frame.npy, the f64 sum accumulator (H, W, 3) the last timed step
+handed its caller. A frame larger than 64 MB is written as a fixed sample of its pixels instead (the same for every run
+with the same arguments): DIR/frame_pixels.npy (n, 3) and DIR/frame_pixel_index.npy, their row-major pixel indices.
 """
 import argparse
 import importlib
@@ -61,12 +68,18 @@ def parse():
     ap.add_argument("--spp", type=int, default=4000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--slots-per-pixel", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel HIP-event timing and roofline figures, the frame check and the CPU-oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--dump-frame", default=None, help="rank 0 saves the last timed frame's f64 sum accumulator (H, W, 3) as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (f64, at most 64 MB in all)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="plumbing check without a GPU: every rank only runs the file rendezvous of pt_comm_create (pt_bootstrap_exchange) and rank 0 reports")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def rendezvous_path():
@@ -172,6 +185,63 @@ def frame_check(pt, ctx, args, acc, height):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20          # 24 MB of f64 RGB + 8 MB of indices
+
+
+def dump_outputs(directory, acc):
+    """--dump-outputs: the last timed frame's f64 sum accumulator, whole or as a fixed sample of pixels (module docstring)."""
+    os.makedirs(directory, exist_ok=True)
+    if acc.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "frame.npy"), acc)
+        return
+    flat = acc.reshape(-1, 3)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], min(DUMP_SAMPLE_PIXELS, flat.shape[0]), replace=False))
+    np.save(os.path.join(directory, "frame_pixels.npy"), flat[idx])
+    np.save(os.path.join(directory, "frame_pixel_index.npy"), idx.astype(np.float64))
+
+
+def roofline_figures(args, stats, world):
+    """--full: the dominant kernel of this rank against the HBM roofline, from the live HIP-event timing of the timed steps."""
+    ms_ext = sum(s["ms_extend"] for s in stats); ms_sh = sum(s["ms_shade"] for s in stats)
+    n_ext = sum(s["launches_extend"] for s in stats); n_sh = sum(s["launches_shade"] for s in stats)
+    my_seg = sum(s["segments"] for s in stats); my_smp = sum(s["samples"] for s in stats)
+    ext_name = {0: "k_extend2", 1: "k_extend"}.get(stats[0]["extend_variant"], "k_extend")
+    sh_name = f"k_shade<{'true' if stats[0]['shade_variant'] >= 10 else 'false'}, {stats[0]['shade_variant'] % 10}>"
+    if ms_ext >= ms_sh:
+        kname, kms, kn = ext_name, ms_ext, n_ext
+        bytes_total = my_seg * B_EXTEND_PER_SEGMENT
+    else:
+        kname, kms, kn = sh_name, ms_sh, n_sh
+        bytes_total = my_seg * B_SHADE_PER_SEGMENT + my_smp * B_FB_PER_SAMPLE
+    avg_ms = kms / max(kn, 1)
+    achieved = (bytes_total / max(kn, 1)) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    # HBM bytes per launch from the PMC counters cannot be collected inside this process: they come from separate
+    # `rocprofv3 --pmc` passes over this same command (tools/run_profiles.sh -> profiles/pmc_latest.json). The value is
+    # attached only for the headline workload it was measured on, and labelled with its source; otherwise null.
+    traffic, traffic_source = None, None
+    pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
+    if os.path.exists(pmc_path) and (args.scene, args.width, args.spp, world) == (6, 1920, 4000, 1):
+        try:
+            pmc = json.load(open(pmc_path))
+            if pmc.get("resident_paths") not in (None, stats[0]["n_slots"]):
+                raise ValueError("per-launch counters of another pool size")
+            traffic = pmc.get("k_extend" if ms_ext >= ms_sh else "k_shade", {}).get("hbm_bytes_per_launch")
+            traffic_source = f"profiles/pmc_latest.json ({pmc.get('source', 'earlier rocprofv3 --pmc passes of this command')}), not measured in this run"
+        except Exception:
+            traffic = None
+    model = (f"algorithmic bytes = SURVEY §8(d) yardstick: K3 {B_SHADE_PER_SEGMENT} B/segment (92 B record in + 4 B hit word + 92 B record out) + {B_FB_PER_SAMPLE} B/sample "
+             f"(f64 accumulator), K2 {B_EXTEND_PER_SEGMENT} B/segment (56 B ray in + 4 B out); the code's compact records move less than the yardstick assumes (DESIGN.md §6)")
+    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "model": model,
+                "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_source, "kernel": kname,
+                "avg_launch_ms": round(avg_ms, 5), "launches": int(kn),
+                "algorithmic_bytes_per_launch": round(bytes_total / max(kn, 1), 1),
+                "other_kernel": {"name": sh_name if ms_ext >= ms_sh else ext_name,
+                                 "avg_launch_ms": round((ms_sh if ms_ext >= ms_sh else ms_ext) / max(n_sh if ms_ext >= ms_sh else n_ext, 1), 5)},
+                "whole_pipeline_GBps": round((my_seg * (B_EXTEND_PER_SEGMENT + B_SHADE_PER_SEGMENT) + my_smp * B_FB_PER_SAMPLE) / max((ms_ext + ms_sh) * 1e-3, 1e-9) / 1e9, 3)}
+    return roofline
+
+
 def main():
     args = parse()
     if "RANK" not in os.environ and args.gpus > 1:
@@ -213,7 +283,7 @@ def main():
     stats = []
     acc = None
     for _ in range(args.steps):
-        acc, st = step(True)
+        acc, st = step(args.full)
         stats.append(st.as_dict())
     comm.barrier()
     elapsed = time.perf_counter() - t_start
@@ -228,43 +298,6 @@ def main():
     if rank == 0:
         samples_per_step = n_pix * args.spp
         value = samples_per_step * args.steps / elapsed / 1e6
-        # dominant kernel on this rank, live HIP-event timing
-        ms_ext = sum(s["ms_extend"] for s in stats); ms_sh = sum(s["ms_shade"] for s in stats)
-        n_ext = sum(s["launches_extend"] for s in stats); n_sh = sum(s["launches_shade"] for s in stats)
-        my_seg = sum(s["segments"] for s in stats); my_smp = sum(s["samples"] for s in stats)
-        ext_name = {0: "k_extend2", 1: "k_extend"}.get(stats[0]["extend_variant"], "k_extend")
-        sh_name = f"k_shade<{'true' if stats[0]['shade_variant'] >= 10 else 'false'}, {stats[0]['shade_variant'] % 10}>"
-        if ms_ext >= ms_sh:
-            kname, kms, kn = ext_name, ms_ext, n_ext
-            bytes_total = my_seg * B_EXTEND_PER_SEGMENT
-        else:
-            kname, kms, kn = sh_name, ms_sh, n_sh
-            bytes_total = my_seg * B_SHADE_PER_SEGMENT + my_smp * B_FB_PER_SAMPLE
-        avg_ms = kms / max(kn, 1)
-        achieved = (bytes_total / max(kn, 1)) / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        # HBM bytes per launch from the PMC counters cannot be collected inside this process: they come from separate
-        # `rocprofv3 --pmc` passes over this same command (tools/run_profiles.sh -> profiles/pmc_latest.json). The value is
-        # attached only for the headline workload it was measured on, and labelled with its source; otherwise null.
-        traffic, traffic_source = None, None
-        pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc_path) and (args.scene, args.width, args.spp, world) == (6, 1920, 4000, 1):
-            try:
-                pmc = json.load(open(pmc_path))
-                if pmc.get("resident_paths") not in (None, stats[0]["n_slots"]):
-                    raise ValueError("per-launch counters of another pool size")
-                traffic = pmc.get("k_extend" if ms_ext >= ms_sh else "k_shade", {}).get("hbm_bytes_per_launch")
-                traffic_source = f"profiles/pmc_latest.json ({pmc.get('source', 'earlier rocprofv3 --pmc passes of this command')}), not measured in this run"
-            except Exception:
-                traffic = None
-        model = (f"algorithmic bytes = SURVEY §8(d) yardstick: K3 {B_SHADE_PER_SEGMENT} B/segment (92 B record in + 4 B hit word + 92 B record out) + {B_FB_PER_SAMPLE} B/sample "
-                 f"(f64 accumulator), K2 {B_EXTEND_PER_SEGMENT} B/segment (56 B ray in + 4 B out); the code's compact records move less than the yardstick assumes (DESIGN.md §6)")
-        roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "model": model,
-                    "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_source, "kernel": kname,
-                    "avg_launch_ms": round(avg_ms, 5), "launches": int(kn),
-                    "algorithmic_bytes_per_launch": round(bytes_total / max(kn, 1), 1),
-                    "other_kernel": {"name": sh_name if ms_ext >= ms_sh else ext_name,
-                                     "avg_launch_ms": round((ms_sh if ms_ext >= ms_sh else ms_ext) / max(n_sh if ms_ext >= ms_sh else n_ext, 1), 5)},
-                    "whole_pipeline_GBps": round((my_seg * (B_EXTEND_PER_SEGMENT + B_SHADE_PER_SEGMENT) + my_smp * B_FB_PER_SAMPLE) / max((ms_ext + ms_sh) * 1e-3, 1e-9) / 1e9, 3)}
         out = {
             "metric": "Msamples/s (WxHxspp/s), scene 6 FHD@4000spp" if (args.scene, args.width, args.spp) == (6, 1920, 4000) else "Msamples/s (WxHxspp/s)",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -275,12 +308,13 @@ def main():
                        "slots_per_pixel": stats[0]["slots_per_pixel"], "resident_paths": stats[0]["n_slots"],
                        "segments_per_sample": round(total_segments / max(total_samples, 1), 4), "scene_build_s": round(build_s, 3),
                        "device": ctx.name()},
-            "roofline": roofline,
         }
-        out["frame_check"] = frame_check(pt, ctx, args, acc, height)
-        if args.dump_frame:
-            np.save(args.dump_frame, acc)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, acc)
+        if args.full:
+            out["roofline"] = roofline_figures(args, stats, world)
+            out["frame_check"] = frame_check(pt, ctx, args, acc, height)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             images = {n: pt.decode_image_rgb8(os.path.join(pt.ASSET_DIR, n)) for n in pt.SCENE_IMAGE_FILES.get(args.scene, [])}
             out["cpu_baseline"] = cpu_baseline(args.scene, args.width, args.cpu_seconds, images)
             out["gpu_over_cpu"] = round(value / max(out["cpu_baseline"]["value"], 1e-9), 1)

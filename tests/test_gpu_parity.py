@@ -740,14 +740,14 @@ def test_two_gpu_render_multi_equals_single_gpu(pt, ctx, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     frames = {}
     for gpus in (1, 2):
-        out = str(tmp_path / f"f{gpus}.npy")
+        out = str(tmp_path / f"f{gpus}")
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--width", "256", "--spp", "16", "--steps", "1", "--warmup", "0",
-                            "--no-cpu-baseline", "--dump-frame", out], capture_output=True, text=True, timeout=600,
+                            "--full", "--no-cpu-baseline", "--dump-outputs", out], capture_output=True, text=True, timeout=600,
                            env={k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")})
         assert r.returncode == 0, r.stderr[-3000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert line["n_gpus"] == gpus and line["frame_check"]["finite"]
-        frames[gpus] = np.load(out)
+        frames[gpus] = np.load(os.path.join(out, "frame.npy"))
     np.testing.assert_allclose(frames[2], frames[1], rtol=1e-12, atol=1e-12)
 
 
