@@ -152,6 +152,38 @@ int pt_render(pt_scene*, const pt_camera*, uint64_t seed, uint32_t spp_begin, ui
 /* camera.rs:109-114,128-130: mean, sqrt gamma, clamp(0,0.999)*256 as u8. Host buffers. */
 int pt_resolve_u8(pt_ctx*, const double* accum, uint32_t n_pixels, uint32_t total_spp, uint8_t* rgb8);
 
+/* ---- pixel lists and adaptive sampling (no counterpart in the reference) ----------------------------------------------
+ * pt_render restricted to the listed pixels (row-major y*W+x, strictly ascending, < W*H; n == 0 is a no-op). Adds (or, with
+ * opts->overwrite, stores) the sums of samples [spp_begin, spp_end) of each LISTED pixel into accum (the full W*H*3 frame, host
+ * or device as opts says); the values of pixels that are not listed are not written. A listed pixel's sums are those pt_render
+ * computes for it (static mode: bit for bit). An unsorted, duplicated or out-of-range list returns -1. */
+int pt_render_pixels(pt_scene*, const pt_camera*, uint64_t seed, const uint32_t* pixels, uint32_t n, uint32_t spp_begin,
+                     uint32_t spp_end, double* accum, const pt_render_opts* opts, pt_render_stats* stats);
+/* Render to a noise target. Schedule (all integer divisions): b_0 = 0, b_1 = min_spp/2, b_2 = min_spp,
+ * b_{i+1} = min(max_spp, b_i + max(min_spp/2, b_i/2)); round i renders [b_i, b_{i+1}) of the active pixels as one
+ * pt_render_pixels pass, even rounds into sums E, odd rounds into sums O. After each round i >= 1 with b_{i+1} < max_spp,
+ * with n_E, n_O the samples of the even / odd rounds so far: A_c = E_c / n_E, B_c = O_c / n_O,
+ * M = (E_r+O_r + E_g+O_g + E_b+O_b) / (n_E+n_O), err = (|A_r-B_r| + |A_g-B_g| + |A_b-B_b|) / (1e-4 + sqrt(M)) (left to right,
+ * one IEEE rounding per operation); an active pixel stays active if !(err < threshold) holds for itself or for any active
+ * pixel among its 8 neighbours, else it stops for good with b_{i+1} samples. */
+typedef struct pt_adaptive_opts {
+    uint32_t min_spp;          /* >= 2: samples every pixel gets before its first test */
+    uint32_t max_spp;          /* >= min_spp: no pixel gets more */
+    double threshold;          /* a pixel stops once err < threshold; <= 0: none stops early */
+    uint32_t slots_per_pixel;  /* as pt_render_opts (1 = the reference's per-pixel order, bit-exact mode) */
+    uint32_t profile;
+    void* stream;              /* hipStream_t; NULL = the context's own stream */
+} pt_adaptive_opts;
+/* round boundaries b_0 = 0 < b_1 < ... < b_R = max_spp: writes the first min(R + 1, cap) of them and returns R + 1, or -1
+ * (min_spp < 2, max_spp < min_spp) */
+int pt_adaptive_schedule(uint32_t min_spp, uint32_t max_spp, uint32_t* bounds, uint32_t cap);
+/* accum: host W*H*3 sums E + O (overwritten); spp_per_pixel: host W*H, the samples each pixel received.
+ * stats: summed over the passes (samples == sum of spp_per_pixel). Device memory on top of the path pool: 68 B per pixel. */
+int pt_render_adaptive(pt_scene*, const pt_camera*, uint64_t seed, const pt_adaptive_opts* opts, double* accum,
+                       uint32_t* spp_per_pixel, pt_render_stats* stats);
+/* pt_resolve_u8 with each pixel's own count (> 0): mean = sum * (1.0 / n_p), then pt_resolve_u8's arithmetic. Host buffers. */
+int pt_resolve_u8_counts(pt_ctx*, const double* accum, uint32_t n_pixels, const uint32_t* spp_per_pixel, uint8_t* rgb8);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

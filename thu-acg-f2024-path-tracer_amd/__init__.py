@@ -85,6 +85,17 @@ class RenderStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptiveOpts(C.Structure):
+    _fields_ = [
+        ("min_spp", C.c_uint32),
+        ("max_spp", C.c_uint32),
+        ("threshold", C.c_double),
+        ("slots_per_pixel", C.c_uint32),
+        ("profile", C.c_uint32),
+        ("stream", C.c_void_p),
+    ]
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -98,6 +109,7 @@ ABI_SYMBOLS = [
     "pt_build_scene", "pt_camera_init", "pt_render", "pt_resolve_u8", "pt_intersect", "pt_math_probe",
     "pt_shard_range", "pt_comm_create", "pt_comm_destroy", "pt_comm_rank", "pt_comm_world", "pt_comm_barrier", "pt_comm_allreduce_f64",
     "pt_bootstrap_exchange", "pt_render_multi",
+    "pt_render_pixels", "pt_adaptive_schedule", "pt_render_adaptive", "pt_resolve_u8_counts",
 ]
 
 
@@ -170,6 +182,13 @@ def _load():
         lib.pt_load_obj_single_index.argtypes = [C.c_char_p, fp, up, C.POINTER(C.POINTER(C.c_uint32)), up, fp, up, fp, up]
     lib.pt_free.argtypes = [C.c_void_p]
     lib.pt_free.restype = None
+    if hasattr(lib, "pt_render_pixels"):
+        lib.pt_render_pixels.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                         C.POINTER(RenderOpts), C.POINTER(RenderStats)]
+        lib.pt_adaptive_schedule.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
+        lib.pt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint64, C.POINTER(AdaptiveOpts), C.c_void_p, C.c_void_p,
+                                           C.POINTER(RenderStats)]
+        lib.pt_resolve_u8_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -238,6 +257,23 @@ class Context:
         out = np.empty(accum.shape, dtype=np.uint8)
         _check(lib.pt_resolve_u8(self.handle, accum.ctypes.data, accum.size // 3, total_spp, out.ctypes.data), "pt_resolve_u8")
         return out
+
+    def resolve_u8_counts(self, accum: np.ndarray, spp_per_pixel: np.ndarray) -> np.ndarray:
+        """resolve_u8 with each pixel's own sample count (the counts of Scene.render_adaptive)."""
+        accum = np.ascontiguousarray(accum, dtype=np.float64)
+        counts = np.ascontiguousarray(spp_per_pixel, dtype=np.uint32)
+        assert counts.size * 3 == accum.size
+        out = np.empty(accum.shape, dtype=np.uint8)
+        _check(lib.pt_resolve_u8_counts(self.handle, accum.ctypes.data, counts.size, counts.ctypes.data, out.ctypes.data), "pt_resolve_u8_counts")
+        return out
+
+
+def adaptive_schedule(min_spp: int, max_spp: int):
+    """Round boundaries [0, b_1, ..., max_spp] of Scene.render_adaptive (pt_adaptive_schedule)."""
+    n = _check(lib.pt_adaptive_schedule(min_spp, max_spp, None, 0), "pt_adaptive_schedule")
+    b = np.zeros(n, dtype=np.uint32)
+    _check(lib.pt_adaptive_schedule(min_spp, max_spp, b.ctypes.data, n), "pt_adaptive_schedule")
+    return [int(x) for x in b]
 
 
 def shard_range(spp: int, rank: int, world: int):
@@ -385,6 +421,39 @@ class Scene:
             ptr = C.c_void_p(accum.ctypes.data)
         _check(lib.pt_render(self.handle, C.byref(cam), seed, spp_begin, spp_end, ptr, C.byref(opts), C.byref(stats)), "pt_render")
         return accum, stats
+
+    def render_pixels(self, cam: Camera, seed: int, pixels, spp_begin: int, spp_end: int, accum=None, slots_per_pixel: int = 0,
+                      profile: bool = False, device_ptr: Optional[int] = None, stream: Optional[int] = None, overwrite: bool = False):
+        """render() restricted to `pixels` (row-major y*W+x, strictly ascending): only their entries of the (H, W, 3) frame are
+        added to (``overwrite``: stored); the others are left as they are. Returns (accum, stats)."""
+        h = image_height(cam)
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        opts = RenderOpts(slots_per_pixel, 1 if device_ptr is not None else 0, 1 if profile else 0, 1 if overwrite else 0, stream)
+        stats = RenderStats()
+        if device_ptr is not None:
+            ptr = C.c_void_p(device_ptr)
+        else:
+            if accum is None:
+                accum = np.zeros((h, cam.image_width, 3), dtype=np.float64)
+            assert accum.dtype == np.float64 and accum.flags["C_CONTIGUOUS"] and accum.size == h * cam.image_width * 3
+            ptr = C.c_void_p(accum.ctypes.data)
+        _check(lib.pt_render_pixels(self.handle, C.byref(cam), seed, px.ctypes.data, px.size, spp_begin, spp_end, ptr, C.byref(opts),
+                                    C.byref(stats)), "pt_render_pixels")
+        return accum, stats
+
+    def render_adaptive(self, cam: Camera, seed: int, min_spp: int, max_spp: int, threshold: float, slots_per_pixel: int = 0,
+                        profile: bool = False, stream: Optional[int] = None):
+        """Render to a noise target (pt_render_adaptive): each pixel stops once its two-sample-set error estimate is below
+        `threshold` (see include/pt_amd.h for the exact rule). Returns (accum (H, W, 3) sums, counts (H, W) samples per pixel,
+        stats summed over the passes)."""
+        h = image_height(cam)
+        accum = np.zeros((h, cam.image_width, 3), dtype=np.float64)
+        counts = np.zeros((h, cam.image_width), dtype=np.uint32)
+        opts = AdaptiveOpts(min_spp, max_spp, threshold, slots_per_pixel, 1 if profile else 0, stream)
+        stats = RenderStats()
+        _check(lib.pt_render_adaptive(self.handle, C.byref(cam), seed, C.byref(opts), accum.ctypes.data, counts.ctypes.data, C.byref(stats)),
+               "pt_render_adaptive")
+        return accum, counts, stats
 
     def render_multi(self, cam: Camera, seed: int, spp_total: int, comm: Comm, accum=None, slots_per_pixel: int = 0, profile: bool = False,
                      overwrite: bool = False):

@@ -14,11 +14,18 @@ void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_
 // the frame's end (dynamic mode): live slots beyond new_end move into dead slots below it; holes / movers: scratch lists of `cap` entries, counts: 2 words
 void launch_compact(const PoolD& pool, uint32_t new_end, uint32_t* holes, uint32_t* movers, uint32_t* counts, uint32_t cap, int max_blocks, hipStream_t st);
 void launch_detile(const PoolD& pool, double* accum, int max_blocks, hipStream_t st);
+// pt_adaptive.hip: the adaptive render's per-round kernels (see there)
+void launch_adapt_error(const double* E, const double* O, const uint32_t* stop, uint32_t n_pixels, double n_e, double n_o, double* err, hipStream_t st);
+void launch_adapt_select(const double* err, uint32_t* stop, uint32_t width, uint32_t height, double threshold, uint32_t stop_value, uint32_t* block_counts,
+                         uint32_t* list_out, uint32_t* n_out, hipStream_t st);
+void launch_adapt_final(double* E, const double* O, const uint32_t* stop, uint32_t n_pixels, uint32_t max_spp, uint32_t* counts, hipStream_t st);
+void launch_quantise_counts(const double* accum, uint32_t n_pixels, const uint32_t* counts, uint8_t* rgb8, hipStream_t st);
+uint32_t adapt_select_blocks(uint32_t width, uint32_t height);   // entries of launch_adapt_select's block_counts
 void launch_quantise(const double* accum, uint32_t n, double scale, uint8_t* rgb8, hipStream_t st);
 void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out, hipStream_t st);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);
 // K2 variant code (`code` of launch_extend / `variant` of kernel_occupancy_blocks): -1 = batch kernel (-2 asks
 // kernel_occupancy_blocks for its flat-top-level instantiation), -(stack*10 + blocks) = two-phase kernel
 // k_extend2<stack, blocks> for stack in {16, 20, 24}.
-int kernel_occupancy_blocks(int which, int variant, bool lights = false);   // lights: k_shade's instantiation for scenes with a lights list   // 0 = extend, 1 = shade; resident blocks per CU
+int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false);   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
 }  // namespace pt

@@ -314,12 +314,35 @@ PT_DEV bool work_to_pixel(const PoolD& pool, unsigned long long w, uint32_t& pix
     col = x;
     return x < pool.width && y < pool.height;
 }
+// pixel-list form: every item is a listed (hence real) pixel, so no item idles at a ragged edge
+PT_DEV bool work_to_pixel_list(const PoolD& pool, unsigned long long w, uint32_t& pixel, uint32_t& sample, uint32_t& row, uint32_t& col) {
+    unsigned long long q;
+    uint32_t i;
+    divmod_u53(w, pool.n_list, q, i);
+    sample = pool.spp_begin + (uint32_t)q;
+    pixel = pool.list[i];
+    divmod_u31(pixel, pool.width, row, col);
+    return true;
+}
+template <bool LIST>
+PT_DEV bool work_item(const PoolD& pool, unsigned long long w, uint32_t& pixel, uint32_t& sample, uint32_t& row, uint32_t& col) {
+    if constexpr (LIST) return work_to_pixel_list(pool, w, pixel, sample, row, col);
+    else return work_to_pixel(pool, w, pixel, sample, row, col);
+}
+// static mode: the pixel slot s owns
+template <bool LIST>
+PT_DEV uint32_t slot_pixel(const PoolD& pool, uint32_t s) {
+    if constexpr (LIST) return pool.list[s % pool.n_list];
+    else return s % pool.n_pixels;
+}
 // shard-local counter value -> global work item: 64-item chunks are dealt round-robin to the shards
 PT_DEV unsigned long long shard_item(unsigned long long c, uint32_t shard) {
     return (c >> 6) * (unsigned long long)(WORK_SHARDS * 64u) + (unsigned long long)shard * 64ull + (c & 63ull);
 }
 
 // ---------------------------------------------------------------------------------------
+// LIST: pixel-list render (PoolD::list)
+template <bool LIST = false>
 __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t seed) {
     for (uint32_t s = blockIdx.x * BLOCK + threadIdx.x; s < pool.n_alloc; s += gridDim.x * BLOCK) {
         uint32_t pixel, sample, row = 0, col = 0;
@@ -327,11 +350,11 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
         bool idle = false;
         if (pool.dynamic) {   // initial work items 0 .. n_slots-1 (the host starts the shard counters there)
             has_work = s < pool.n_slots && (unsigned long long)s < pool.total_work;
-            idle = has_work && !work_to_pixel(pool, s, pixel, sample, row, col);
+            idle = has_work && !work_item<LIST>(pool, s, pixel, sample, row, col);
             if (!has_work || idle) { pixel = 0; sample = 0; }
         } else {
-            pixel = s % pool.n_pixels;
-            sample = pool.spp_begin + s / pool.n_pixels;
+            pixel = slot_pixel<LIST>(pool, s);
+            sample = pool.spp_begin + s / (LIST ? pool.n_list : pool.n_pixels);
             divmod_u31(pixel, cam.width, row, col);
             has_work = s < pool.n_slots && sample < pool.spp_end;
             pool.ax[s] = 0.0; pool.ay[s] = 0.0; pool.az[s] = 0.0;
@@ -1077,7 +1100,7 @@ struct NoPrefetch {
 // younger load is waited for — hence the phase discipline (tex values fetched up front, pt_dev_bsdf.h fetch_tex).
 // LIGHTS: the scene has a lights list (World::lights non-empty). The instantiation without compiles lights.sample / lights.pdf, the
 // selector draw and the later prefetch point out: p_light = 0 there (camera.rs:199-200), so no result changes.
-template <bool LIGHTS, class Prefetch>
+template <bool LIGHTS, bool LIST, class Prefetch>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, uint32_t s, int lane, const SlotIn& in,
@@ -1128,7 +1151,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     PT_STAMP_VAR(a1);
     if (live) {
         if (!pool.dynamic) {
-            pixel = s % pool.n_pixels;
+            pixel = slot_pixel<LIST>(pool, s);
             rad = V3{pool.rx[s], pool.ry[s], pool.rz[s]};
         }
         rng = Rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, in.draw};
@@ -1230,7 +1253,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 const unsigned long long w = shard_item(base + (unsigned long long)__popcll(need & ((1ull << lane) - 1ull)), from);
                 if (w < pool.total_work) {
                     more = true;
-                    next_idle = !work_to_pixel(pool, w, next_pixel, next_sample, next_row, next_col);
+                    next_idle = !work_item<LIST>(pool, w, next_pixel, next_sample, next_row, next_col);
                 }
             }
             if (__ballot(asking && !more)) {
@@ -1323,7 +1346,7 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // waves of the block (work stealing), and every slot's records are moved whole by its own lane.
 // KB: threads per block (256, or [r3] 512 with a 4096-slot window: the sort's barriers and the window's end are paid once per twice
 // as many slots and eight waves level a window's end better than four; one block per CU then).
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK>
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed) {
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
     const int lane = (int)(threadIdx.x & 63u);
@@ -1339,7 +1362,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS>(sc, cam, pool, cnt, seed, s, lane, in, shard, n_done, n_died, NoPrefetch{});
+            shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, lane, in, shard, n_done, n_died, NoPrefetch{});
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -1514,7 +1537,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS>(sc, cam, pool, cnt, seed, s, lane, in, shard, n_done, n_died, prefetch, pre_mask, pre_base, pre_shard);
+                shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, lane, in, shard, n_done, n_died, prefetch, pre_mask, pre_base, pre_shard);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;
                 pre_shard = pre_shard_next;
@@ -1552,27 +1575,47 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 
 // accum[p*3+c] += sum over the k slots of pixel p, in slot order (k == 1: the exact
 // sample-order sum the reference computes at camera.rs:106-108)
+// LIST: the slots of list entry i are j * n_list + i; only the listed pixels are written (stored with PoolD::list_store)
+template <bool LIST = false>
 __global__ __launch_bounds__(BLOCK) void k_resolve(PoolD pool, double* accum) {
-    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < pool.n_pixels; p += gridDim.x * BLOCK) {
+    const uint32_t n = LIST ? pool.n_list : pool.n_pixels;
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         double sx = 0.0, sy = 0.0, sz = 0.0;
         for (uint32_t j = 0; j < pool.k; ++j) {
-            const uint32_t s = j * pool.n_pixels + p;
+            const uint32_t s = j * n + i;
             if (j == 0) { sx = pool.ax[s]; sy = pool.ay[s]; sz = pool.az[s]; }
             else { sx += pool.ax[s]; sy += pool.ay[s]; sz += pool.az[s]; }
         }
-        accum[3 * (size_t)p] += sx;
-        accum[3 * (size_t)p + 1] += sy;
-        accum[3 * (size_t)p + 2] += sz;
+        const uint32_t p = LIST ? pool.list[i] : i;
+        if (LIST && pool.list_store) {
+            accum[3 * (size_t)p] = sx;
+            accum[3 * (size_t)p + 1] = sy;
+            accum[3 * (size_t)p + 2] = sz;
+        } else {
+            accum[3 * (size_t)p] += sx;
+            accum[3 * (size_t)p + 1] += sy;
+            accum[3 * (size_t)p + 2] += sz;
+        }
     }
 }
 
 // dynamic mode with the tiled frame accumulator (PoolD::accum_tiled): accum[p*3+c] += plane c's sum of pixel p — once per render
+// LIST: the listed pixels only (stored with PoolD::list_store)
+template <bool LIST = false>
 __global__ __launch_bounds__(BLOCK) void k_detile(PoolD pool, double* accum) {
-    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < pool.n_pixels; p += gridDim.x * BLOCK) {
+    const uint32_t n = LIST ? pool.n_list : pool.n_pixels;
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const uint32_t p = LIST ? pool.list[i] : i;
         const double* a = pool.accum + tiled_index(pool, p);
-        accum[3 * (size_t)p] += a[0];
-        accum[3 * (size_t)p + 1] += a[pool.n_tile_pixels];
-        accum[3 * (size_t)p + 2] += a[2 * (size_t)pool.n_tile_pixels];
+        if (LIST && pool.list_store) {
+            accum[3 * (size_t)p] = a[0];
+            accum[3 * (size_t)p + 1] = a[pool.n_tile_pixels];
+            accum[3 * (size_t)p + 2] = a[2 * (size_t)pool.n_tile_pixels];
+        } else {
+            accum[3 * (size_t)p] += a[0];
+            accum[3 * (size_t)p + 1] += a[pool.n_tile_pixels];
+            accum[3 * (size_t)p + 2] += a[2 * (size_t)pool.n_tile_pixels];
+        }
     }
 }
 
@@ -1715,7 +1758,8 @@ static inline dim3 grid_for(uint32_t n, int max_blocks) {
     return dim3(b);
 }
 void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st) {
-    hipLaunchKernelGGL(k_init, grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
+    if (pool.list) hipLaunchKernelGGL(k_init<true>, grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
+    else hipLaunchKernelGGL(k_init<false>, grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
 }
 typedef void (*extend2_fn)(SceneD, PoolD, CountersD*);
 static extend2_fn pick_extend2(int code) {   // code = stack entries * 10 + min blocks per CU
@@ -1747,7 +1791,10 @@ void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_
     else hipLaunchKernelGGL(pick_extend_batch(sc.tlas_flat, sc.flat_pairs), grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, sc, pool, cnt);
 }
 typedef void (*shade_fn)(SceneD, CamD, PoolD, CountersD*, uint64_t);
-static shade_fn pick_shade(int variant, bool lights) {   // variant = sort*10 + min waves per SIMD; 22 = sorted, 512 threads / 4096-slot windows
+static shade_fn pick_shade(int variant, bool lights, bool list = false) {   // variant = sort*10 + min waves per SIMD; 22 = sorted, 512 threads / 4096-slot windows
+    if (list)   // pixel-list renders: the default's two forms only (launch_shade maps every other variant to 42)
+        return variant == 22 ? (lights ? k_shade<true, 2, true, 512, 8, true> : k_shade<true, 2, false, 512, 8, true>)
+                             : (lights ? k_shade<true, 2, true, 512, 16, true> : k_shade<true, 2, false, 512, 16, true>);
     switch (variant) {
     case 2: return lights ? k_shade<false, 2, true> : k_shade<false, 2, false>;
     case 3: return lights ? k_shade<false, 3, true> : k_shade<false, 3, false>;
@@ -1765,15 +1812,17 @@ void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, Counters
                   hipStream_t st, uint32_t wide_window_min) {
     // 42: 8192-slot windows while the pool holds at least PT_WIDE_WINDOW_MIN of them per block launched, 4096-slot windows below
     // (a thinner pool — smaller frames, one rank's share, the frame's end after compaction — levels its end better with more, smaller windows)
+    if (pool.list && variant != 22 && variant != 32) variant = 42;
     if (variant == 42) variant = pool.n_alloc / 8192u >= (uint32_t)max_blocks * (wide_window_min ? wide_window_min : 1u) ? 32 : 22;
     const int kb = shade_threads(variant);
     uint32_t blocks = variant >= 10 ? pool.n_alloc / (uint32_t)shade_window(variant) : (pool.n_alloc + (uint32_t)kb - 1u) / (uint32_t)kb;   // one block per window / chunk
     if (blocks > (uint32_t)max_blocks) blocks = (uint32_t)max_blocks;
     if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(pick_shade(variant, sc.n_lights != 0u), dim3(blocks), dim3((uint32_t)kb), 0, st, sc, cam, pool, cnt, seed);
+    hipLaunchKernelGGL(pick_shade(variant, sc.n_lights != 0u, pool.list != nullptr), dim3(blocks), dim3((uint32_t)kb), 0, st, sc, cam, pool, cnt, seed);
 }
 void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_t st) {
-    hipLaunchKernelGGL(k_resolve, grid_for(pool.n_pixels, max_blocks), dim3(BLOCK), 0, st, pool, accum);
+    if (pool.list) hipLaunchKernelGGL(k_resolve<true>, grid_for(pool.n_list, max_blocks), dim3(BLOCK), 0, st, pool, accum);
+    else hipLaunchKernelGGL(k_resolve<false>, grid_for(pool.n_pixels, max_blocks), dim3(BLOCK), 0, st, pool, accum);
 }
 void launch_compact(const PoolD& pool, uint32_t new_end, uint32_t* holes, uint32_t* movers, uint32_t* counts, uint32_t cap, int max_blocks, hipStream_t st) {
     (void)hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), st);
@@ -1781,7 +1830,8 @@ void launch_compact(const PoolD& pool, uint32_t new_end, uint32_t* holes, uint32
     hipLaunchKernelGGL(k_compact_move, grid_for(cap, max_blocks), dim3(BLOCK), 0, st, pool, holes, movers, counts, cap);
 }
 void launch_detile(const PoolD& pool, double* accum, int max_blocks, hipStream_t st) {
-    hipLaunchKernelGGL(k_detile, grid_for(pool.n_pixels, max_blocks), dim3(BLOCK), 0, st, pool, accum);
+    if (pool.list) hipLaunchKernelGGL(k_detile<true>, grid_for(pool.n_list, max_blocks), dim3(BLOCK), 0, st, pool, accum);
+    else hipLaunchKernelGGL(k_detile<false>, grid_for(pool.n_pixels, max_blocks), dim3(BLOCK), 0, st, pool, accum);
 }
 void launch_quantise(const double* accum, uint32_t n, double scale, uint8_t* rgb8, hipStream_t st) {
     hipLaunchKernelGGL(k_quantise, grid_for(n, 4096), dim3(BLOCK), 0, st, accum, n, scale, rgb8);
@@ -1792,9 +1842,9 @@ void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out,
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st) {
     hipLaunchKernelGGL(k_math_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, which, in, n, out);
 }
-int kernel_occupancy_blocks(int which, int variant, bool lights) {
+int kernel_occupancy_blocks(int which, int variant, bool lights, bool list) {
     int nb = 0;
-    const void* f = which == 0 ? (variant <= -100 ? (const void*)pick_extend2(-variant) : (const void*)pick_extend_batch(variant <= -2, variant == -3)) : (const void*)pick_shade(variant, lights);
+    const void* f = which == 0 ? (variant <= -100 ? (const void*)pick_extend2(-variant) : (const void*)pick_extend_batch(variant <= -2, variant == -3)) : (const void*)pick_shade(variant, lights, list);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, which == 1 ? shade_threads(variant) : variant <= -100 ? extend2_threads(-variant) : BLOCK, 0) != hipSuccess || nb < 1) nb = 1;
     return nb;
 }

@@ -151,8 +151,11 @@ struct EventTimer {   // per-launch HIP-event timing, drained at the polling syn
 };
 }  // namespace
 
-extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum,
-                         const pt_render_opts* opts_in, pt_render_stats* stats) {
+// The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
+// pixels) / n_list: a pixel-list render (PoolD::list; d_list sorted by tiled index, n_list > 0), or null: the whole frame — then the
+// path below is exactly pt_render's.
+static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum,
+                       const pt_render_opts* opts_in, pt_render_stats* stats, const uint32_t* d_list, const uint32_t* h_list, uint32_t n_list) {
     if (!s || !s->built) return set_error("pt_render: world not built (call pt_world_build)");
     if (!accum) return set_error("pt_render: null accumulator");
     if (spp_end < spp_begin) return set_error("pt_render: spp_end < spp_begin");
@@ -202,6 +205,8 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
     if (n_pixels64 == 0 || n_pixels64 > 0x7FFFFFFFull) return set_error("pt_render: bad image size");
     const uint32_t n_pixels = (uint32_t)n_pixels64;
     const uint32_t spp = spp_end - spp_begin;
+    const bool list = d_list != nullptr;
+    const uint32_t n_items = list ? n_list : n_pixels;   // pixels rendered
 
     // pool sizing. slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
     // the machine several times over; finished paths pull the next (pixel, sample) from a global
@@ -214,7 +219,7 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
     const uint32_t tiles_x = (dc.width + 7) / 8, tiles_y = (dc.height + 7) / 8;
     const uint64_t n_tile_pixels64 = (uint64_t)tiles_x * tiles_y * 64;
     if (n_tile_pixels64 > 0x7FFFFFFFull) return set_error("pt_render: image too large");
-    const uint64_t total_work = dynamic ? n_tile_pixels64 * spp : (uint64_t)n_pixels * spp;
+    const uint64_t total_work = dynamic ? (list ? (uint64_t)n_list : n_tile_pixels64) * spp : (uint64_t)n_items * spp;
     uint64_t n_slots64;
     if (dynamic) {
         // Resident paths: enough that per-launch fixed costs and kernel tails amortise (16.8M slots are 9% faster than
@@ -242,8 +247,8 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
     } else {
         if (k > spp) k = spp;
         if (k == 0) k = 1;
-        while ((uint64_t)k * n_pixels > 0x40000000ull && k > 1) --k;
-        n_slots64 = (uint64_t)k * n_pixels;
+        while ((uint64_t)k * n_items > 0x40000000ull && k > 1) --k;
+        n_slots64 = (uint64_t)k * n_items;
     }
     if (n_slots64 > 0x7FFFFFC0ull) return set_error("pt_render: image too large for the path pool");
     const uint32_t n_slots = (uint32_t)n_slots64;
@@ -289,6 +294,9 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
     pool.height = dc.height;
     pool.tiles_x = tiles_x;
     pool.n_tile_pixels = (uint32_t)n_tile_pixels64;
+    pool.list = d_list;
+    pool.n_list = list ? n_list : 0u;
+    pool.list_store = list && opts.accum_on_device && opts.overwrite ? 1u : 0u;   // (a host accumulator is written below, pixel by pixel)
 
     // accumulator on the device (freed on every return path when it is ours)
     double* d_accum = accum;
@@ -301,7 +309,7 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
         if (!hip_ok(hipMalloc((void**)&d_accum, accum_bytes), "hipMalloc(accum)")) return -1;
         own_accum.p = d_accum;
         if (!hip_ok(hipMemsetAsync(d_accum, 0, accum_bytes, st), "hipMemset(accum)")) return -1;
-    } else if (opts.overwrite) {
+    } else if (opts.overwrite && !list) {   // (a list render stores its pixels instead: the others are not written)
         if (!hip_ok(hipMemsetAsync(d_accum, 0, accum_bytes, st), "hipMemset(accum)")) return -1;
     }
 
@@ -313,6 +321,7 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
                               // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
+    if (list && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list forms of k_shade (launch_shade)
     uint32_t wide_window_min = 16;
     if (const char* e = exp_env("PT_WIDE_WINDOW_MIN")) wide_window_min = (uint32_t)std::max(1, atoi(e));
     // K2 variant: two-phase kernel when there are meshes to defer and its LDS stack covers the scene's BVHs, else the
@@ -340,7 +349,7 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
         if (!strcmp(e, "batch")) extend_code = -1;
         else if (!strcmp(e, "twophase") && extend2_code() != 0) extend_code = -extend2_code();
     }
-    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u);
+    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list);
     const int grid_extend = ctx->n_cus * blocks_extend * mult, grid_shade = ctx->n_cus * blocks_shade * mult;
 
     pool.accum = d_accum;
@@ -444,7 +453,15 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
     auto t1 = std::chrono::steady_clock::now();
     if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
 
-    if (!opts.accum_on_device) {
+    if (!opts.accum_on_device && list) {   // only the listed pixels of the caller's frame are written
+        std::vector<double> tmp((size_t)n_pixels * 3);
+        if (!hip_ok(hipMemcpy(tmp.data(), d_accum, accum_bytes, hipMemcpyDeviceToHost), "hipMemcpy(accum)")) return -1;
+        for (uint32_t i = 0; i < n_list; ++i)
+            for (uint32_t c = 0; c < 3; ++c) {
+                const size_t j = 3 * (size_t)h_list[i] + c;
+                accum[j] = opts.overwrite ? tmp[j] : accum[j] + tmp[j];
+            }
+    } else if (!opts.accum_on_device) {
         if (opts.overwrite) {
             if (!hip_ok(hipMemcpy(accum, d_accum, accum_bytes, hipMemcpyDeviceToHost), "hipMemcpy(accum)")) return -1;
         } else {
@@ -492,6 +509,205 @@ extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint3
         stats->n_alloc_end = pool.n_alloc;
     }
     return 0;
+}
+
+extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum,
+                         const pt_render_opts* opts, pt_render_stats* stats) {
+    return render_core(s, cam, seed, spp_begin, spp_end, accum, opts, stats, nullptr, nullptr, 0);
+}
+
+namespace {
+uint32_t tiled_key(uint32_t p, uint32_t width, uint32_t tiles_x) {   // row-major pixel -> its tiled index (k_detile's tiled_index)
+    const uint32_t y = p / width, x = p % width;
+    return ((y >> 3) * tiles_x + (x >> 3)) * 64u + ((y & 7u) << 3) + (x & 7u);
+}
+// the scene's device pixel list (re-used like tile_accum), at least n entries
+bool pixel_list_buffer(pt_scene* s, size_t n) {
+    if (n <= s->pixel_list_words) return true;
+    if (s->pixel_list) (void)hipFree(s->pixel_list);
+    s->pixel_list = nullptr;
+    s->pixel_list_words = 0;
+    if (!hip_ok(hipMalloc((void**)&s->pixel_list, n * sizeof(uint32_t)), "hipMalloc(pixel list)")) return false;
+    s->pixel_list_words = n;
+    return true;
+}
+}  // namespace
+
+extern "C" int pt_render_pixels(pt_scene* s, const pt_camera* cam, uint64_t seed, const uint32_t* pixels, uint32_t n, uint32_t spp_begin,
+                                uint32_t spp_end, double* accum, const pt_render_opts* opts, pt_render_stats* stats) {
+    if (!s || !s->built) return set_error("pt_render_pixels: world not built (call pt_world_build)");
+    if (!accum) return set_error("pt_render_pixels: null accumulator");
+    if (spp_end < spp_begin) return set_error("pt_render_pixels: spp_end < spp_begin");
+    CamDerived cd;
+    if (derive_camera(cam, cd) != 0) return -1;
+    const uint64_t n_pixels = (uint64_t)cam->image_width * cd.height;
+    if (n_pixels > 0x7FFFFFFFull) return set_error("pt_render_pixels: bad image size");
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof *stats);
+        return 0;
+    }
+    if (!pixels) return set_error("pt_render_pixels: null pixel list");
+    for (uint32_t i = 0; i < n; ++i) {
+        if (pixels[i] >= n_pixels) return set_error("pt_render_pixels: pixel index out of range (must be < width * height)");
+        if (i > 0 && pixels[i] <= pixels[i - 1]) return set_error("pt_render_pixels: the pixel list must be strictly ascending (sorted, no duplicates)");
+    }
+    // the device list in tiled order: a run of 64 work items then covers an 8x8 tile, as in a whole-frame render
+    const uint32_t width = cam->image_width, tiles_x = (width + 7) / 8;
+    std::vector<uint32_t> sorted(pixels, pixels + n);
+    std::sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return tiled_key(a, width, tiles_x) < tiled_key(b, width, tiles_x); });
+    if (!hip_ok(hipSetDevice(s->ctx->device), "hipSetDevice")) return -1;
+    if (!pixel_list_buffer(s, n)) return -1;
+    if (!hip_ok(hipMemcpy(s->pixel_list, sorted.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(pixel list)")) return -1;
+    return render_core(s, cam, seed, spp_begin, spp_end, accum, opts, stats, s->pixel_list, sorted.data(), n);
+}
+
+extern "C" int pt_adaptive_schedule(uint32_t min_spp, uint32_t max_spp, uint32_t* bounds, uint32_t cap) {
+    if (min_spp < 2) return set_error("pt_adaptive_schedule: min_spp must be at least 2");
+    if (max_spp < min_spp) return set_error("pt_adaptive_schedule: max_spp must be at least min_spp");
+    if (cap && !bounds) return set_error("pt_adaptive_schedule: null bounds");
+    uint32_t count = 0;
+    auto put = [&](uint32_t b) {
+        if (count < cap) bounds[count] = b;
+        ++count;
+    };
+    const uint32_t half = min_spp / 2;
+    put(0);
+    put(half);
+    uint32_t b = min_spp;
+    put(b);
+    while (b < max_spp) {
+        b = (uint32_t)std::min<uint64_t>(max_spp, (uint64_t)b + std::max(half, b / 2));
+        put(b);
+    }
+    return (int)count;
+}
+
+extern "C" int pt_render_adaptive(pt_scene* s, const pt_camera* cam, uint64_t seed, const pt_adaptive_opts* ao, double* accum,
+                                  uint32_t* spp_per_pixel, pt_render_stats* stats) {
+    if (!s || !s->built) return set_error("pt_render_adaptive: world not built (call pt_world_build)");
+    if (!ao) return set_error("pt_render_adaptive: null options");
+    if (!accum || !spp_per_pixel) return set_error("pt_render_adaptive: null output buffer");
+    const int n_bounds = pt_adaptive_schedule(ao->min_spp, ao->max_spp, nullptr, 0);
+    if (n_bounds < 0) return set_error((std::string("pt_render_adaptive: ") + pt_last_error()).c_str());
+    std::vector<uint32_t> b((size_t)n_bounds);
+    (void)pt_adaptive_schedule(ao->min_spp, ao->max_spp, b.data(), (uint32_t)n_bounds);
+    CamDerived cd;
+    if (derive_camera(cam, cd) != 0) return -1;
+    const uint32_t width = cam->image_width, height = cd.height;
+    const uint64_t n64 = (uint64_t)width * height;
+    if (n64 > 0x7FFFFFFFull) return set_error("pt_render_adaptive: bad image size");
+    const uint32_t n_pixels = (uint32_t)n64;
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    hipStream_t st = ao->stream ? (hipStream_t)ao->stream : ctx->stream;
+    auto t0 = std::chrono::steady_clock::now();
+
+    // device state: E, O (3 f64 per pixel each), the error map, two pixel lists, the stop counts, the select kernels' block counts
+    const uint32_t n_blocks = adapt_select_blocks(width, height);
+    const size_t f64s = (size_t)n_pixels * 7, u32s = (size_t)n_pixels * 3 + n_blocks + 1;
+    struct Mem {
+        void* p = nullptr;
+        ~Mem() { if (p) (void)hipFree(p); }
+    } mem;
+    if (!hip_ok(hipMalloc(&mem.p, f64s * sizeof(double) + u32s * sizeof(uint32_t)), "hipMalloc(adaptive state)")) return -1;
+    double* E = (double*)mem.p;
+    double* O = E + 3 * (size_t)n_pixels;
+    double* err = O + 3 * (size_t)n_pixels;
+    uint32_t* list_a = (uint32_t*)(err + n_pixels);
+    uint32_t* list_b = list_a + n_pixels;
+    uint32_t* stop = list_b + n_pixels;
+    uint32_t* block_counts = stop + n_pixels;
+    uint32_t* d_active = block_counts + n_blocks;
+    if (!hip_ok(hipMemsetAsync(E, 0, 6 * (size_t)n_pixels * sizeof(double), st), "hipMemset(adaptive sums)") ||
+        !hip_ok(hipMemsetAsync(stop, 0, (size_t)n_pixels * sizeof(uint32_t), st), "hipMemset(adaptive counts)"))
+        return -1;
+    std::vector<uint32_t> all;   // every pixel, in tiled order
+    all.reserve(n_pixels);
+    const uint32_t tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx)
+            for (uint32_t i = 0; i < 64; ++i) {
+                const uint32_t x = tx * 8 + (i & 7), y = ty * 8 + (i >> 3);
+                if (x < width && y < height) all.push_back(y * width + x);
+            }
+    if (!hip_ok(hipMemcpyAsync(list_a, all.data(), (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, st), "hipMemcpy(pixel list)") ||
+        !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(adaptive)"))
+        return -1;
+
+    pt_render_opts po;
+    memset(&po, 0, sizeof po);
+    po.slots_per_pixel = ao->slots_per_pixel;
+    po.accum_on_device = 1;
+    po.profile = ao->profile;
+    po.stream = (void*)st;
+    pt_render_stats sum;
+    memset(&sum, 0, sizeof sum);
+    uint32_t n_active = n_pixels;
+    double n_e = 0.0, n_o = 0.0;
+    const uint32_t max_spp = ao->max_spp;
+    for (int i = 0; i + 1 < n_bounds && n_active != 0; ++i) {
+        const uint32_t lo = b[(size_t)i], hi = b[(size_t)i + 1];
+        pt_render_stats ps;
+        if (render_core(s, cam, seed, lo, hi, (i & 1) ? O : E, &po, &ps, list_a, nullptr, n_active) != 0) return -1;
+        sum.samples += ps.samples;
+        sum.segments += ps.segments;
+        sum.iterations += ps.iterations;
+        sum.n_slots = std::max(sum.n_slots, ps.n_slots);
+        sum.slots_per_pixel = ps.slots_per_pixel;
+        sum.ms_extend += ps.ms_extend;
+        sum.ms_shade += ps.ms_shade;
+        sum.ms_other += ps.ms_other;
+        sum.launches_extend += ps.launches_extend;
+        sum.launches_shade += ps.launches_shade;
+        sum.extend_variant = ps.extend_variant;
+        sum.shade_variant = ps.shade_variant;
+        sum.blocks_extend = ps.blocks_extend;
+        sum.blocks_shade = ps.blocks_shade;
+        sum.compactions += ps.compactions;
+        sum.n_alloc_end = ps.n_alloc_end;
+        ((i & 1) ? n_o : n_e) += (double)(hi - lo);
+        if (i >= 1 && hi < max_spp) {   // the test: who goes on into round i + 1
+            launch_adapt_error(E, O, stop, n_pixels, n_e, n_o, err, st);
+            launch_adapt_select(err, stop, width, height, ao->threshold, hi, block_counts, list_b, d_active, st);
+            if (!hip_ok(hipMemcpyAsync(&n_active, d_active, sizeof n_active, hipMemcpyDeviceToHost, st), "hipMemcpy(active count)") ||
+                !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(adaptive select)"))
+                return -1;
+            std::swap(list_a, list_b);
+        }
+    }
+    launch_adapt_final(E, O, stop, n_pixels, max_spp, list_b, st);
+    if (!hip_ok(hipMemcpyAsync(accum, E, (size_t)n_pixels * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(accum)") ||
+        !hip_ok(hipMemcpyAsync(spp_per_pixel, list_b, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "hipMemcpy(spp per pixel)") ||
+        !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(adaptive)") || !hip_ok(hipGetLastError(), "kernel launch"))
+        return -1;
+    sum.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) *stats = sum;
+    return 0;
+}
+
+extern "C" int pt_resolve_u8_counts(pt_ctx* ctx, const double* accum, uint32_t n_pixels, const uint32_t* spp_per_pixel, uint8_t* rgb8) {
+    if (!ctx) return set_error("pt_resolve_u8_counts: null context");
+    if (!accum || !spp_per_pixel || !rgb8) return set_error("pt_resolve_u8_counts: null buffer");
+    for (uint32_t p = 0; p < n_pixels; ++p)
+        if (spp_per_pixel[p] == 0) return set_error("pt_resolve_u8_counts: a pixel has no samples");
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    const size_t n = (size_t)n_pixels * 3;
+    double* d_in = nullptr;
+    uint32_t* d_cnt = nullptr;
+    uint8_t* d_out = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&d_in, n * sizeof(double) + 8), "hipMalloc") && hip_ok(hipMalloc((void**)&d_cnt, (size_t)n_pixels * 4 + 4), "hipMalloc") &&
+              hip_ok(hipMalloc((void**)&d_out, n + 1), "hipMalloc") &&
+              hip_ok(hipMemcpyAsync(d_in, accum, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy") &&
+              hip_ok(hipMemcpyAsync(d_cnt, spp_per_pixel, (size_t)n_pixels * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    if (ok) {
+        launch_quantise_counts(d_in, n_pixels, d_cnt, d_out, ctx->stream);
+        ok = hip_ok(hipMemcpyAsync(rgb8, d_out, n, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    if (d_in) (void)hipFree(d_in);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (d_out) (void)hipFree(d_out);
+    return ok ? 0 : -1;
 }
 
 extern "C" int pt_resolve_u8(pt_ctx* ctx, const double* accum, uint32_t n_pixels, uint32_t total_spp, uint8_t* rgb8) {

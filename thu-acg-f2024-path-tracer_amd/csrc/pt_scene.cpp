@@ -44,6 +44,7 @@ pt_scene::~pt_scene() {
     if (pool_mem) (void)hipFree(pool_mem);
     if (tile_accum) (void)hipFree(tile_accum);
     if (compact_scratch) (void)hipFree(compact_scratch);
+    if (pixel_list) (void)hipFree(pixel_list);
     if (d_counters) (void)hipFree(d_counters);
     if (h_counters) (void)hipHostFree(h_counters);
 }

@@ -80,6 +80,8 @@ struct pt_scene {
     size_t tile_accum_bytes = 0;
     uint32_t* compact_scratch = nullptr;   // the end-of-frame compaction's hole / mover lists + counters (pt_render.cpp)
     size_t compact_scratch_words = 0;
+    uint32_t* pixel_list = nullptr;   // pt_render_pixels: the device pixel list (tiled order), re-used like tile_accum
+    size_t pixel_list_words = 0;
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned
     ~pt_scene();

@@ -234,6 +234,12 @@ struct PoolD {
     uint32_t defer_regen, compact;                   // dynamic mode: a path that ends ON A SURFACE (roulette, sampler, depth) parks its slot
                                                   // as SLOT_IDLE; it is refilled next iteration among the idle slots (k_shade)
     uint32_t width, height, tiles_x, n_tile_pixels;   // dynamic mode: 8x8 tiling, n_tile_pixels = tiles_x*tiles_y*64
+    // pixel-list renders (pt_render_pixels, pt_render_adaptive; the kernels' LIST = true forms only): n_list row-major pixel ids
+    // in TILED-index order, so that consecutive work items / slots are neighbouring pixels as in a whole-frame render. Dynamic mode:
+    // work item w = (pixel list[w mod n_list], sample spp_begin + w / n_list); static mode: slot s owns pixel list[s mod n_list].
+    // list_store: k_resolve / k_detile store the listed pixels' sums instead of adding them (device accumulator + overwrite).
+    const uint32_t* list;
+    uint32_t n_list, list_store;
 };
 
 // The work counter of the dynamic mode is SHARDED: one word saturates at ~88 dequeues/us on this

@@ -1,7 +1,9 @@
 // CLI with the reference's two flags (src/main.rs:620-645): -q/--quality toggles
 // 1920 px @ 4000 spp vs 600 px @ 100 spp, -s/--scene N picks the scene script. Extra,
 // explicit overrides (not in the reference): --width, --spp, --seed, --out, --assets, --device, --float-hdr
-// (.hdr environments keep their f32 samples instead of the reference's .to_rgb8() squash, texture.rs:67).
+// (.hdr environments keep their f32 samples instead of the reference's .to_rgb8() squash, texture.rs:67),
+// --adaptive T [--min-spp M] (adaptive sampling to the noise target T, pt_render_adaptive; --spp is then the cap).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -13,7 +15,9 @@ using namespace path_tracer;
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
-    long width = -1, spp = -1;
+    long width = -1, spp = -1, min_spp = 16;
+    double adaptive = 0.0;
+    bool use_adaptive = false;
     uint64_t seed = 1;
     std::string out, assets = "assets";
     for (int i = 1; i < argc; ++i) {
@@ -31,8 +35,10 @@ int main(int argc, char** argv) {
         else if (a == "--assets") assets = next();
         else if (a == "--device") device = atoi(next());
         else if (a == "--float-hdr") float_hdr = true;
+        else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
+        else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr]\n";
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--adaptive T [--min-spp M]]\n";
             return 0;
         } else { std::cerr << "unknown argument " << a << "\n"; return 2; }
     }
@@ -51,7 +57,12 @@ int main(int argc, char** argv) {
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();
         std::cerr << "rendering production\n";   // camera.rs:101
-        setup.camera.render(setup.world, out.empty() ? setup.output : out, seed);
+        if (use_adaptive) {
+            const uint32_t m = (uint32_t)std::max(2L, std::min(min_spp, (long)s));
+            setup.camera.render_adaptive(setup.world, out.empty() ? setup.output : out, adaptive, m, seed);
+        } else {
+            setup.camera.render(setup.world, out.empty() ? setup.output : out, seed);
+        }
         setup.world.release();
     } catch (const std::exception& e) {
         std::cerr << "panic: " << e.what() << "\n";   // the reference unwrap()s asset errors

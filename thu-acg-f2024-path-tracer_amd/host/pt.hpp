@@ -439,6 +439,29 @@ struct Camera {
                      st.ms_total * 1e-3, (double)st.samples / (st.ms_total * 1e-3) * 1e-6);
         if (stats_out) *stats_out = st;
     }
+    // not in the reference: render to a noise target (pt_render_adaptive) with samples_per_pixel as the cap; each pixel is
+    // resolved with its own sample count (pt_resolve_u8_counts); prints the mean samples per pixel
+    void render_adaptive(World& world, const std::string& filename, double threshold, uint32_t min_spp, uint64_t seed = 1) const {
+        auto start = std::chrono::steady_clock::now();
+        pt_camera c = to_c(&world);
+        const size_t n = image_width * image_height;
+        std::vector<double> accum(n * 3, 0.0);
+        std::vector<uint32_t> counts(n, 0);
+        pt_adaptive_opts ao;
+        std::memset(&ao, 0, sizeof ao);
+        ao.min_spp = min_spp;
+        ao.max_spp = (uint32_t)samples_per_pixel;
+        ao.threshold = threshold;
+        pt_render_stats st;
+        if (pt_render_adaptive(world.scene, &c, seed, &ao, accum.data(), counts.data(), &st) != 0) panic(std::string("Camera::render_adaptive: ") + pt_last_error());
+        std::vector<uint8_t> rgb(n * 3);
+        if (pt_resolve_u8_counts(pt_scene_ctx(world.scene), accum.data(), (uint32_t)n, counts.data(), rgb.data()) != 0) panic("Camera::render_adaptive");
+        if (pt_save_png(filename.c_str(), (uint32_t)image_width, (uint32_t)image_height, rgb.data()) != 0)
+            std::fprintf(stderr, "Failed to save image %s\n", pt_last_error());
+        double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        std::fprintf(stderr, "adaptive: threshold %g, min spp %u, max spp %u: mean spp %.2f (%llu samples) in %.6f s\n", threshold, min_spp,
+                     (uint32_t)samples_per_pixel, (double)st.samples / (double)n, (unsigned long long)st.samples, secs);
+    }
 };
 
 inline int ImageTexture::emit(Emitter& e) const {
