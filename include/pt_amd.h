@@ -184,6 +184,45 @@ int pt_render_adaptive(pt_scene*, const pt_camera*, uint64_t seed, const pt_adap
 /* pt_resolve_u8 with each pixel's own count (> 0): mean = sum * (1.0 / n_p), then pt_resolve_u8's arithmetic. Host buffers. */
 int pt_resolve_u8_counts(pt_ctx*, const double* accum, uint32_t n_pixels, const uint32_t* spp_per_pixel, uint8_t* rgb8);
 
+/* ---- feature buffers and denoising (no counterpart in the reference) ----------------------------------------------------
+ * First-hit AOVs. For every pixel and each sample s in [spp_begin, spp_end), the camera ray is the one pt_render traces for
+ * (pixel, s): same seed, same RNG draws. The ray's first hit adds to aov[(y*W+x)*8 + k]. These are SUMS over samples, like
+ * accum, so sample ranges add up:
+ *   k = 0..2  albedo r,g,b   (every sample): diffuse / metal / principled: the colour texture at the hit; sheen: its base colour;
+ *             glass, clearcoat, light and a miss: (1, 1, 1) (glass's base colour reaches no radiance, emitted and environment
+ *             light is not reflected); mix: (1 - t) * A(child1) + t * A(child2), recursively over the two levels allowed
+ *   k = 3..5  normal x,y,z   (hits only: the shading normal of the hit, normal map applied)
+ *   k = 6     depth          (hits only: t of the first hit; camera rays are unit length)
+ *   k = 7     hits           (number of samples whose camera ray hit something)
+ * opts: accum_on_device, overwrite and stream as pt_render; the other fields are ignored. Deterministic (no atomics).
+ * A null aov, an unbuilt world or spp_end < spp_begin returns -1; an empty range adds nothing (overwrite: stores zeros). */
+int pt_render_aovs(pt_scene*, const pt_camera*, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov,
+                   const pt_render_opts* opts);
+/* Variance-guided a-trous denoiser (edge-avoiding wavelet filter on demodulated colour). Host buffers, W*H row-major.
+ * sum_a / sum_b: the W*H*3 sums of two DISJOINT sample sets of n_a / n_b samples (e.g. pt_render over [0, n/2) and [n/2, n));
+ * aov: pt_render_aovs sums over n_aov samples; out: W*H*3 MEANS. The rule, per pixel (f64, one IEEE rounding per operation):
+ *   L(c) = 0.2126 r + 0.7152 g + 0.0722 b;  mu = (sum_a + sum_b) / (n_a + n_b)
+ *   background: hits == 0. Foreground: z = depth / hits, N = normal / sqrt(x^2 + y^2 + z^2) (0 if that length is 0),
+ *     a = max(albedo / n_aov, 1e-3) per channel, c = mu / a, cA = (sum_a / n_a) / a, cB = (sum_b / n_b) / a,
+ *     v = (L(cA) - L(cB))^2 * (n_a n_b / (n_a + n_b)^2)   (the variance of the mean the two halves imply)
+ *   level k = 0 .. K-1, step s = 2^k, for each foreground pixel p (background pixels keep c and v):
+ *     g_p = the 3x3 filter (1/4, 1/2, 1/4)^2 of v over the in-image foreground neighbours, divided by the weight present
+ *     taps q = p + s*(i, j), j then i in -2..2, in the image and foreground, with h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *     w = h_i h_j * exp(-|L(c_p) - L(c_q)| / (sigma_l sqrt(g_p) + 1e-10) - |z_p - z_q| / (sigma_z z_p + 1e-10)) * max(0, N_p.N_q)^128
+ *     (one deterministic exp; the power as seven squarings);  c'_p = sum w c_q / sum w,  v'_p = sum w^2 v_q / (sum w)^2
+ *     (sum w == 0, possible only with a zero normal: c and v are kept)
+ *   out = c^(K) * a on the foreground, mu on the background.
+ * Defaults (opts NULL), calibrated on scenes 3 and 6: K = 5, sigma_l = 4, sigma_z = 0.1.
+ * Returns -1 for a null pointer, W or H = 0, n_a, n_b or n_aov = 0, K > 10, sigma_l or sigma_z <= 0 or NaN.
+ * Device memory: 232 B per pixel for the call's duration. */
+typedef struct pt_denoise_opts {
+    uint32_t iterations;   /* a-trous levels K (steps 1, 2, ..., 2^(K-1)); <= 10. Default 5 */
+    double sigma_l;        /* luminance edge-stopping, in standard deviations. Default 4 */
+    double sigma_z;        /* relative-depth edge-stopping. Default 0.1 */
+} pt_denoise_opts;
+int pt_denoise(pt_ctx*, uint32_t width, uint32_t height, const double* sum_a, uint32_t n_a, const double* sum_b, uint32_t n_b,
+               const double* aov, uint32_t n_aov, const pt_denoise_opts* opts, double* out);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

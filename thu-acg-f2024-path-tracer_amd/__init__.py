@@ -96,6 +96,16 @@ class AdaptiveOpts(C.Structure):
     ]
 
 
+class DenoiseOpts(C.Structure):
+    """pt_denoise_opts: a-trous levels and the two edge-stopping widths (include/pt_amd.h has the rule)."""
+
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("sigma_l", C.c_double),
+        ("sigma_z", C.c_double),
+    ]
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -110,6 +120,7 @@ ABI_SYMBOLS = [
     "pt_shard_range", "pt_comm_create", "pt_comm_destroy", "pt_comm_rank", "pt_comm_world", "pt_comm_barrier", "pt_comm_allreduce_f64",
     "pt_bootstrap_exchange", "pt_render_multi",
     "pt_render_pixels", "pt_adaptive_schedule", "pt_render_adaptive", "pt_resolve_u8_counts",
+    "pt_render_aovs", "pt_denoise",
 ]
 
 
@@ -189,6 +200,10 @@ def _load():
         lib.pt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint64, C.POINTER(AdaptiveOpts), C.c_void_p, C.c_void_p,
                                            C.POINTER(RenderStats)]
         lib.pt_resolve_u8_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pt_render_aovs"):
+        lib.pt_render_aovs.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOpts)]
+        lib.pt_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                   C.POINTER(DenoiseOpts), C.c_void_p]
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -265,6 +280,21 @@ class Context:
         assert counts.size * 3 == accum.size
         out = np.empty(accum.shape, dtype=np.uint8)
         _check(lib.pt_resolve_u8_counts(self.handle, accum.ctypes.data, counts.size, counts.ctypes.data, out.ctypes.data), "pt_resolve_u8_counts")
+        return out
+
+    def denoise(self, sum_a: np.ndarray, n_a: int, sum_b: np.ndarray, n_b: int, aov: np.ndarray, n_aov: int, iterations: int = 5,
+                sigma_l: float = 4.0, sigma_z: float = 0.1) -> np.ndarray:
+        """pt_denoise: the (H, W, 3) denoised MEANS of a frame rendered as two disjoint sample sets (sums `sum_a` of n_a samples,
+        `sum_b` of n_b), guided by the (H, W, 8) first-hit sums `aov` of n_aov samples (Scene.render_aovs)."""
+        sum_a = np.ascontiguousarray(sum_a, dtype=np.float64)
+        sum_b = np.ascontiguousarray(sum_b, dtype=np.float64)
+        aov = np.ascontiguousarray(aov, dtype=np.float64)
+        h, w = sum_a.shape[0], sum_a.shape[1]
+        assert sum_a.shape == (h, w, 3) and sum_b.shape == (h, w, 3) and aov.shape == (h, w, 8)
+        out = np.empty((h, w, 3), dtype=np.float64)
+        opts = DenoiseOpts(iterations, sigma_l, sigma_z)
+        _check(lib.pt_denoise(self.handle, w, h, sum_a.ctypes.data, n_a, sum_b.ctypes.data, n_b, aov.ctypes.data, n_aov, C.byref(opts),
+                              out.ctypes.data), "pt_denoise")
         return out
 
 
@@ -454,6 +484,23 @@ class Scene:
         _check(lib.pt_render_adaptive(self.handle, C.byref(cam), seed, C.byref(opts), accum.ctypes.data, counts.ctypes.data, C.byref(stats)),
                "pt_render_adaptive")
         return accum, counts, stats
+
+    def render_aovs(self, cam: Camera, seed: int, spp_begin: int, spp_end: int, aov=None, overwrite: bool = False,
+                    device_ptr: Optional[int] = None, stream: Optional[int] = None):
+        """pt_render_aovs: first-hit feature SUMS over samples [spp_begin, spp_end), the camera rays of render() for the same
+        seed: (H, W, 8) = albedo rgb, shading normal xyz, depth, hits. Added to ``aov`` (``overwrite``: stored);
+        ``device_ptr``: device memory instead (then returns None)."""
+        h = image_height(cam)
+        opts = RenderOpts(0, 1 if device_ptr is not None else 0, 0, 1 if overwrite else 0, stream)
+        if device_ptr is not None:
+            ptr = C.c_void_p(device_ptr)
+        else:
+            if aov is None:
+                aov = np.zeros((h, cam.image_width, 8), dtype=np.float64)
+            assert aov.dtype == np.float64 and aov.flags["C_CONTIGUOUS"] and aov.size == h * cam.image_width * 8
+            ptr = C.c_void_p(aov.ctypes.data)
+        _check(lib.pt_render_aovs(self.handle, C.byref(cam), seed, spp_begin, spp_end, ptr, C.byref(opts)), "pt_render_aovs")
+        return aov
 
     def render_multi(self, cam: Camera, seed: int, spp_total: int, comm: Comm, accum=None, slots_per_pixel: int = 0, profile: bool = False,
                      overwrite: bool = False):

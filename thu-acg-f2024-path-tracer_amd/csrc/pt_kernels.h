@@ -23,6 +23,12 @@ void launch_quantise_counts(const double* accum, uint32_t n_pixels, const uint32
 uint32_t adapt_select_blocks(uint32_t width, uint32_t height);   // entries of launch_adapt_select's block_counts
 void launch_quantise(const double* accum, uint32_t n, double scale, uint8_t* rgb8, hipStream_t st);
 void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out, hipStream_t st);
+// pt_render_aovs: first-hit feature sums of samples [spp_begin, spp_end) of every pixel (aov: device, 8 doubles per pixel)
+void launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
+                hipStream_t st);
+// pt_denoise.hip: the a-trous denoiser (see there). Device buffers; tmp: 12 doubles per pixel of scratch
+void launch_denoise(uint32_t width, uint32_t height, const double* sum_a, double n_a, const double* sum_b, double n_b, const double* aov, double n_aov,
+                    uint32_t iterations, double sigma_l, double sigma_z, double* tmp, double* out, hipStream_t st);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);
 // K2 variant code (`code` of launch_extend / `variant` of kernel_occupancy_blocks): -1 = batch kernel (-2 asks
 // kernel_occupancy_blocks for its flat-top-level instantiation), -(stack*10 + blocks) = two-phase kernel

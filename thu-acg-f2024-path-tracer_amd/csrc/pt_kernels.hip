@@ -1723,6 +1723,54 @@ __global__ __launch_bounds__(BLOCK) void k_probe(SceneD sc, const double* rays /
     }
 }
 
+// First-hit feature buffers (pt_render_aovs; no counterpart in the reference). The colour the first bounce multiplies by:
+// the colour texture of diffuse / metal / principled, sheen's base colour, (1, 1, 1) for glass (Q4: its base colour reaches
+// no radiance), clearcoat and lights; a mix weights its children as mix.rs's pdf / eval do, down the MIX_MAX_DEPTH levels.
+PT_DEV V3 aov_albedo(const SceneD& sc, const MatD& m, const HitD& h) {
+    const V3 one{1.0, 1.0, 1.0};
+    auto leaf = [&](const MatD& l) -> V3 {
+        if (l.kind == MAT_DIFFUSE || l.kind == MAT_METAL || l.kind == MAT_PRINCIPLED) return fetch_tex(sc, l, h).color;
+        if (l.kind == MAT_SHEEN) return V3{l.p[0], l.p[1], l.p[2]};
+        return one;
+    };
+    auto child = [&](const MatD& c) -> V3 {   // a mix's child: a leaf, or a mix of leaves
+        if (c.kind != MAT_MIX) return leaf(c);
+        return (1.0 - c.p[0]) * leaf(sc.mats[c.color_tex]) + c.p[0] * leaf(sc.mats[c.rough_tex]);
+    };
+    if (m.kind != MAT_MIX) return leaf(m);
+    return (1.0 - m.p[0]) * child(sc.mats[m.color_tex]) + m.p[0] * child(sc.mats[m.rough_tex]);
+}
+// One thread per pixel walks samples [spp_begin, spp_end) in order; sample s's camera ray is k_init's for (pixel, s) — same Rng,
+// same generate_ray — and its closest hit is the one K2 finds (tree-independent). Adds (overwrite: stores) the
+// sums aov[8 * pixel + k]: albedo rgb, shading normal xyz, depth, hits. No atomics: every pixel has one writer.
+__global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, uint32_t overwrite) {
+    __shared__ uint32_t stack[TRAVERSAL_STACK * BLOCK];
+    const uint32_t n_pixels = cam.width * cam.height;
+    for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < n_pixels; p += gridDim.x * BLOCK) {
+        uint32_t row, col;
+        divmod_u31(p, cam.width, row, col);
+        V3 alb{0.0, 0.0, 0.0}, nrm{0.0, 0.0, 0.0};
+        double depth = 0.0, hits = 0.0;
+        for (uint32_t s = spp_begin; s < spp_end; ++s) {
+            Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), p, s, 0u};
+            const RayD r = generate_ray(cam, row, col, rng);
+            const Closest c = closest_hit(sc, r, 1e-3, &stack[threadIdx.x]);
+            HitD h;
+            if (c.id != HIT_NONE && reconstruct_hit(sc, r, c.id, 1e-3, h)) {
+                alb = alb + aov_albedo(sc, sc.mats[h.mat], h);
+                nrm = nrm + h.sn;
+                depth = depth + h.dist;
+                hits = hits + 1.0;
+            } else {
+                alb = alb + V3{1.0, 1.0, 1.0};   // a miss: environment radiance is not reflected light
+            }
+        }
+        double* o = aov + 8 * (size_t)p;
+        const double v[8] = {alb.x, alb.y, alb.z, nrm.x, nrm.y, nrm.z, depth, hits};
+        for (int k = 0; k < 8; ++k) o[k] = overwrite ? v[k] : o[k] + v[k];
+    }
+}
+
 // Elementwise probes of the device arithmetic (sqrt/div/fma-free mul-add, libm calls, RNG)
 // so that tests can compare them with the host bit for bit / ulp for ulp.
 __global__ void k_math_probe(int which, const double* in, uint32_t n, double* out) {
@@ -1838,6 +1886,10 @@ void launch_quantise(const double* accum, uint32_t n, double scale, uint8_t* rgb
 }
 void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out, hipStream_t st) {
     hipLaunchKernelGGL(k_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, sc, rays, n, out);
+}
+void launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
+                hipStream_t st) {
+    hipLaunchKernelGGL(k_aov, grid_for(cam.width * cam.height, max_blocks), dim3(BLOCK), 0, st, sc, cam, seed, spp_begin, spp_end, aov, overwrite ? 1u : 0u);
 }
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st) {
     hipLaunchKernelGGL(k_math_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, which, in, n, out);

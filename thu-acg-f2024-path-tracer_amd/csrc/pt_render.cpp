@@ -151,24 +151,11 @@ struct EventTimer {   // per-launch HIP-event timing, drained at the polling syn
 };
 }  // namespace
 
-// The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
-// pixels) / n_list: a pixel-list render (PoolD::list; d_list sorted by tiled index, n_list > 0), or null: the whole frame — then the
-// path below is exactly pt_render's.
-static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum,
-                       const pt_render_opts* opts_in, pt_render_stats* stats, const uint32_t* d_list, const uint32_t* h_list, uint32_t n_list) {
-    if (!s || !s->built) return set_error("pt_render: world not built (call pt_world_build)");
-    if (!accum) return set_error("pt_render: null accumulator");
-    if (spp_end < spp_begin) return set_error("pt_render: spp_end < spp_begin");
-    pt_render_opts opts;
-    memset(&opts, 0, sizeof opts);
-    if (opts_in) opts = *opts_in;
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    hipStream_t st = opts.stream ? (hipStream_t)opts.stream : ctx->stream;
-
+// The device camera of a render (CamD) from the public one: Camera::init's derived vectors plus what K1 and K3 read per sample.
+// pt_render's core and pt_render_aovs both start here, so an AOV sample traces the same camera ray as the render sample.
+static int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
     CamDerived cd;
     if (derive_camera(cam, cd) != 0) return -1;
-    CamD dc;
     memset(&dc, 0, sizeof dc);
     st3(dc.center, cd.center); st3(dc.pixel00, cd.pixel00); st3(dc.pixel_du, cd.pixel_du); st3(dc.pixel_dv, cd.pixel_dv);
     double lens_radius = std::tan((cam->defocus_angle / 2.0) * (PI / 180.0)) * cam->focal_length;   // camera.rs:159
@@ -201,6 +188,26 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         if (cam->env_tex < 0 || (size_t)cam->env_tex >= s->tex.size() || (s->tex[cam->env_tex].d.kind != TEX_IMAGE && s->tex[cam->env_tex].d.kind != TEX_IMAGE_F32))
             return set_error("pt_render: env_tex must be an image texture of this scene");
     }
+    return 0;
+}
+
+// The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
+// pixels) / n_list: a pixel-list render (PoolD::list; d_list sorted by tiled index, n_list > 0), or null: the whole frame — then the
+// path below is exactly pt_render's.
+static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum,
+                       const pt_render_opts* opts_in, pt_render_stats* stats, const uint32_t* d_list, const uint32_t* h_list, uint32_t n_list) {
+    if (!s || !s->built) return set_error("pt_render: world not built (call pt_world_build)");
+    if (!accum) return set_error("pt_render: null accumulator");
+    if (spp_end < spp_begin) return set_error("pt_render: spp_end < spp_begin");
+    pt_render_opts opts;
+    memset(&opts, 0, sizeof opts);
+    if (opts_in) opts = *opts_in;
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    hipStream_t st = opts.stream ? (hipStream_t)opts.stream : ctx->stream;
+
+    CamD dc;
+    if (make_camd(s, cam, dc) != 0) return -1;
     const uint64_t n_pixels64 = (uint64_t)dc.width * dc.height;
     if (n_pixels64 == 0 || n_pixels64 > 0x7FFFFFFFull) return set_error("pt_render: bad image size");
     const uint32_t n_pixels = (uint32_t)n_pixels64;
@@ -708,6 +715,76 @@ extern "C" int pt_resolve_u8_counts(pt_ctx* ctx, const double* accum, uint32_t n
     if (d_cnt) (void)hipFree(d_cnt);
     if (d_out) (void)hipFree(d_out);
     return ok ? 0 : -1;
+}
+
+extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov,
+                              const pt_render_opts* opts_in) {
+    if (!s || !s->built) return set_error("pt_render_aovs: world not built (call pt_world_build)");
+    if (!aov) return set_error("pt_render_aovs: null aov buffer");
+    if (!cam) return set_error("pt_render_aovs: null camera");
+    if (spp_end < spp_begin) return set_error("pt_render_aovs: spp_end < spp_begin");
+    pt_render_opts opts;
+    memset(&opts, 0, sizeof opts);
+    if (opts_in) opts = *opts_in;
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    hipStream_t st = opts.stream ? (hipStream_t)opts.stream : ctx->stream;
+    CamD dc;
+    if (make_camd(s, cam, dc) != 0) return -1;
+    const uint64_t n_pixels = (uint64_t)dc.width * dc.height;
+    if (n_pixels == 0 || n_pixels > 0x7FFFFFFFull) return set_error("pt_render_aovs: bad image size");
+    const size_t bytes = (size_t)n_pixels * 8 * sizeof(double);
+    struct Mem {
+        double* p = nullptr;
+        ~Mem() { if (p) (void)hipFree(p); }
+    } own;
+    double* d_aov = aov;
+    if (!opts.accum_on_device) {   // a host buffer: its sums travel to the device and back, the kernel adds to them there
+        if (!hip_ok(hipMalloc((void**)&own.p, bytes), "hipMalloc(aov)")) return -1;
+        d_aov = own.p;
+        if (!opts.overwrite && !hip_ok(hipMemcpyAsync(d_aov, aov, bytes, hipMemcpyHostToDevice, st), "hipMemcpy(aov)")) return -1;
+    }
+    launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st);
+    if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
+    if (!opts.accum_on_device && !hip_ok(hipMemcpyAsync(aov, d_aov, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(aov)")) return -1;
+    return hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(aov)") ? 0 : -1;
+}
+
+extern "C" int pt_denoise(pt_ctx* ctx, uint32_t width, uint32_t height, const double* sum_a, uint32_t n_a, const double* sum_b, uint32_t n_b,
+                          const double* aov, uint32_t n_aov, const pt_denoise_opts* opts_in, double* out) {
+    if (!ctx) return set_error("pt_denoise: null context");
+    if (!sum_a || !sum_b || !aov || !out) return set_error("pt_denoise: null buffer");
+    if (width == 0 || height == 0) return set_error("pt_denoise: width and height must be positive");
+    if ((uint64_t)width * height > 0x7FFFFFFFull) return set_error("pt_denoise: image too large");
+    if (n_a == 0 || n_b == 0 || n_aov == 0) return set_error("pt_denoise: n_a, n_b and n_aov must be positive");
+    pt_denoise_opts o{5u, 4.0, 0.1};
+    if (opts_in) o = *opts_in;
+    if (o.iterations > 10) return set_error("pt_denoise: at most 10 iterations");
+    if (!(o.sigma_l > 0.0) || !(o.sigma_z > 0.0)) return set_error("pt_denoise: sigma_l and sigma_z must be positive");
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    const size_t n = (size_t)width * height;
+    // scratch (12 per pixel: two colour + variance buffers and the guides, 32-B records: first), sum_a, sum_b, out (3 each), aov (8)
+    struct Mem {
+        double* p = nullptr;
+        ~Mem() { if (p) (void)hipFree(p); }
+    } mem;
+    if (!hip_ok(hipMalloc((void**)&mem.p, n * 29 * sizeof(double)), "hipMalloc(denoise)")) return -1;
+    double* d_tmp = mem.p;
+    double* d_a = d_tmp + 12 * n;
+    double* d_b = d_a + 3 * n;
+    double* d_out = d_b + 3 * n;
+    double* d_aov = d_out + 3 * n;
+    hipStream_t st = ctx->stream;
+    if (!hip_ok(hipMemcpyAsync(d_a, sum_a, 3 * n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(sum_a)") ||
+        !hip_ok(hipMemcpyAsync(d_b, sum_b, 3 * n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(sum_b)") ||
+        !hip_ok(hipMemcpyAsync(d_aov, aov, 8 * n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(aov)"))
+        return -1;
+    launch_denoise(width, height, d_a, (double)n_a, d_b, (double)n_b, d_aov, (double)n_aov, o.iterations, o.sigma_l, o.sigma_z, d_tmp, d_out, st);
+    if (!hip_ok(hipGetLastError(), "kernel launch") ||
+        !hip_ok(hipMemcpyAsync(out, d_out, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(out)") ||
+        !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(denoise)"))
+        return -1;
+    return 0;
 }
 
 extern "C" int pt_resolve_u8(pt_ctx* ctx, const double* accum, uint32_t n_pixels, uint32_t total_spp, uint8_t* rgb8) {

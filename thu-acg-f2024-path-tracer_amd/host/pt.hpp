@@ -462,6 +462,31 @@ struct Camera {
         std::fprintf(stderr, "adaptive: threshold %g, min spp %u, max spp %u: mean spp %.2f (%llu samples) in %.6f s\n", threshold, min_spp,
                      (uint32_t)samples_per_pixel, (double)st.samples / (double)n, (unsigned long long)st.samples, secs);
     }
+    // not in the reference: render samples [0, s/2) and [s/2, s) into two sums, the first-hit AOVs over [0, min(aov_spp, s)),
+    // denoise (pt_denoise, default options) and save the denoised means; needs samples_per_pixel >= 2
+    void render_denoised(World& world, const std::string& filename, uint32_t aov_spp, uint64_t seed = 1) const {
+        auto start = std::chrono::steady_clock::now();
+        pt_camera c = to_c(&world);
+        const size_t n = image_width * image_height;
+        const uint32_t s = (uint32_t)samples_per_pixel, half = s / 2, n_aov = std::min(aov_spp, s);
+        std::vector<double> sum_a(n * 3, 0.0), sum_b(n * 3, 0.0), aov(n * 8, 0.0), out(n * 3);
+        pt_render_stats sa, sb;
+        if (pt_render(world.scene, &c, seed, 0, half, sum_a.data(), nullptr, &sa) != 0 ||
+            pt_render(world.scene, &c, seed, half, s, sum_b.data(), nullptr, &sb) != 0)
+            panic(std::string("Camera::render_denoised: ") + pt_last_error());
+        if (pt_render_aovs(world.scene, &c, seed, 0, n_aov, aov.data(), nullptr) != 0) panic(std::string("Camera::render_denoised: ") + pt_last_error());
+        pt_ctx* ctx = pt_scene_ctx(world.scene);
+        if (pt_denoise(ctx, (uint32_t)image_width, (uint32_t)image_height, sum_a.data(), half, sum_b.data(), s - half, aov.data(), n_aov, nullptr,
+                       out.data()) != 0)
+            panic(std::string("Camera::render_denoised: ") + pt_last_error());
+        std::vector<uint8_t> rgb(n * 3);
+        if (pt_resolve_u8(ctx, out.data(), (uint32_t)n, 1, rgb.data()) != 0) panic("Camera::render_denoised");
+        if (pt_save_png(filename.c_str(), (uint32_t)image_width, (uint32_t)image_height, rgb.data()) != 0)
+            std::fprintf(stderr, "Failed to save image %s\n", pt_last_error());
+        double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        std::fprintf(stderr, "denoise: %u spp as %u + %u, aov %u spp: %.6f s (render kernel time %.3f s)\n", s, half, s - half, n_aov, secs,
+                     (sa.ms_total + sb.ms_total) * 1e-3);
+    }
 };
 
 inline int ImageTexture::emit(Emitter& e) const {
