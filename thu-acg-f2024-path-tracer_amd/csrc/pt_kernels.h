@@ -10,6 +10,8 @@ void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_
 // wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
 void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
                   hipStream_t st, uint32_t wide_window_min = 16);
+// whether the k_shade variant sorts its windows by class (the shading-order output, PoolD::reorder, needs the sort's positions)
+bool shade_variant_sorts(int variant);
 void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_t st);
 // the frame's end (dynamic mode): live slots beyond new_end move into dead slots below it; holes / movers: scratch lists of `cap` entries, counts: 2 words
 void launch_compact(const PoolD& pool, uint32_t new_end, uint32_t* holes, uint32_t* movers, uint32_t* counts, uint32_t cap, int max_blocks, hipStream_t st);

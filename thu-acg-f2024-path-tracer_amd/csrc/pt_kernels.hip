@@ -57,8 +57,9 @@ PT_DEV RayD load_ray(const PoolD& pool, uint32_t s, uint32_t& sample, uint32_t& 
     tail[1] = d.y;
     return RayD{V3{a.x, a.y, b.x}, V3{b.y, c.x, c.y}, pool.compact ? 0.0 : __hiloint2double((int)d.y, (int)d.x)};
 }
-PT_DEV void store_ray(const PoolD& pool, uint32_t s, const RayD& r, uint32_t sample, uint32_t draw, uint32_t pixel, uint32_t bounce) {
-    d2v* p = reinterpret_cast<d2v*>(&pool.ray[s]);
+// `rays` / `paths`: the pool's record area written — PoolD::ray / path, or k_shade's output area PoolD::ray_out / path_out
+PT_DEV void store_ray(const PoolD& pool, RayRec* rays, uint32_t s, const RayD& r, uint32_t sample, uint32_t draw, uint32_t pixel, uint32_t bounce) {
+    d2v* p = reinterpret_cast<d2v*>(&rays[s]);
     p[0] = d2v{r.o.x, r.o.y};
     p[1] = d2v{r.o.z, r.d.x};
     p[2] = d2v{r.d.y, r.d.z};
@@ -73,8 +74,8 @@ PT_DEV V3 load_path(const PoolD& pool, uint32_t s, uint32_t& pixel, uint32_t& bo
     bounce = b.w;
     return V3{a.x, a.y, __hiloint2double((int)b.y, (int)b.x)};
 }
-PT_DEV void store_path(const PoolD& pool, uint32_t s, V3 thr, uint32_t pixel, uint32_t bounce) {
-    d2v* p = reinterpret_cast<d2v*>(&pool.path[s]);
+PT_DEV void store_path(PathRec* paths, uint32_t s, V3 thr, uint32_t pixel, uint32_t bounce) {
+    d2v* p = reinterpret_cast<d2v*>(&paths[s]);
     p[0] = d2v{thr.x, thr.y};
     *reinterpret_cast<u4v*>(p + 1) = u4v{(uint32_t)__double2loint(thr.z), (uint32_t)__double2hiint(thr.z), pixel, bounce};
 #if PT_PATHREC_BYTES == 64
@@ -349,8 +350,12 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
         bool has_work;
         bool idle = false;
         if (pool.dynamic) {   // initial work items 0 .. n_slots-1 (the host starts the shard counters there)
-            has_work = s < pool.n_slots && (unsigned long long)s < pool.total_work;
-            idle = has_work && !work_item<LIST>(pool, s, pixel, sample, row, col);
+            // experiment (PT_INIT_SHUFFLE): inside every whole 8192-slot granule below n_slots, slot s takes item
+            // granule + (s * init_perm mod 8192) — an odd multiplier permutes the granule, so the same items are handed out
+            uint32_t item = s;
+            if (pool.init_perm != 0u && s < (pool.n_slots & ~8191u)) item = (s & ~8191u) | ((s * pool.init_perm) & 8191u);
+            has_work = s < pool.n_slots && (unsigned long long)item < pool.total_work;
+            idle = has_work && !work_item<LIST>(pool, item, pixel, sample, row, col);
             if (!has_work || idle) { pixel = 0; sample = 0; }
         } else {
             pixel = slot_pixel<LIST>(pool, s);
@@ -361,15 +366,15 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
             pool.rx[s] = 0.0; pool.ry[s] = 0.0; pool.rz[s] = 0.0;
         }
         pool.hit_prim[s] = (CLASS_DEAD << HIT_CLASS_SHIFT) | HIT_ID_MASK;   // overwritten by the first K2 launch
-        if (!pool.compact) store_path(pool, s, V3{1.0, 1.0, 1.0}, pixel, 0u);
+        if (!pool.compact) store_path(pool.path, s, V3{1.0, 1.0, 1.0}, pixel, 0u);
         if (!has_work || idle) {
             pool.bounce[s] = idle ? SLOT_IDLE : SLOT_DEAD;
-            store_ray(pool, s, RayD{}, sample, 0u, pixel, 0u);
+            store_ray(pool, pool.ray, s, RayD{}, sample, 0u, pixel, 0u);
             continue;
         }
         Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, 0u};
         RayD r = generate_ray(cam, row, col, rng);
-        store_ray(pool, s, r, sample, rng.draw, pixel, 0u);
+        store_ray(pool, pool.ray, s, r, sample, rng.draw, pixel, 0u);
         pool.bounce[s] = 0;
     }
 }
@@ -1003,9 +1008,10 @@ struct SlotIn {
 // straight from the pool (first group of a window, static mode, unsorted K3). `enable` = false: bystander lane.
 // `hw_known`: the caller has the slot's result word already (k_shade's sort keeps the window's words in LDS).
 // Whether a slot is alive, idle or dead is in the class of K2's result word (K2 read PoolD::bounce, the slots' STATE array,
-// coalesced); the bounce NUMBER of a live path travels in its PathRec. k_shade therefore never reads the state array and writes
-// it only when a slot changes state (parked, regenerated from idle, dead) — it used to gather 4 bytes per lane from it and
-// scatter 4 bytes per lane back on every bounce of every path.
+// coalesced); the bounce NUMBER of a live path travels in its PathRec. k_shade therefore never reads the state array and, in
+// place, writes it only when a slot changes state (parked, regenerated from idle, dead) — it used to gather 4 bytes per lane from
+// it and scatter 4 bytes per lane back on every bounce of every path. (In shading order, PoolD::reorder, every position gets its
+// state: 4 bytes per lane at consecutive addresses.)
 PT_DEV uint32_t state_of_class(uint32_t hw) {
     const uint32_t cls = hw >> HIT_CLASS_SHIFT;
     return cls == CLASS_IDLE ? SLOT_IDLE : cls == CLASS_DEAD ? SLOT_DEAD : 0u;
@@ -1103,7 +1109,9 @@ struct NoPrefetch {
 template <bool LIGHTS, bool LIST, class Prefetch>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
-PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, uint32_t s, int lane, const SlotIn& in,
+// o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
+// bounce_out at o_base + lane, its position in the window's sorted order; without reorder they are written in place, at `s`.
+PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, uint32_t s, uint32_t o_base, int lane, const SlotIn& in,
                        uint32_t& shard, uint32_t& n_done, uint32_t& n_died, Prefetch&& prefetch, unsigned long long pre_mask = 0ull,
                        unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u) {
     PT_STAMP(1);
@@ -1275,7 +1283,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     const unsigned long long prof_regen = __ballot(alive && finished && more && !next_idle && !(parked && pool.dynamic));
 #endif
     PT_STAMP(3);
-    // ---- phase D: regeneration in place, stores -----------------------------------------------------------------------------
+    // ---- phase D: regeneration, stores (in place, or at the slot's sorted position in the output area: PoolD::reorder) ---------
     if (alive && finished) {
         if (!was_idle) ++n_done;
         if (parked && pool.dynamic) {
@@ -1297,11 +1305,14 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         }
     }
     if (alive) {
+        // in place the state array changes only with the slot's state; in shading order every position gets its state written
+        const bool reorder = !LIST && pool.reorder != 0u;
+        const uint32_t o = reorder ? o_base + (uint32_t)lane : s;
         const uint32_t state_new = bounce < SLOT_IDLE ? 0u : bounce, state_old = was_idle ? SLOT_IDLE : 0u;
-        if (state_new != state_old) pool.bounce[s] = state_new;       // the state array changes only with the slot's state
+        if (reorder || state_new != state_old) pool.bounce_out[o] = state_new;
         if (bounce < SLOT_IDLE) {
-            store_ray(pool, s, ray, sample, rng.draw, pixel, bounce);
-            if (!pool.compact || bounce != 0u) store_path(pool, s, thr, pixel, bounce);
+            store_ray(pool, pool.ray_out, o, ray, sample, rng.draw, pixel, bounce);
+            if (!pool.compact || bounce != 0u) store_path(pool.path_out, o, thr, pixel, bounce);
             if (!pool.dynamic) { pool.rx[s] = rad.x; pool.ry[s] = rad.y; pool.rz[s] = rad.z; }
         }
     }
@@ -1362,7 +1373,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, lane, in, shard, n_done, n_died, NoPrefetch{});
+            shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{});
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -1469,6 +1480,8 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
             }
             __syncthreads();
             const uint32_t n_live = (uint32_t)WIN - s_hist[K_DEAD];
+            if (!LIST && pool.reorder)                               // shading order: the dead slots sort last, their positions are the window's tail
+                for (uint32_t q = n_live + threadIdx.x; q < (uint32_t)WIN; q += KB) pool.bounce_out[wbase + q] = SLOT_DEAD;
             PT_STAMP(w1);
             // groups are taken from the END of the sorted order: the expensive classes (principled, glass) sort
             // last, and starting with them keeps the four waves level when the window runs out (the cheap
@@ -1537,7 +1550,8 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, lane, in, shard, n_done, n_died, prefetch, pre_mask, pre_base, pre_shard);
+                shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done, n_died, prefetch,
+                                         pre_mask, pre_base, pre_shard);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;
                 pre_shard = pre_shard_next;
@@ -1853,6 +1867,9 @@ static shade_fn pick_shade(int variant, bool lights, bool list = false) {   // v
     case 52: return lights ? k_shade<true, 2, true, 256, 16> : k_shade<true, 2, false, 256, 16>;   // A/B: 256 threads over 4096-slot windows (window size vs block size)
     default: return lights ? k_shade<false, 2, true> : k_shade<false, 2, false>;
     }
+}
+bool shade_variant_sorts(int variant) {
+    return variant == 12 || variant == 13 || variant == 22 || variant == 32 || variant == 42 || variant == 52;   // pick_shade's SORT = true cases
 }
 static int shade_threads(int variant) { return variant == 22 || variant == 32 || variant == 42 ? 512 : BLOCK; }
 static int shade_window(int variant) { return variant == 32 ? 8192 : variant == 22 || variant == 52 ? 4096 : SORT_WINDOW; }

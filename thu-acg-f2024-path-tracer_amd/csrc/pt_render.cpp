@@ -259,10 +259,21 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     }
     if (n_slots64 > 0x7FFFFFC0ull) return set_error("pt_render: image too large for the path pool");
     const uint32_t n_slots = (uint32_t)n_slots64;
-    // one allocation: the two record arrays (RayRec, PathRec), the static mode's f64 arrays, the two u32 state arrays
+    int shade_variant = 42;   // k_shade<sort, min waves/SIMD>: sort*10 + waves (12 = windowed material sort with 256 threads / 2048-slot windows, 2 = plain;
+                              // [r3] 22 = the same with 512 threads / 4096-slot windows: K3 -2 % on scenes 6, 3 and 5; 32 = 8192-slot windows: another
+                              // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
+                              // windows per block launched, else 22)
+    if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
+    if (list && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list forms of k_shade (launch_shade)
+    // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
+    // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
+    // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
+    const bool ordered = dynamic && !list && shade_variant_sorts(shade_variant) && !exp_env("PT_POOL_IN_PLACE");
+    // one allocation: the two record arrays (RayRec, PathRec), the static mode's f64 arrays, the two u32 state arrays (+ the output area)
     const size_t n_al = ((size_t)n_slots + 8191) & ~(size_t)8191;   // whole windows: 2048 slots (k_extend2, k_shade) / 4096 (k_shade with 512 threads)
     const size_t n_f64 = dynamic ? 0 : 6;   // the per-slot sample sums and radiances exist in the static mode only (the dynamic mode adds into the frame)
-    const size_t bytes = n_al * (sizeof(RayRec) + sizeof(PathRec) + n_f64 * sizeof(double) + 2 * sizeof(uint32_t));
+    const size_t bytes = n_al * (sizeof(RayRec) + sizeof(PathRec) + n_f64 * sizeof(double) + 2 * sizeof(uint32_t)) +
+                         (ordered ? n_al * (sizeof(RayRec) + sizeof(PathRec) + sizeof(uint32_t)) : 0);
     if (bytes > s->pool_bytes) {
         if (s->pool_mem) (void)hipFree(s->pool_mem);
         s->pool_mem = nullptr;
@@ -286,6 +297,16 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         uint32_t* u = (uint32_t*)d;
         uint32_t** u32s[2] = {&pool.hit_prim, &pool.bounce};
         for (auto p : u32s) { *p = u; u += n_al; }
+        pool.ray_out = pool.ray;
+        pool.path_out = pool.path;
+        pool.bounce_out = pool.bounce;
+        if (ordered) {   // (u is 64-B aligned: n_al is a multiple of 8192)
+            m = (char*)u;
+            pool.ray_out = (RayRec*)m; m += n_al * sizeof(RayRec);
+            pool.path_out = (PathRec*)m; m += n_al * sizeof(PathRec);
+            pool.bounce_out = (uint32_t*)m;
+            pool.reorder = 1u;
+        }
     }
     pool.n_slots = n_slots;
     pool.n_alloc = (uint32_t)n_al;
@@ -304,6 +325,9 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     pool.list = d_list;
     pool.n_list = list ? n_list : 0u;
     pool.list_store = list && opts.accum_on_device && opts.overwrite ? 1u : 0u;   // (a host accumulator is written below, pixel by pixel)
+    // experiment (PT_INIT_SHUFFLE=1): k_init hands the initial items out permuted inside each 8192-slot granule (an odd multiplier), so
+    // that the first K2 launch traces incoherent chunks — the measure of what tile-ordered chunks are worth
+    if (dynamic && !list && exp_env("PT_INIT_SHUFFLE")) pool.init_perm = 0x9E3779B1u;
 
     // accumulator on the device (freed on every return path when it is ours)
     double* d_accum = accum;
@@ -323,12 +347,6 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     // persistent grids: resident blocks per CU x CUs
     int mult = 1;
     if (const char* e = exp_env("PT_GRID_MULT")) mult = std::max(1, atoi(e));
-    int shade_variant = 42;   // k_shade<sort, min waves/SIMD>: sort*10 + waves (12 = windowed material sort with 256 threads / 2048-slot windows, 2 = plain;
-                              // [r3] 22 = the same with 512 threads / 4096-slot windows: K3 -2 % on scenes 6, 3 and 5; 32 = 8192-slot windows: another
-                              // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
-                              // windows per block launched, else 22)
-    if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
-    if (list && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list forms of k_shade (launch_shade)
     uint32_t wide_window_min = 16;
     if (const char* e = exp_env("PT_WIDE_WINDOW_MIN")) wide_window_min = (uint32_t)std::max(1, atoi(e));
     // K2 variant: two-phase kernel when there are meshes to defer and its LDS stack covers the scene's BVHs, else the
@@ -418,6 +436,11 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             timer.begin(1, st);
             launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min);
             timer.end(st);
+            if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
+                std::swap(pool.ray, pool.ray_out);
+                std::swap(pool.path, pool.path_out);
+                std::swap(pool.bounce, pool.bounce_out);
+            }
             ++iterations;
         }
         if (!hip_ok(hipMemcpyAsync(s->h_counters, s->d_counters, sizeof(CountersD), hipMemcpyDeviceToHost, st), "hipMemcpy(counters)")) return -1;

@@ -240,6 +240,17 @@ struct PoolD {
     // list_store: k_resolve / k_detile store the listed pixels' sums instead of adding them (device accumulator + overwrite).
     const uint32_t* list;
     uint32_t n_list, list_store;
+    // Shading-order output (dynamic mode, sorted whole-frame k_shade; PoolD::reorder): k_shade reads a window's records where they
+    // are and writes every surviving path, its regenerated camera ray or its parked slot to ray_out / path_out / bounce_out at the
+    // window's base + the lane's position in the window's SORTED order (64 * group + lane), and the state of every other position
+    // of the window as SLOT_DEAD. The host swaps the two areas after each k_shade launch, so K2 and the next K3 read what K3 wrote:
+    // a K2 chunk of 64 consecutive slots is one K3 group — a tile's camera rays in pixel order, or 64 paths of one material class.
+    // reorder = 0 (static mode, pixel lists, PT_POOL_IN_PLACE): the out pointers equal ray / path / bounce and K3 writes in place.
+    RayRec* ray_out;
+    PathRec* path_out;
+    uint32_t* bounce_out;
+    uint32_t reorder;
+    uint32_t init_perm;                           // experiment (PT_INIT_SHUFFLE): k_init gives slot s the item pi(s) inside each 8192-slot granule, 0 = identity
 };
 
 // The work counter of the dynamic mode is SHARDED: one word saturates at ~88 dequeues/us on this
