@@ -84,6 +84,39 @@ int pt_tex_image_rgb8(pt_scene*, uint32_t w, uint32_t h, const uint8_t* rgb);   
 int pt_tex_image_rgbf32(pt_scene*, uint32_t w, uint32_t h, const float* rgb);
 int pt_scene_set_float_hdr(pt_scene*, int on);
 int pt_scene_float_hdr(pt_scene*);
+/* Environment importance sampling (no counterpart in the reference). Opt-in, a setting of the scene: f = the
+ * mixture weight p_env, 0 <= f < 1 and finite (else -1); the default 0 is off. It is IN EFFECT for a render when f > 0, the
+ * camera's environment is a map (env_is_map) and that map's weight Z (below) is finite and > 0. When it is not in effect every
+ * render is the estimator of camera.rs:177-226 bit for bit; pt_render_aovs never uses it.
+ *
+ * Distribution, over the W x H texels of the environment texture (texel (i, j) = the one sample_environment reads: row j covers
+ * theta in [j pi/H, (j+1) pi/H), column i covers phi in [-pi + 2 pi i/W, -pi + 2 pi (i+1)/W)):
+ *   lum_ij = max(0, 0.2126 r + 0.7152 g + 0.0722 b) of the texel value as tex_image returns it (RGB8 * (1/255), or f32 widened;
+ *            NaN -> 0), summed left to right;  c_j = cos(j pi / H) (the argument formed as (j * pi) / H);
+ *   w_ij = (lum_ij * (c_j - c_{j+1})) * ((2 pi) / W);
+ *   row j: P_j[0] = 0, P_j[i+1] = P_j[i] + w_ij for i = 0 .. W-1 in order, R_j = P_j[W];
+ *   rows:  Q[0] = 0, Q[j+1] = Q[j] + R_j for j = 0 .. H-1 in order, Z = Q[H];
+ *   env_pdf(d) = lum(texel(d)) / Z per steradian.
+ * Sampling, draws u1 then u2 in [0, 1): x = u1 * Z (if x >= Z: the largest double below Z); j = the smallest row with x < Q[j+1];
+ *   t1 = (x - Q[j]) / (Q[j+1] - Q[j]); cos_t = c_j - t1 * (c_j - c_{j+1}); y = u2 * R_j (same rule against R_j); i = the smallest
+ *   column with y < P_j[i+1]; t2 = (y - P_j[i]) / (P_j[i+1] - P_j[i]); phi = -pi + ((2 pi) * (i + t2)) / W;
+ *   sin_t = sqrt(max(0, 1 - cos_t^2)); d = (sin_t cos(phi), cos_t, sin_t sin(phi)); its pdf = lum_ij / Z. Zero-weight rows and
+ *   texels are never chosen.
+ * Estimator, at every surface bounce after Russian roulette whose material is in the env set E: one selector draw r;
+ *   p_env = f, p_light = lights ? (1 - f) / 2 : 0, p_bsdf = 1 - p_light - p_env; r < p_light: lights.sample, r < p_light + p_env:
+ *   an env sample (two more draws), else mat.sample. q_env(d) = env_pdf(d) if d lies on the positive side of the material's local
+ *   frame (z > 0 after make_local_frame's rotation), else 0; an env direction with q_env = 0 ends the path.
+ *   pdf = p_bsdf * s_b + p_light * light_pdf + p_env * q_env(d), throughput *= eval * k / pdf, where s_b is the BSDF sampler's
+ *   density and k = (today's density / today's pdf) at d: diffuse: s_b = its pdf, k = 1; metal (its sampler draws GGX visible
+ *   normals with alpha = roughness^2 while its pdf uses alpha = roughness): s_b = G1_s(v) D_s(h) / (4 v.z) with alpha_s =
+ *   roughness^2 for l.z > 0 (0 below), k = (p0_bsdf s_b + p0_light light_pdf) / (p0_bsdf bsdf_pdf + p0_light light_pdf) with
+ *   today's weights p0 (0.5 / 0.5 with lights, else 1 / 0). So the expectation is today's wherever light_pdf is the light
+ *   sampler's density. A bounce whose pdf is 0 (or metal's today-pdf is 0), or whose new throughput is exactly (0, 0, 0), ends
+ *   the path.
+ *   E = diffuse, and metal with roughness >= 0.05 seen from the front of its frame (v.z > 0). Every other hit (glass, lights,
+ *   principled, sheen, clearcoat, mixes, near-mirror metal) bounces exactly as today. */
+int pt_scene_set_env_sampling(pt_scene*, double f);
+double pt_scene_env_sampling(pt_scene*);
 /* ---- materials: src/bsdf/, src/material.rs ---------------------------------------------- */
 int pt_mat_diffuse(pt_scene*, int color_tex, int normal_map_tex);       /* DiffuseBRDF::{new,from_rgb,from_textures} diffuse.rs:21-47; -1 = no map */
 int pt_mat_metal(pt_scene*, int color_tex, int rough_tex);              /* MetalBRDF::new metal.rs:23-35 */
@@ -255,6 +288,10 @@ int pt_intersect(pt_scene*, const double* rays, uint32_t n, double* out);
 /* elementwise device arithmetic: which = 0 sqrt(a) 1 a/b 2 a*b+a 3 sin 4 cos 5 acos 6 atan2(a,b)
  * 7 pow(a,b) 8 log2 9 rng uniform(seed=a, pixel=b, sample=7, draw=i); in = n pairs (a,b) */
 int pt_math_probe(pt_ctx*, int which, const double* in, uint32_t n, double* out);
+/* the device functions of environment sampling that k_shade calls (pt_scene_set_env_sampling's rule): which = 0: in = n pairs
+ * (u1, u2), out = n x {dir.xyz, pdf}; which = 1: in = n directions xyz, out = n env_pdf values. Builds the scene's tables if
+ * needed (the world must be built). -1 when the camera's environment is not a map or its Z is 0. */
+int pt_env_probe(pt_scene*, const pt_camera*, int which, const double* in, uint32_t n, double* out);
 
 #ifdef __cplusplus
 }

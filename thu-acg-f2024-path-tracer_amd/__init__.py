@@ -111,6 +111,7 @@ ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
     "pt_scene_create", "pt_scene_destroy", "pt_scene_ctx",
     "pt_tex_solid_rgb", "pt_tex_solid_f", "pt_tex_checker", "pt_tex_image_rgb8", "pt_tex_image_rgbf32", "pt_scene_set_float_hdr", "pt_scene_float_hdr",
+    "pt_scene_set_env_sampling", "pt_scene_env_sampling", "pt_env_probe",
     "pt_mat_diffuse", "pt_mat_metal", "pt_mat_glass", "pt_mat_principled", "pt_mat_light", "pt_mat_mix", "pt_mat_sheen", "pt_mat_clearcoat",
     "pt_sphere", "pt_quad", "pt_cuboid", "pt_mesh", "pt_instance",
     "pt_world_add_object", "pt_world_add_light", "pt_world_build", "pt_world_prim_count",
@@ -149,6 +150,9 @@ def _load():
     lib.pt_tex_image_rgbf32.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.pt_scene_set_float_hdr.argtypes = [C.c_void_p, C.c_int]
     lib.pt_scene_float_hdr.argtypes = [C.c_void_p]
+    lib.pt_scene_set_env_sampling.argtypes = [C.c_void_p, C.c_double]
+    lib.pt_scene_env_sampling.argtypes = [C.c_void_p]
+    lib.pt_scene_env_sampling.restype = C.c_double
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -182,6 +186,7 @@ def _load():
     lib.pt_resolve_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.pt_intersect.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.pt_math_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.pt_env_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.pt_load_obj.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)),
                                 C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32)]
     lib.pt_load_hdr_rgb8.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -381,6 +386,13 @@ class Scene:
         """Scene scripts (build_scene) load Radiance .hdr files as f32 textures from now on."""
         return _check(lib.pt_scene_set_float_hdr(self.handle, 1 if on else 0), "set_float_hdr")
 
+    def set_env_sampling(self, f: float):
+        """Environment importance sampling with mixture weight f, 0 <= f < 1 (0 = off, the default)."""
+        return _check(lib.pt_scene_set_env_sampling(self.handle, float(f)), "set_env_sampling")
+
+    def env_sampling(self) -> float:
+        return lib.pt_scene_env_sampling(self.handle)
+
     def mat_diffuse(self, color_tex, normal_map_tex=-1): return _check(lib.pt_mat_diffuse(self.handle, color_tex, normal_map_tex), "mat_diffuse")
     def mat_metal(self, color_tex, rough_tex): return _check(lib.pt_mat_metal(self.handle, color_tex, rough_tex), "mat_metal")
     def mat_glass(self, color_tex, rough_tex, aniso, ior): return _check(lib.pt_mat_glass(self.handle, color_tex, rough_tex, aniso, ior), "mat_glass")
@@ -523,6 +535,14 @@ class Scene:
         rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 7)
         out = np.empty((len(rays), 15), dtype=np.float64)
         _check(lib.pt_intersect(self.handle, rays.ctypes.data, len(rays), out.ctypes.data), "pt_intersect")
+        return out
+
+    def env_probe(self, cam: Camera, which: int, arr: np.ndarray) -> np.ndarray:
+        """The device functions of environment sampling for cam's environment map. which 0: arr = (n, 2) draws (u1, u2) ->
+        (n, 4) {dir.xyz, pdf}; which 1: arr = (n, 3) directions -> (n,) env_pdf."""
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape(-1, 2 if which == 0 else 3)
+        out = np.empty((len(arr), 4) if which == 0 else (len(arr),), dtype=np.float64)
+        _check(lib.pt_env_probe(self.handle, C.byref(cam), which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_env_probe")
         return out
 
 

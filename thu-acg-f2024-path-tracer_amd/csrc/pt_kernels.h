@@ -8,8 +8,14 @@ namespace pt {
 void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st);
 void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st);
 // wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
+// env: the environment-sampling tables or null. Non-null launches k_shade's ENV forms (the default variant's two shapes:
+// any other variant is mapped to 42, as for pixel lists).
 void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
-                  hipStream_t st, uint32_t wide_window_min = 16);
+                  hipStream_t st, uint32_t wide_window_min = 16, const EnvTabD* env = nullptr);
+// pt_envmap.hip: the environment-sampling tables of image texture `tex` (device TexD values; col: H * (W + 1), row: H + 1 doubles),
+// and the probe behind pt_env_probe (which 0: (u1, u2) pairs -> {dir.xyz, pdf}; 1: directions -> env_pdf)
+void launch_env_tables(const SceneD& sc, const TexD& tex, double* col, double* row, hipStream_t st);
+void launch_env_probe(const SceneD& sc, const TexD& tex, const EnvTabD& e, int which, const double* in, uint32_t n, double* out, hipStream_t st);
 // whether the k_shade variant sorts its windows by class (the shading-order output, PoolD::reorder, needs the sort's positions)
 bool shade_variant_sorts(int variant);
 void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_t st);
@@ -35,5 +41,5 @@ void launch_math_probe(int which, const double* in, uint32_t n, double* out, hip
 // K2 variant code (`code` of launch_extend / `variant` of kernel_occupancy_blocks): -1 = batch kernel (-2 asks
 // kernel_occupancy_blocks for its flat-top-level instantiation), -(stack*10 + blocks) = two-phase kernel
 // k_extend2<stack, blocks> for stack in {16, 20, 24}.
-int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false);   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
+int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false, bool env = false);   // env: k_shade's ENV form   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
 }  // namespace pt

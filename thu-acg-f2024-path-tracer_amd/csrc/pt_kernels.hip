@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "pt_dev_geom.h"
+#include "pt_envmap.h"
 #include "pt_kernels.h"
 
 namespace pt {
@@ -1106,14 +1107,18 @@ struct NoPrefetch {
 // younger load is waited for — hence the phase discipline (tex values fetched up front, pt_dev_bsdf.h fetch_tex).
 // LIGHTS: the scene has a lights list (World::lights non-empty). The instantiation without compiles lights.sample / lights.pdf, the
 // selector draw and the later prefetch point out: p_light = 0 there (camera.rs:199-200), so no result changes.
-template <bool LIGHTS, bool LIST, class Prefetch>
+// ENV: environment importance sampling is in effect (the rule in pt_amd.h; `env` holds the tables). At a hit in the env
+// set E the bounce draws its direction from the one-sample mixture {lights, environment, BSDF}; everywhere else it is the bounce above
+// bit for bit. The tables are read in B1 (the env sample; env_pdf's texel gather for a BSDF or light direction), so the ENV forms
+// prefetch at P1b like the LIGHTS forms and B2 stays arithmetic.
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
 // bounce_out at o_base + lane, its position in the window's sorted order; without reorder they are written in place, at `s`.
 PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, uint32_t s, uint32_t o_base, int lane, const SlotIn& in,
                        uint32_t& shard, uint32_t& n_done, uint32_t& n_died, Prefetch&& prefetch, unsigned long long pre_mask = 0ull,
-                       unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u) {
+                       unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u, const EnvTabD* env = nullptr) {
     PT_STAMP(1);
     uint32_t bounce = in.bounce;
     const bool alive = bounce != SLOT_DEAD;
@@ -1183,13 +1188,15 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     PT_STAMP(a2);
     const bool any_hit = __ballot(is_hit) != 0ull;
     bool fetched = false;                                              // wave-uniform
-    if (any_hit && !LIGHTS) { prefetch(); fetched = true; }            // P1
+    if (any_hit && !LIGHTS && !ENV) { prefetch(); fetched = true; }    // P1
     // ---- phase B1: roulette and the next direction ------------------------------------------------------------------------
     const double p_light = LIGHTS ? 0.5 : 0.0;                         // :199-200 (the host picks the instantiation by World::lights)
     const double p_bsdf = 1.0 - p_light;
     const V3 wo = -ray.d;
     V3 dir{};
     bool have_dir = false;
+    bool env_lane = false, env_dir = false;                            // ENV: the bounce takes the mixture / its direction is an env sample
+    double q_env = 0.0;                                                // ENV: q_env(dir) (pt_amd.h)
     if (is_hit) {
         if (bounce > 5) {                                              // russian roulette :190-196
             double p = clampd(luminance(thr), 0.01, 1.0);
@@ -1200,7 +1207,28 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             // :201 draws the selector even when there are no lights (p_light = 0: never below it) — then only the counter moves
             double rsel = 1.0;
             bool ok = true;
-            if constexpr (LIGHTS) {
+            if constexpr (ENV) env_lane = env_in_set(*mp, tv, lf);
+            if (ENV && env_lane) {
+                // one selector draw: lights below p_light, the environment below p_light + p_env, the BSDF above (pt_amd.h)
+                const double p_env = env->f, p_l = LIGHTS ? (1.0 - p_env) / 2.0 : 0.0;
+                rsel = rng_f64(rng);
+                if (LIGHTS && rsel < p_l) {
+                    dir = lights_sample(sc, hit.point, ray.time, rng);
+                } else if (rsel < p_l + p_env) {
+                    uint64_t a, b;
+                    rng_u64x2(rng, a, b);
+                    dir = env_sample(sc, ldu(&sc.tex[cam.env_tex]), *env, u64_to_unit(a), u64_to_unit(b), q_env);
+                    env_dir = true;
+                } else {
+                    ok = mat_sample(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir);
+                }
+                if (ok) {
+                    // support: q_env is zero below the material's local frame; an env direction there ends the path
+                    const bool above = to_local(lf.f, dir).z > 0.0;
+                    if (!env_dir) q_env = above ? env_pdf(sc, ldu(&sc.tex[cam.env_tex]), *env, dir) : 0.0;
+                    else if (!above) ok = false;
+                }
+            } else if constexpr (LIGHTS) {
                 rsel = rng_f64(rng);
                 if (rsel < p_light) dir = lights_sample(sc, hit.point, ray.time, rng);
                 else ok = mat_sample(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir);
@@ -1223,11 +1251,34 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         if constexpr (LIGHTS) light_pdf = lights_pdf(sc, hit.point, dir, ray.time);
         double pdf = p_bsdf * bsdf_pdf + p_light * light_pdf;
         V3 attenuation = brdf / pdf;
-        double e = 1e-3 * signum(dot(dir, hit.gn));                    // :217-222
-        ray = make_ray(hit.point + e * hit.gn, dir, ray.time);
-        thr = thr * attenuation;
-        ++bounce;
-        if (bounce >= cam.max_depth) finished = parked = true;         // loop bound :177
+        bool env_end = false;
+        if constexpr (ENV) {
+            if (env_lane) {
+                // the mixture's density: p_bsdf * s_b + p_light * light_pdf + p_env * q_env, with s_b the BSDF sampler's density. Diffuse:
+                // s_b = bsdf_pdf. Metal (Q2): s_b = metal_sample_density, and the integrand keeps today's weight (today's density / pdf),
+                // so that the expectation is today's (pt_amd.h).
+                const double pe = env->f, pl = LIGHTS ? (1.0 - pe) / 2.0 : 0.0, pb = 1.0 - pl - pe;
+                double s_b = bsdf_pdf, w = 1.0;
+                if (mp->kind == MAT_METAL) {
+                    s_b = metal_sample_density(lf.v, to_local(lf.f, dir), tv.rough);
+                    w = (p_bsdf * s_b + p_light * light_pdf) / pdf;
+                    env_end = !(pdf > 0.0);
+                }
+                const double pm = pb * s_b + pl * light_pdf + pe * q_env;
+                attenuation = brdf * w / pm;
+                const V3 t = thr * attenuation;
+                env_end = env_end || !(pm > 0.0) || (t.x == 0.0 && t.y == 0.0 && t.z == 0.0);
+            }
+        }
+        if (env_end) {
+            finished = parked = true;                                  // (ENV: a zero-density or zero-throughput bounce ends the path)
+        } else {
+            double e = 1e-3 * signum(dot(dir, hit.gn));                // :217-222
+            ray = make_ray(hit.point + e * hit.gn, dir, ray.time);
+            thr = thr * attenuation;
+            ++bounce;
+            if (bounce >= cam.max_depth) finished = parked = true;     // loop bound :177
+        }
     }
 #ifdef PT_STAMPS
     const unsigned long long prof_live = __ballot(live), prof_hit = __ballot(is_hit), prof_dir = __ballot(have_dir);
@@ -1357,8 +1408,9 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // waves of the block (work stealing), and every slot's records are moved whole by its own lane.
 // KB: threads per block (256, or [r3] 512 with a 4096-slot window: the sort's barriers and the window's end are paid once per twice
 // as many slots and eight waves level a window's end better than four; one block per CU then).
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false>
-__global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed) {
+// ENV: environment importance sampling (shade_slot; `env` is read by these forms only)
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false>
+__global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
     const int lane = (int)(threadIdx.x & 63u);
 #ifdef PT_STAMPS
@@ -1373,7 +1425,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{});
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -1540,7 +1592,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
                         // the next group's lanes that are certain to end there (ray left the scene / idle slot): their work items now.
                         // Scenes without a lights list only: K3 -1.2 % (scene 6), -0.7 % (scene 5); the lights instantiation, three
                         // registers from the limit, got 0.9 % SLOWER with it (closed scenes have next to no leaving rays anyway).
-                        if constexpr (!LIGHTS) {
+                        if constexpr (!LIGHTS && !ENV) {
                         const uint32_t cn = s_hw[sn - wbase] >> HIT_CLASS_SHIFT;
                         pre_mask_next = __ballot(en && (cn == CLASS_MISS || cn == CLASS_IDLE));
                         pre_shard_next = shard;
@@ -1550,8 +1602,8 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done, n_died, prefetch,
-                                         pre_mask, pre_base, pre_shard);
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                                                             n_died, prefetch, pre_mask, pre_base, pre_shard, &env);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;
                 pre_shard = pre_shard_next;
@@ -1852,8 +1904,15 @@ void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_
     }
     else hipLaunchKernelGGL(pick_extend_batch(sc.tlas_flat, sc.flat_pairs), grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, sc, pool, cnt);
 }
-typedef void (*shade_fn)(SceneD, CamD, PoolD, CountersD*, uint64_t);
-static shade_fn pick_shade(int variant, bool lights, bool list = false) {   // variant = sort*10 + min waves per SIMD; 22 = sorted, 512 threads / 4096-slot windows
+typedef void (*shade_fn)(SceneD, CamD, PoolD, CountersD*, uint64_t, EnvTabD);
+static shade_fn pick_shade(int variant, bool lights, bool list = false, bool env = false) {   // variant = sort*10 + min waves per SIMD; 22 = sorted, 512 threads / 4096-slot windows
+    if (env) {   // environment sampling: the default's two forms only (launch_shade maps every other variant to 42), whole frame or pixel list
+        if (variant == 22)
+            return list ? (lights ? k_shade<true, 2, true, 512, 8, true, true> : k_shade<true, 2, false, 512, 8, true, true>)
+                        : (lights ? k_shade<true, 2, true, 512, 8, false, true> : k_shade<true, 2, false, 512, 8, false, true>);
+        return list ? (lights ? k_shade<true, 2, true, 512, 16, true, true> : k_shade<true, 2, false, 512, 16, true, true>)
+                    : (lights ? k_shade<true, 2, true, 512, 16, false, true> : k_shade<true, 2, false, 512, 16, false, true>);
+    }
     if (list)   // pixel-list renders: the default's two forms only (launch_shade maps every other variant to 42)
         return variant == 22 ? (lights ? k_shade<true, 2, true, 512, 8, true> : k_shade<true, 2, false, 512, 8, true>)
                              : (lights ? k_shade<true, 2, true, 512, 16, true> : k_shade<true, 2, false, 512, 16, true>);
@@ -1874,16 +1933,17 @@ bool shade_variant_sorts(int variant) {
 static int shade_threads(int variant) { return variant == 22 || variant == 32 || variant == 42 ? 512 : BLOCK; }
 static int shade_window(int variant) { return variant == 32 ? 8192 : variant == 22 || variant == 52 ? 4096 : SORT_WINDOW; }
 void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
-                  hipStream_t st, uint32_t wide_window_min) {
+                  hipStream_t st, uint32_t wide_window_min, const EnvTabD* env) {
     // 42: 8192-slot windows while the pool holds at least PT_WIDE_WINDOW_MIN of them per block launched, 4096-slot windows below
     // (a thinner pool — smaller frames, one rank's share, the frame's end after compaction — levels its end better with more, smaller windows)
-    if (pool.list && variant != 22 && variant != 32) variant = 42;
+    if ((pool.list || env) && variant != 22 && variant != 32) variant = 42;
     if (variant == 42) variant = pool.n_alloc / 8192u >= (uint32_t)max_blocks * (wide_window_min ? wide_window_min : 1u) ? 32 : 22;
     const int kb = shade_threads(variant);
     uint32_t blocks = variant >= 10 ? pool.n_alloc / (uint32_t)shade_window(variant) : (pool.n_alloc + (uint32_t)kb - 1u) / (uint32_t)kb;   // one block per window / chunk
     if (blocks > (uint32_t)max_blocks) blocks = (uint32_t)max_blocks;
     if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(pick_shade(variant, sc.n_lights != 0u, pool.list != nullptr), dim3(blocks), dim3((uint32_t)kb), 0, st, sc, cam, pool, cnt, seed);
+    const EnvTabD e = env ? *env : EnvTabD{};
+    hipLaunchKernelGGL(pick_shade(variant, sc.n_lights != 0u, pool.list != nullptr, env != nullptr), dim3(blocks), dim3((uint32_t)kb), 0, st, sc, cam, pool, cnt, seed, e);
 }
 void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_t st) {
     if (pool.list) hipLaunchKernelGGL(k_resolve<true>, grid_for(pool.n_list, max_blocks), dim3(BLOCK), 0, st, pool, accum);
@@ -1911,9 +1971,9 @@ void launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_b
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st) {
     hipLaunchKernelGGL(k_math_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, which, in, n, out);
 }
-int kernel_occupancy_blocks(int which, int variant, bool lights, bool list) {
+int kernel_occupancy_blocks(int which, int variant, bool lights, bool list, bool env) {
     int nb = 0;
-    const void* f = which == 0 ? (variant <= -100 ? (const void*)pick_extend2(-variant) : (const void*)pick_extend_batch(variant <= -2, variant == -3)) : (const void*)pick_shade(variant, lights, list);
+    const void* f = which == 0 ? (variant <= -100 ? (const void*)pick_extend2(-variant) : (const void*)pick_extend_batch(variant <= -2, variant == -3)) : (const void*)pick_shade(variant, lights, list, env);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, which == 1 ? shade_threads(variant) : variant <= -100 ? extend2_threads(-variant) : BLOCK, 0) != hipSuccess || nb < 1) nb = 1;
     return nb;
 }

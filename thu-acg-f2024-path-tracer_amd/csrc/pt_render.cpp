@@ -191,6 +191,46 @@ static int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
     return 0;
 }
 
+// Environment importance sampling: the tables of the camera's environment map, built once per (scene, texture) at the
+// first call that needs them — from the device atlas, by pt_envmap.hip — and kept until pt_scene_destroy (one texture's at a time).
+// `e` gets the tables and Z; e.z > 0 (finite) is the map's half of the in-effect rule. The caller has checked dc.env_is_map.
+static int env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e) {
+    memset(&e, 0, sizeof e);
+    if (s->env_tab_tex != dc.env_tex) {
+        TexD T;
+        if (!hip_ok(hipMemcpyAsync(&T, s->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, st), "hipMemcpy(env texture)") ||
+            !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(env texture)"))
+            return -1;
+        if (s->env_tab) (void)hipFree(s->env_tab);
+        s->env_tab = nullptr;
+        s->env_tab_bytes = 0;
+        s->env_tab_tex = -1;
+        s->env_tab_w = T.w;
+        s->env_tab_h = T.h;
+        s->env_tab_z = 0.0;
+        if (T.w != 0 && T.h != 0) {
+            const size_t n_col = (size_t)T.h * (T.w + 1), bytes = (n_col + T.h + 1) * sizeof(double);
+            if (!hip_ok(hipMalloc((void**)&s->env_tab, bytes), "hipMalloc(env tables)")) return -1;
+            s->env_tab_bytes = bytes;
+            launch_env_tables(s->dev.view, T, s->env_tab, s->env_tab + n_col, st);
+            if (!hip_ok(hipGetLastError(), "env tables") ||
+                !hip_ok(hipMemcpyAsync(&s->env_tab_z, s->env_tab + n_col + T.h, sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(env Z)") ||
+                !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(env tables)"))
+                return -1;
+        }
+        s->env_tab_tex = dc.env_tex;
+    }
+    e.w = s->env_tab_w;
+    e.h = s->env_tab_h;
+    e.f = s->env_f;
+    if (s->env_tab && std::isfinite(s->env_tab_z) && s->env_tab_z > 0.0) {
+        e.col = s->env_tab;
+        e.row = s->env_tab + (size_t)e.h * (e.w + 1);
+        e.z = s->env_tab_z;
+    }
+    return 0;
+}
+
 // The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
 // pixels) / n_list: a pixel-list render (PoolD::list; d_list sorted by tiled index, n_list > 0), or null: the whole frame — then the
 // path below is exactly pt_render's.
@@ -214,6 +254,13 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     const uint32_t spp = spp_end - spp_begin;
     const bool list = d_list != nullptr;
     const uint32_t n_items = list ? n_list : n_pixels;   // pixels rendered
+    // environment sampling is in effect: f > 0, the environment is a map and its weight Z > 0 (pt_amd.h); otherwise no new code runs
+    EnvTabD env{};
+    bool env_on = false;
+    if (s->env_f > 0.0 && dc.env_is_map) {
+        if (env_tables(s, dc, st, env) != 0) return -1;
+        env_on = env.z > 0.0;
+    }
 
     // pool sizing. slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
     // the machine several times over; finished paths pull the next (pixel, sample) from a global
@@ -264,7 +311,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                               // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
-    if (list && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list forms of k_shade (launch_shade)
+    if ((list || env_on) && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list / ENV forms of k_shade (launch_shade)
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
     // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
@@ -374,7 +421,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         if (!strcmp(e, "batch")) extend_code = -1;
         else if (!strcmp(e, "twophase") && extend2_code() != 0) extend_code = -extend2_code();
     }
-    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list);
+    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list, env_on);
     const int grid_extend = ctx->n_cus * blocks_extend * mult, grid_shade = ctx->n_cus * blocks_shade * mult;
 
     pool.accum = d_accum;
@@ -434,7 +481,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             launch_extend(s->dev.view, pool, s->d_counters, grid_extend, extend_code, st);
             timer.end(st);
             timer.begin(1, st);
-            launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min);
+            launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min, env_on ? &env : nullptr);
             timer.end(st);
             if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
                 std::swap(pool.ray, pool.ray_out);
@@ -842,6 +889,36 @@ extern "C" int pt_intersect(pt_scene* s, const double* rays, uint32_t n, double*
              hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     }
     if (d_r) (void)hipFree(d_r);
+    if (d_o) (void)hipFree(d_o);
+    return ok ? 0 : -1;
+}
+
+extern "C" int pt_env_probe(pt_scene* s, const pt_camera* cam, int which, const double* in, uint32_t n, double* out) {
+    if (!s || !s->built) return set_error("pt_env_probe: world not built");
+    if (!cam || (which != 0 && which != 1)) return set_error("pt_env_probe: which must be 0 or 1");
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    CamD dc;
+    if (make_camd(s, cam, dc) != 0) return -1;
+    if (!dc.env_is_map) return set_error("pt_env_probe: the camera's environment is not a map");
+    EnvTabD e;
+    if (env_tables(s, dc, ctx->stream, e) != 0) return -1;
+    if (!(e.z > 0.0)) return set_error("pt_env_probe: the environment map has no weight (Z = 0)");
+    TexD T;
+    if (!hip_ok(hipMemcpyAsync(&T, s->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") ||
+        !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
+        return -1;
+    const size_t n_in = (size_t)n * (which == 0 ? 2 : 3), n_out = (size_t)n * (which == 0 ? 4 : 1);
+    double *d_i = nullptr, *d_o = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double) + 8), "hipMalloc") &&
+              hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double) + 8), "hipMalloc") &&
+              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    if (ok) {
+        launch_env_probe(s->dev.view, T, e, which, d_i, n, d_o, ctx->stream);
+        ok = hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    if (d_i) (void)hipFree(d_i);
     if (d_o) (void)hipFree(d_o);
     return ok ? 0 : -1;
 }

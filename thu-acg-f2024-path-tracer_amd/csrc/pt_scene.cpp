@@ -45,6 +45,7 @@ pt_scene::~pt_scene() {
     if (tile_accum) (void)hipFree(tile_accum);
     if (compact_scratch) (void)hipFree(compact_scratch);
     if (pixel_list) (void)hipFree(pixel_list);
+    if (env_tab) (void)hipFree(env_tab);
     if (d_counters) (void)hipFree(d_counters);
     if (h_counters) (void)hipHostFree(h_counters);
 }
@@ -106,6 +107,13 @@ extern "C" int pt_scene_set_float_hdr(pt_scene* s, int on) {
     return 0;
 }
 extern "C" int pt_scene_float_hdr(pt_scene* s) { return s && s->float_hdr ? 1 : 0; }
+extern "C" int pt_scene_set_env_sampling(pt_scene* s, double f) {
+    if (!s) return set_error("pt_scene_set_env_sampling: null scene");
+    if (!(f >= 0.0 && f < 1.0)) return set_error("pt_scene_set_env_sampling: f must be finite and in [0, 1)");
+    s->env_f = f;
+    return 0;
+}
+extern "C" double pt_scene_env_sampling(pt_scene* s) { return s ? s->env_f : 0.0; }
 extern "C" int pt_register_image(pt_scene* s, const char* name, uint32_t w, uint32_t h, const uint8_t* rgb) {
     int t = pt_tex_image_rgb8(s, w, h, rgb);
     if (t < 0) return -1;

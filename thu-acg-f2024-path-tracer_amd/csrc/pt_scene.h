@@ -82,6 +82,14 @@ struct pt_scene {
     size_t compact_scratch_words = 0;
     uint32_t* pixel_list = nullptr;   // pt_render_pixels: the device pixel list (tiled order), re-used like tile_accum
     size_t pixel_list_words = 0;
+    // environment importance sampling (pt_scene_set_env_sampling): the mixture weight, and the f64 tables of ONE
+    // environment texture, built at the first render that needs them (pt_render.cpp env_tables) and kept until destroy
+    double env_f = 0.0;
+    int env_tab_tex = -1;          // texture the tables below belong to (-1: none built)
+    double* env_tab = nullptr;     // H * (W + 1) row prefix sums, then H + 1 row-total prefix sums (EnvTabD)
+    size_t env_tab_bytes = 0;
+    uint32_t env_tab_w = 0, env_tab_h = 0;
+    double env_tab_z = 0.0;
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned
     ~pt_scene();

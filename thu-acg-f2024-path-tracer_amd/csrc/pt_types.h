@@ -138,6 +138,17 @@ struct CamD {
     uint32_t motionless;     // no moving sphere in the scene: Ray::time is drawn (camera.rs:165) but its value is never used
 };
 
+// Environment importance sampling (pt_scene_set_env_sampling): the f64 tables of the camera's environment map,
+// built by pt_envmap.hip, and the mixture weight. A separate kernel argument of k_shade's ENV forms and of k_env_probe — CamD and
+// SceneD keep their layouts. col: H rows of W + 1 prefix sums of the texel weights w_ij (col[j*(W+1)] = 0, col[j*(W+1)+W] = R_j);
+// row: H + 1 prefix sums of the row totals (row[0] = 0, row[H] = z).
+struct EnvTabD {
+    const double* col;
+    const double* row;
+    double z, f;
+    uint32_t w, h;
+};
+
 struct SceneD {
     const BvhNode* nodes;
     const Entry* entries;

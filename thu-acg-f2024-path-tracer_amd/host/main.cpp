@@ -17,7 +17,7 @@ int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
     long width = -1, spp = -1, min_spp = 16;
-    double adaptive = 0.0;
+    double adaptive = 0.0, env_sampling = 0.0;
     bool use_adaptive = false, use_denoise = false;
     long aov_spp = 16;
     uint64_t seed = 1;
@@ -37,12 +37,16 @@ int main(int argc, char** argv) {
         else if (a == "--assets") assets = next();
         else if (a == "--device") device = atoi(next());
         else if (a == "--float-hdr") float_hdr = true;
+        else if (a == "--env-sampling") {
+            env_sampling = atof(next());
+            if (!(env_sampling >= 0.0 && env_sampling < 1.0)) { std::cerr << "--env-sampling must be in [0, 1)\n"; return 2; }
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n";
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n";
             return 0;
         } else { std::cerr << "unknown argument " << a << "\n"; return 2; }
     }
@@ -61,6 +65,7 @@ int main(int argc, char** argv) {
     try {
         SceneSetup setup = make_scene(scene, w, s, assets, 1);
         setup.world.float_hdr = float_hdr;
+        setup.world.env_sampling = env_sampling;
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();
         std::cerr << "rendering production\n";   // camera.rs:101
