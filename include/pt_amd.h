@@ -117,6 +117,31 @@ int pt_scene_float_hdr(pt_scene*);
  *   principled, sheen, clearcoat, mixes, near-mirror metal) bounces exactly as today. */
 int pt_scene_set_env_sampling(pt_scene*, double f);
 double pt_scene_env_sampling(pt_scene*);
+/* The sampler: where a path's random numbers come from. kind 0 (default) = independent draws, the reference's thread_rng stand-in:
+ * draw d of sample s of pixel p is half of Philox4x32-10(counter = (d >> 1, s, seed_hi, 0), key = (seed_lo, p)); every entry point
+ * is then the code it was before this setting existed, bit for bit. kind 1 = an Owen-scrambled Sobol (0,2)-sequence per pixel and
+ * per pair of draws, padded across pairs by independent keys (hash-based Owen scrambling: Burley 2020, Laine-Karras hash). Any
+ * other kind returns -1 and leaves the setting. In effect for pt_render, pt_render_pixels, pt_render_adaptive, pt_render_multi
+ * and pt_render_aovs (whose camera ray stays the one pt_render traces for (pixel, s)). The sample index is the global one, so
+ * sample ranges, pixel lists, adaptive rounds, the denoiser's halves and multi-GPU shards stay pieces of one sequence — and
+ * renders of DIFFERENT ranges of one seed are stratified against each other, not independent: independent estimates need
+ * different seeds. The rule of kind 1, all arithmetic on uint32 (wrapping):
+ *   rev(x)     = the 32 bits of x in reverse order
+ *   lk(x, k)   : x += k; x ^= x * 0x6c50b47c; x ^= x * 0xb82f1e52; x ^= x * 0xc7afe638; x ^= x * 0x8d22f6e6
+ *   owen(x, k) = rev(lk(rev(x), k))
+ *   sobol0(i)  = rev(i);   sobol1(i) = rev(y), y = i; y ^= (y & 0xAAAAAAAA) >> 1; y ^= (y & 0xCCCCCCCC) >> 2;
+ *                y ^= (y & 0xF0F0F0F0) >> 4; y ^= (y & 0xFF00FF00) >> 8; y ^= (y & 0xFFFF0000) >> 16   (Sobol's second dimension)
+ *   draw d: pair k = d >> 1, component c = d & 1;  K[0..3] = Philox4x32-10(counter = (k, 0, seed_hi, 1), key = (seed_lo, p))
+ *   j = owen(s, K[0]);  x = owen(c == 0 ? sobol0(j) : sobol1(j), K[1 + c]);  value = (uint64(x) << 32) | lk(x, K[3] + c)
+ * The 64-bit value is consumed exactly where the Philox value is (the same conversions to f64, ranges and indices, the same
+ * draws made and not used), at every draw of a path — there is no depth beyond which the sampler falls back to independent
+ * draws. One addition, kind 1 only: a two-value draw (the pixel offsets, the lens offsets, the environment sample, the two
+ * numbers of a BSDF direction or of a point on a quad light) first advances the draw index to the next even one, so that
+ * its two coordinates are the two components of one pair; the draw indices of a Sobol path therefore differ from those of an
+ * independent one. The 2^m points of a pair for samples [a 2^m, (a+1) 2^m) put one point into every elementary interval
+ * 2^-q x 2^-(m-q). */
+int pt_scene_set_sampler(pt_scene*, int kind);
+int pt_scene_sampler(pt_scene*);
 /* ---- materials: src/bsdf/, src/material.rs ---------------------------------------------- */
 int pt_mat_diffuse(pt_scene*, int color_tex, int normal_map_tex);       /* DiffuseBRDF::{new,from_rgb,from_textures} diffuse.rs:21-47; -1 = no map */
 int pt_mat_metal(pt_scene*, int color_tex, int rough_tex);              /* MetalBRDF::new metal.rs:23-35 */
@@ -292,6 +317,11 @@ int pt_math_probe(pt_ctx*, int which, const double* in, uint32_t n, double* out)
  * (u1, u2), out = n x {dir.xyz, pdf}; which = 1: in = n directions xyz, out = n env_pdf values. Builds the scene's tables if
  * needed (the world must be built). -1 when the camera's environment is not a map or its Z is 0. */
 int pt_env_probe(pt_scene*, const pt_camera*, int which, const double* in, uint32_t n, double* out);
+/* the samplers' draw functions as the kernels call them (pt_scene_set_sampler's rule): out[i * n_draws + j] = the 64-bit value of
+ * the single draw draw_begin + j (no two-value alignment) of sample sample_begin + i of `pixel` under `seed`; kind as there
+ * (0: the Philox values). At most 2^28 values a call. */
+int pt_sampler_probe(pt_ctx*, int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin,
+                     uint32_t n_draws, uint64_t* out);
 
 #ifdef __cplusplus
 }

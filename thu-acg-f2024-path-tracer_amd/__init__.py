@@ -112,6 +112,7 @@ ABI_SYMBOLS = [
     "pt_scene_create", "pt_scene_destroy", "pt_scene_ctx",
     "pt_tex_solid_rgb", "pt_tex_solid_f", "pt_tex_checker", "pt_tex_image_rgb8", "pt_tex_image_rgbf32", "pt_scene_set_float_hdr", "pt_scene_float_hdr",
     "pt_scene_set_env_sampling", "pt_scene_env_sampling", "pt_env_probe",
+    "pt_scene_set_sampler", "pt_scene_sampler", "pt_sampler_probe",
     "pt_mat_diffuse", "pt_mat_metal", "pt_mat_glass", "pt_mat_principled", "pt_mat_light", "pt_mat_mix", "pt_mat_sheen", "pt_mat_clearcoat",
     "pt_sphere", "pt_quad", "pt_cuboid", "pt_mesh", "pt_instance",
     "pt_world_add_object", "pt_world_add_light", "pt_world_build", "pt_world_prim_count",
@@ -153,6 +154,10 @@ def _load():
     lib.pt_scene_set_env_sampling.argtypes = [C.c_void_p, C.c_double]
     lib.pt_scene_env_sampling.argtypes = [C.c_void_p]
     lib.pt_scene_env_sampling.restype = C.c_double
+    if hasattr(lib, "pt_scene_set_sampler"):       # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_scene_set_sampler.argtypes = [C.c_void_p, C.c_int]
+        lib.pt_scene_sampler.argtypes = [C.c_void_p]
+        lib.pt_sampler_probe.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -229,6 +234,9 @@ def _load():
 lib = _load()
 
 
+SAMPLERS = {"independent": 0, "sobol": 1}   # pt_scene_set_sampler's kinds
+
+
 def _check(rc, what="pt call"):
     if rc < 0:
         raise PtError(f"{what}: {lib.pt_last_error().decode()}")
@@ -270,6 +278,14 @@ class Context:
         ab = np.ascontiguousarray(ab, dtype=np.float64).reshape(-1, 2)
         out = np.empty(len(ab), dtype=np.float64)
         _check(lib.pt_math_probe(self.handle, which, ab.ctypes.data, len(ab), out.ctypes.data), "pt_math_probe")
+        return out
+
+    def sampler_probe(self, kind, seed: int, pixel: int, sample_begin: int, n_samples: int, draw_begin: int, n_draws: int) -> np.ndarray:
+        """The 64-bit values of single draws [draw_begin, +n_draws) of samples [sample_begin, +n_samples) of a pixel, by the
+        device functions the kernels call; uint64 array of shape (n_samples, n_draws)."""
+        out = np.empty((n_samples, n_draws), dtype=np.uint64)
+        _check(lib.pt_sampler_probe(self.handle, SAMPLERS.get(kind, kind), seed, pixel, sample_begin, n_samples, draw_begin, n_draws, out.ctypes.data),
+               "pt_sampler_probe")
         return out
 
     def resolve_u8(self, accum: np.ndarray, total_spp: int) -> np.ndarray:
@@ -392,6 +408,17 @@ class Scene:
 
     def env_sampling(self) -> float:
         return lib.pt_scene_env_sampling(self.handle)
+
+    def set_sampler(self, kind):
+        """Where the paths' random numbers come from: "independent" (0, the default: the reference's draws) or "sobol" (1: an
+        Owen-scrambled Sobol sequence per pixel; the rule is in include/pt_amd.h)."""
+        kind = SAMPLERS.get(kind, kind)
+        if isinstance(kind, bool) or not isinstance(kind, int):
+            raise PtError(f"set_sampler: unknown sampler {kind!r}")
+        return _check(lib.pt_scene_set_sampler(self.handle, kind), "set_sampler")
+
+    def sampler(self) -> int:
+        return lib.pt_scene_sampler(self.handle)
 
     def mat_diffuse(self, color_tex, normal_map_tex=-1): return _check(lib.pt_mat_diffuse(self.handle, color_tex, normal_map_tex), "mat_diffuse")
     def mat_metal(self, color_tex, rough_tex): return _check(lib.pt_mat_metal(self.handle, color_tex, rough_tex), "mat_metal")

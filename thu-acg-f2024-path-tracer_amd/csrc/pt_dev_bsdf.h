@@ -114,7 +114,8 @@ PT_DEV double gtr1_D(double abs_cos_theta, double alpha_g) {
     double t = 1.0 + (alpha2 - 1.0) * abs_cos_theta * abs_cos_theta;
     return (alpha2 - 1.0) / (D_PI * t * dev_log2(alpha2));
 }
-PT_DEV V3 cosine_sample_hemisphere(Rng& rng, double two_pi_scale) {   // sampling.rs:18-24
+template <class R>
+PT_DEV V3 cosine_sample_hemisphere(R& rng, double two_pi_scale) {   // sampling.rs:18-24
     uint64_t a, b;
     rng_u64x2(rng, a, b);
     double phi = ((double)(a >> 12) * (1.0 / 4503599627370496.0)) * two_pi_scale;
@@ -124,7 +125,8 @@ PT_DEV V3 cosine_sample_hemisphere(Rng& rng, double two_pi_scale) {   // samplin
     const double sn = sc_phi.s, cs = sc_phi.c;
     return V3{r2s * cs, r2s * sn, sqrt(1.0 - r2)};
 }
-PT_DEV V3 ggx_sample_microfacet_normal(V3 v_in, double roughness, Rng& rng) {   // sampling.rs:57-94
+template <class R>
+PT_DEV V3 ggx_sample_microfacet_normal(V3 v_in, double roughness, R& rng) {   // sampling.rs:57-94
     double a2 = roughness * roughness;
     V3 v = normalize(V3{v_in.x * a2, v_in.y * a2, v_in.z});
     V3 t1 = v.z < 0.9999 ? normalize(cross(v, V3{0.0, 0.0, 1.0})) : V3{1.0, 0.0, 0.0};
@@ -143,7 +145,8 @@ PT_DEV V3 ggx_sample_microfacet_normal(V3 v_in, double roughness, Rng& rng) {   
     V3 h = normalize(V3{a2 * n.x, a2 * n.y, fmax(n.z, 0.0)});
     return h.z < 0.0 ? -h : h;
 }
-PT_DEV V3 gtr1_sample_microfacet_normal(double alpha, Rng& rng) {   // sampling.rs:126-142
+template <class R>
+PT_DEV V3 gtr1_sample_microfacet_normal(double alpha, R& rng) {   // sampling.rs:126-142
     uint64_t ua, ub;
     rng_u64x2(rng, ua, ub);
     double e1 = u64_to_unit(ua), e2 = u64_to_unit(ub);
@@ -174,7 +177,8 @@ PT_DEV double glass_factor(double f, double g, double d, V3 v, V3 l, V3 h, doubl
     double term2 = (eta_o * eta_o) / powi2(eta_i * v_dot_h + eta_o * l_dot_h);
     return term1 * term2 * (1.0 - f) * g * d;
 }
-PT_DEV V3 sample_dielectric(V3 v, V3 h, double eta_i, double eta_o, Rng& rng) {   // glass.rs:79-89
+template <class R>
+PT_DEV V3 sample_dielectric(V3 v, V3 h, double eta_i, double eta_o, R& rng) {   // glass.rs:79-89
     double f = fresnel_dielectric(v, h, eta_i, eta_o);
     if (rng_f64(rng) < f) return reflect(-v, h);
     V3 t = refract(-v, h, eta_i / eta_o);
@@ -218,7 +222,8 @@ PT_DEV TexVals fetch_tex(const SceneD& sc, const MatD& m, const HitD& h) {
 
 // ---- BxDFMaterial::sample (bsdf/mod.rs:23) ----------------------------------------------
 // wo = -ray.direction. Returns false where the reference returns None.
-PT_DEV bool mat_sample(const SceneD& sc, const MatD& mat, const HitD& h, V3 wo, Rng& rng, double two_pi_scale, const TexVals& tv, const LocalFrame& lf, V3& dir) {
+template <class R>
+PT_DEV bool mat_sample(const SceneD& sc, const MatD& mat, const HitD& h, V3 wo, R& rng, double two_pi_scale, const TexVals& tv, const LocalFrame& lf, V3& dir) {
     const MatD* leaf = &mat;
     double rough = tv.rough;
     const bool own = mat.kind == MAT_MIX;   // a mix's child builds its own frame; everything else uses the bounce's (make_local_frame)

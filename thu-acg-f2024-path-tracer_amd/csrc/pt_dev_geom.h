@@ -175,7 +175,8 @@ PT_DEV bool reconstruct_hit(const SceneD& sc, const RayD& world_ray, uint32_t gi
 
 // ---- lights list: Hittable::sample / pdf for every kind of object (list.rs:78-96, quad.rs:80-98,
 // sphere.rs:110-135, mesh.rs:122-141, cuboid.rs:78-84, instance.rs:64-75) ---------------------------
-PT_DEV V3 sample_quad_dir(const QuadD& q, V3 origin, Rng& rng) {                  // quad.rs:80-86
+template <class R>
+PT_DEV V3 sample_quad_dir(const QuadD& q, V3 origin, R& rng) {                  // quad.rs:80-86
     uint64_t ua, ub;
     rng_u64x2(rng, ua, ub);                                                        // two consecutive draws: one Philox block when they share it
     double a = u64_to_unit(ua), b = u64_to_unit(ub);
@@ -195,8 +196,8 @@ PT_DEV double pdf_quad(const SceneD& sc, const QuadD& q, uint32_t mat, V3 origin
 // ONE: the lights list has a single entry (the Cornell box, scene 7): the index draw still happens (list.rs:82 draws it), but the
 // light is the same for every lane, so its entry, transform chain and quad / sphere record arrive by scalar loads instead of four
 // DEPENDENT vector gathers (lights[i] -> entries -> prims -> quads, ~700 cycles each in k_shade).
-template <bool ONE>
-PT_DEV V3 lights_sample_impl(const SceneD& sc, V3 origin_w, double time, Rng& rng) {
+template <bool ONE, class R>
+PT_DEV V3 lights_sample_impl(const SceneD& sc, V3 origin_w, double time, R& rng) {
     uint32_t i = rng_index(rng, sc.n_lights);
     Entry e;
     if constexpr (ONE) e = ldu(&sc.entries[ldu(&sc.lights[0])]); else e = sc.entries[sc.lights[i]];
@@ -252,7 +253,8 @@ PT_DEV V3 lights_sample_impl(const SceneD& sc, V3 origin_w, double time, Rng& rn
     }
     return dir;
 }
-PT_DEV V3 lights_sample(const SceneD& sc, V3 origin_w, double time, Rng& rng) {
+template <class R>
+PT_DEV V3 lights_sample(const SceneD& sc, V3 origin_w, double time, R& rng) {
     if (sc.n_lights == 1u) return lights_sample_impl<true>(sc, origin_w, time, rng);
     return lights_sample_impl<false>(sc, origin_w, time, rng);
 }
@@ -332,7 +334,8 @@ PT_DEV double lights_pdf(const SceneD& sc, V3 origin_w, V3 direction_w, double t
 }
 
 // ---- camera.rs:133-168 -----------------------------------------------------------------
-PT_DEV void random_offsets(Rng& rng, double& ox, double& oy) {
+template <class R>
+PT_DEV void random_offsets(R& rng, double& ox, double& oy) {
     uint64_t a, b;
     rng_u64x2(rng, a, b);
     double radius = sqrt(u64_to_unit(a));
@@ -342,7 +345,8 @@ PT_DEV void random_offsets(Rng& rng, double& ox, double& oy) {
     ox = radius * cs;
     oy = radius * sn;
 }
-PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, Rng& rng) {
+template <class R>
+PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, R& rng) {
     double bx, by;
     random_offsets(rng, bx, by);
     bx = bx * cam.blur_strength;
@@ -350,7 +354,7 @@ PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, Rng& rng) 
     V3 sample_location = ld3(cam.pixel00) + (ld3(cam.pixel_dv) * ((double)row + bx)) + (ld3(cam.pixel_du) * ((double)col + by));
     V3 origin = ld3(cam.center);
     if (cam.lens_zero) {
-        rng.draw += 2;   // the two lens draws are made all the same (camera.rs:160); their products with a zero radius add nothing
+        rng_skip2(rng);   // the two lens draws are made all the same (camera.rs:160); their products with a zero radius add nothing
     } else {
         double px, py;
         random_offsets(rng, px, py);

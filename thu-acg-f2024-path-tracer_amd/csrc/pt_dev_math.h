@@ -156,7 +156,7 @@ struct PhiloxOut {
 #else
 #define PT_PHILOX_CALL __device__ __forceinline__
 #endif
-PT_PHILOX_CALL PhiloxOut philox_block(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+PT_DEV PhiloxOut philox_rounds(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
     const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -166,6 +166,9 @@ PT_PHILOX_CALL PhiloxOut philox_block(uint32_t c0, uint32_t c1, uint32_t c2, uin
         k0 += W0; k1 += W1;
     }
     return PhiloxOut{c0, c1, c2, c3};
+}
+PT_PHILOX_CALL PhiloxOut philox_block(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+    return philox_rounds(c0, c1, c2, c3, k0, k1);
 }
 PT_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
     const PhiloxOut o = philox_block(c0, c1, c2, c3, k0, k1);
@@ -192,11 +195,65 @@ PT_DEV void rng_u64x2(Rng& r, uint64_t& a, uint64_t& b) {
     }
 }
 PT_DEV double u64_to_unit(uint64_t v) { return (double)(v >> 11) * (1.0 / 9007199254740992.0); }
-PT_DEV double rng_f64(Rng& r) { return u64_to_unit(rng_u64(r)); }                  // rand Standard f64
-PT_DEV double rng_range_inclusive(Rng& r, double scale) {                          // gen_range(0.0..=hi)
+
+// ---- Owen-scrambled Sobol sampler (opt-in: pt_scene_set_sampler, the rule in pt_amd.h) ----
+// RngQ has Rng's fields and its own draw functions; every consumer below and in pt_dev_geom.h / pt_dev_bsdf.h is a template on the
+// generator type, picked at compile time by the kernels' QMC parameter, so the independent sampler's instantiations hold no Sobol code.
+// It is a type of its own, not derived from Rng: a consumer that still took `Rng&` would not compile instead of drawing Philox values.
+struct RngQ {
+    uint32_t seed_lo, seed_hi, pixel, sample, draw;
+};
+PT_DEV uint32_t lk_hash(uint32_t x, uint32_t k) {   // Laine-Karras: a scramble of the bits ABOVE each bit, i.e. nested uniform on the reversed word
+    x += k;
+    x ^= x * 0x6c50b47cu;
+    x ^= x * 0xb82f1e52u;
+    x ^= x * 0xc7afe638u;
+    x ^= x * 0x8d22f6e6u;
+    return x;
+}
+// Both values of pair k of (pixel, sample): one Philox block of keys (counter word 3 = 1: disjoint from the independent sampler's
+// blocks), the shuffled index j, the two Sobol coordinates and their filler words. The bit reversals of owen() and of the two
+// generator matrices telescope: owen(sobol0(j), K) = rev(lk(j, K)), owen(sobol1(j), K) = rev(lk(y, K)) with y = j under t -> t+1
+// (the second matrix is Pascal's triangle mod 2) in five steps. No loop, no table; a real function like philox_block, so k_shade
+// holds it once. The Philox rounds are inlined here (philox_block has no other caller in a QMC kernel).
+struct SobolPair {
+    uint64_t a, b;
+};
+PT_PHILOX_CALL SobolPair sobol_pair(uint32_t seed_lo, uint32_t seed_hi, uint32_t pixel, uint32_t sample, uint32_t k) {
+    const PhiloxOut key = philox_rounds(k, 0u, seed_hi, 1u, seed_lo, pixel);
+    const uint32_t j = __brev(lk_hash(__brev(sample), key.x));
+    uint32_t y = j;
+    y ^= (y & 0xAAAAAAAAu) >> 1;
+    y ^= (y & 0xCCCCCCCCu) >> 2;
+    y ^= (y & 0xF0F0F0F0u) >> 4;
+    y ^= (y & 0xFF00FF00u) >> 8;
+    y ^= (y & 0xFFFF0000u) >> 16;
+    const uint32_t x0 = __brev(lk_hash(j, key.y)), x1 = __brev(lk_hash(y, key.z));
+    return SobolPair{((uint64_t)x0 << 32) | lk_hash(x0, key.w), ((uint64_t)x1 << 32) | lk_hash(x1, key.w + 1u)};
+}
+PT_DEV uint64_t rng_u64(RngQ& r) {
+    const SobolPair p = sobol_pair(r.seed_lo, r.seed_hi, r.pixel, r.sample, r.draw >> 1);
+    const uint64_t v = (r.draw & 1u) ? p.b : p.a;
+    ++r.draw;
+    return v;
+}
+// a two-value draw starts at the next even index: both coordinates come from one (0,2) pair (pt_amd.h)
+PT_DEV void rng_u64x2(RngQ& r, uint64_t& a, uint64_t& b) {
+    r.draw = (r.draw + 1u) & ~1u;
+    const SobolPair p = sobol_pair(r.seed_lo, r.seed_hi, r.pixel, r.sample, r.draw >> 1);
+    a = p.a;
+    b = p.b;
+    r.draw += 2;
+}
+// the two-value draw that is made but not used (generate_ray's lens pair on a pinhole camera): the same index arithmetic
+PT_DEV void rng_skip2(Rng& r) { r.draw += 2; }
+PT_DEV void rng_skip2(RngQ& r) { r.draw = ((r.draw + 1u) & ~1u) + 2u; }
+
+template <class R> PT_DEV double rng_f64(R& r) { return u64_to_unit(rng_u64(r)); }                  // rand Standard f64
+template <class R> PT_DEV double rng_range_inclusive(R& r, double scale) {                          // gen_range(0.0..=hi)
     return ((double)(rng_u64(r) >> 12) * (1.0 / 4503599627370496.0)) * scale;
 }
-PT_DEV uint32_t rng_index(Rng& r, uint32_t n) {                                    // gen_range(0..n) usize
+template <class R> PT_DEV uint32_t rng_index(R& r, uint32_t n) {                                    // gen_range(0..n) usize
     uint64_t range = n;
     uint64_t zone = (range << __clzll((long long)range)) - 1;
     for (int it = 0; it < 64; ++it) {

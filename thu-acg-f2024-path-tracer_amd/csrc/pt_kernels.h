@@ -5,13 +5,23 @@
 #include "pt_types.h"
 
 namespace pt {
-void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st);
+// qmc (launch_init, launch_shade, launch_aov, kernel_occupancy_blocks): the Sobol sampler's forms (pt_scene_set_sampler). They live in
+// pt_kernels_qmc.hip — pt_kernels.hip compiled a second time for those forms alone — and cover the default k_shade variant's two shapes:
+// launch_shade maps any other variant to 42, as for pixel lists and environment sampling.
+void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc = false);
+void launch_init_qmc(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st);
+const void* pick_shade_qmc(int variant /* 22 or 32 */, bool lights, bool list, bool env);
+void launch_aov_qmc(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
+                    hipStream_t st);
+// pt_sampler_probe: the 64-bit values of single draws, by the draw functions the kernels call (kind 0: Rng, 1: RngQ); out: device
+void launch_sampler_probe(int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin, uint32_t n_draws, uint64_t* out,
+                          hipStream_t st);
 void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st);
 // wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
 // env: the environment-sampling tables or null. Non-null launches k_shade's ENV forms (the default variant's two shapes:
 // any other variant is mapped to 42, as for pixel lists).
 void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
-                  hipStream_t st, uint32_t wide_window_min = 16, const EnvTabD* env = nullptr);
+                  hipStream_t st, uint32_t wide_window_min = 16, const EnvTabD* env = nullptr, bool qmc = false);
 // pt_envmap.hip: the environment-sampling tables of image texture `tex` (device TexD values; col: H * (W + 1), row: H + 1 doubles),
 // and the probe behind pt_env_probe (which 0: (u1, u2) pairs -> {dir.xyz, pdf}; 1: directions -> env_pdf)
 void launch_env_tables(const SceneD& sc, const TexD& tex, double* col, double* row, hipStream_t st);
@@ -33,7 +43,7 @@ void launch_quantise(const double* accum, uint32_t n, double scale, uint8_t* rgb
 void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out, hipStream_t st);
 // pt_render_aovs: first-hit feature sums of samples [spp_begin, spp_end) of every pixel (aov: device, 8 doubles per pixel)
 void launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
-                hipStream_t st);
+                hipStream_t st, bool qmc = false);
 // pt_denoise.hip: the a-trous denoiser (see there). Device buffers; tmp: 12 doubles per pixel of scratch
 void launch_denoise(uint32_t width, uint32_t height, const double* sum_a, double n_a, const double* sum_b, double n_b, const double* aov, double n_aov,
                     uint32_t iterations, double sigma_l, double sigma_z, double* tmp, double* out, hipStream_t st);
@@ -41,5 +51,5 @@ void launch_math_probe(int which, const double* in, uint32_t n, double* out, hip
 // K2 variant code (`code` of launch_extend / `variant` of kernel_occupancy_blocks): -1 = batch kernel (-2 asks
 // kernel_occupancy_blocks for its flat-top-level instantiation), -(stack*10 + blocks) = two-phase kernel
 // k_extend2<stack, blocks> for stack in {16, 20, 24}.
-int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false, bool env = false);   // env: k_shade's ENV form   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
+int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false, bool env = false, bool qmc = false);   // qmc: k_shade's Sobol form   // env: k_shade's ENV form   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
 }  // namespace pt

@@ -344,7 +344,8 @@ PT_DEV unsigned long long shard_item(unsigned long long c, uint32_t shard) {
 
 // ---------------------------------------------------------------------------------------
 // LIST: pixel-list render (PoolD::list)
-template <bool LIST = false>
+// QMC: the Sobol sampler (pt_scene_set_sampler; RngQ in pt_dev_math.h) — forms of their own, compiled in pt_kernels_qmc.hip
+template <bool LIST = false, bool QMC = false>
 __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t seed) {
     for (uint32_t s = blockIdx.x * BLOCK + threadIdx.x; s < pool.n_alloc; s += gridDim.x * BLOCK) {
         uint32_t pixel, sample, row = 0, col = 0;
@@ -373,7 +374,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
             store_ray(pool, pool.ray, s, RayD{}, sample, 0u, pixel, 0u);
             continue;
         }
-        Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, 0u};
+        std::conditional_t<QMC, RngQ, Rng> rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, 0u};
         RayD r = generate_ray(cam, row, col, rng);
         store_ray(pool, pool.ray, s, r, sample, rng.draw, pixel, 0u);
         pool.bounce[s] = 0;
@@ -1111,7 +1112,8 @@ struct NoPrefetch {
 // set E the bounce draws its direction from the one-sample mixture {lights, environment, BSDF}; everywhere else it is the bounce above
 // bit for bit. The tables are read in B1 (the env sample; env_pdf's texel gather for a BSDF or light direction), so the ENV forms
 // prefetch at P1b like the LIGHTS forms and B2 stays arithmetic.
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false>
+// QMC: the path's draws come from the Sobol sampler (RngQ); nothing else differs.
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
@@ -1133,7 +1135,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     uint32_t pixel = in.pixel, sample = in.sample;
     RayD ray = in.ray;
     V3 thr = in.thr, rad{};
-    Rng rng{};
+    typedef std::conditional_t<QMC, RngQ, Rng> RngT;
+    RngT rng{};
 #ifdef PT_STAMPS
     uint32_t prof_class = was_idle ? CLASS_IDLE : CLASS_DEAD;
     if (live) prof_class = in.hw >> HIT_CLASS_SHIFT;
@@ -1167,7 +1170,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             pixel = slot_pixel<LIST>(pool, s);
             rad = V3{pool.rx[s], pool.ry[s], pool.rz[s]};
         }
-        rng = Rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, in.draw};
+        rng = RngT{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, in.draw};
         const uint32_t gid = in.hw & HIT_ID_MASK;
         const bool surface = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS && reconstruct_hit(sc, ray, gid, 1e-3, hit);
         PT_STAMP_SET(a1);
@@ -1342,7 +1345,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         } else if (more && next_idle) {
             bounce = SLOT_IDLE;
         } else if (more) {
-            rng = Rng{(uint32_t)seed, (uint32_t)(seed >> 32), next_pixel, next_sample, 0u};
+            rng = RngT{(uint32_t)seed, (uint32_t)(seed >> 32), next_pixel, next_sample, 0u};
             if (!pool.dynamic) divmod_u31(next_pixel, cam.width, next_row, next_col);
             ray = generate_ray(cam, next_row, next_col, rng);
             thr = V3{1.0, 1.0, 1.0};
@@ -1409,7 +1412,8 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // KB: threads per block (256, or [r3] 512 with a 4096-slot window: the sort's barriers and the window's end are paid once per twice
 // as many slots and eight waves level a window's end better than four; one block per CU then).
 // ENV: environment importance sampling (shade_slot; `env` is read by these forms only)
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false>
+// QMC: the Sobol sampler (shade_slot)
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
     const int lane = (int)(threadIdx.x & 63u);
@@ -1425,7 +1429,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -1602,7 +1606,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;
@@ -1693,6 +1697,7 @@ __global__ __launch_bounds__(BLOCK) void k_detile(PoolD pool, double* accum) {
 // [0, L) only. k_compact_scan lists both kinds (one atomic per wave and list, any order); k_compact_move copies mover i's two
 // records and its state into hole i and marks the old slot dead. Which slot a path sits in decides nothing (the RNG is keyed by
 // pixel and sample, the frame accumulator by pixel): no result changes.
+#ifndef PT_QMC_TU   // (pt_kernels_qmc.hip compiles this file's QMC forms only)
 __global__ __launch_bounds__(BLOCK) void k_compact_scan(PoolD pool, uint32_t new_end, uint32_t* holes, uint32_t* movers, uint32_t* counts /* [0] holes, [1] movers */,
                                                         uint32_t cap) {
     // [r3] A block takes 4096 slots at a time (n_alloc is a multiple of 8192), keeps their sixteen states per thread in registers,
@@ -1789,6 +1794,8 @@ __global__ __launch_bounds__(BLOCK) void k_probe(SceneD sc, const double* rays /
     }
 }
 
+#endif   // PT_QMC_TU
+
 // First-hit feature buffers (pt_render_aovs; no counterpart in the reference). The colour the first bounce multiplies by:
 // the colour texture of diffuse / metal / principled, sheen's base colour, (1, 1, 1) for glass (Q4: its base colour reaches
 // no radiance), clearcoat and lights; a mix weights its children as mix.rs's pdf / eval do, down the MIX_MAX_DEPTH levels.
@@ -1809,7 +1816,8 @@ PT_DEV V3 aov_albedo(const SceneD& sc, const MatD& m, const HitD& h) {
 // One thread per pixel walks samples [spp_begin, spp_end) in order; sample s's camera ray is k_init's for (pixel, s) — same Rng,
 // same generate_ray — and its closest hit is the one K2 finds (tree-independent). Adds (overwrite: stores) the
 // sums aov[8 * pixel + k]: albedo rgb, shading normal xyz, depth, hits. No atomics: every pixel has one writer.
-__global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, uint32_t overwrite) {
+template <bool QMC>
+PT_DEV void aov_pixels(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, uint32_t overwrite) {
     __shared__ uint32_t stack[TRAVERSAL_STACK * BLOCK];
     const uint32_t n_pixels = cam.width * cam.height;
     for (uint32_t p = blockIdx.x * BLOCK + threadIdx.x; p < n_pixels; p += gridDim.x * BLOCK) {
@@ -1818,7 +1826,7 @@ __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t see
         V3 alb{0.0, 0.0, 0.0}, nrm{0.0, 0.0, 0.0};
         double depth = 0.0, hits = 0.0;
         for (uint32_t s = spp_begin; s < spp_end; ++s) {
-            Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), p, s, 0u};
+            std::conditional_t<QMC, RngQ, Rng> rng{(uint32_t)seed, (uint32_t)(seed >> 32), p, s, 0u};
             const RayD r = generate_ray(cam, row, col, rng);
             const Closest c = closest_hit(sc, r, 1e-3, &stack[threadIdx.x]);
             HitD h;
@@ -1835,6 +1843,61 @@ __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t see
         const double v[8] = {alb.x, alb.y, alb.z, nrm.x, nrm.y, nrm.z, depth, hits};
         for (int k = 0; k < 8; ++k) o[k] = overwrite ? v[k] : o[k] + v[k];
     }
+}
+
+static inline dim3 grid_for(uint32_t n, int max_blocks) {
+    uint32_t b = (n + BLOCK - 1) / BLOCK;
+    if (b > (uint32_t)max_blocks) b = (uint32_t)max_blocks;
+    if (b == 0) b = 1;
+    return dim3(b);
+}
+
+#ifdef PT_QMC_TU
+// ------------------------------------------------------------------ the Sobol sampler's kernels and launchers (pt_kernels_qmc.hip)
+__global__ __launch_bounds__(BLOCK) void k_aov_qmc(SceneD sc, CamD cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, uint32_t overwrite) {
+    aov_pixels<true>(sc, cam, seed, spp_begin, spp_end, aov, overwrite);
+}
+// pt_sampler_probe: out[i * n_draws + j] = the single draw (no two-value alignment) sample_begin + i, draw_begin + j of `pixel` — the
+// draw functions K1 / K3 call
+template <class R>
+__global__ __launch_bounds__(BLOCK) void k_sampler_probe(uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin, uint32_t n_draws,
+                                                         unsigned long long* out) {
+    const unsigned long long n = (unsigned long long)n_samples * n_draws;
+    for (unsigned long long i = blockIdx.x * (unsigned long long)BLOCK + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * BLOCK) {
+        R g{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample_begin + (uint32_t)(i / n_draws), draw_begin + (uint32_t)(i % n_draws)};
+        out[i] = rng_u64(g);
+    }
+}
+void launch_init_qmc(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st) {
+    if (pool.list) hipLaunchKernelGGL((k_init<true, true>), grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
+    else hipLaunchKernelGGL((k_init<false, true>), grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
+}
+// the default variant's two shapes (22: 4096-slot windows, 32: 8192-slot windows), LIGHTS x LIST x ENV
+typedef void (*shade_fn)(SceneD, CamD, PoolD, CountersD*, uint64_t, EnvTabD);
+template <int PER> static shade_fn pick_shade_qmc_per(bool lights, bool list, bool env) {
+    if (env)
+        return list ? (lights ? k_shade<true, 2, true, 512, PER, true, true, true> : k_shade<true, 2, false, 512, PER, true, true, true>)
+                    : (lights ? k_shade<true, 2, true, 512, PER, false, true, true> : k_shade<true, 2, false, 512, PER, false, true, true>);
+    return list ? (lights ? k_shade<true, 2, true, 512, PER, true, false, true> : k_shade<true, 2, false, 512, PER, true, false, true>)
+                : (lights ? k_shade<true, 2, true, 512, PER, false, false, true> : k_shade<true, 2, false, 512, PER, false, false, true>);
+}
+const void* pick_shade_qmc(int variant, bool lights, bool list, bool env) {
+    return (const void*)(variant == 22 ? pick_shade_qmc_per<8>(lights, list, env) : pick_shade_qmc_per<16>(lights, list, env));
+}
+void launch_aov_qmc(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
+                    hipStream_t st) {
+    hipLaunchKernelGGL(k_aov_qmc, grid_for(cam.width * cam.height, max_blocks), dim3(BLOCK), 0, st, sc, cam, seed, spp_begin, spp_end, aov, overwrite ? 1u : 0u);
+}
+void launch_sampler_probe(int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin, uint32_t n_draws, uint64_t* out,
+                          hipStream_t st) {
+    const unsigned long long n = (unsigned long long)n_samples * n_draws;
+    const dim3 grid = grid_for((uint32_t)(n > 0xFFFFFF00ull ? 0xFFFFFF00ull : n), 2048);
+    if (kind == 1) hipLaunchKernelGGL(k_sampler_probe<RngQ>, grid, dim3(BLOCK), 0, st, seed, pixel, sample_begin, n_samples, draw_begin, n_draws, (unsigned long long*)out);
+    else hipLaunchKernelGGL(k_sampler_probe<Rng>, grid, dim3(BLOCK), 0, st, seed, pixel, sample_begin, n_samples, draw_begin, n_draws, (unsigned long long*)out);
+}
+#else
+__global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, uint32_t overwrite) {
+    aov_pixels<false>(sc, cam, seed, spp_begin, spp_end, aov, overwrite);
 }
 
 // Elementwise probes of the device arithmetic (sqrt/div/fma-free mul-add, libm calls, RNG)
@@ -1865,13 +1928,8 @@ __global__ void k_math_probe(int which, const double* in, uint32_t n, double* ou
 }
 
 // ------------------------------------------------------------------------------- launchers
-static inline dim3 grid_for(uint32_t n, int max_blocks) {
-    uint32_t b = (n + BLOCK - 1) / BLOCK;
-    if (b > (uint32_t)max_blocks) b = (uint32_t)max_blocks;
-    if (b == 0) b = 1;
-    return dim3(b);
-}
-void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st) {
+void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc) {
+    if (qmc) return launch_init_qmc(cam, pool, seed, max_blocks, st);
     if (pool.list) hipLaunchKernelGGL(k_init<true>, grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
     else hipLaunchKernelGGL(k_init<false>, grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
 }
@@ -1933,17 +1991,19 @@ bool shade_variant_sorts(int variant) {
 static int shade_threads(int variant) { return variant == 22 || variant == 32 || variant == 42 ? 512 : BLOCK; }
 static int shade_window(int variant) { return variant == 32 ? 8192 : variant == 22 || variant == 52 ? 4096 : SORT_WINDOW; }
 void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
-                  hipStream_t st, uint32_t wide_window_min, const EnvTabD* env) {
+                  hipStream_t st, uint32_t wide_window_min, const EnvTabD* env, bool qmc) {
     // 42: 8192-slot windows while the pool holds at least PT_WIDE_WINDOW_MIN of them per block launched, 4096-slot windows below
     // (a thinner pool — smaller frames, one rank's share, the frame's end after compaction — levels its end better with more, smaller windows)
-    if ((pool.list || env) && variant != 22 && variant != 32) variant = 42;
+    if ((pool.list || env || qmc) && variant != 22 && variant != 32) variant = 42;
     if (variant == 42) variant = pool.n_alloc / 8192u >= (uint32_t)max_blocks * (wide_window_min ? wide_window_min : 1u) ? 32 : 22;
     const int kb = shade_threads(variant);
     uint32_t blocks = variant >= 10 ? pool.n_alloc / (uint32_t)shade_window(variant) : (pool.n_alloc + (uint32_t)kb - 1u) / (uint32_t)kb;   // one block per window / chunk
     if (blocks > (uint32_t)max_blocks) blocks = (uint32_t)max_blocks;
     if (blocks == 0) blocks = 1;
     const EnvTabD e = env ? *env : EnvTabD{};
-    hipLaunchKernelGGL(pick_shade(variant, sc.n_lights != 0u, pool.list != nullptr, env != nullptr), dim3(blocks), dim3((uint32_t)kb), 0, st, sc, cam, pool, cnt, seed, e);
+    const shade_fn f = qmc ? (shade_fn)pick_shade_qmc(variant, sc.n_lights != 0u, pool.list != nullptr, env != nullptr)
+                           : pick_shade(variant, sc.n_lights != 0u, pool.list != nullptr, env != nullptr);
+    hipLaunchKernelGGL(f, dim3(blocks), dim3((uint32_t)kb), 0, st, sc, cam, pool, cnt, seed, e);
 }
 void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_t st) {
     if (pool.list) hipLaunchKernelGGL(k_resolve<true>, grid_for(pool.n_list, max_blocks), dim3(BLOCK), 0, st, pool, accum);
@@ -1965,17 +2025,21 @@ void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out,
     hipLaunchKernelGGL(k_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, sc, rays, n, out);
 }
 void launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
-                hipStream_t st) {
+                hipStream_t st, bool qmc) {
+    if (qmc) return launch_aov_qmc(sc, cam, seed, spp_begin, spp_end, aov, overwrite, max_blocks, st);
     hipLaunchKernelGGL(k_aov, grid_for(cam.width * cam.height, max_blocks), dim3(BLOCK), 0, st, sc, cam, seed, spp_begin, spp_end, aov, overwrite ? 1u : 0u);
 }
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st) {
     hipLaunchKernelGGL(k_math_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, which, in, n, out);
 }
-int kernel_occupancy_blocks(int which, int variant, bool lights, bool list, bool env) {
+int kernel_occupancy_blocks(int which, int variant, bool lights, bool list, bool env, bool qmc) {
     int nb = 0;
-    const void* f = which == 0 ? (variant <= -100 ? (const void*)pick_extend2(-variant) : (const void*)pick_extend_batch(variant <= -2, variant == -3)) : (const void*)pick_shade(variant, lights, list, env);
+    const void* f = which == 0 ? (variant <= -100 ? (const void*)pick_extend2(-variant) : (const void*)pick_extend_batch(variant <= -2, variant == -3))
+                  : qmc ? pick_shade_qmc(variant, lights, list, env) : (const void*)pick_shade(variant, lights, list, env);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, which == 1 ? shade_threads(variant) : variant <= -100 ? extend2_threads(-variant) : BLOCK, 0) != hipSuccess || nb < 1) nb = 1;
     return nb;
 }
+
+#endif   // PT_QMC_TU
 
 }  // namespace pt

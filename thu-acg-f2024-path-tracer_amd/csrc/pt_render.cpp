@@ -311,7 +311,8 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                               // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
-    if ((list || env_on) && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list / ENV forms of k_shade (launch_shade)
+    const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
+    if ((list || env_on || qmc) && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list / ENV / QMC forms of k_shade (launch_shade)
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
     // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
@@ -421,7 +422,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         if (!strcmp(e, "batch")) extend_code = -1;
         else if (!strcmp(e, "twophase") && extend2_code() != 0) extend_code = -extend2_code();
     }
-    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list, env_on);
+    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc);
     const int grid_extend = ctx->n_cus * blocks_extend * mult, grid_shade = ctx->n_cus * blocks_shade * mult;
 
     pool.accum = d_accum;
@@ -458,7 +459,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     t0 = std::chrono::steady_clock::now();
 
     timer.begin(2, st);
-    launch_init(dc, pool, seed, grid_shade, st);
+    launch_init(dc, pool, seed, grid_shade, st, qmc);
     timer.end(st);
     uint64_t iterations = 0;
     const uint64_t per_slot = dynamic ? (total_work + n_slots - 1) / std::max<uint64_t>(n_slots, 1) + 1 : (spp + k - 1) / k;
@@ -481,7 +482,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             launch_extend(s->dev.view, pool, s->d_counters, grid_extend, extend_code, st);
             timer.end(st);
             timer.begin(1, st);
-            launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min, env_on ? &env : nullptr);
+            launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min, env_on ? &env : nullptr, qmc);
             timer.end(st);
             if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
                 std::swap(pool.ray, pool.ray_out);
@@ -814,7 +815,7 @@ extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, 
         d_aov = own.p;
         if (!opts.overwrite && !hip_ok(hipMemcpyAsync(d_aov, aov, bytes, hipMemcpyHostToDevice, st), "hipMemcpy(aov)")) return -1;
     }
-    launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st);
+    launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, s->sampler == 1);
     if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
     if (!opts.accum_on_device && !hip_ok(hipMemcpyAsync(aov, d_aov, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(aov)")) return -1;
     return hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(aov)") ? 0 : -1;
@@ -919,6 +920,26 @@ extern "C" int pt_env_probe(pt_scene* s, const pt_camera* cam, int which, const 
              hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     }
     if (d_i) (void)hipFree(d_i);
+    if (d_o) (void)hipFree(d_o);
+    return ok ? 0 : -1;
+}
+
+extern "C" int pt_sampler_probe(pt_ctx* ctx, int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin,
+                                uint32_t n_draws, uint64_t* out) {
+    if (!ctx) return set_error("pt_sampler_probe: null context");
+    if (kind != 0 && kind != 1) return set_error("pt_sampler_probe: kind must be 0 (independent) or 1 (Sobol)");
+    const uint64_t n = (uint64_t)n_samples * n_draws;
+    if (n == 0) return 0;
+    if (!out || n > (1ull << 28)) return set_error("pt_sampler_probe: null output or more than 2^28 values");
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    uint64_t* d_o = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&d_o, n * sizeof(uint64_t)), "hipMalloc");
+    if (ok) {
+        launch_sampler_probe(kind, seed, pixel, sample_begin, n_samples, draw_begin, n_draws, d_o, ctx->stream);
+        ok = hip_ok(hipGetLastError(), "kernel launch") &&
+             hip_ok(hipMemcpyAsync(out, d_o, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
     if (d_o) (void)hipFree(d_o);
     return ok ? 0 : -1;
 }

@@ -114,6 +114,13 @@ extern "C" int pt_scene_set_env_sampling(pt_scene* s, double f) {
     return 0;
 }
 extern "C" double pt_scene_env_sampling(pt_scene* s) { return s ? s->env_f : 0.0; }
+extern "C" int pt_scene_set_sampler(pt_scene* s, int kind) {
+    if (!s) return set_error("pt_scene_set_sampler: null scene");
+    if (kind != 0 && kind != 1) return set_error("pt_scene_set_sampler: kind must be 0 (independent) or 1 (Sobol)");
+    s->sampler = kind;
+    return 0;
+}
+extern "C" int pt_scene_sampler(pt_scene* s) { return s ? s->sampler : 0; }
 extern "C" int pt_register_image(pt_scene* s, const char* name, uint32_t w, uint32_t h, const uint8_t* rgb) {
     int t = pt_tex_image_rgb8(s, w, h, rgb);
     if (t < 0) return -1;

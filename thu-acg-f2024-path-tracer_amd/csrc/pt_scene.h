@@ -90,6 +90,7 @@ struct pt_scene {
     size_t env_tab_bytes = 0;
     uint32_t env_tab_w = 0, env_tab_h = 0;
     double env_tab_z = 0.0;
+    int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned
     ~pt_scene();

@@ -19,6 +19,7 @@ int main(int argc, char** argv) {
     long width = -1, spp = -1, min_spp = 16;
     double adaptive = 0.0, env_sampling = 0.0;
     bool use_adaptive = false, use_denoise = false;
+    int sampler = 0;
     long aov_spp = 16;
     uint64_t seed = 1;
     std::string out, assets = "assets";
@@ -41,12 +42,18 @@ int main(int argc, char** argv) {
             env_sampling = atof(next());
             if (!(env_sampling >= 0.0 && env_sampling < 1.0)) { std::cerr << "--env-sampling must be in [0, 1)\n"; return 2; }
         }
+        else if (a == "--sampler") {
+            const std::string v = next();
+            if (v == "independent") sampler = 0;
+            else if (v == "sobol") sampler = 1;
+            else { std::cerr << "--sampler must be independent or sobol\n"; return 2; }
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n";
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n";
             return 0;
         } else { std::cerr << "unknown argument " << a << "\n"; return 2; }
     }
@@ -66,6 +73,7 @@ int main(int argc, char** argv) {
         SceneSetup setup = make_scene(scene, w, s, assets, 1);
         setup.world.float_hdr = float_hdr;
         setup.world.env_sampling = env_sampling;
+        setup.world.sampler = sampler;
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();
         std::cerr << "rendering production\n";   // camera.rs:101

@@ -51,6 +51,8 @@ def headline(args):
     ref, ref_ms = timed(lambda: gs.render(cam, args.seed + 1000, 0, args.ref_spp)[0])
     ref /= float(args.ref_spp)
     out["reference"]["ms"] = round(ref_ms, 1)
+    gs.set_sampler(args.sampler)   # (after the reference render)
+    out["sampler"] = args.sampler
     uni, uni_ms = timed(lambda: gs.render(cam, args.seed, 0, args.max_spp)[0])
     out["uniform_max_spp"] = {"spp": args.max_spp, "ms": round(uni_ms, 1), "relmse": rel_mse(uni / args.max_spp, ref)}
     # threshold 0: nothing stops, every pass renders the whole frame
@@ -112,6 +114,8 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=16000)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--thresholds", type=float, nargs="+", default=[0.02, 0.01, 0.005])
+    ap.add_argument("--sampler", default="independent", choices=["independent", "sobol"],
+                    help="sampler of the renders under test (the reference render always uses the independent one)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--calibrate", action="store_true")
     args = ap.parse_args()

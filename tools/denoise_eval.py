@@ -39,7 +39,8 @@ def table(args):
     gs.render(cam, 99, 0, 4)   # warm-up (pool allocation, code load)
     gs.render_aovs(cam, 99, 0, 1)
     ref, ref_ms = timed(lambda: gs.render(cam, 7777, 0, args.ref_spp)[0] / float(args.ref_spp))
-    out = {"scene": args.scene, "width": args.width, "ref_spp": args.ref_spp, "aov_spp": args.aov_spp, "device": ctx.name(),
+    gs.set_sampler(args.sampler)   # (after the reference render)
+    out = {"scene": args.scene, "width": args.width, "ref_spp": args.ref_spp, "aov_spp": args.aov_spp, "device": ctx.name(), "sampler": args.sampler,
            "relmse": "mean((x - ref)^2 / (ref^2 + 1e-2)); trimmed: without the 0.1 % of pixels with the largest error", "rows": []}
     for s in args.spp:
         half, n_aov = s // 2, min(args.aov_spp, s)
@@ -97,6 +98,8 @@ def main():
     ap.add_argument("--cal-k", type=int, nargs="+", default=[3, 4, 5, 6])
     ap.add_argument("--cal-sigma-l", type=float, nargs="+", default=[2.0, 4.0, 8.0])
     ap.add_argument("--cal-sigma-z", type=float, nargs="+", default=[0.05, 0.1, 0.3])
+    ap.add_argument("--sampler", default="independent", choices=["independent", "sobol"],
+                    help="sampler of the renders under test (the reference render always uses the independent one)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     out = calibrate(args) if args.calibrate else table(args)
