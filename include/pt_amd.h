@@ -148,6 +148,51 @@ int pt_mat_metal(pt_scene*, int color_tex, int rough_tex);              /* Metal
 int pt_mat_glass(pt_scene*, int color_tex, int rough_tex, double anisotropic, double ior);   /* GlassBSDF::new glass.rs:28-40 */
 int pt_mat_principled(pt_scene*, int color_tex, const double params[11]);   /* PrincipledBSDF::new principled.rs:45-73, same argument order */
 int pt_mat_light(pt_scene*, int emission_tex);                          /* DiffuseLight::new material.rs:155-164 */
+/* ---- homogeneous participating media: fog, smoke (the reference's commented-out volume.rs `HomogeneousVolume`) ----
+ * A medium is a material. density = sigma_t, finite and > 0; (r, g, b) = the single-scattering albedo sigma_s / sigma_t, each in
+ * [0, 1]; hg_g = the Henyey-Greenstein asymmetry, |hg_g| < 1 (0 = isotropic). Anything else returns -1, and so does a handle that
+ * would reach 4094 (a path keeps its medium in 12 bits: create media early in scenes with thousands of materials). Any closed object
+ * (sphere, cuboid, mesh, an instance of these) may carry it: its surface is then the medium's BOUNDARY — invisible — and the medium
+ * fills its inside. A medium inside pt_mat_mix and a medium object in the lights list are refused (-1).
+ * pt_scene_set_camera_medium: the medium camera rays start in — the camera inside a fog box, or an unbounded fog when no boundary
+ * carries that material; -1 (default) = none; a handle that is not a medium returns -1 and leaves the setting.
+ * Media are IN EFFECT for a render when some world object's material is a medium or the camera medium is set; otherwise every
+ * entry point runs exactly the kernels it ran before media existed (a medium material nothing uses does not count).
+ * Not supported: nested or overlapping media (leaving ANY boundary puts the path into "no medium"), boundaries that touch or lie
+ * within 2e-3 of each other, chromatic density, textured albedo, emission from media; a transmissive object inside a medium is
+ * treated as filled by it. Environment importance sampling together with media in effect: the render returns -1. max_depth must
+ * be below 2^20 then.
+ *
+ * The estimator: analog tracking with the reference's one-sample MIS. Each path carries m, a medium or none; a camera ray starts with
+ * m = the camera medium. Whenever K3 visits a live path whose segment is resolved (a hit at distance t = HitInfo::dist, or a miss,
+ * t = +inf), with o, dir the segment's ray:
+ *  1 Free flight, only if m is set: one draw u in [0, 1) (converted like every unit draw: (v >> 11) * 2^-53);
+ *    d = -log(1 - u) / density with the deterministic log of pt_detmath.h. d < t: a MEDIUM VERTEX at x = o + d * dir (step 2). Else
+ *    the surface hit or miss is processed unweighted (step 3 or 4): transmittance and free-flight density cancel.
+ *    One exception, before the draw: a MISS while m is a medium that some world object bounds. A boundary is closed, so such a
+ *    ray is not inside m: the path lost a crossing — an exit closer than the 1e-3 of K2's t_min to an offset entry point, which
+ *    happens at the edges of cuboids and meshes — and would scatter for ever outside. m becomes none, no draw is made, and the
+ *    miss is processed (step 4). Until its ray leaves the scene such a path carries the wrong medium; about 1 crossing in 10^4.
+ *  2 Medium vertex. No emission. Russian roulette exactly as at a surface (bounce > 5: p = clamp(luminance(thr), 0.01, 1), one draw,
+ *    end if draw > p, else thr /= p). Then the selector draw (camera.rs:199-201; made even without lights). Below p_light (0.5 with a
+ *    lights list, else 0): w = lights.sample(x). Otherwise a two-value draw (u1, u2) (pair-aligned under the Sobol sampler):
+ *      cos_t = 1 - 2 u1 when |g| < 1e-3, else (1 + g^2 - ((1 - g^2) / (1 - g + 2 g u1))^2) / (2 g); clamped to [-1, 1];
+ *      sin_t = sqrt(max(0, 1 - cos_t^2)); phi = (2 pi) u2; w = the local vector (sin_t cos phi, sin_t sin phi, cos_t) taken to the
+ *      world by the shading frame built around dir (the shortest-arc quaternion of vec3.rs:23-29): g > 0 scatters forward.
+ *    ph(c) = (1 - g^2) / (4 pi s sqrt(s)), s = 1 + g^2 - 2 g c, c = dot(dir, w). pdf = p_bsdf ph + p_light lights.pdf(x, w).
+ *    A zero or non-finite pdf ends the path. thr *= albedo * ph / pdf. The new ray starts at x (no offset) along w (normalised as
+ *    Ray::new does). m is unchanged. ++bounce; the depth bound applies as at a surface.
+ *  3 Boundary hit (the surface's material is a medium k): no draw, no roulette, no emission, no change of throughput.
+ *    m = (m == k) ? none : k — a toggle, independent of face orientation, so cuboid faces and meshes of either winding work. The
+ *    ray continues with the same direction from point + 1e-3 * signum(dot(dir, gn)) * gn (the offset camera.rs:217-222 applies to
+ *    every continued ray). ++bounce, and the depth bound applies: counting a crossing as a bounce guarantees termination, needs no
+ *    extra state, and is what a glass surface of ior 1 would cost.
+ *  4 Any other surface hit, or a miss: exactly the code without media. m is kept.
+ * A miss inside an unbounded medium is only reached through d >= +inf, i.e. never: such a path scatters until roulette or the
+ * depth bound ends it. pt_render_aovs and pt_intersect see a boundary as an ordinary first hit (albedo (1, 1, 1)). */
+int pt_mat_medium(pt_scene*, double density, double r, double g, double b, double hg_g);
+int pt_scene_set_camera_medium(pt_scene*, int mat);
+int pt_scene_camera_medium(pt_scene*);
 /* the three bsdf/ materials no reference scene instantiates */
 int pt_mat_mix(pt_scene*, double t, int mat1, int mat2);                /* MixBxDf::new mix.rs:14-20; a child may itself be a mix of non-mix materials (two levels) */
 int pt_mat_sheen(pt_scene*, double r, double g, double b, double sheen_tint);   /* SheenBRDF::new sheen.rs:17-22 */
@@ -247,8 +292,8 @@ int pt_resolve_u8_counts(pt_ctx*, const double* accum, uint32_t n_pixels, const 
  * (pixel, s): same seed, same RNG draws. The ray's first hit adds to aov[(y*W+x)*8 + k]. These are SUMS over samples, like
  * accum, so sample ranges add up:
  *   k = 0..2  albedo r,g,b   (every sample): diffuse / metal / principled: the colour texture at the hit; sheen: its base colour;
- *             glass, clearcoat, light and a miss: (1, 1, 1) (glass's base colour reaches no radiance, emitted and environment
- *             light is not reflected); mix: (1 - t) * A(child1) + t * A(child2), recursively over the two levels allowed
+ *             glass, clearcoat, light, a medium's boundary and a miss: (1, 1, 1) (glass's base colour reaches no radiance, emitted
+ *             and environment light is not reflected, a boundary is a first hit like glass); mix: (1 - t) * A(child1) + t * A(child2), recursively over the two levels allowed
  *   k = 3..5  normal x,y,z   (hits only: the shading normal of the hit, normal map applied)
  *   k = 6     depth          (hits only: t of the first hit; camera rays are unit length)
  *   k = 7     hits           (number of samples whose camera ray hit something)
@@ -322,6 +367,11 @@ int pt_env_probe(pt_scene*, const pt_camera*, int which, const double* in, uint3
  * (0: the Philox values). At most 2^28 values a call. */
 int pt_sampler_probe(pt_ctx*, int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin,
                      uint32_t n_draws, uint64_t* out);
+
+/* the device functions of participating media that k_shade calls (pt_mat_medium's rule), for medium material `mat`:
+ * which = 0: in = n x (u1, u2, dir.xyz), out = n x (w.xyz, ph(dot(dir, w))); which = 1: in = n x u, out = n free-flight distances.
+ * The world need not be built. */
+int pt_medium_probe(pt_scene*, int mat, int which, const double* in, uint32_t n, double* out);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,7 @@ ABI_SYMBOLS = [
     "pt_bootstrap_exchange", "pt_render_multi",
     "pt_render_pixels", "pt_adaptive_schedule", "pt_render_adaptive", "pt_resolve_u8_counts",
     "pt_render_aovs", "pt_denoise",
+    "pt_mat_medium", "pt_scene_set_camera_medium", "pt_scene_camera_medium", "pt_medium_probe",
 ]
 
 
@@ -158,6 +159,11 @@ def _load():
         lib.pt_scene_set_sampler.argtypes = [C.c_void_p, C.c_int]
         lib.pt_scene_sampler.argtypes = [C.c_void_p]
         lib.pt_sampler_probe.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "pt_mat_medium"):              # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_mat_medium.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
+        lib.pt_scene_set_camera_medium.argtypes = [C.c_void_p, C.c_int]
+        lib.pt_scene_camera_medium.argtypes = [C.c_void_p]
+        lib.pt_medium_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -419,6 +425,27 @@ class Scene:
 
     def sampler(self) -> int:
         return lib.pt_scene_sampler(self.handle)
+
+    def mat_medium(self, density: float, albedo=(1.0, 1.0, 1.0), g: float = 0.0):
+        """A homogeneous participating medium (fog, smoke) as a material: the object that carries it is the medium's invisible
+        boundary. density = sigma_t > 0, albedo = sigma_s / sigma_t per channel in [0, 1], |g| < 1 the Henyey-Greenstein asymmetry
+        (the rule is in include/pt_amd.h)."""
+        return _check(lib.pt_mat_medium(self.handle, float(density), float(albedo[0]), float(albedo[1]), float(albedo[2]), float(g)), "mat_medium")
+
+    def set_camera_medium(self, mat: int):
+        """The medium camera rays start in (a mat_medium handle; -1 = none, the default)."""
+        return _check(lib.pt_scene_set_camera_medium(self.handle, int(mat)), "set_camera_medium")
+
+    def camera_medium(self) -> int:
+        return lib.pt_scene_camera_medium(self.handle)
+
+    def medium_probe(self, mat: int, which: int, arr: np.ndarray) -> np.ndarray:
+        """The device functions of medium `mat` that the kernels call. which 0: arr = (n, 5) (u1, u2, dir.xyz) -> (n, 4)
+        {new_dir.xyz, ph}; which 1: arr = (n,) unit draws -> (n,) free-flight distances."""
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, 5) if which == 0 else (-1,))
+        out = np.empty((len(arr), 4) if which == 0 else (len(arr),), dtype=np.float64)
+        _check(lib.pt_medium_probe(self.handle, int(mat), which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_medium_probe")
+        return out
 
     def mat_diffuse(self, color_tex, normal_map_tex=-1): return _check(lib.pt_mat_diffuse(self.handle, color_tex, normal_map_tex), "mat_diffuse")
     def mat_metal(self, color_tex, rough_tex): return _check(lib.pt_mat_metal(self.handle, color_tex, rough_tex), "mat_metal")

@@ -8,7 +8,14 @@ namespace pt {
 // qmc (launch_init, launch_shade, launch_aov, kernel_occupancy_blocks): the Sobol sampler's forms (pt_scene_set_sampler). They live in
 // pt_kernels_qmc.hip — pt_kernels.hip compiled a second time for those forms alone — and cover the default k_shade variant's two shapes:
 // launch_shade maps any other variant to 42, as for pixel lists and environment sampling.
-void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc = false);
+// med (launch_init, launch_shade, kernel_occupancy_blocks): participating media are in effect: the MED forms, in
+// pt_kernels_med.hip — the default variant's two shapes like the QMC forms, with or without qmc, never with env.
+void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc = false, bool med = false);
+void launch_init_med(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc);
+const void* pick_shade_med(int variant /* 22 or 32 */, bool lights, bool list, bool qmc);
+// pt_medium_probe: the medium functions k_shade's MED forms call (which 0: n x (u1, u2, dir.xyz) -> n x (new_dir.xyz, ph); 1: n x u ->
+// n free-flight distances); in / out: device
+void launch_medium_probe(int which, double density, double g, const double* in, uint32_t n, double* out, hipStream_t st);
 void launch_init_qmc(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st);
 const void* pick_shade_qmc(int variant /* 22 or 32 */, bool lights, bool list, bool env);
 void launch_aov_qmc(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
@@ -21,7 +28,7 @@ void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_
 // env: the environment-sampling tables or null. Non-null launches k_shade's ENV forms (the default variant's two shapes:
 // any other variant is mapped to 42, as for pixel lists).
 void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
-                  hipStream_t st, uint32_t wide_window_min = 16, const EnvTabD* env = nullptr, bool qmc = false);
+                  hipStream_t st, uint32_t wide_window_min = 16, const EnvTabD* env = nullptr, bool qmc = false, bool med = false);
 // pt_envmap.hip: the environment-sampling tables of image texture `tex` (device TexD values; col: H * (W + 1), row: H + 1 doubles),
 // and the probe behind pt_env_probe (which 0: (u1, u2) pairs -> {dir.xyz, pdf}; 1: directions -> env_pdf)
 void launch_env_tables(const SceneD& sc, const TexD& tex, double* col, double* row, hipStream_t st);
@@ -51,5 +58,5 @@ void launch_math_probe(int which, const double* in, uint32_t n, double* out, hip
 // K2 variant code (`code` of launch_extend / `variant` of kernel_occupancy_blocks): -1 = batch kernel (-2 asks
 // kernel_occupancy_blocks for its flat-top-level instantiation), -(stack*10 + blocks) = two-phase kernel
 // k_extend2<stack, blocks> for stack in {16, 20, 24}.
-int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false, bool env = false, bool qmc = false);   // qmc: k_shade's Sobol form   // env: k_shade's ENV form   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
+int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false, bool env = false, bool qmc = false, bool med = false);   // qmc: k_shade's Sobol form   // env: k_shade's ENV form   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
 }  // namespace pt

@@ -15,8 +15,15 @@
 #include <type_traits>
 
 #include "pt_dev_geom.h"
+#include "pt_dev_medium.h"
 #include "pt_envmap.h"
 #include "pt_kernels.h"
+
+// pt_kernels_qmc.hip and pt_kernels_med.hip compile this file again for their forms of the template kernels alone: the
+// non-template kernels and the launchers below belong to the first translation unit
+#if defined(PT_QMC_TU) || defined(PT_MED_TU)
+#define PT_FORMS_TU 1
+#endif
 
 namespace pt {
 
@@ -345,8 +352,11 @@ PT_DEV unsigned long long shard_item(unsigned long long c, uint32_t shard) {
 // ---------------------------------------------------------------------------------------
 // LIST: pixel-list render (PoolD::list)
 // QMC: the Sobol sampler (pt_scene_set_sampler; RngQ in pt_dev_math.h) — forms of their own, compiled in pt_kernels_qmc.hip
-template <bool LIST = false, bool QMC = false>
+// MED: participating media are in effect — a camera ray's bounce word carries the camera medium (pt_types.h MEDIUM_SHIFT);
+// forms of their own, compiled in pt_kernels_med.hip
+template <bool LIST = false, bool QMC = false, bool MED = false>
 __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t seed) {
+    const uint32_t bounce0 = MED ? cam.medium << MEDIUM_SHIFT : 0u;   // the bounce word of a camera ray
     for (uint32_t s = blockIdx.x * BLOCK + threadIdx.x; s < pool.n_alloc; s += gridDim.x * BLOCK) {
         uint32_t pixel, sample, row = 0, col = 0;
         bool has_work;
@@ -368,7 +378,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
             pool.rx[s] = 0.0; pool.ry[s] = 0.0; pool.rz[s] = 0.0;
         }
         pool.hit_prim[s] = (CLASS_DEAD << HIT_CLASS_SHIFT) | HIT_ID_MASK;   // overwritten by the first K2 launch
-        if (!pool.compact) store_path(pool.path, s, V3{1.0, 1.0, 1.0}, pixel, 0u);
+        if (!pool.compact) store_path(pool.path, s, V3{1.0, 1.0, 1.0}, pixel, bounce0);
         if (!has_work || idle) {
             pool.bounce[s] = idle ? SLOT_IDLE : SLOT_DEAD;
             store_ray(pool, pool.ray, s, RayD{}, sample, 0u, pixel, 0u);
@@ -376,7 +386,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
         }
         std::conditional_t<QMC, RngQ, Rng> rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, 0u};
         RayD r = generate_ray(cam, row, col, rng);
-        store_ray(pool, pool.ray, s, r, sample, rng.draw, pixel, 0u);
+        store_ray(pool, pool.ray, s, r, sample, rng.draw, pixel, bounce0);
         pool.bounce[s] = 0;
     }
 }
@@ -1113,7 +1123,12 @@ struct NoPrefetch {
 // bit for bit. The tables are read in B1 (the env sample; env_pdf's texel gather for a BSDF or light direction), so the ENV forms
 // prefetch at P1b like the LIGHTS forms and B2 stays arithmetic.
 // QMC: the path's draws come from the Sobol sampler (RngQ); nothing else differs.
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false>
+// MED: participating media are in effect (the rule in pt_amd.h). The path's medium rides in the upper bits of its bounce
+// word. Phase A makes the free-flight draw of a path inside a medium: a lane whose distance falls short of the hit (or whose ray left
+// the scene) is at a MEDIUM VERTEX — no surface code runs for it; B1 draws roulette, selector and a light or Henyey-Greenstein
+// direction, B2 the phase function, the MIS density and the next ray. A lane that reached a medium's BOUNDARY toggles its medium and
+// continues straight on. Every other lane is the bounce above bit for bit. Never together with ENV (pt_render refuses it).
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
@@ -1123,6 +1138,13 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                        unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u, const EnvTabD* env = nullptr) {
     PT_STAMP(1);
     uint32_t bounce = in.bounce;
+    uint32_t med = 0u;                                                 // MED: the path's medium (material index + 1), 0 = none
+    if constexpr (MED) {
+        if (bounce < SLOT_IDLE) {
+            med = bounce >> MEDIUM_SHIFT;
+            bounce &= MEDIUM_BOUNCE_MASK;
+        }
+    }
     const bool alive = bounce != SLOT_DEAD;
     const bool was_idle = bounce == SLOT_IDLE;
     const bool live = alive && !was_idle;
@@ -1135,6 +1157,10 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     uint32_t pixel = in.pixel, sample = in.sample;
     RayD ray = in.ray;
     V3 thr = in.thr, rad{};
+    if constexpr (MED) {
+        // compact layout: the loaders take "bounce word != 0" for "has a PathRec" — a camera ray inside the camera medium has none
+        if (pool.compact && bounce == 0u) thr = V3{1.0, 1.0, 1.0};
+    }
     typedef std::conditional_t<QMC, RngQ, Rng> RngT;
     RngT rng{};
 #ifdef PT_STAMPS
@@ -1152,7 +1178,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     unsigned long long early = 0ull, early_base = 0ull;
     uint32_t early_shard = shard;
     if (pool.dynamic) {
-        early = __ballot(alive && (was_idle || (in.hw >> HIT_CLASS_SHIFT) == CLASS_MISS));
+        // (MED: a ray that left the scene inside an unbounded medium scatters instead of ending)
+        early = __ballot(alive && (was_idle || ((in.hw >> HIT_CLASS_SHIFT) == CLASS_MISS && (!MED || med == 0u))));
         early_shard = shard;
         if (pre_mask != 0ull) { early_base = pre_base; early_shard = pre_shard; }   // (the same lanes by construction: both come from the slots' result words;
                                                                                     //  the wave may have moved on to another shard since it asked)
@@ -1160,6 +1187,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     }
     // ---- phase A: all global-memory reads of the bounce -------------------------------------------------------------
     bool is_hit = false;
+    bool scatter = false, boundary = false;                            // MED: the lane is at a medium vertex (hit.point) / at a medium's boundary
+    MediumD medium{};
     HitD hit{};
     const MatD* mp = nullptr;
     TexVals tv{};
@@ -1174,9 +1203,29 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         const uint32_t gid = in.hw & HIT_ID_MASK;
         const bool surface = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS && reconstruct_hit(sc, ray, gid, 1e-3, hit);
         PT_STAMP_SET(a1);
-        if (!surface) {
+        if constexpr (MED) {
+            if (med != 0u) {                                           // free flight: one draw, d = -log(1 - u) / density
+                medium = load_medium(sc, med);
+                if (!surface && medium.bounded) {
+                    // the ray left the scene, so it is not inside a medium that an object bounds: the path lost a crossing (an exit closer
+                    // than t_min to an offset entry point, at an edge of a cuboid or mesh). No draw; the miss is processed.
+                    med = 0u;
+                } else {
+                    const double d = medium_free_flight(rng_f64(rng), medium.density);
+                    if (d < (surface ? hit.dist : D_INF)) {
+                        scatter = true;
+                        hit.point = ray.o + ray.d * d;
+                    }
+                }
+            }
+        }
+        if (MED && scatter) {
+            // a medium vertex: no emission, no surface
+        } else if (!surface) {
             add_radiance(pool, pixel, rad, thr * sample_environment(sc, cam, ray.d));   // camera.rs:180-183
             finished = true;
+        } else if (MED && sc.mats[hit.mat].kind == MAT_MEDIUM) {
+            boundary = true;                                           // a medium's boundary: invisible, no emission
         } else {
             is_hit = true;
             mp = &sc.mats[hit.mat];
@@ -1189,7 +1238,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         }
     }
     PT_STAMP(a2);
-    const bool any_hit = __ballot(is_hit) != 0ull;
+    const bool any_hit = __ballot(is_hit || (MED && (scatter || boundary))) != 0ull;
     bool fetched = false;                                              // wave-uniform
     if (any_hit && !LIGHTS && !ENV) { prefetch(); fetched = true; }    // P1
     // ---- phase B1: roulette and the next direction ------------------------------------------------------------------------
@@ -1243,6 +1292,29 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             else have_dir = true;
         }
     }
+    bool have_mdir = false;                                            // MED: a medium vertex with a next direction (in `dir`)
+    if constexpr (MED) {
+        if (scatter) {
+            if (bounce > 5) {                                          // roulette exactly as at a surface
+                double p = clampd(luminance(thr), 0.01, 1.0);
+                if (rng_f64(rng) > p) finished = parked = true;
+                else thr = thr / p;
+            }
+            if (!finished) {
+                bool from_light = false;
+                if constexpr (LIGHTS) from_light = rng_f64(rng) < p_light;
+                else ++rng.draw;                                       // the selector is drawn even without lights
+                if (from_light) {
+                    dir = lights_sample(sc, hit.point, ray.time, rng);
+                } else {
+                    uint64_t a, b;
+                    rng_u64x2(rng, a, b);
+                    dir = hg_sample(medium.g, u64_to_unit(a), u64_to_unit(b), ray.d);
+                }
+                have_mdir = true;
+            }
+        }
+    }
     PT_STAMP(b1);
     if (any_hit && !fetched) { prefetch(); fetched = true; }           // P1b
     // ---- phase B2: pdf, eval, throughput, next ray (arithmetic only; lights.pdf reads through the scalar cache) -----------------
@@ -1281,6 +1353,29 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             thr = thr * attenuation;
             ++bounce;
             if (bounce >= cam.max_depth) finished = parked = true;     // loop bound :177
+        }
+    }
+    if constexpr (MED) {
+        if (have_mdir) {
+            const double ph = hg_phase(medium.g, dot(ray.d, dir));
+            double light_pdf = 0.0;
+            if constexpr (LIGHTS) light_pdf = lights_pdf(sc, hit.point, dir, ray.time);
+            const double pdf = p_bsdf * ph + p_light * light_pdf;
+            if (!(pdf > 0.0) || !(pdf < D_INF)) {
+                finished = parked = true;                              // a zero or non-finite density ends the path
+            } else {
+                thr = thr * (medium.albedo * ph / pdf);
+                ray = make_ray(hit.point, dir, ray.time);              // no offset: nothing to leave
+                ++bounce;
+                if (bounce >= cam.max_depth) finished = parked = true;
+            }
+        } else if (boundary) {
+            // no draw, no roulette, no emission: the path changes medium and goes straight on, offset like every continued ray
+            med = med == hit.mat + 1u ? 0u : hit.mat + 1u;
+            const double e = 1e-3 * signum(dot(ray.d, hit.gn));
+            ray.o = hit.point + e * hit.gn;
+            ++bounce;
+            if (bounce >= cam.max_depth) finished = parked = true;
         }
     }
 #ifdef PT_STAMPS
@@ -1351,6 +1446,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             thr = V3{1.0, 1.0, 1.0};
             rad = V3{0.0, 0.0, 0.0};
             bounce = 0;
+            if constexpr (MED) med = cam.medium;
             sample = next_sample;
             pixel = next_pixel;
         } else {
@@ -1365,8 +1461,9 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         const uint32_t state_new = bounce < SLOT_IDLE ? 0u : bounce, state_old = was_idle ? SLOT_IDLE : 0u;
         if (reorder || state_new != state_old) pool.bounce_out[o] = state_new;
         if (bounce < SLOT_IDLE) {
-            store_ray(pool, pool.ray_out, o, ray, sample, rng.draw, pixel, bounce);
-            if (!pool.compact || bounce != 0u) store_path(pool.path_out, o, thr, pixel, bounce);
+            const uint32_t bounce_word = MED ? bounce | (med << MEDIUM_SHIFT) : bounce;
+            store_ray(pool, pool.ray_out, o, ray, sample, rng.draw, pixel, bounce_word);
+            if (!pool.compact || bounce != 0u) store_path(pool.path_out, o, thr, pixel, bounce_word);
             if (!pool.dynamic) { pool.rx[s] = rad.x; pool.ry[s] = rad.y; pool.rz[s] = rad.z; }
         }
     }
@@ -1413,7 +1510,9 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // as many slots and eight waves level a window's end better than four; one block per CU then).
 // ENV: environment importance sampling (shade_slot; `env` is read by these forms only)
 // QMC: the Sobol sampler (shade_slot)
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false>
+// MED: participating media (shade_slot). A slot's class says nothing certain about a path inside a medium — it may scatter before the
+// hit, or instead of leaving — so these forms do not request work items a group ahead.
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false, bool MED = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
     const int lane = (int)(threadIdx.x & 63u);
@@ -1429,7 +1528,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -1596,7 +1695,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
                         // the next group's lanes that are certain to end there (ray left the scene / idle slot): their work items now.
                         // Scenes without a lights list only: K3 -1.2 % (scene 6), -0.7 % (scene 5); the lights instantiation, three
                         // registers from the limit, got 0.9 % SLOWER with it (closed scenes have next to no leaving rays anyway).
-                        if constexpr (!LIGHTS && !ENV) {
+                        if constexpr (!LIGHTS && !ENV && !MED) {
                         const uint32_t cn = s_hw[sn - wbase] >> HIT_CLASS_SHIFT;
                         pre_mask_next = __ballot(en && (cn == CLASS_MISS || cn == CLASS_IDLE));
                         pre_shard_next = shard;
@@ -1606,7 +1705,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;
@@ -1697,7 +1796,7 @@ __global__ __launch_bounds__(BLOCK) void k_detile(PoolD pool, double* accum) {
 // [0, L) only. k_compact_scan lists both kinds (one atomic per wave and list, any order); k_compact_move copies mover i's two
 // records and its state into hole i and marks the old slot dead. Which slot a path sits in decides nothing (the RNG is keyed by
 // pixel and sample, the frame accumulator by pixel): no result changes.
-#ifndef PT_QMC_TU   // (pt_kernels_qmc.hip compiles this file's QMC forms only)
+#ifndef PT_FORMS_TU   // (pt_kernels_qmc.hip / pt_kernels_med.hip compile this file's QMC / MED forms only)
 __global__ __launch_bounds__(BLOCK) void k_compact_scan(PoolD pool, uint32_t new_end, uint32_t* holes, uint32_t* movers, uint32_t* counts /* [0] holes, [1] movers */,
                                                         uint32_t cap) {
     // [r3] A block takes 4096 slots at a time (n_alloc is a multiple of 8192), keeps their sixteen states per thread in registers,
@@ -1794,7 +1893,7 @@ __global__ __launch_bounds__(BLOCK) void k_probe(SceneD sc, const double* rays /
     }
 }
 
-#endif   // PT_QMC_TU
+#endif   // PT_FORMS_TU
 
 // First-hit feature buffers (pt_render_aovs; no counterpart in the reference). The colour the first bounce multiplies by:
 // the colour texture of diffuse / metal / principled, sheen's base colour, (1, 1, 1) for glass (Q4: its base colour reaches
@@ -1895,6 +1994,47 @@ void launch_sampler_probe(int kind, uint64_t seed, uint32_t pixel, uint32_t samp
     if (kind == 1) hipLaunchKernelGGL(k_sampler_probe<RngQ>, grid, dim3(BLOCK), 0, st, seed, pixel, sample_begin, n_samples, draw_begin, n_draws, (unsigned long long*)out);
     else hipLaunchKernelGGL(k_sampler_probe<Rng>, grid, dim3(BLOCK), 0, st, seed, pixel, sample_begin, n_samples, draw_begin, n_draws, (unsigned long long*)out);
 }
+#elif defined(PT_MED_TU)
+// ------------------------------------------------------------------ the participating-media forms and their launchers (pt_kernels_med.hip)
+// pt_medium_probe: which 0: in = n x (u1, u2, dir.xyz) -> out = n x (new_dir.xyz, ph); which 1: in = n x u -> out = n free-flight
+// distances — the functions shade_slot's MED forms call
+__global__ __launch_bounds__(BLOCK) void k_medium_probe(int which, double density, double g, const double* in, uint32_t n, double* out) {
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        if (which == 0) {
+            const double* q = in + 5 * (size_t)i;
+            const V3 axis{q[2], q[3], q[4]};
+            const V3 d = hg_sample(g, q[0], q[1], axis);
+            double* o = out + 4 * (size_t)i;
+            o[0] = d.x; o[1] = d.y; o[2] = d.z;
+            o[3] = hg_phase(g, dot(axis, d));
+        } else {
+            out[i] = medium_free_flight(in[i], density);
+        }
+    }
+}
+void launch_medium_probe(int which, double density, double g, const double* in, uint32_t n, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_medium_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, which, density, g, in, n, out);
+}
+void launch_init_med(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc) {
+    const dim3 grid = grid_for(pool.n_alloc, max_blocks);
+    if (qmc) {
+        if (pool.list) hipLaunchKernelGGL((k_init<true, true, true>), grid, dim3(BLOCK), 0, st, cam, pool, seed);
+        else hipLaunchKernelGGL((k_init<false, true, true>), grid, dim3(BLOCK), 0, st, cam, pool, seed);
+    } else {
+        if (pool.list) hipLaunchKernelGGL((k_init<true, false, true>), grid, dim3(BLOCK), 0, st, cam, pool, seed);
+        else hipLaunchKernelGGL((k_init<false, false, true>), grid, dim3(BLOCK), 0, st, cam, pool, seed);
+    }
+}
+// the default variant's two shapes (22: 4096-slot windows, 32: 8192-slot windows), LIGHTS x LIST x QMC; never ENV
+typedef void (*shade_fn)(SceneD, CamD, PoolD, CountersD*, uint64_t, EnvTabD);
+template <int PER, bool QMC> static shade_fn pick_shade_med_per(bool lights, bool list) {
+    return list ? (lights ? k_shade<true, 2, true, 512, PER, true, false, QMC, true> : k_shade<true, 2, false, 512, PER, true, false, QMC, true>)
+                : (lights ? k_shade<true, 2, true, 512, PER, false, false, QMC, true> : k_shade<true, 2, false, 512, PER, false, false, QMC, true>);
+}
+const void* pick_shade_med(int variant, bool lights, bool list, bool qmc) {
+    if (variant == 22) return (const void*)(qmc ? pick_shade_med_per<8, true>(lights, list) : pick_shade_med_per<8, false>(lights, list));
+    return (const void*)(qmc ? pick_shade_med_per<16, true>(lights, list) : pick_shade_med_per<16, false>(lights, list));
+}
 #else
 __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, uint32_t overwrite) {
     aov_pixels<false>(sc, cam, seed, spp_begin, spp_end, aov, overwrite);
@@ -1928,7 +2068,8 @@ __global__ void k_math_probe(int which, const double* in, uint32_t n, double* ou
 }
 
 // ------------------------------------------------------------------------------- launchers
-void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc) {
+void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc, bool med) {
+    if (med) return launch_init_med(cam, pool, seed, max_blocks, st, qmc);
     if (qmc) return launch_init_qmc(cam, pool, seed, max_blocks, st);
     if (pool.list) hipLaunchKernelGGL(k_init<true>, grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
     else hipLaunchKernelGGL(k_init<false>, grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, cam, pool, seed);
@@ -1991,17 +2132,18 @@ bool shade_variant_sorts(int variant) {
 static int shade_threads(int variant) { return variant == 22 || variant == 32 || variant == 42 ? 512 : BLOCK; }
 static int shade_window(int variant) { return variant == 32 ? 8192 : variant == 22 || variant == 52 ? 4096 : SORT_WINDOW; }
 void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
-                  hipStream_t st, uint32_t wide_window_min, const EnvTabD* env, bool qmc) {
+                  hipStream_t st, uint32_t wide_window_min, const EnvTabD* env, bool qmc, bool med) {
     // 42: 8192-slot windows while the pool holds at least PT_WIDE_WINDOW_MIN of them per block launched, 4096-slot windows below
     // (a thinner pool — smaller frames, one rank's share, the frame's end after compaction — levels its end better with more, smaller windows)
-    if ((pool.list || env || qmc) && variant != 22 && variant != 32) variant = 42;
+    if ((pool.list || env || qmc || med) && variant != 22 && variant != 32) variant = 42;
     if (variant == 42) variant = pool.n_alloc / 8192u >= (uint32_t)max_blocks * (wide_window_min ? wide_window_min : 1u) ? 32 : 22;
     const int kb = shade_threads(variant);
     uint32_t blocks = variant >= 10 ? pool.n_alloc / (uint32_t)shade_window(variant) : (pool.n_alloc + (uint32_t)kb - 1u) / (uint32_t)kb;   // one block per window / chunk
     if (blocks > (uint32_t)max_blocks) blocks = (uint32_t)max_blocks;
     if (blocks == 0) blocks = 1;
     const EnvTabD e = env ? *env : EnvTabD{};
-    const shade_fn f = qmc ? (shade_fn)pick_shade_qmc(variant, sc.n_lights != 0u, pool.list != nullptr, env != nullptr)
+    const shade_fn f = med ? (shade_fn)pick_shade_med(variant, sc.n_lights != 0u, pool.list != nullptr, qmc)   // (never with env: pt_render refuses it)
+                     : qmc ? (shade_fn)pick_shade_qmc(variant, sc.n_lights != 0u, pool.list != nullptr, env != nullptr)
                            : pick_shade(variant, sc.n_lights != 0u, pool.list != nullptr, env != nullptr);
     hipLaunchKernelGGL(f, dim3(blocks), dim3((uint32_t)kb), 0, st, sc, cam, pool, cnt, seed, e);
 }
@@ -2032,14 +2174,15 @@ void launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_b
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st) {
     hipLaunchKernelGGL(k_math_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, which, in, n, out);
 }
-int kernel_occupancy_blocks(int which, int variant, bool lights, bool list, bool env, bool qmc) {
+int kernel_occupancy_blocks(int which, int variant, bool lights, bool list, bool env, bool qmc, bool med) {
     int nb = 0;
     const void* f = which == 0 ? (variant <= -100 ? (const void*)pick_extend2(-variant) : (const void*)pick_extend_batch(variant <= -2, variant == -3))
+                  : med ? pick_shade_med(variant, lights, list, qmc)
                   : qmc ? pick_shade_qmc(variant, lights, list, env) : (const void*)pick_shade(variant, lights, list, env);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, which == 1 ? shade_threads(variant) : variant <= -100 ? extend2_threads(-variant) : BLOCK, 0) != hipSuccess || nb < 1) nb = 1;
     return nb;
 }
 
-#endif   // PT_QMC_TU
+#endif   // PT_QMC_TU / PT_MED_TU
 
 }  // namespace pt

@@ -175,6 +175,7 @@ static int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
     dc.env_is_map = cam->env_is_map ? 1u : 0u;
     dc.env_tex = cam->env_tex;
     dc.n_lights = s->dev.view.n_lights;
+    dc.medium = s->camera_medium >= 0 ? (uint32_t)s->camera_medium + 1u : 0u;
     {   // camera.rs:159-163 with radius 0: origin = center + 0 * px + 0 * py = center bit for bit (px, py are finite), unless a
         // component of center is -0.0 (then -0 + +0 = +0): only then must the products be formed
         bool zero = true;
@@ -262,6 +263,11 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         env_on = env.z > 0.0;
     }
 
+    // participating media are in effect (pt_amd.h): a world object carries a medium material, or the camera medium is set
+    const bool med = s->media_on();
+    if (med && env_on) return set_error("pt_render: environment importance sampling together with participating media is not supported (set one of them off)");
+    if (med && dc.max_depth > MEDIUM_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^20 when participating media are in effect");
+
     // pool sizing. slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
     // the machine several times over; finished paths pull the next (pixel, sample) from a global
     // counter. slots_per_pixel = k >= 1: STATIC ownership (deterministic; k = 1 is the reference's
@@ -312,7 +318,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
     const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
-    if ((list || env_on || qmc) && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list / ENV / QMC forms of k_shade (launch_shade)
+    if ((list || env_on || qmc || med) && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list / ENV / QMC forms of k_shade (launch_shade)
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
     // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
@@ -422,7 +428,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         if (!strcmp(e, "batch")) extend_code = -1;
         else if (!strcmp(e, "twophase") && extend2_code() != 0) extend_code = -extend2_code();
     }
-    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc);
+    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med);
     const int grid_extend = ctx->n_cus * blocks_extend * mult, grid_shade = ctx->n_cus * blocks_shade * mult;
 
     pool.accum = d_accum;
@@ -459,7 +465,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     t0 = std::chrono::steady_clock::now();
 
     timer.begin(2, st);
-    launch_init(dc, pool, seed, grid_shade, st, qmc);
+    launch_init(dc, pool, seed, grid_shade, st, qmc, med);
     timer.end(st);
     uint64_t iterations = 0;
     const uint64_t per_slot = dynamic ? (total_work + n_slots - 1) / std::max<uint64_t>(n_slots, 1) + 1 : (spp + k - 1) / k;
@@ -482,7 +488,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             launch_extend(s->dev.view, pool, s->d_counters, grid_extend, extend_code, st);
             timer.end(st);
             timer.begin(1, st);
-            launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min, env_on ? &env : nullptr, qmc);
+            launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min, env_on ? &env : nullptr, qmc, med);
             timer.end(st);
             if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
                 std::swap(pool.ray, pool.ray_out);
@@ -917,6 +923,29 @@ extern "C" int pt_env_probe(pt_scene* s, const pt_camera* cam, int which, const 
     if (ok) {
         launch_env_probe(s->dev.view, T, e, which, d_i, n, d_o, ctx->stream);
         ok = hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    if (d_i) (void)hipFree(d_i);
+    if (d_o) (void)hipFree(d_o);
+    return ok ? 0 : -1;
+}
+
+extern "C" int pt_medium_probe(pt_scene* s, int mat, int which, const double* in, uint32_t n, double* out) {
+    if (!s || !s->ctx) return set_error("pt_medium_probe: null scene");
+    if (mat < 0 || (size_t)mat >= s->mats.size() || s->mats[mat].kind != MAT_MEDIUM) return set_error("pt_medium_probe: not a medium material");
+    if (which != 0 && which != 1) return set_error("pt_medium_probe: which must be 0 or 1");
+    if (n == 0) return 0;
+    if (!in || !out) return set_error("pt_medium_probe: null buffer");
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    const size_t n_in = (size_t)n * (which == 0 ? 5 : 1), n_out = (size_t)n * (which == 0 ? 4 : 1);
+    double *d_i = nullptr, *d_o = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double)), "hipMalloc") &&
+              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    if (ok) {
+        launch_medium_probe(which, s->mats[mat].p[0], s->mats[mat].p[1], d_i, n, d_o, ctx->stream);
+        ok = hip_ok(hipGetLastError(), "kernel launch") &&
+             hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
              hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     }
     if (d_i) (void)hipFree(d_i);

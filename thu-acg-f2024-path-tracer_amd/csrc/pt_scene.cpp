@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -183,6 +184,7 @@ extern "C" int pt_mat_principled(pt_scene* s, int color_tex, const double p[11])
 }
 extern "C" int pt_mat_mix(pt_scene* s, double t, int m1, int m2) {   // MixBxDf::new mix.rs:14-20
     if (!MAT_OK(s, m1) || !MAT_OK(s, m2)) return set_error("pt_mat_mix: bad material handle");
+    if (s->mats[m1].kind == MAT_MEDIUM || s->mats[m2].kind == MAT_MEDIUM) return set_error("pt_mat_mix: a medium cannot be mixed (it is a volume, not a BxDF)");
     // a child may be a mix (MixBxDf::new takes any Arc<dyn BxDFMaterial>, mix.rs:14-20) — of leaves: the kernels evaluate two levels
     for (int c : {m1, m2})
         if (s->mats[c].kind == MAT_MIX && (s->mats[s->mats[c].color_tex].kind == MAT_MIX || s->mats[s->mats[c].rough_tex].kind == MAT_MIX))
@@ -203,6 +205,27 @@ extern "C" int pt_mat_clearcoat(pt_scene* s, double clearcoat_gloss) {   // Clea
     m.alpha_g = (1.0 - clearcoat_gloss) * 0.1 + clearcoat_gloss * 0.001;
     return push_mat(s, m);
 }
+// HomogeneousVolume of the reference's commented-out volume.rs, as a material: the object that carries it is the medium's boundary
+extern "C" int pt_mat_medium(pt_scene* s, double density, double r, double g, double b, double hg_g) {
+    if (!s) return set_error("pt_mat_medium: null scene");
+    if (!(density > 0.0) || !std::isfinite(density)) return set_error("pt_mat_medium: density must be finite and > 0");
+    for (double a : {r, g, b})
+        if (!(a >= 0.0 && a <= 1.0)) return set_error("pt_mat_medium: each albedo channel must be in [0, 1]");
+    if (!(std::fabs(hg_g) < 1.0)) return set_error("pt_mat_medium: |hg_g| must be below 1");
+    if (s->mats.size() >= MEDIUM_MAX_MATS) return set_error("pt_mat_medium: a medium's material handle must be below 4094 (create media before other materials)");
+    MatD m = blank_mat(MAT_MEDIUM);
+    m.p[0] = density;
+    m.p[1] = hg_g;
+    m.p[2] = r; m.p[3] = g; m.p[4] = b;
+    return push_mat(s, m);
+}
+extern "C" int pt_scene_set_camera_medium(pt_scene* s, int mat) {
+    if (!s) return set_error("pt_scene_set_camera_medium: null scene");
+    if (mat != -1 && (!MAT_OK(s, mat) || s->mats[mat].kind != MAT_MEDIUM)) return set_error("pt_scene_set_camera_medium: not a medium material (-1 = none)");
+    s->camera_medium = mat;
+    return 0;
+}
+extern "C" int pt_scene_camera_medium(pt_scene* s) { return s ? s->camera_medium : -1; }
 extern "C" int pt_mat_light(pt_scene* s, int tex) {
     if (!TEX_RGB_OK(s, tex)) return set_error("pt_mat_light: bad emission texture");
     MatD m = blank_mat(MAT_LIGHT);
@@ -330,7 +353,15 @@ static int place(pt_scene* s, int obj, std::vector<int>& list, const char* who) 
     return 0;
 }
 extern "C" int pt_world_add_object(pt_scene* s, int obj) { return place(s, obj, s->world_objects, "pt_world_add_object"); }
-extern "C" int pt_world_add_light(pt_scene* s, int obj) { return place(s, obj, s->world_lights, "pt_world_add_light"); }
+extern "C" int pt_world_add_light(pt_scene* s, int obj) {
+    if (OBJ_OK(s, obj)) {   // a medium's boundary is invisible: it cannot be a light (the object an instance chain finally wraps decides)
+        int oi = obj;
+        for (int guard = 0; s->objs[oi].kind == OBJ_INSTANCE && guard <= 64; ++guard) oi = s->objs[oi].child;
+        if (MAT_OK(s, s->objs[oi].mat) && s->mats[s->objs[oi].mat].kind == MAT_MEDIUM)
+            return set_error("pt_world_add_light: an object with a medium material cannot be in the lights list");
+    }
+    return place(s, obj, s->world_lights, "pt_world_add_light");
+}
 extern "C" uint32_t pt_world_prim_count(pt_scene* s) { return s->n_prims; }
 extern "C" int pt_world_set_device_bvh_threshold(pt_scene* s, uint32_t min_triangles) {
     if (!s) return set_error("pt_world_set_device_bvh_threshold: null scene");
@@ -732,7 +763,13 @@ int pt::scene_build(pt_scene* s) {
         entries.push_back(e);
     }
     if (prims.size() >= (size_t)HIT_ID_MASK - 4) return set_error("pt_world_build: too many primitives (28-bit ids)");
-    for (PrimRef& pr : prims) pr.kind |= (uint32_t)s->mats[pr.mat].kind << PRIM_MAT_KIND_SHIFT;
+    // (a medium's boundary sorts with glass — the other kind that sends the ray on — so that K2's result word keeps its classes: pt_types.h)
+    s->world_has_medium = false;
+    for (PrimRef& pr : prims) {
+        const uint32_t kind = s->mats[pr.mat].kind;
+        s->world_has_medium = s->world_has_medium || kind == MAT_MEDIUM;
+        pr.kind |= (kind == MAT_MEDIUM ? MEDIUM_SORT_KIND : kind) << PRIM_MAT_KIND_SHIFT;
+    }
     std::vector<Box> entry_boxes(tlas_items.size());
     for (const BuildItem& it : tlas_items) entry_boxes[it.ref_payload] = it.box;
     // Build the TLAS over world entries (one entry per leaf).
@@ -765,6 +802,8 @@ int pt::scene_build(pt_scene* s) {
             for (int c = 0; c < 3; ++c) { t.c1[c] = solid ? a.v[c] : 0.0; t.c2[c] = solid ? b.v[c] : 0.0; }
         }
     std::vector<MatD> mats = s->mats;   // solid textures' values into the material records (MatD::color_solid)
+    for (const PrimRef& pr : prims)   // a medium that bounds something in the world (MatD::p[5], pt_dev_medium.h)
+        if (mats[pr.mat].kind == MAT_MEDIUM) mats[pr.mat].p[5] = 1.0;
     for (MatD& m : mats) {
         m.color_solid = m.rough_solid = 0u;
         const bool has_color = m.kind == MAT_DIFFUSE || m.kind == MAT_METAL || m.kind == MAT_PRINCIPLED || m.kind == MAT_LIGHT;

@@ -90,6 +90,11 @@ struct pt_scene {
     size_t env_tab_bytes = 0;
     uint32_t env_tab_w = 0, env_tab_h = 0;
     double env_tab_z = 0.0;
+    // participating media (pt_mat_medium). camera_medium: the medium material camera rays start in, -1 = none.
+    // world_has_medium (set by scene_build): some world object's material is a medium.
+    int camera_medium = -1;
+    bool world_has_medium = false;
+    bool media_on() const { return world_has_medium || camera_medium >= 0; }   // "in effect": the kernels' MED forms run
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned

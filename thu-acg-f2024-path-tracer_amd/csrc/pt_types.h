@@ -106,7 +106,18 @@ struct TexD {
     double c1[3], c2[3];
 };
 enum MatKind : uint32_t { MAT_DIFFUSE = 0, MAT_METAL = 1, MAT_GLASS = 2, MAT_PRINCIPLED = 3, MAT_LIGHT = 4,
-                          MAT_SHEEN = 5, MAT_CLEARCOAT = 6, MAT_MIX = 7, MAT_KINDS = 8 };
+                          MAT_SHEEN = 5, MAT_CLEARCOAT = 6, MAT_MIX = 7, MAT_KINDS = 8,
+                          // A homogeneous participating medium (pt_mat_medium): p[0] = density (sigma_t), p[1] = the
+                          // Henyey-Greenstein g, p[2..4] = the single-scattering albedo, p[5] = 1 when a world object carries it (scene_build). Not one of the MAT_KINDS sort classes: the
+                          // primitives of a medium's boundary carry MAT_GLASS in PrimRef::kind (MEDIUM_SORT_KIND), so K2's result word
+                          // and the default k_shade forms' sort stay what they were; only k_shade's MED forms look at MatD::kind.
+                          MAT_MEDIUM = 9 };
+constexpr uint32_t MEDIUM_SORT_KIND = MAT_GLASS;
+// The medium a path is in travels in the upper bits of its record's bounce word (RayRec's in the compact layout, else PathRec's):
+// word = bounce | (material index + 1) << MEDIUM_SHIFT, 0 = no medium. Only the MED forms of k_init / k_shade pack and unpack it;
+// without media in effect the field is zero and the word is the bounce number, as before. The host refuses a medium material whose
+// index does not fit and a max_depth that reaches into the field (pt_mat_medium, pt_render).
+constexpr uint32_t MEDIUM_SHIFT = 20, MEDIUM_BOUNCE_MASK = (1u << MEDIUM_SHIFT) - 1u, MEDIUM_MAX_MATS = 4094;
 constexpr uint32_t CLASS_MISS = 0u, CLASS_IDLE = 1u + MAT_KINDS, CLASS_DEAD = 2u + MAT_KINDS, N_CLASSES = 3u + MAT_KINDS;
 // MAT_SHEEN: p[0..2] = base colour, p[3] = sheen_tint (sheen.rs). MAT_CLEARCOAT: alpha_g (clearcoat.rs).
 // MAT_MIX: p[0] = t, color_tex / rough_tex hold the two child MATERIAL indices (mix.rs; children are leaves).
@@ -136,6 +147,7 @@ struct CamD {
     uint32_t n_lights;
     uint32_t lens_zero;      // defocus radius 0 (dof_right = dof_up = 0, no -0.0 in center): the lens point is `center` exactly
     uint32_t motionless;     // no moving sphere in the scene: Ray::time is drawn (camera.rs:165) but its value is never used
+    uint32_t medium;         // the medium camera rays start in: material index + 1, 0 = none (pt_scene_set_camera_medium; read by the MED forms only)
 };
 
 // Environment importance sampling (pt_scene_set_env_sampling): the f64 tables of the camera's environment map,
@@ -215,7 +227,7 @@ struct alignas(64) RayRec {                       // current ray (direction norm
 #endif
 struct alignas(PT_PATHREC_BYTES) PathRec {
     double tx, ty, tz;                            // throughput
-    uint32_t pixel, pad;                          // dynamic mode: pixel of the sample in flight
+    uint32_t pixel, pad;                          // dynamic mode: pixel of the sample in flight; pad: the bounce word (number, and the medium: MEDIUM_SHIFT)
 #if PT_PATHREC_BYTES == 64
     double reserved[4];
 #endif

@@ -3,11 +3,16 @@
 // explicit overrides (not in the reference): --width, --spp, --seed, --out, --assets, --device, --float-hdr
 // (.hdr environments keep their f32 samples instead of the reference's .to_rgb8() squash, texture.rs:67),
 // --adaptive T [--min-spp M] (adaptive sampling to the noise target T, pt_render_adaptive; --spp is then the cap),
-// --denoise [--aov-spp N] (two half-frames + first-hit AOVs over min(N, spp) samples through pt_denoise; N defaults to 16).
+// --denoise [--aov-spp N] (two half-frames + first-hit AOVs over min(N, spp) samples through pt_denoise; N defaults to 16),
+// --fog DENSITY[,R,G,B[,G]] (the built world's bounds, grown by 1 %, become the boundary of a homogeneous medium of that density,
+// albedo (default 1,1,1) and Henyey-Greenstein g (default 0); the camera starts inside it when look_from lies inside).
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <limits>
+#include <vector>
 
 #include "scenes.hpp"
 
@@ -20,6 +25,8 @@ int main(int argc, char** argv) {
     double adaptive = 0.0, env_sampling = 0.0;
     bool use_adaptive = false, use_denoise = false;
     int sampler = 0;
+    bool fog = false;
+    double fog_v[5] = {0.0, 1.0, 1.0, 1.0, 0.0};   // density, albedo r g b, g
     long aov_spp = 16;
     uint64_t seed = 1;
     std::string out, assets = "assets";
@@ -48,12 +55,33 @@ int main(int argc, char** argv) {
             else if (v == "sobol") sampler = 1;
             else { std::cerr << "--sampler must be independent or sobol\n"; return 2; }
         }
+        else if (a == "--fog") {
+            // DENSITY[,R,G,B[,G]]: one, four or five numbers, each parsed whole
+            const std::string v = next();
+            std::vector<double> f;
+            bool ok = !v.empty();
+            for (size_t pos = 0; ok && pos <= v.size();) {
+                const size_t comma = std::min(v.find(',', pos), v.size());
+                const std::string tok = v.substr(pos, comma - pos);
+                char* end = nullptr;
+                const double x = strtod(tok.c_str(), &end);
+                ok = !tok.empty() && end == tok.c_str() + tok.size();
+                f.push_back(x);
+                pos = comma + 1;
+            }
+            ok = ok && (f.size() == 1 || f.size() == 4 || f.size() == 5);
+            for (size_t k = 0; ok && k < f.size(); ++k) fog_v[k] = f[k];
+            ok = ok && fog_v[0] > 0.0 && fog_v[0] < std::numeric_limits<double>::infinity() && std::fabs(fog_v[4]) < 1.0;
+            for (int k = 1; k <= 3; ++k) ok = ok && fog_v[k] >= 0.0 && fog_v[k] <= 1.0;
+            if (!ok) { std::cerr << "--fog must be DENSITY[,R,G,B[,G]]: density > 0, albedo channels in [0, 1], |G| < 1\n"; return 2; }
+            fog = true;
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n";
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n";
             return 0;
         } else { std::cerr << "unknown argument " << a << "\n"; return 2; }
     }
@@ -63,6 +91,7 @@ int main(int argc, char** argv) {
     if (use_denoise && use_adaptive) { std::cerr << "--denoise and --adaptive cannot be combined\n"; return 2; }
     if (use_denoise && s < 2) { std::cerr << "--denoise needs at least 2 samples per pixel\n"; return 2; }
     if (use_denoise && aov_spp < 1) { std::cerr << "--aov-spp must be positive\n"; return 2; }
+    if (fog && env_sampling > 0.0) { std::cerr << "--fog and --env-sampling cannot be combined\n"; return 2; }
     if (scene < 1 || scene > 7) return 0;   // `_ => ()` main.rs:643
     pt_ctx* ctx = nullptr;
     if (pt_ctx_create(device, &ctx) != 0) {
@@ -74,6 +103,18 @@ int main(int argc, char** argv) {
         setup.world.float_hdr = float_hdr;
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;
+        if (fog) {
+            const double inf = std::numeric_limits<double>::infinity();
+            Vec3 lo{inf, inf, inf}, hi{-inf, -inf, -inf};
+            setup.world.bounds(lo, hi);
+            const Vec3 grow{0.005 * (hi.x - lo.x), 0.005 * (hi.y - lo.y), 0.005 * (hi.z - lo.z)};   // 1 % larger, about its centre
+            lo = Vec3{lo.x - grow.x, lo.y - grow.y, lo.z - grow.z};
+            hi = Vec3{hi.x + grow.x, hi.y + grow.y, hi.z + grow.z};
+            auto vol = HomogeneousVolume::from_albedo(Cuboid::new_(lo, hi, nullptr), fog_v[0], Vec3{fog_v[1], fog_v[2], fog_v[3]}, fog_v[4]);
+            setup.world.add_object(vol);
+            const Vec3 c = setup.camera.look_from;
+            if (c.x > lo.x && c.x < hi.x && c.y > lo.y && c.y < hi.y && c.z > lo.z && c.z < hi.z) setup.world.camera_medium = vol;
+        }
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();
         std::cerr << "rendering production\n";   // camera.rs:101

@@ -10,10 +10,13 @@
 // Error behaviour follows the reference: asset/handle errors are fatal (Rust: unwrap()/panic;
 // here: std::runtime_error), a failed image save is only reported (camera.rs:118-123).
 #pragma once
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -42,6 +45,7 @@ struct Emitter {
     pt_scene* scene;
     std::string asset_dir;
     std::map<const void*, int> done;
+    int override_mat = -1;   // >= 0: the primitives emitted now carry this material instead of their own (HomogeneousVolume's boundary)
 };
 
 // ---- textures (src/texture.rs) ---------------------------------------------------------
@@ -232,7 +236,13 @@ struct ClearcoatBRDF : BxDFMaterial {   // clearcoat.rs:14-18
 struct Hittable {
     virtual ~Hittable() = default;
     virtual int emit(Emitter& e) const = 0;
+    // grows [lo, hi] by the object's world-space bounds (the role of Hittable::bounding_box; pt_render --fog wraps the world in them)
+    virtual void bounds(Vec3& lo, Vec3& hi) const = 0;
 };
+inline void grow_bounds(Vec3& lo, Vec3& hi, Vec3 p) {
+    lo = Vec3{std::min(lo.x, p.x), std::min(lo.y, p.y), std::min(lo.z, p.z)};
+    hi = Vec3{std::max(hi.x, p.x), std::max(hi.y, p.y), std::max(hi.z, p.z)};
+}
 using HitPtr = std::shared_ptr<Hittable>;
 
 struct Sphere : Hittable {   // sphere.rs:22-46
@@ -247,9 +257,15 @@ struct Sphere : Hittable {   // sphere.rs:22-46
     }
     int emit(Emitter& e) const override {
         const double a[3] = {position1.x, position1.y, position1.z}, b[3] = {position2.x, position2.y, position2.z};
-        int h = pt_sphere(e.scene, radius, a, b, material->emit(e));
+        int h = pt_sphere(e.scene, radius, a, b, e.override_mat >= 0 ? e.override_mat : material->emit(e));
         if (h < 0) panic("Sphere");
         return h;
+    }
+    void bounds(Vec3& lo, Vec3& hi) const override {
+        for (Vec3 c : {position1, position2}) {
+            grow_bounds(lo, hi, Vec3{c.x - radius, c.y - radius, c.z - radius});
+            grow_bounds(lo, hi, Vec3{c.x + radius, c.y + radius, c.z + radius});
+        }
     }
 };
 struct Quad : Hittable {   // quad.rs:17-36
@@ -262,9 +278,13 @@ struct Quad : Hittable {   // quad.rs:17-36
     }
     int emit(Emitter& e) const override {
         const double a[3] = {q.x, q.y, q.z}, b[3] = {u.x, u.y, u.z}, c[3] = {v.x, v.y, v.z};
-        int h = pt_quad(e.scene, a, b, c, material->emit(e));
+        int h = pt_quad(e.scene, a, b, c, e.override_mat >= 0 ? e.override_mat : material->emit(e));
         if (h < 0) panic("Quad");
         return h;
+    }
+    void bounds(Vec3& lo, Vec3& hi) const override {
+        for (int i = 0; i < 4; ++i)
+            grow_bounds(lo, hi, Vec3{q.x + (i & 1) * u.x + (i >> 1) * v.x, q.y + (i & 1) * u.y + (i >> 1) * v.y, q.z + (i & 1) * u.z + (i >> 1) * v.z});
     }
 };
 struct Cuboid : Hittable {   // cuboid.rs:11-58
@@ -277,10 +297,11 @@ struct Cuboid : Hittable {   // cuboid.rs:11-58
     }
     int emit(Emitter& e) const override {
         const double p[3] = {a.x, a.y, a.z}, q[3] = {b.x, b.y, b.z};
-        int h = pt_cuboid(e.scene, p, q, material->emit(e));
+        int h = pt_cuboid(e.scene, p, q, e.override_mat >= 0 ? e.override_mat : material->emit(e));
         if (h < 0) panic("Cuboid");
         return h;
     }
+    void bounds(Vec3& lo, Vec3& hi) const override { grow_bounds(lo, hi, a); grow_bounds(lo, hi, b); }
 };
 // tobj::Mesh as the reference consumes it (mesh.rs:149-170): f32 attributes, u32 position indices
 struct Mesh {
@@ -314,9 +335,13 @@ struct TriangleMesh : Hittable {   // mesh.rs:149-197
     int emit(Emitter& e) const override {
         int h = pt_mesh(e.scene, scale, (uint32_t)(mesh.positions.size() / 3), mesh.positions.data(), (uint32_t)mesh.indices.size(),
                         mesh.indices.data(), (uint32_t)(mesh.normals.size() / 3), mesh.normals.data(),
-                        (uint32_t)(mesh.texcoords.size() / 2), mesh.texcoords.data(), material->emit(e));
+                        (uint32_t)(mesh.texcoords.size() / 2), mesh.texcoords.data(), e.override_mat >= 0 ? e.override_mat : material->emit(e));
         if (h < 0) panic("TriangleMesh");
         return h;
+    }
+    void bounds(Vec3& lo, Vec3& hi) const override {
+        for (size_t i = 0; i + 2 < mesh.positions.size(); i += 3)
+            grow_bounds(lo, hi, Vec3{mesh.positions[i] * scale, mesh.positions[i + 1] * scale, mesh.positions[i + 2] * scale});
     }
 };
 struct Instance : Hittable {   // instance.rs:20-30 — rotate, then translate
@@ -334,6 +359,49 @@ struct Instance : Hittable {   // instance.rs:20-30 — rotate, then translate
         if (h < 0) panic("Instance");
         return h;
     }
+    void bounds(Vec3& lo, Vec3& hi) const override {   // the box of the wrapped object's box, rotated (Rodrigues) and translated
+        const double inf = std::numeric_limits<double>::infinity();
+        Vec3 l{inf, inf, inf}, h{-inf, -inf, -inf};
+        object->bounds(l, h);
+        const double c = std::cos(angle), s = std::sin(angle);
+        for (int i = 0; i < 8; ++i) {
+            const Vec3 p{(i & 1) ? h.x : l.x, (i & 2) ? h.y : l.y, (i & 4) ? h.z : l.z};
+            const double d = axis.x * p.x + axis.y * p.y + axis.z * p.z;
+            const Vec3 x{axis.y * p.z - axis.z * p.y, axis.z * p.x - axis.x * p.z, axis.x * p.y - axis.y * p.x};
+            grow_bounds(lo, hi, Vec3{p.x * c + x.x * s + axis.x * d * (1.0 - c) + translation.x, p.y * c + x.y * s + axis.y * d * (1.0 - c) + translation.y,
+                                     p.z * c + x.z * s + axis.z * d * (1.0 - c) + translation.z});
+        }
+    }
+};
+// HomogeneousVolume of the reference's commented-out volume.rs:15-41: a boundary filled with a medium of constant density and
+// albedo. `g` (Henyey-Greenstein) is this build's addition; 0 is the isotropic phase function the stub names. The boundary's own
+// material is replaced by the medium (pt_mat_medium): it is invisible. A volume without a boundary serves as World::camera_medium
+// alone — an unbounded fog.
+struct HomogeneousVolume : Hittable {
+    HitPtr boundary;
+    double density = 1.0, g = 0.0;
+    Vec3 albedo;
+    static std::shared_ptr<HomogeneousVolume> from_albedo(HitPtr boundary, double density, Vec3 albedo, double g = 0.0) {
+        auto v = std::make_shared<HomogeneousVolume>();
+        v->boundary = boundary; v->density = density; v->albedo = albedo; v->g = g;
+        return v;
+    }
+    int medium(Emitter& e) const {   // the medium's material handle
+        auto it = e.done.find(this);
+        if (it != e.done.end()) return it->second;
+        int h = pt_mat_medium(e.scene, density, albedo.x, albedo.y, albedo.z, g);
+        if (h < 0) panic("HomogeneousVolume");
+        return e.done[this] = h;
+    }
+    int emit(Emitter& e) const override {
+        if (!boundary) panic("HomogeneousVolume without a boundary in the world");
+        const int saved = e.override_mat;
+        e.override_mat = medium(e);
+        const int h = boundary->emit(e);
+        e.override_mat = saved;
+        return h;
+    }
+    void bounds(Vec3& lo, Vec3& hi) const override { if (boundary) boundary->bounds(lo, hi); }
 };
 
 // ---- World (src/hittable/world.rs:10-29) -------------------------------------------------
@@ -352,9 +420,15 @@ struct World {
         for (auto& o : objects) if (pt_world_add_object(s, o->emit(e)) != 0) panic("World::add_object");
         for (auto& l : lights) if (pt_world_add_light(s, l->emit(e)) != 0) panic("World::add_light");
         if (env) env->emit(e);
+        if (camera_medium && pt_scene_set_camera_medium(s, camera_medium->medium(e)) != 0) panic("World::camera_medium");
         if (pt_world_build(s) != 0) panic("World::build_bvh");
         scene = s;
         handles = e.done;
+    }
+    std::shared_ptr<HomogeneousVolume> camera_medium;   // the medium camera rays start in (pt_scene_set_camera_medium); null = none
+    void bounds(Vec3& lo, Vec3& hi) const {             // of objects and lights
+        for (auto& o : objects) o->bounds(lo, hi);
+        for (auto& l : lights) l->bounds(lo, hi);
     }
     bool float_hdr = false;   // this build's option: Radiance .hdr images keep their f32 samples (no .to_rgb8(), texture.rs:67)
     int sampler = 0;             // this build's option: 0 independent draws (the reference's), 1 Owen-scrambled Sobol (pt_scene_set_sampler)
