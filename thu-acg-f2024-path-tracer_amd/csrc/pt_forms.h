@@ -1,0 +1,65 @@
+// Which forms of k_shade and k_init exist, which translation unit compiles them, and how a run-time ShadeForm (pt_kernels.h) becomes a
+// kernel pointer. A new feature flag is one more bool in ShadeForm, one clause in shade_form_exists and, if its forms want a unit of
+// their own, one more value of form_unit with its accessor.
+#pragma once
+#include <utility>
+
+#include "pt_k3_shade.h"
+
+namespace pt {
+
+typedef void (*shade_fn)(SceneD, CamD, PoolD, CountersD*, uint64_t, EnvTabD);
+typedef void (*init_fn)(CamD, PoolD, uint64_t);
+typedef void (*aov_fn)(SceneD, CamD, uint64_t, uint32_t, uint32_t, double*, uint32_t);
+
+// THE list of k_shade's shapes: variant code = sort * 10 + min waves per SIMD -> k_shade<SORT, MINW, LIGHTS, KB, PER, ...>
+struct ShadeShape { int variant; bool sort; int minw, kb, per; };   // KB threads per block; a sorted block takes windows of KB * PER slots
+constexpr ShadeShape SHADE_SHAPES[] = {
+    {2, false, 2, BLOCK, 8},                                  // unsorted — row 0 is also what an unknown code given through PT_SHADE_VARIANT gets
+    {3, false, 3, BLOCK, 8},
+    {12, true, 2, BLOCK, 8},                                  // sorted, 2048-slot windows
+    {13, true, 3, BLOCK, 8},
+    {22, true, 2, 512, 8},                                    // sorted, 512 threads / 4096-slot windows
+    {32, true, 2, 512, 16},                                   // the same over 8192-slot windows
+    {42, true, 2, 512, 16},                                   // 32 or 22 per launch (launch_shade); its occupancy is asked on the 8192-slot shape
+    {52, true, 2, BLOCK, 16},                                 // A/B: 256 threads over 4096-slot windows (window size vs block size)
+};
+constexpr int N_SHADE_SHAPES = sizeof(SHADE_SHAPES) / sizeof(SHADE_SHAPES[0]);
+constexpr int shade_row(int variant, int i = N_SHADE_SHAPES - 1) { return i == 0 || SHADE_SHAPES[i].variant == variant ? i : shade_row(variant, i - 1); }
+// THE list of feature combinations: pixel list / ENV / QMC / MED exist only for the default variant's shapes, ENV never with MED
+constexpr bool shade_form_exists(const ShadeShape& s, bool list, bool env, bool qmc, bool med) {
+    return (s.variant == 22 || s.variant == 32 || s.variant == 42 || !(list || env || qmc || med)) && !(env && med);
+}
+// the unit that compiles a form: pt_k3.hip, pt_k3_qmc.hip or pt_k3_med.hip (§12)
+enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED };
+constexpr FormUnit form_unit(bool qmc, bool med) { return med ? UNIT_MED : qmc ? UNIT_QMC : UNIT_PLAIN; }
+
+// run-time bools -> template arguments: f is called with one std::bool_constant per bool
+template <class F> auto expand_bools(F&& f) { return f(); }
+template <class F, class... Rest> auto expand_bools(F&& f, bool b, Rest... rest) {
+    return b ? expand_bools([&](auto... tail) { return f(std::true_type{}, tail...); }, rest...)
+             : expand_bools([&](auto... tail) { return f(std::false_type{}, tail...); }, rest...);
+}
+
+// The kernels of unit U for a form; null where the form does not exist or belongs to another unit. Every unit instantiates exactly the
+// forms it owns by compiling unit_forms<its U>.
+struct FormKernels { shade_fn shade; init_fn init; aov_fn aov; };   // (k_aov / k_aov_qmc are not templates: the unit's accessor names its own)
+template <FormUnit U, int ROW, bool LIGHTS, bool LIST, bool ENV, bool QMC, bool MED> shade_fn shade_kernel() {
+    constexpr ShadeShape S = SHADE_SHAPES[ROW];
+    if constexpr (shade_form_exists(S, LIST, ENV, QMC, MED) && form_unit(QMC, MED) == U) return k_shade<S.sort, S.minw, LIGHTS, S.kb, S.per, LIST, ENV, QMC, MED>;
+    else return nullptr;
+}
+template <FormUnit U, size_t... ROW> shade_fn shade_of(const ShadeForm& f, std::index_sequence<ROW...>) {
+    shade_fn k = nullptr;
+    ((shade_row(f.variant) == (int)ROW ? k = expand_bools([](auto... b) { return shade_kernel<U, (int)ROW, decltype(b)::value...>(); }, f.lights, f.list, f.env, f.qmc, f.med) : k), ...);
+    return k;
+}
+template <FormUnit U> FormKernels unit_forms(const ShadeForm& f, aov_fn aov) {
+    return FormKernels{shade_of<U>(f, std::make_index_sequence<N_SHADE_SHAPES>{}),
+                       expand_bools([](auto list, auto qmc, auto med) -> init_fn { if constexpr (form_unit(qmc, med) == U) return k_init<list, qmc, med>; else return nullptr; },
+                                    f.list, f.qmc, f.med), aov};
+}
+// the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip) — the only calls from one kernel unit into another
+FormKernels forms_plain(const ShadeForm& f), forms_qmc(const ShadeForm& f), forms_med(const ShadeForm& f);
+
+}  // namespace pt

@@ -1,40 +1,42 @@
-// Host-callable launchers of the HIP kernels in pt_kernels.hip.
+// Host-callable launchers of the HIP kernels: one per stage. K2 is in pt_k2.hip, K1 / K3 / the AOV walk in pt_k3.hip (their Sobol forms in
+// pt_k3_qmc.hip, their media forms in pt_k3_med.hip), the small kernels in pt_kernels.hip.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include "pt_types.h"
 
 namespace pt {
-// qmc (launch_init, launch_shade, launch_aov, kernel_occupancy_blocks): the Sobol sampler's forms (pt_scene_set_sampler). They live in
-// pt_kernels_qmc.hip — pt_kernels.hip compiled a second time for those forms alone — and cover the default k_shade variant's two shapes:
-// launch_shade maps any other variant to 42, as for pixel lists and environment sampling.
-// med (launch_init, launch_shade, kernel_occupancy_blocks): participating media are in effect: the MED forms, in
-// pt_kernels_med.hip — the default variant's two shapes like the QMC forms, with or without qmc, never with env.
-void launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc = false, bool med = false);
-void launch_init_med(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, bool qmc);
-const void* pick_shade_med(int variant /* 22 or 32 */, bool lights, bool list, bool qmc);
+// What a render asks of K1 / K3 / the AOV walk. variant: k_shade's shape code (pt_forms.h SHADE_SHAPES; PT_SHADE_VARIANT); lights: the scene
+// has a lights list; list: pixel-list render (PoolD::list); env: environment sampling; qmc: the Sobol sampler
+// (pt_scene_set_sampler, §11); med: participating media are in effect (§12). Which combinations exist: pt_forms.h shade_form_exists.
+struct ShadeForm { int variant; bool lights, list, env, qmc, med; };
+// The form a render gets: pixel lists, env, qmc and med exist for the default variant's shapes only — any other variant becomes 42.
+// The launchers and queries below take the form this returns.
+ShadeForm shade_form(ShadeForm asked);
+// whether the form's k_shade sorts its windows by class (the shading-order output, PoolD::reorder, needs the sort's positions)
+bool shade_form_sorts(const ShadeForm& form);
+// The launchers that take a form return false, having launched nothing, when no kernel of that form exists.
+bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, const ShadeForm& form);
+// K2 variant code (`code` of launch_extend / extend_occupancy_blocks): -1 = batch kernel (-2 / -3 ask extend_occupancy_blocks for its
+// flat-top-level instantiation without / with pair passes), -(stack*10 + blocks) = two-phase kernel k_extend2<stack, blocks> for stack in {16, 20, 24}.
+void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st);
+// wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
+// env: the environment-sampling tables of a form with `env`, else null
+bool launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, const ShadeForm& form, hipStream_t st,
+                  uint32_t wide_window_min = 16, const EnvTabD* env = nullptr);
+// resident blocks per CU of the K2 / K3 kernel a render launches (shade: 0 when no kernel of that form exists)
+int extend_occupancy_blocks(int code);
+int shade_occupancy_blocks(const ShadeForm& form);
 // pt_medium_probe: the medium functions k_shade's MED forms call (which 0: n x (u1, u2, dir.xyz) -> n x (new_dir.xyz, ph); 1: n x u ->
 // n free-flight distances); in / out: device
 void launch_medium_probe(int which, double density, double g, const double* in, uint32_t n, double* out, hipStream_t st);
-void launch_init_qmc(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st);
-const void* pick_shade_qmc(int variant /* 22 or 32 */, bool lights, bool list, bool env);
-void launch_aov_qmc(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
-                    hipStream_t st);
 // pt_sampler_probe: the 64-bit values of single draws, by the draw functions the kernels call (kind 0: Rng, 1: RngQ); out: device
 void launch_sampler_probe(int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin, uint32_t n_draws, uint64_t* out,
                           hipStream_t st);
-void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st);
-// wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
-// env: the environment-sampling tables or null. Non-null launches k_shade's ENV forms (the default variant's two shapes:
-// any other variant is mapped to 42, as for pixel lists).
-void launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, int variant,
-                  hipStream_t st, uint32_t wide_window_min = 16, const EnvTabD* env = nullptr, bool qmc = false, bool med = false);
 // pt_envmap.hip: the environment-sampling tables of image texture `tex` (device TexD values; col: H * (W + 1), row: H + 1 doubles),
 // and the probe behind pt_env_probe (which 0: (u1, u2) pairs -> {dir.xyz, pdf}; 1: directions -> env_pdf)
 void launch_env_tables(const SceneD& sc, const TexD& tex, double* col, double* row, hipStream_t st);
 void launch_env_probe(const SceneD& sc, const TexD& tex, const EnvTabD& e, int which, const double* in, uint32_t n, double* out, hipStream_t st);
-// whether the k_shade variant sorts its windows by class (the shading-order output, PoolD::reorder, needs the sort's positions)
-bool shade_variant_sorts(int variant);
 void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_t st);
 // the frame's end (dynamic mode): live slots beyond new_end move into dead slots below it; holes / movers: scratch lists of `cap` entries, counts: 2 words
 void launch_compact(const PoolD& pool, uint32_t new_end, uint32_t* holes, uint32_t* movers, uint32_t* counts, uint32_t cap, int max_blocks, hipStream_t st);
@@ -48,15 +50,11 @@ void launch_quantise_counts(const double* accum, uint32_t n_pixels, const uint32
 uint32_t adapt_select_blocks(uint32_t width, uint32_t height);   // entries of launch_adapt_select's block_counts
 void launch_quantise(const double* accum, uint32_t n, double scale, uint8_t* rgb8, hipStream_t st);
 void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out, hipStream_t st);
-// pt_render_aovs: first-hit feature sums of samples [spp_begin, spp_end) of every pixel (aov: device, 8 doubles per pixel)
-void launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
-                hipStream_t st, bool qmc = false);
+// pt_render_aovs: first-hit feature sums of samples [spp_begin, spp_end) of every pixel (aov: device, 8 doubles per pixel); of `form`, qmc matters
+bool launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
+                hipStream_t st, const ShadeForm& form);
 // pt_denoise.hip: the a-trous denoiser (see there). Device buffers; tmp: 12 doubles per pixel of scratch
 void launch_denoise(uint32_t width, uint32_t height, const double* sum_a, double n_a, const double* sum_b, double n_b, const double* aov, double n_aov,
                     uint32_t iterations, double sigma_l, double sigma_z, double* tmp, double* out, hipStream_t st);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);
-// K2 variant code (`code` of launch_extend / `variant` of kernel_occupancy_blocks): -1 = batch kernel (-2 asks
-// kernel_occupancy_blocks for its flat-top-level instantiation), -(stack*10 + blocks) = two-phase kernel
-// k_extend2<stack, blocks> for stack in {16, 20, 24}.
-int kernel_occupancy_blocks(int which, int variant, bool lights = false, bool list = false, bool env = false, bool qmc = false, bool med = false);   // qmc: k_shade's Sobol form   // env: k_shade's ENV form   // lights: k_shade's instantiation for scenes with a lights list; list: its pixel-list form (variant 22, 32 or 42)   // 0 = extend, 1 = shade; resident blocks per CU
 }  // namespace pt

@@ -318,11 +318,12 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
     const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
-    if ((list || env_on || qmc || med) && shade_variant != 22 && shade_variant != 32) shade_variant = 42;   // the pixel-list / ENV / QMC forms of k_shade (launch_shade)
+    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med});   // the form of k_init / k_shade that exists for it
+    shade_variant = form.variant;
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
     // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
-    const bool ordered = dynamic && !list && shade_variant_sorts(shade_variant) && !exp_env("PT_POOL_IN_PLACE");
+    const bool ordered = dynamic && !list && shade_form_sorts(form) && !exp_env("PT_POOL_IN_PLACE");
     // one allocation: the two record arrays (RayRec, PathRec), the static mode's f64 arrays, the two u32 state arrays (+ the output area)
     const size_t n_al = ((size_t)n_slots + 8191) & ~(size_t)8191;   // whole windows: 2048 slots (k_extend2, k_shade) / 4096 (k_shade with 512 threads)
     const size_t n_f64 = dynamic ? 0 : 6;   // the per-slot sample sums and radiances exist in the static mode only (the dynamic mode adds into the frame)
@@ -428,7 +429,8 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         if (!strcmp(e, "batch")) extend_code = -1;
         else if (!strcmp(e, "twophase") && extend2_code() != 0) extend_code = -extend2_code();
     }
-    const int blocks_extend = kernel_occupancy_blocks(0, extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = kernel_occupancy_blocks(1, shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med);
+    const int blocks_extend = extend_occupancy_blocks(extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = shade_occupancy_blocks(form);
+    if (blocks_shade < 1) return set_error("pt_render: no k_shade form for this combination of pixel list, environment sampling, sampler and media");
     const int grid_extend = ctx->n_cus * blocks_extend * mult, grid_shade = ctx->n_cus * blocks_shade * mult;
 
     pool.accum = d_accum;
@@ -465,7 +467,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     t0 = std::chrono::steady_clock::now();
 
     timer.begin(2, st);
-    launch_init(dc, pool, seed, grid_shade, st, qmc, med);
+    if (!launch_init(dc, pool, seed, grid_shade, st, form)) return set_error("pt_render: no k_init form for this render");
     timer.end(st);
     uint64_t iterations = 0;
     const uint64_t per_slot = dynamic ? (total_work + n_slots - 1) / std::max<uint64_t>(n_slots, 1) + 1 : (spp + k - 1) / k;
@@ -488,7 +490,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             launch_extend(s->dev.view, pool, s->d_counters, grid_extend, extend_code, st);
             timer.end(st);
             timer.begin(1, st);
-            launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, shade_variant, st, wide_window_min, env_on ? &env : nullptr, qmc, med);
+            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, form, st, wide_window_min, env_on ? &env : nullptr)) return set_error("pt_render: no k_shade form for this render");
             timer.end(st);
             if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
                 std::swap(pool.ray, pool.ray_out);
@@ -821,7 +823,8 @@ extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, 
         d_aov = own.p;
         if (!opts.overwrite && !hip_ok(hipMemcpyAsync(d_aov, aov, bytes, hipMemcpyHostToDevice, st), "hipMemcpy(aov)")) return -1;
     }
-    launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, s->sampler == 1);
+    if (!launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, ShadeForm{0, false, false, false, s->sampler == 1, false}))
+        return set_error("pt_render_aovs: no k_aov form for this sampler");
     if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
     if (!opts.accum_on_device && !hip_ok(hipMemcpyAsync(aov, d_aov, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(aov)")) return -1;
     return hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(aov)") ? 0 : -1;

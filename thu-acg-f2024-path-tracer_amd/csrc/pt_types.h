@@ -9,7 +9,7 @@ namespace pt {
 // ---- BVH -----------------------------------------------------------------------------
 // One node format for the top-level tree (over world objects) and every per-mesh tree.
 // Boxes are stored as f32 rounded OUTWARD from the padded f64 bounds (conservative); the slab
-// test runs in f32 with a per-ray error margin (pt_kernels.hip, slab_f32) — box tests only have
+// test runs in f32 with a per-ray error margin (pt_k_trace.h, slab_f32) — box tests only have
 // to be conservative, the f64 primitive tests decide the result. 64 B = four 16-B loads per visit.
 // Child reference (32 bit):
 //   00xx.. internal node index
