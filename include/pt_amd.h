@@ -191,6 +191,41 @@ int pt_mat_light(pt_scene*, int emission_tex);                          /* Diffu
  * A miss inside an unbounded medium is only reached through d >= +inf, i.e. never: such a path scatters until roulette or the
  * depth bound ends it. pt_render_aovs and pt_intersect see a boundary as an ordinary first hit (albedo (1, 1, 1)). */
 int pt_mat_medium(pt_scene*, double density, double r, double g, double b, double hg_g);
+/* ---- grid-density participating media: smoke plumes, clouds, uneven haze (no counterpart in the reference) ----
+ * A medium whose extinction varies in space: sigma(x) = scale * V(x), V the trilinear interpolation of a 3-D grid of f32 samples.
+ * The handle is a medium material like pt_mat_medium's and works wherever that one does: carried by a closed object (its boundary),
+ * or set with pt_scene_set_camera_medium — then, with no boundary object, an unbounded medium that is empty outside the grid's box.
+ * Every refusal of pt_mat_medium applies (handle limit 4094, no mix child, no lights list); (r, g, b) and hg_g as there.
+ * values[(k * ny + j) * nx + i] is the sample at the centre of cell (i, j, k) of the world-space axis-aligned box [box_lo, box_hi];
+ * the values are copied. Returns -1, creating nothing, when: scale is not finite or not > 0; a value is negative or not finite; all
+ * values are 0; some n_a < 2; nx * ny * nz > 2^28; box_lo[a] >= box_hi[a] or a box coordinate is not finite; the albedo or hg_g is
+ * outside pt_mat_medium's ranges; or the majorant optical diagonal scale * max(values) * |box_hi - box_lo| exceeds 4096 — a design
+ * limit that bounds the expected trip count of the longest tracking loop a lane can run (a medium that thick is opaque: model it as
+ * a surface).
+ * Grid media are IN EFFECT for a render when some world object's material is one or the camera medium is one; otherwise every
+ * render runs exactly the kernels it ran before they existed, and a homogeneous medium keeps pt_mat_medium's rule and bits either way.
+ * Not supported, besides pt_mat_medium's list, which carries over unchanged: a grid that follows an instance's transform or a moving
+ * sphere — the grid is fixed in world space whatever carries the medium.
+ *
+ * Density, all in f64. For x outside the box (any x_a < lo_a or x_a > hi_a; a NaN coordinate counts as outside): sigma(x) = 0.
+ * Inside, per axis a with c_a = (double)n_a / (hi_a - lo_a):  q_a = (x_a - lo_a) * c_a - 0.5, clamped to [0, n_a - 1];
+ * i_a = min(floor(q_a), n_a - 2); f_a = q_a - i_a. With v_xyz the sample at (i_x + x, i_y + y, i_z + z) widened to f64, every blend
+ * written as lerp(a, b, f) = a + f * (b - a):  x pairs first: c_yz = lerp(v_0yz, v_1yz, f_x); then y: c_z = lerp(c_0z, c_1z, f_y);
+ * then z: V = lerp(c_0, c_1, f_z).  sigma(x) = scale * V.  The majorant is mu = scale * (double)max(values).
+ *
+ * Estimator: step 1 of pt_mat_medium's rule when m is a grid medium; steps 2-4, the "miss while m is bounded" exception before any
+ * draw, the boundary toggle and roulette are unchanged. With o, dir, t the resolved segment (t = +inf on a miss):
+ *   Clip to the box by the slab test: start from near = 0, far = t. Per axis with dir_a != 0: inv = 1 / dir_a, ta = (lo_a - o_a) * inv,
+ *   tb = (hi_a - o_a) * inv; near = max(near, min(ta, tb)), far = min(far, max(ta, tb)). An axis with dir_a == 0 changes nothing when
+ *   lo_a <= o_a <= hi_a and empties the interval otherwise. [t0, t1] = [near, far]. Unless t0 < t1 and t1 is finite — and always when
+ *   a component of o or dir is not finite — no draw is made and the surface or miss is processed.
+ *   Otherwise s = t0 and repeat: a single draw u, s += -log(1 - u) / mu (the deterministic log); if s >= t1 there is no collision:
+ *   the surface or miss is processed unweighted; else a single draw v: if v * mu < sigma(o + s * dir), a MEDIUM VERTEX at o + s * dir
+ *   (step 2, with the medium's albedo and g); else continue.
+ * Both draws are single draws (not pair-aligned under the Sobol sampler). A miss inside an UNBOUNDED grid medium is reachable: the
+ * ray leaves the box without a collision and the environment is added. pt_render_aovs and pt_intersect do not change. */
+int pt_mat_medium_grid(pt_scene*, double scale, double r, double g, double b, double hg_g, uint32_t nx, uint32_t ny, uint32_t nz, const float* values,
+                       const double box_lo[3], const double box_hi[3]);
 int pt_scene_set_camera_medium(pt_scene*, int mat);
 int pt_scene_camera_medium(pt_scene*);
 /* the three bsdf/ materials no reference scene instantiates */
@@ -370,7 +405,9 @@ int pt_sampler_probe(pt_ctx*, int kind, uint64_t seed, uint32_t pixel, uint32_t 
 
 /* the device functions of participating media that k_shade calls (pt_mat_medium's rule), for medium material `mat`:
  * which = 0: in = n x (u1, u2, dir.xyz), out = n x (w.xyz, ph(dot(dir, w))); which = 1: in = n x u, out = n free-flight distances.
- * The world need not be built. */
+ * For a grid medium (pt_mat_medium_grid's rule; -1 for a medium without a grid): which = 2: in = n points xyz, out = n sigma values;
+ * which = 3: in = n x (o.xyz, dir.xyz, t), |dir| <= 1 (else -1); row i is tracked with the independent sampler's draws of (seed 0,
+ * pixel i, sample 0) from draw 0; out = n x (collided 0 / 1, s or 0, draws consumed). The world need not be built. */
 int pt_medium_probe(pt_scene*, int mat, int which, const double* in, uint32_t n, double* out);
 
 #ifdef __cplusplus

@@ -124,6 +124,7 @@ ABI_SYMBOLS = [
     "pt_render_pixels", "pt_adaptive_schedule", "pt_render_adaptive", "pt_resolve_u8_counts",
     "pt_render_aovs", "pt_denoise",
     "pt_mat_medium", "pt_scene_set_camera_medium", "pt_scene_camera_medium", "pt_medium_probe",
+    "pt_mat_medium_grid",
 ]
 
 
@@ -164,6 +165,9 @@ def _load():
         lib.pt_scene_set_camera_medium.argtypes = [C.c_void_p, C.c_int]
         lib.pt_scene_camera_medium.argtypes = [C.c_void_p]
         lib.pt_medium_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "pt_mat_medium_grid"):         # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_mat_medium_grid.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -432,8 +436,22 @@ class Scene:
         (the rule is in include/pt_amd.h)."""
         return _check(lib.pt_mat_medium(self.handle, float(density), float(albedo[0]), float(albedo[1]), float(albedo[2]), float(g)), "mat_medium")
 
+    def mat_medium_grid(self, scale: float, albedo, g: float, values: np.ndarray, box_lo, box_hi):
+        """A participating medium whose density varies in space (a smoke plume, a cloud): sigma_t(x) = scale * V(x), V the trilinear
+        interpolation of `values`, a float32 array of shape (nz, ny, nx) of samples at the cell centres of the world-space box
+        [box_lo, box_hi] (copied); 0 outside the box. Used like a mat_medium handle: on a closed object, or as the camera medium
+        (unbounded). Sampled by delta tracking (the rule is in include/pt_amd.h)."""
+        values = np.asarray(values)
+        if values.ndim != 3:
+            raise PtError("mat_medium_grid: values must have shape (nz, ny, nx)")
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        nz, ny, nx = values.shape
+        lo, hi = (C.c_double * 3)(*[float(v) for v in box_lo]), (C.c_double * 3)(*[float(v) for v in box_hi])
+        return _check(lib.pt_mat_medium_grid(self.handle, float(scale), float(albedo[0]), float(albedo[1]), float(albedo[2]), float(g), nx, ny, nz,
+                                             values.ctypes.data, lo, hi), "mat_medium_grid")
+
     def set_camera_medium(self, mat: int):
-        """The medium camera rays start in (a mat_medium handle; -1 = none, the default)."""
+        """The medium camera rays start in (a mat_medium / mat_medium_grid handle; -1 = none, the default)."""
         return _check(lib.pt_scene_set_camera_medium(self.handle, int(mat)), "set_camera_medium")
 
     def camera_medium(self) -> int:
@@ -441,9 +459,12 @@ class Scene:
 
     def medium_probe(self, mat: int, which: int, arr: np.ndarray) -> np.ndarray:
         """The device functions of medium `mat` that the kernels call. which 0: arr = (n, 5) (u1, u2, dir.xyz) -> (n, 4)
-        {new_dir.xyz, ph}; which 1: arr = (n,) unit draws -> (n,) free-flight distances."""
-        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, 5) if which == 0 else (-1,))
-        out = np.empty((len(arr), 4) if which == 0 else (len(arr),), dtype=np.float64)
+        {new_dir.xyz, ph}; which 1: arr = (n,) unit draws -> (n,) free-flight distances. A mat_medium_grid medium also has which 2:
+        arr = (n, 3) points -> (n,) sigma_t, and which 3: arr = (n, 7) (o.xyz, dir.xyz, t) -> (n, 3) {collided 0/1, s or 0, draws
+        consumed}, row i tracked with the independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0."""
+        cols_in, cols_out = {0: (5, 4), 1: (None, None), 2: (3, None), 3: (7, 3)}.get(which, (None, None))
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, cols_in) if cols_in else (-1,))
+        out = np.empty((len(arr), cols_out) if cols_out else (len(arr),), dtype=np.float64)
         _check(lib.pt_medium_probe(self.handle, int(mat), which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_medium_probe")
         return out
 

@@ -26,13 +26,15 @@ constexpr ShadeShape SHADE_SHAPES[] = {
 };
 constexpr int N_SHADE_SHAPES = sizeof(SHADE_SHAPES) / sizeof(SHADE_SHAPES[0]);
 constexpr int shade_row(int variant, int i = N_SHADE_SHAPES - 1) { return i == 0 || SHADE_SHAPES[i].variant == variant ? i : shade_row(variant, i - 1); }
-// THE list of feature combinations: pixel list / ENV / QMC / MED exist only for the default variant's shapes, ENV never with MED
-constexpr bool shade_form_exists(const ShadeShape& s, bool list, bool env, bool qmc, bool med) {
-    return (s.variant == 22 || s.variant == 32 || s.variant == 42 || !(list || env || qmc || med)) && !(env && med);
+// THE list of feature combinations: pixel list / ENV / QMC / MED exist only for the default variant's shapes, ENV never with MED,
+// HET (grid-density media) only with MED
+constexpr bool shade_form_exists(const ShadeShape& s, bool list, bool env, bool qmc, bool med, bool het = false) {
+    return (s.variant == 22 || s.variant == 32 || s.variant == 42 || !(list || env || qmc || med)) && !(env && med) && (med || !het);
 }
-// the unit that compiles a form: pt_k3.hip, pt_k3_qmc.hip or pt_k3_med.hip (§12)
-enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED };
-constexpr FormUnit form_unit(bool qmc, bool med) { return med ? UNIT_MED : qmc ? UNIT_QMC : UNIT_PLAIN; }
+// the unit that compiles a form: pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip (§12) or pt_k3_het.hip (§13). K1 has no HET
+// form — a camera ray's bounce word is the MED form's — so a HET render's k_init is the one of the form without het (form_kernels).
+enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED, UNIT_HET };
+constexpr FormUnit form_unit(bool qmc, bool med, bool het = false) { return het ? UNIT_HET : med ? UNIT_MED : qmc ? UNIT_QMC : UNIT_PLAIN; }
 
 // run-time bools -> template arguments: f is called with one std::bool_constant per bool
 template <class F> auto expand_bools(F&& f) { return f(); }
@@ -44,14 +46,14 @@ template <class F, class... Rest> auto expand_bools(F&& f, bool b, Rest... rest)
 // The kernels of unit U for a form; null where the form does not exist or belongs to another unit. Every unit instantiates exactly the
 // forms it owns by compiling unit_forms<its U>.
 struct FormKernels { shade_fn shade; init_fn init; aov_fn aov; };   // (k_aov / k_aov_qmc are not templates: the unit's accessor names its own)
-template <FormUnit U, int ROW, bool LIGHTS, bool LIST, bool ENV, bool QMC, bool MED> shade_fn shade_kernel() {
+template <FormUnit U, int ROW, bool LIGHTS, bool LIST, bool ENV, bool QMC, bool MED, bool HET> shade_fn shade_kernel() {
     constexpr ShadeShape S = SHADE_SHAPES[ROW];
-    if constexpr (shade_form_exists(S, LIST, ENV, QMC, MED) && form_unit(QMC, MED) == U) return k_shade<S.sort, S.minw, LIGHTS, S.kb, S.per, LIST, ENV, QMC, MED>;
+    if constexpr (shade_form_exists(S, LIST, ENV, QMC, MED, HET) && form_unit(QMC, MED, HET) == U) return k_shade<S.sort, S.minw, LIGHTS, S.kb, S.per, LIST, ENV, QMC, MED, HET>;
     else return nullptr;
 }
 template <FormUnit U, size_t... ROW> shade_fn shade_of(const ShadeForm& f, std::index_sequence<ROW...>) {
     shade_fn k = nullptr;
-    ((shade_row(f.variant) == (int)ROW ? k = expand_bools([](auto... b) { return shade_kernel<U, (int)ROW, decltype(b)::value...>(); }, f.lights, f.list, f.env, f.qmc, f.med) : k), ...);
+    ((shade_row(f.variant) == (int)ROW ? k = expand_bools([](auto... b) { return shade_kernel<U, (int)ROW, decltype(b)::value...>(); }, f.lights, f.list, f.env, f.qmc, f.med, f.het) : k), ...);
     return k;
 }
 template <FormUnit U> FormKernels unit_forms(const ShadeForm& f, aov_fn aov) {
@@ -59,7 +61,7 @@ template <FormUnit U> FormKernels unit_forms(const ShadeForm& f, aov_fn aov) {
                        expand_bools([](auto list, auto qmc, auto med) -> init_fn { if constexpr (form_unit(qmc, med) == U) return k_init<list, qmc, med>; else return nullptr; },
                                     f.list, f.qmc, f.med), aov};
 }
-// the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip) — the only calls from one kernel unit into another
-FormKernels forms_plain(const ShadeForm& f), forms_qmc(const ShadeForm& f), forms_med(const ShadeForm& f);
+// the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip, pt_k3_het.hip) — the only calls from one kernel unit into another
+FormKernels forms_plain(const ShadeForm& f), forms_qmc(const ShadeForm& f), forms_med(const ShadeForm& f), forms_het(const ShadeForm& f);
 
 }  // namespace pt

@@ -186,7 +186,10 @@ struct NoPrefetch {
 // the scene) is at a MEDIUM VERTEX — no surface code runs for it; B1 draws roulette, selector and a light or Henyey-Greenstein
 // direction, B2 the phase function, the MIS density and the next ray. A lane that reached a medium's BOUNDARY toggles its medium and
 // continues straight on. Every other lane is the bounce above bit for bit. Never together with ENV (pt_render refuses it).
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false>
+// HET (only with MED): a grid-density medium is in effect (the rule in pt_amd.h). A path whose medium has a grid makes
+// phase A's free flight by delta tracking (grid_track: a lane-divergent loop, nothing sorts around it); a homogeneous medium and every
+// other lane are the MED form bit for bit.
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
@@ -269,7 +272,18 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                     // than t_min to an offset entry point, at an edge of a cuboid or mesh). No draw; the miss is processed.
                     med = 0u;
                 } else {
-                    const double d = medium_free_flight(rng_f64(rng), medium.density);
+                    double d = D_INF;                                  // the distance to the medium vertex, +inf: none
+                    bool tracked = false;
+                    if constexpr (HET) {
+                        const uint32_t grid = (uint32_t)sc.mats[med - 1u].p[6];   // the medium's row of SceneD::grids + 1, 0 = homogeneous
+                        if (grid != 0u) {                              // delta tracking through the grid, clipped to its box
+                            const GridTrack tr = grid_track(sc.grids + (grid - 1u), sc.grid_vals, ray.o, ray.d, surface ? hit.dist : D_INF, rng);
+                            rng.draw = tr.draw;
+                            if (tr.collided) d = tr.s;
+                            tracked = true;
+                        }
+                    }
+                    if (!tracked) d = medium_free_flight(rng_f64(rng), medium.density);
                     if (d < (surface ? hit.dist : D_INF)) {
                         scatter = true;
                         hit.point = ray.o + ray.d * d;
@@ -570,7 +584,9 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // QMC: the Sobol sampler (shade_slot)
 // MED: participating media (shade_slot). A slot's class says nothing certain about a path inside a medium — it may scatter before the
 // hit, or instead of leaving — so these forms do not request work items a group ahead.
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false, bool MED = false>
+// HET: grid-density media (shade_slot)
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false, bool MED = false,
+          bool HET = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
     const int lane = (int)(threadIdx.x & 63u);
@@ -586,7 +602,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -763,7 +779,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

@@ -318,7 +318,8 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
     const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
-    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med});   // the form of k_init / k_shade that exists for it
+    const bool het = med && s->grid_media_on();   // a grid-density medium is in effect: the HET forms of k_shade
+    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het});   // the form of k_init / k_shade that exists for it
     shade_variant = form.variant;
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
@@ -936,23 +937,42 @@ extern "C" int pt_env_probe(pt_scene* s, const pt_camera* cam, int which, const 
 extern "C" int pt_medium_probe(pt_scene* s, int mat, int which, const double* in, uint32_t n, double* out) {
     if (!s || !s->ctx) return set_error("pt_medium_probe: null scene");
     if (mat < 0 || (size_t)mat >= s->mats.size() || s->mats[mat].kind != MAT_MEDIUM) return set_error("pt_medium_probe: not a medium material");
-    if (which != 0 && which != 1) return set_error("pt_medium_probe: which must be 0 or 1");
+    if (which < 0 || which > 3) return set_error("pt_medium_probe: which must be 0, 1, 2 or 3");
+    const bool grid = which >= 2;
+    if (grid && s->mats[mat].p[6] == 0.0) return set_error("pt_medium_probe: which 2 and 3 need a grid-density medium (pt_mat_medium_grid)");
     if (n == 0) return 0;
     if (!in || !out) return set_error("pt_medium_probe: null buffer");
+    static const size_t IN_COLS[4] = {5, 1, 3, 7}, OUT_COLS[4] = {4, 1, 1, 3};
+    const size_t n_in = (size_t)n * IN_COLS[which], n_out = (size_t)n * OUT_COLS[which];
+    if (which == 3)   // the loop's expected trip count is bounded for unit directions (pt_mat_medium_grid): longer ones are refused
+        for (uint32_t i = 0; i < n; ++i) {
+            const double* d = in + 7 * (size_t)i + 3;
+            if (!(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= 1.0 + 1e-9)) return set_error("pt_medium_probe: which 3 takes directions of length <= 1");
+        }
     pt_ctx* ctx = s->ctx;
     if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    const size_t n_in = (size_t)n * (which == 0 ? 5 : 1), n_out = (size_t)n * (which == 0 ? 4 : 1);
     double *d_i = nullptr, *d_o = nullptr;
+    GridD* d_g = nullptr;
+    float* d_v = nullptr;
     bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double)), "hipMalloc") &&
               hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    if (ok && grid) {   // the medium's own grid, uploaded for the call (the world need not be built)
+        const HostGrid& hg = s->grids[(size_t)s->mats[mat].p[6] - 1];
+        ok = hip_ok(hipMalloc((void**)&d_g, sizeof(GridD)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_v, hg.vals.size() * sizeof(float)), "hipMalloc") &&
+             hip_ok(hipMemcpyAsync(d_g, &hg.d, sizeof(GridD), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipMemcpyAsync(d_v, hg.vals.data(), hg.vals.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    }
     if (ok) {
-        launch_medium_probe(which, s->mats[mat].p[0], s->mats[mat].p[1], d_i, n, d_o, ctx->stream);
+        if (grid) launch_grid_probe(which, d_g, d_v, d_i, n, d_o, ctx->stream);
+        else launch_medium_probe(which, s->mats[mat].p[0], s->mats[mat].p[1], d_i, n, d_o, ctx->stream);
         ok = hip_ok(hipGetLastError(), "kernel launch") &&
              hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
              hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     }
     if (d_i) (void)hipFree(d_i);
     if (d_o) (void)hipFree(d_o);
+    if (d_g) (void)hipFree(d_g);
+    if (d_v) (void)hipFree(d_v);
     return ok ? 0 : -1;
 }
 

@@ -219,6 +219,53 @@ extern "C" int pt_mat_medium(pt_scene* s, double density, double r, double g, do
     m.p[2] = r; m.p[3] = g; m.p[4] = b;
     return push_mat(s, m);
 }
+// A medium whose extinction is scale * V(x), V trilinear in a grid of f32 samples (the rule is in pt_amd.h): the same material kind,
+// with its row of the grid table in p[6] and its majorant in p[0]
+extern "C" int pt_mat_medium_grid(pt_scene* s, double scale, double r, double g, double b, double hg_g, uint32_t nx, uint32_t ny, uint32_t nz, const float* values,
+                                  const double box_lo[3], const double box_hi[3]) {
+    if (!s) return set_error("pt_mat_medium_grid: null scene");
+    if (!values || !box_lo || !box_hi) return set_error("pt_mat_medium_grid: null argument");
+    if (!(scale > 0.0) || !std::isfinite(scale)) return set_error("pt_mat_medium_grid: scale must be finite and > 0");
+    for (double a : {r, g, b})
+        if (!(a >= 0.0 && a <= 1.0)) return set_error("pt_mat_medium_grid: each albedo channel must be in [0, 1]");
+    if (!(std::fabs(hg_g) < 1.0)) return set_error("pt_mat_medium_grid: |hg_g| must be below 1");
+    if (nx < 2 || ny < 2 || nz < 2) return set_error("pt_mat_medium_grid: every grid dimension must be at least 2");
+    if ((uint64_t)nx * ny > (1ull << 28) || (uint64_t)nx * ny * nz > (1ull << 28)) return set_error("pt_mat_medium_grid: more than 2^28 grid values");
+    double diag2 = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(box_lo[a]) || !std::isfinite(box_hi[a]) || !(box_lo[a] < box_hi[a])) return set_error("pt_mat_medium_grid: the box must be finite with box_lo < box_hi on every axis");
+        diag2 += (box_hi[a] - box_lo[a]) * (box_hi[a] - box_lo[a]);
+    }
+    const size_t n = (size_t)nx * ny * nz;
+    float vmax = 0.0f;
+    for (size_t i = 0; i < n; ++i) {
+        if (!(values[i] >= 0.0f) || !std::isfinite(values[i])) return set_error("pt_mat_medium_grid: every value must be finite and >= 0");
+        vmax = std::max(vmax, values[i]);
+    }
+    if (!(vmax > 0.0f)) return set_error("pt_mat_medium_grid: all values are 0 (no medium)");
+    const double mu = scale * (double)vmax;
+    // a design limit: the expected trip count of the longest tracking loop a lane can run (the box's diagonal at the majorant)
+    if (!(mu * std::sqrt(diag2) <= 4096.0)) return set_error("pt_mat_medium_grid: the majorant optical diagonal scale * max(values) * |box_hi - box_lo| exceeds 4096 (model a medium that thick as a surface)");
+    if (s->mats.size() >= MEDIUM_MAX_MATS) return set_error("pt_mat_medium_grid: a medium's material handle must be below 4094 (create media before other materials)");
+    HostGrid hg;
+    hg.d.nx = nx; hg.d.ny = ny; hg.d.nz = nz;
+    const uint32_t dims[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; ++a) {
+        hg.d.lo[a] = box_lo[a];
+        hg.d.hi[a] = box_hi[a];
+        hg.d.cells[a] = (double)dims[a] / (box_hi[a] - box_lo[a]);
+    }
+    hg.d.scale = scale;
+    hg.d.mu = mu;
+    hg.vals.assign(values, values + n);
+    s->grids.push_back(std::move(hg));
+    MatD m = blank_mat(MAT_MEDIUM);
+    m.p[0] = mu;
+    m.p[1] = hg_g;
+    m.p[2] = r; m.p[3] = g; m.p[4] = b;
+    m.p[6] = (double)s->grids.size();
+    return push_mat(s, m);
+}
 extern "C" int pt_scene_set_camera_medium(pt_scene* s, int mat) {
     if (!s) return set_error("pt_scene_set_camera_medium: null scene");
     if (mat != -1 && (!MAT_OK(s, mat) || s->mats[mat].kind != MAT_MEDIUM)) return set_error("pt_scene_set_camera_medium: not a medium material (-1 = none)");
@@ -764,10 +811,11 @@ int pt::scene_build(pt_scene* s) {
     }
     if (prims.size() >= (size_t)HIT_ID_MASK - 4) return set_error("pt_world_build: too many primitives (28-bit ids)");
     // (a medium's boundary sorts with glass — the other kind that sends the ray on — so that K2's result word keeps its classes: pt_types.h)
-    s->world_has_medium = false;
+    s->world_has_medium = s->world_has_grid_medium = false;
     for (PrimRef& pr : prims) {
         const uint32_t kind = s->mats[pr.mat].kind;
         s->world_has_medium = s->world_has_medium || kind == MAT_MEDIUM;
+        s->world_has_grid_medium = s->world_has_grid_medium || (kind == MAT_MEDIUM && s->mats[pr.mat].p[6] != 0.0);
         pr.kind |= (kind == MAT_MEDIUM ? MEDIUM_SORT_KIND : kind) << PRIM_MAT_KIND_SHIFT;
     }
     std::vector<Box> entry_boxes(tlas_items.size());
@@ -855,6 +903,13 @@ int pt::scene_build(pt_scene* s) {
             cuboid_box.push_back(cb);
             entry_box.push_back(eb);
         }
+    std::vector<GridD> grids;          // the grid-density media's table and their samples, one array
+    std::vector<float> grid_vals;
+    for (const HostGrid& hg : s->grids) {
+        grids.push_back(hg.d);
+        grids.back().ofs = grid_vals.size();
+        grid_vals.insert(grid_vals.end(), hg.vals.begin(), hg.vals.end());
+    }
     SceneD v{};
     DeviceBuffers& dev = s->dev;
     bool ok = upload(dev, nodes, v.nodes) && upload(dev, entries, v.entries) && upload(dev, prims, v.prims) &&
@@ -862,6 +917,7 @@ int pt::scene_build(pt_scene* s) {
               upload(dev, tri_gid, v.tri_gid) && upload(dev, insts, v.insts) && upload(dev, tex, v.tex) &&
               upload(dev, mats, v.mats) && upload(dev, atlas, v.atlas) && upload(dev, atlas_f, v.atlas_f) && upload(dev, lights, v.lights) && upload(dev, entry_box, v.entry_box) && upload(dev, cuboid_box, v.cuboid_box);
     if (ok && any_attr) ok = upload(dev, tri_attr, v.tri_attr);
+    if (ok && !grids.empty()) ok = upload(dev, grids, v.grids) && upload(dev, grid_vals, v.grid_vals);
     if (!ok) {
         dev.release();
         return -1;

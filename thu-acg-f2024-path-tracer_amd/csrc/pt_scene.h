@@ -48,6 +48,11 @@ struct HostObj {
     // may wrap an instance (Instance::new / World::add_object take an Arc<dyn Hittable>, instance.rs:20-30, world.rs:18-24).
 };
 
+struct HostGrid {                   // one grid-density medium (pt_mat_medium_grid): its descriptor (ofs filled at upload) and its samples
+    GridD d{};
+    std::vector<float> vals;
+};
+
 struct DeviceBuffers {
     std::vector<void*> allocs;
     SceneD view{};
@@ -95,6 +100,13 @@ struct pt_scene {
     int camera_medium = -1;
     bool world_has_medium = false;
     bool media_on() const { return world_has_medium || camera_medium >= 0; }   // "in effect": the kernels' MED forms run
+    // grid-density media (pt_mat_medium_grid): MatD::p[6] of a medium = its index here + 1. world_has_grid_medium (set by
+    // scene_build): some world object's material is one.
+    std::vector<pt::HostGrid> grids;
+    bool world_has_grid_medium = false;
+    bool grid_media_on() const {   // "in effect": the kernels' HET forms run
+        return world_has_grid_medium || (camera_medium >= 0 && mats[camera_medium].p[6] != 0.0);
+    }
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned

@@ -111,6 +111,8 @@ enum MatKind : uint32_t { MAT_DIFFUSE = 0, MAT_METAL = 1, MAT_GLASS = 2, MAT_PRI
                           // Henyey-Greenstein g, p[2..4] = the single-scattering albedo, p[5] = 1 when a world object carries it (scene_build). Not one of the MAT_KINDS sort classes: the
                           // primitives of a medium's boundary carry MAT_GLASS in PrimRef::kind (MEDIUM_SORT_KIND), so K2's result word
                           // and the default k_shade forms' sort stay what they were; only k_shade's MED forms look at MatD::kind.
+                          // A grid-density medium (pt_mat_medium_grid) is the same kind with p[6] = its row of SceneD::grids + 1
+                          // (0 = homogeneous) and p[0] = its majorant mu; only k_shade's HET forms and the probe read p[6].
                           MAT_MEDIUM = 9 };
 constexpr uint32_t MEDIUM_SORT_KIND = MAT_GLASS;
 // The medium a path is in travels in the upper bits of its record's bounce word (RayRec's in the compact layout, else PathRec's):
@@ -134,6 +136,16 @@ struct MatD {
     // MAT_DIFFUSE / METAL / GLASS / PRINCIPLED / LIGHT; a mix's children are looked up the long way.
     uint32_t color_solid, rough_solid;
     double color_v[3], rough_v;
+};
+
+// One grid-density medium (pt_mat_medium_grid; the rule is in include/pt_amd.h): sigma(x) = scale * V(x), V the trilinear
+// blend of the f32 samples vals[ofs + (k*ny + j)*nx + i] at the cell centres of the world-space box [lo, hi]. cells[a] = n_a / (hi_a - lo_a);
+// mu = scale * max(values), the majorant delta tracking runs at.
+struct GridD {
+    uint32_t nx, ny, nz, pad;
+    uint64_t ofs;            // first value of this grid in SceneD::grid_vals
+    double lo[3], hi[3], cells[3];
+    double scale, mu;
 };
 
 // ---- camera --------------------------------------------------------------------------
@@ -183,6 +195,8 @@ struct SceneD {
     const EntryBox* entry_box;   // the flat top level's walk list: one record per entry, NON-MESH entries first (each group in entry order)
     uint32_t tlas_flat;          // n_entries <= TLAS_FLAT_MAX: K2 walks the entry list instead of the top-level tree
     uint32_t flat_pairs;         // tlas_flat and the scene has cuboids: the batch K2 runs its (ray, primitive) pair passes
+    const GridD* grids;          // grid-density media (MatD::p[6] - 1 indexes it); read by k_shade's HET forms and the medium probe only
+    const float* grid_vals;      // their f32 samples, one array (GridD::ofs)
 };
 constexpr uint32_t TLAS_FLAT_MAX = 24;   // round 1 (vector loads): 8-10 entries -26 % / -7 % K2 time, 17 entries (scene 5) +20 % -> limit 12;
                                           // round 2 (scalar loads, ldu): 17 entries -20 % -> limit raised

@@ -5,7 +5,9 @@
 // --adaptive T [--min-spp M] (adaptive sampling to the noise target T, pt_render_adaptive; --spp is then the cap),
 // --denoise [--aov-spp N] (two half-frames + first-hit AOVs over min(N, spp) samples through pt_denoise; N defaults to 16),
 // --fog DENSITY[,R,G,B[,G]] (the built world's bounds, grown by 1 %, become the boundary of a homogeneous medium of that density,
-// albedo (default 1,1,1) and Henyey-Greenstein g (default 0); the camera starts inside it when look_from lies inside).
+// albedo (default 1,1,1) and Henyey-Greenstein g (default 0); the camera starts inside it when look_from lies inside),
+// --smoke SCALE[,R,G,B[,G]] (a fixed closed-form plume, smoke_plume below, sampled into a 64^3 grid over the box --fog would build, as an
+// unbounded grid-density camera medium of extinction SCALE * V).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -18,6 +20,34 @@
 
 using namespace path_tracer;
 
+// The plume of --smoke at the normalised position (x, y, z) in [0, 1]^3 of the box, y up: a column that rises from the floor's centre,
+// sways, widens and thins:  cx = 0.5 + 0.08 sin(3 pi y),  cz = 0.5 + 0.08 cos(2 pi y),  r = 0.06 + 0.22 y,
+//   V = (1 - 0.7 y) * exp(-((x - cx)^2 + (z - cz)^2) / r^2)
+static double smoke_plume(double x, double y, double z) {
+    const double pi = 3.14159265358979323846;
+    const double cx = 0.5 + 0.08 * std::sin(3.0 * pi * y), cz = 0.5 + 0.08 * std::cos(2.0 * pi * y), r = 0.06 + 0.22 * y;
+    return (1.0 - 0.7 * y) * std::exp(-((x - cx) * (x - cx) + (z - cz) * (z - cz)) / (r * r));
+}
+// STRENGTH[,R,G,B[,G]] of --fog / --smoke: one, four or five numbers, each parsed whole; strength > 0, albedo in [0, 1], |G| < 1
+static bool parse_medium(const std::string& v, double out[5]) {
+    std::vector<double> f;
+    bool ok = !v.empty();
+    for (size_t pos = 0; ok && pos <= v.size();) {
+        const size_t comma = std::min(v.find(',', pos), v.size());
+        const std::string tok = v.substr(pos, comma - pos);
+        char* end = nullptr;
+        const double x = strtod(tok.c_str(), &end);
+        ok = !tok.empty() && end == tok.c_str() + tok.size();
+        f.push_back(x);
+        pos = comma + 1;
+    }
+    ok = ok && (f.size() == 1 || f.size() == 4 || f.size() == 5);
+    for (size_t k = 0; ok && k < f.size(); ++k) out[k] = f[k];
+    ok = ok && out[0] > 0.0 && out[0] < std::numeric_limits<double>::infinity() && std::fabs(out[4]) < 1.0;
+    for (int k = 1; k <= 3; ++k) ok = ok && out[k] >= 0.0 && out[k] <= 1.0;
+    return ok;
+}
+
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
@@ -27,6 +57,8 @@ int main(int argc, char** argv) {
     int sampler = 0;
     bool fog = false;
     double fog_v[5] = {0.0, 1.0, 1.0, 1.0, 0.0};   // density, albedo r g b, g
+    bool smoke = false;
+    double smoke_v[5] = {0.0, 1.0, 1.0, 1.0, 0.0};   // scale, albedo r g b, g
     long aov_spp = 16;
     uint64_t seed = 1;
     std::string out, assets = "assets";
@@ -56,32 +88,23 @@ int main(int argc, char** argv) {
             else { std::cerr << "--sampler must be independent or sobol\n"; return 2; }
         }
         else if (a == "--fog") {
-            // DENSITY[,R,G,B[,G]]: one, four or five numbers, each parsed whole
-            const std::string v = next();
-            std::vector<double> f;
-            bool ok = !v.empty();
-            for (size_t pos = 0; ok && pos <= v.size();) {
-                const size_t comma = std::min(v.find(',', pos), v.size());
-                const std::string tok = v.substr(pos, comma - pos);
-                char* end = nullptr;
-                const double x = strtod(tok.c_str(), &end);
-                ok = !tok.empty() && end == tok.c_str() + tok.size();
-                f.push_back(x);
-                pos = comma + 1;
-            }
-            ok = ok && (f.size() == 1 || f.size() == 4 || f.size() == 5);
-            for (size_t k = 0; ok && k < f.size(); ++k) fog_v[k] = f[k];
-            ok = ok && fog_v[0] > 0.0 && fog_v[0] < std::numeric_limits<double>::infinity() && std::fabs(fog_v[4]) < 1.0;
-            for (int k = 1; k <= 3; ++k) ok = ok && fog_v[k] >= 0.0 && fog_v[k] <= 1.0;
-            if (!ok) { std::cerr << "--fog must be DENSITY[,R,G,B[,G]]: density > 0, albedo channels in [0, 1], |G| < 1\n"; return 2; }
+            if (!parse_medium(next(), fog_v)) { std::cerr << "--fog must be DENSITY[,R,G,B[,G]]: density > 0, albedo channels in [0, 1], |G| < 1\n"; return 2; }
             fog = true;
+        }
+        else if (a == "--smoke") {
+            if (!parse_medium(next(), smoke_v)) { std::cerr << "--smoke must be SCALE[,R,G,B[,G]]: scale > 0, albedo channels in [0, 1], |G| < 1\n"; return 2; }
+            smoke = true;
         }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n";
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n"
+                         "  --smoke: an unbounded grid-density camera medium of extinction SCALE * V over the world's bounds grown by 1 % (the box --fog fills),\n"
+                         "           V sampled at the centres of 64^3 cells; at the normalised position (x, y, z) of the box, y up:\n"
+                         "           cx = 0.5 + 0.08 sin(3 pi y), cz = 0.5 + 0.08 cos(2 pi y), r = 0.06 + 0.22 y,\n"
+                         "           V = (1 - 0.7 y) exp(-((x - cx)^2 + (z - cz)^2) / r^2)\n";
             return 0;
         } else { std::cerr << "unknown argument " << a << "\n"; return 2; }
     }
@@ -92,6 +115,8 @@ int main(int argc, char** argv) {
     if (use_denoise && s < 2) { std::cerr << "--denoise needs at least 2 samples per pixel\n"; return 2; }
     if (use_denoise && aov_spp < 1) { std::cerr << "--aov-spp must be positive\n"; return 2; }
     if (fog && env_sampling > 0.0) { std::cerr << "--fog and --env-sampling cannot be combined\n"; return 2; }
+    if (smoke && env_sampling > 0.0) { std::cerr << "--smoke and --env-sampling cannot be combined\n"; return 2; }
+    if (smoke && fog) { std::cerr << "--smoke and --fog cannot be combined\n"; return 2; }
     if (scene < 1 || scene > 7) return 0;   // `_ => ()` main.rs:643
     pt_ctx* ctx = nullptr;
     if (pt_ctx_create(device, &ctx) != 0) {
@@ -103,17 +128,26 @@ int main(int argc, char** argv) {
         setup.world.float_hdr = float_hdr;
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;
-        if (fog) {
+        if (fog || smoke) {
             const double inf = std::numeric_limits<double>::infinity();
             Vec3 lo{inf, inf, inf}, hi{-inf, -inf, -inf};
             setup.world.bounds(lo, hi);
             const Vec3 grow{0.005 * (hi.x - lo.x), 0.005 * (hi.y - lo.y), 0.005 * (hi.z - lo.z)};   // 1 % larger, about its centre
             lo = Vec3{lo.x - grow.x, lo.y - grow.y, lo.z - grow.z};
             hi = Vec3{hi.x + grow.x, hi.y + grow.y, hi.z + grow.z};
-            auto vol = HomogeneousVolume::from_albedo(Cuboid::new_(lo, hi, nullptr), fog_v[0], Vec3{fog_v[1], fog_v[2], fog_v[3]}, fog_v[4]);
-            setup.world.add_object(vol);
-            const Vec3 c = setup.camera.look_from;
-            if (c.x > lo.x && c.x < hi.x && c.y > lo.y && c.y < hi.y && c.z > lo.z && c.z < hi.z) setup.world.camera_medium = vol;
+            if (fog) {
+                auto vol = HomogeneousVolume::from_albedo(Cuboid::new_(lo, hi, nullptr), fog_v[0], Vec3{fog_v[1], fog_v[2], fog_v[3]}, fog_v[4]);
+                setup.world.add_object(vol);
+                const Vec3 c = setup.camera.look_from;
+                if (c.x > lo.x && c.x < hi.x && c.y > lo.y && c.y < hi.y && c.z > lo.z && c.z < hi.z) setup.world.camera_medium = vol;
+            } else {   // no boundary: the density is 0 outside the box, so the grid serves as the medium of all space
+                constexpr uint32_t N = 64;
+                std::vector<float> v((size_t)N * N * N);
+                for (uint32_t k = 0; k < N; ++k)
+                    for (uint32_t j = 0; j < N; ++j)
+                        for (uint32_t i = 0; i < N; ++i) v[((size_t)k * N + j) * N + i] = (float)smoke_plume((i + 0.5) / N, (j + 0.5) / N, (k + 0.5) / N);
+                setup.world.camera_medium = HeterogeneousVolume::from_grid(nullptr, smoke_v[0], Vec3{smoke_v[1], smoke_v[2], smoke_v[3]}, smoke_v[4], N, N, N, std::move(v), lo, hi);
+            }
         }
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();

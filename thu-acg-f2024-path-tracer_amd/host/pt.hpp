@@ -373,28 +373,21 @@ struct Instance : Hittable {   // instance.rs:20-30 — rotate, then translate
         }
     }
 };
-// HomogeneousVolume of the reference's commented-out volume.rs:15-41: a boundary filled with a medium of constant density and
-// albedo. `g` (Henyey-Greenstein) is this build's addition; 0 is the isotropic phase function the stub names. The boundary's own
-// material is replaced by the medium (pt_mat_medium): it is invisible. A volume without a boundary serves as World::camera_medium
-// alone — an unbounded fog.
-struct HomogeneousVolume : Hittable {
+// A participating medium and the closed object that bounds it. The boundary's own material is replaced by the medium: it is invisible.
+// A volume without a boundary serves as World::camera_medium alone — an unbounded medium.
+struct Volume : Hittable {
     HitPtr boundary;
-    double density = 1.0, g = 0.0;
-    Vec3 albedo;
-    static std::shared_ptr<HomogeneousVolume> from_albedo(HitPtr boundary, double density, Vec3 albedo, double g = 0.0) {
-        auto v = std::make_shared<HomogeneousVolume>();
-        v->boundary = boundary; v->density = density; v->albedo = albedo; v->g = g;
-        return v;
-    }
+    virtual int create(Emitter& e) const = 0;   // the medium's material (pt_mat_medium / pt_mat_medium_grid), or -1
+    virtual const char* name() const = 0;
     int medium(Emitter& e) const {   // the medium's material handle
         auto it = e.done.find(this);
         if (it != e.done.end()) return it->second;
-        int h = pt_mat_medium(e.scene, density, albedo.x, albedo.y, albedo.z, g);
-        if (h < 0) panic("HomogeneousVolume");
+        int h = create(e);
+        if (h < 0) panic(name());
         return e.done[this] = h;
     }
     int emit(Emitter& e) const override {
-        if (!boundary) panic("HomogeneousVolume without a boundary in the world");
+        if (!boundary) panic(std::string(name()) + " without a boundary in the world");
         const int saved = e.override_mat;
         e.override_mat = medium(e);
         const int h = boundary->emit(e);
@@ -402,6 +395,41 @@ struct HomogeneousVolume : Hittable {
         return h;
     }
     void bounds(Vec3& lo, Vec3& hi) const override { if (boundary) boundary->bounds(lo, hi); }
+};
+// HomogeneousVolume of the reference's commented-out volume.rs:15-41: a boundary filled with a medium of constant density and
+// albedo. `g` (Henyey-Greenstein) is this build's addition; 0 is the isotropic phase function the stub names (pt_mat_medium).
+struct HomogeneousVolume : Volume {
+    double density = 1.0, g = 0.0;
+    Vec3 albedo;
+    static std::shared_ptr<HomogeneousVolume> from_albedo(HitPtr boundary, double density, Vec3 albedo, double g = 0.0) {
+        auto v = std::make_shared<HomogeneousVolume>();
+        v->boundary = boundary; v->density = density; v->albedo = albedo; v->g = g;
+        return v;
+    }
+    int create(Emitter& e) const override { return pt_mat_medium(e.scene, density, albedo.x, albedo.y, albedo.z, g); }
+    const char* name() const override { return "HomogeneousVolume"; }
+};
+// No counterpart in the reference: a medium whose density is scale * V(x), V trilinear in an nx x ny x nz grid of samples at the cell
+// centres of the world-space box [box_lo, box_hi] (values[(k * ny + j) * nx + i]; pt_mat_medium_grid). The grid is fixed
+// in world space whatever carries the medium.
+struct HeterogeneousVolume : Volume {
+    double scale = 1.0, g = 0.0;
+    Vec3 albedo, box_lo, box_hi;
+    uint32_t nx = 0, ny = 0, nz = 0;
+    std::vector<float> values;
+    static std::shared_ptr<HeterogeneousVolume> from_grid(HitPtr boundary, double scale, Vec3 albedo, double g, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                          std::vector<float> values, Vec3 box_lo, Vec3 box_hi) {
+        auto v = std::make_shared<HeterogeneousVolume>();
+        v->boundary = boundary; v->scale = scale; v->albedo = albedo; v->g = g;
+        v->nx = nx; v->ny = ny; v->nz = nz; v->values = std::move(values); v->box_lo = box_lo; v->box_hi = box_hi;
+        return v;
+    }
+    int create(Emitter& e) const override {
+        if (values.size() != (size_t)nx * ny * nz) return pt_set_error_message("HeterogeneousVolume: values must hold nx * ny * nz samples");
+        const double lo[3] = {box_lo.x, box_lo.y, box_lo.z}, hi[3] = {box_hi.x, box_hi.y, box_hi.z};
+        return pt_mat_medium_grid(e.scene, scale, albedo.x, albedo.y, albedo.z, g, nx, ny, nz, values.data(), lo, hi);
+    }
+    const char* name() const override { return "HeterogeneousVolume"; }
 };
 
 // ---- World (src/hittable/world.rs:10-29) -------------------------------------------------
@@ -425,7 +453,7 @@ struct World {
         scene = s;
         handles = e.done;
     }
-    std::shared_ptr<HomogeneousVolume> camera_medium;   // the medium camera rays start in (pt_scene_set_camera_medium); null = none
+    std::shared_ptr<Volume> camera_medium;   // the medium camera rays start in (pt_scene_set_camera_medium); null = none
     void bounds(Vec3& lo, Vec3& hi) const {             // of objects and lights
         for (auto& o : objects) o->bounds(lo, hi);
         for (auto& l : lights) l->bounds(lo, hi);
