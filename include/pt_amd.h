@@ -159,8 +159,8 @@ int pt_mat_light(pt_scene*, int emission_tex);                          /* Diffu
  * Media are IN EFFECT for a render when some world object's material is a medium or the camera medium is set; otherwise every
  * entry point runs exactly the kernels it ran before media existed (a medium material nothing uses does not count).
  * Not supported: nested or overlapping media (leaving ANY boundary puts the path into "no medium"), boundaries that touch or lie
- * within 2e-3 of each other, chromatic density, textured albedo, emission from media; a transmissive object inside a medium is
- * treated as filled by it. Environment importance sampling together with media in effect: the render returns -1. max_depth must
+ * within 2e-3 of each other, chromatic density (chromatic absorption: pt_mat_medium_tinted), textured albedo, emission from media;
+ * a transmissive object inside a medium is treated as filled by it (a glass object with a medium of its own: pt_mat_glass_set_interior). Environment importance sampling together with media in effect: the render returns -1. max_depth must
  * be below 2^20 then.
  *
  * The estimator: analog tracking with the reference's one-sample MIS. Each path carries m, a medium or none; a camera ray starts with
@@ -228,6 +228,45 @@ int pt_mat_medium_grid(pt_scene*, double scale, double r, double g, double b, do
                        const double box_lo[3], const double box_hi[3]);
 int pt_scene_set_camera_medium(pt_scene*, int mat);
 int pt_scene_camera_medium(pt_scene*);
+/* ---- interior media and chromatic absorption: coloured glass, whisky, tea, milk, wax, jade (no counterpart in the reference, whose
+ * GlassBSDF::eval ignores base_color) ----
+ * pt_mat_medium_tinted: a homogeneous medium like pt_mat_medium's with an extra absorption coefficient per channel. density >= 0 and
+ * finite (0 = no scattering, pure absorption; pt_mat_medium itself goes on refusing 0); albedo and hg_g as in pt_mat_medium, also when
+ * density is 0; each absorption[c] finite and >= 0; density + max(absorption) > 0. pt_mat_medium's handle limit (4094) and its mix and
+ * lights refusals apply. A refused call returns -1 and creates nothing. There is no tinted grid medium.
+ * pt_mat_glass_set_interior: the medium that fills objects of glass material glass_mat: medium_mat = any medium handle (homogeneous,
+ * tinted or grid), or -1 to detach. Returns -1 and leaves the setting when glass_mat is not a pt_mat_glass handle, when medium_mat is
+ * neither a medium nor -1, or when the glass is a child of a mix; pt_mat_mix with a child that has an interior returns -1. The world
+ * must be (re)built after the call. pt_mat_glass_interior: the medium handle, or -1.
+ * Media are IN EFFECT for a render (pt_mat_medium) also when a world object's material is a glass whose interior is set. The code of
+ * this section runs only when some world object's glass has an interior, or a tinted medium is the material of a world object or the
+ * camera medium; otherwise every render launches exactly the kernels it launched before and produces the same bits (a tinted medium
+ * nothing uses, or an interior set and detached again, does not count). An interior medium is bounded — an object carries it — so
+ * step 1's exception applies to it unchanged: a miss while inside resets the medium. pt_scene_set_camera_medium(interior) puts the
+ * camera inside such a body.
+ *
+ * The rule: additions to pt_mat_medium's steps. No step makes a new draw; draw indices and Sobol pair alignment do not move.
+ *  Absorption, in step 1, before anything else at this visit uses the throughput. At the start of the visit m is a tinted medium with
+ *    coefficients a_c; l is the distance travelled on this segment: d at a medium vertex, otherwise t, +inf on a miss (traced rays are
+ *    unit length). For each channel with a_c > 0: thr_c *= exp(-(a_c * l)), with the deterministic exp of pt_detmath.h and the product
+ *    formed first; a channel with a_c == 0 is not touched (no 0 * inf). So the emission of a light hit inside the medium, the
+ *    environment on a miss and the roulette probability are attenuated. When density == 0, step 1 makes no draw and d = +inf; a miss
+ *    inside an unbounded density-0 medium is reachable and its absorbed channels arrive as exactly 0. The lost-crossing reset (a miss
+ *    while m is bounded: m becomes none) happens first, and that segment is not attenuated.
+ *  Interior, in step 4, at a surface hit whose own material is a glass with interior k. The hit is processed exactly as without one
+ *    (roulette, selector, light or BSDF direction, eval / pdf, the offset e = 1e-3 * signum(dot(dir, gn))), with one addition: the
+ *    bounce CROSSED the surface when signum(dot(dir, gn)) is not NaN and equals signum(dot(ray.d, gn)) — the continued ray starts on
+ *    the side the incoming ray was heading to. That covers refraction, and a lights-list direction that happens to go through. On a
+ *    crossing at a front-face hit (HitInfo::front_face, which glass uses for eta): m = k; at a back-face hit: m = none. Without a
+ *    crossing (reflection outside, internal reflection inside) m is kept. Front face, not step 3's toggle: glass needs correct
+ *    winding for its eta anyway, and the state heals itself at the next crossing after a lost one.
+ *  The free flight and the absorption inside the body are step 1 of the next visit, unchanged.
+ * Not supported, besides pt_mat_medium's list: a glass with an interior that stands inside another medium (entering forgets the outer
+ * medium, leaving gives "no medium"); hollow or nested glass shells; interiors on principled or mix materials; a grid interior that
+ * moves with an instance (as for pt_mat_medium_grid). pt_render_aovs does not change: glass stays albedo (1, 1, 1). */
+int pt_mat_medium_tinted(pt_scene*, double density, double r, double g, double b, double hg_g, const double absorption[3]);
+int pt_mat_glass_set_interior(pt_scene*, int glass_mat, int medium_mat);
+int pt_mat_glass_interior(pt_scene*, int glass_mat);
 /* the three bsdf/ materials no reference scene instantiates */
 int pt_mat_mix(pt_scene*, double t, int mat1, int mat2);                /* MixBxDf::new mix.rs:14-20; a child may itself be a mix of non-mix materials (two levels) */
 int pt_mat_sheen(pt_scene*, double r, double g, double b, double sheen_tint);   /* SheenBRDF::new sheen.rs:17-22 */
@@ -407,7 +446,8 @@ int pt_sampler_probe(pt_ctx*, int kind, uint64_t seed, uint32_t pixel, uint32_t 
  * which = 0: in = n x (u1, u2, dir.xyz), out = n x (w.xyz, ph(dot(dir, w))); which = 1: in = n x u, out = n free-flight distances.
  * For a grid medium (pt_mat_medium_grid's rule; -1 for a medium without a grid): which = 2: in = n points xyz, out = n sigma values;
  * which = 3: in = n x (o.xyz, dir.xyz, t), |dir| <= 1 (else -1); row i is tracked with the independent sampler's draws of (seed 0,
- * pixel i, sample 0) from draw 0; out = n x (collided 0 / 1, s or 0, draws consumed). The world need not be built. */
+ * pixel i, sample 0) from draw 0; out = n x (collided 0 / 1, s or 0, draws consumed). which = 4 (any medium; pt_mat_medium_tinted's
+ * rule): in = n segment lengths, out = n x 3 factors exp(-(a_c * l)), exactly 1 where a_c == 0. The world need not be built. */
 int pt_medium_probe(pt_scene*, int mat, int which, const double* in, uint32_t n, double* out);
 
 #ifdef __cplusplus

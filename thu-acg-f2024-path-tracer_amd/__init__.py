@@ -125,6 +125,7 @@ ABI_SYMBOLS = [
     "pt_render_aovs", "pt_denoise",
     "pt_mat_medium", "pt_scene_set_camera_medium", "pt_scene_camera_medium", "pt_medium_probe",
     "pt_mat_medium_grid",
+    "pt_mat_medium_tinted", "pt_mat_glass_set_interior", "pt_mat_glass_interior",
 ]
 
 
@@ -168,6 +169,10 @@ def _load():
     if hasattr(lib, "pt_mat_medium_grid"):         # (absent from an older build in an A/B run: PT_AMD_LIB)
         lib.pt_mat_medium_grid.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(lib, "pt_mat_medium_tinted"):       # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_mat_medium_tinted.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
+        lib.pt_mat_glass_set_interior.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.pt_mat_glass_interior.argtypes = [C.c_void_p, C.c_int]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -450,8 +455,24 @@ class Scene:
         return _check(lib.pt_mat_medium_grid(self.handle, float(scale), float(albedo[0]), float(albedo[1]), float(albedo[2]), float(g), nx, ny, nz,
                                              values.ctypes.data, lo, hi), "mat_medium_grid")
 
+    def mat_medium_tinted(self, density: float, albedo=(1.0, 1.0, 1.0), g: float = 0.0, absorption=(0.0, 0.0, 0.0)):
+        """A homogeneous medium with an absorption coefficient per channel on top of its scattering (coloured glass, tea, wax):
+        density >= 0 (0 = no scattering, pure Beer-Lambert absorption), albedo and g as mat_medium, absorption >= 0 per channel and
+        density + max(absorption) > 0 (the rule is in include/pt_amd.h)."""
+        a = (C.c_double * 3)(*[float(v) for v in absorption])
+        return _check(lib.pt_mat_medium_tinted(self.handle, float(density), float(albedo[0]), float(albedo[1]), float(albedo[2]), float(g), a),
+                      "mat_medium_tinted")
+
+    def mat_glass_set_interior(self, glass_mat: int, medium_mat: int):
+        """The medium that fills objects of glass material `glass_mat` (any medium handle; -1 detaches): a path enters it when it
+        refracts in, keeps it under internal reflection and leaves it when it refracts out. Rebuild the world after."""
+        return _check(lib.pt_mat_glass_set_interior(self.handle, int(glass_mat), int(medium_mat)), "mat_glass_set_interior")
+
+    def mat_glass_interior(self, glass_mat: int) -> int:
+        return lib.pt_mat_glass_interior(self.handle, int(glass_mat))
+
     def set_camera_medium(self, mat: int):
-        """The medium camera rays start in (a mat_medium / mat_medium_grid handle; -1 = none, the default)."""
+        """The medium camera rays start in (a mat_medium / mat_medium_tinted / mat_medium_grid handle; -1 = none, the default)."""
         return _check(lib.pt_scene_set_camera_medium(self.handle, int(mat)), "set_camera_medium")
 
     def camera_medium(self) -> int:
@@ -461,8 +482,9 @@ class Scene:
         """The device functions of medium `mat` that the kernels call. which 0: arr = (n, 5) (u1, u2, dir.xyz) -> (n, 4)
         {new_dir.xyz, ph}; which 1: arr = (n,) unit draws -> (n,) free-flight distances. A mat_medium_grid medium also has which 2:
         arr = (n, 3) points -> (n,) sigma_t, and which 3: arr = (n, 7) (o.xyz, dir.xyz, t) -> (n, 3) {collided 0/1, s or 0, draws
-        consumed}, row i tracked with the independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0."""
-        cols_in, cols_out = {0: (5, 4), 1: (None, None), 2: (3, None), 3: (7, 3)}.get(which, (None, None))
+        consumed}, row i tracked with the independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0. which 4: arr = (n,)
+        segment lengths -> (n, 3) the factors exp(-(a_c * l)) the medium's absorption puts on a throughput (exactly 1 where a_c = 0)."""
+        cols_in, cols_out = {0: (5, 4), 1: (None, None), 2: (3, None), 3: (7, 3), 4: (None, 3)}.get(which, (None, None))
         arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, cols_in) if cols_in else (-1,))
         out = np.empty((len(arr), cols_out) if cols_out else (len(arr),), dtype=np.float64)
         _check(lib.pt_medium_probe(self.handle, int(mat), which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_medium_probe")

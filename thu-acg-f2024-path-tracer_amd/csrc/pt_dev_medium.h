@@ -1,7 +1,9 @@
 // Device-side participating media (the rules are in include/pt_amd.h). Homogeneous (pt_mat_medium): the free-flight
 // distance and the Henyey-Greenstein phase function. Grid density (pt_mat_medium_grid): the trilinear density, the
 // clip of a segment to the grid's box and the delta-tracking loop. Called by k_shade's MED / HET forms and by the probe behind
-// pt_medium_probe — the same functions, so what the probe returns is what a path computes.
+// pt_medium_probe — the same functions, so what the probe returns is what a path computes. Interior media and chromatic absorption
+// (pt_mat_glass_set_interior, pt_mat_medium_tinted): the absorption coefficients of a medium's record and the
+// Beer-Lambert attenuation of a segment, called by k_shade's INT forms.
 #pragma once
 #include "pt_dev_math.h"
 #include "pt_types.h"
@@ -20,6 +22,23 @@ struct MediumD {
 PT_DEV MediumD load_medium(const SceneD& sc, uint32_t med) {
     const MatD& m = sc.mats[med - 1u];
     return MediumD{m.p[0], m.p[1], V3{m.p[2], m.p[3], m.p[4]}, m.p[5] != 0.0};
+}
+// pt_mat_medium_tinted's absorption coefficients (MatD::p[7..9]; zero for every other medium) — read by the INT forms only, where they
+// are used, so that they do not stay live across the free flight
+PT_DEV V3 load_absorption(const SceneD& sc, uint32_t med) {
+    const MatD& m = sc.mats[med - 1u];
+    return V3{m.p[7], m.p[8], m.p[9]};
+}
+
+// a real function like dev_log: k_shade's INT forms hold the exponential once
+PT_DM_CALL double dev_exp(double x) { return detmath::exp(x); }
+// Beer-Lambert along a segment of length l (+inf on a miss) in a medium with absorption a: thr_c *= exp(-(a_c * l)), the product formed
+// first; a channel with a_c == 0 is not touched (no 0 * inf)
+PT_DEV V3 medium_absorb(V3 a, V3 thr, double l) {
+    if (a.x > 0.0) thr.x = thr.x * dev_exp(-(a.x * l));
+    if (a.y > 0.0) thr.y = thr.y * dev_exp(-(a.y * l));
+    if (a.z > 0.0) thr.z = thr.z * dev_exp(-(a.z * l));
+    return thr;
 }
 
 // d = -log(1 - u) / density, u in [0, 1)

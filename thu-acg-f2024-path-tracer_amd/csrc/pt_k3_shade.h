@@ -189,7 +189,11 @@ struct NoPrefetch {
 // HET (only with MED): a grid-density medium is in effect (the rule in pt_amd.h). A path whose medium has a grid makes
 // phase A's free flight by delta tracking (grid_track: a lane-divergent loop, nothing sorts around it); a homogeneous medium and every
 // other lane are the MED form bit for bit.
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false>
+// INT (only with MED and HET): interior media or chromatic absorption are in effect (the rule in pt_amd.h). Phase A
+// attenuates the throughput of a path inside a tinted medium over the segment it has just travelled, and makes no free-flight draw in a
+// medium of density 0; B2 sets the medium of a bounce that crossed a glass surface with an interior. Every other lane is the HET form bit
+// for bit.
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
@@ -250,6 +254,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     bool is_hit = false;
     bool scatter = false, boundary = false;                            // MED: the lane is at a medium vertex (hit.point) / at a medium's boundary
     MediumD medium{};
+    uint32_t interior = 0u;                                            // INT: the hit is on a glass with an interior: that medium (material index + 1)
     HitD hit{};
     const MatD* mp = nullptr;
     TexVals tv{};
@@ -283,11 +288,14 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                             tracked = true;
                         }
                     }
-                    if (!tracked) d = medium_free_flight(rng_f64(rng), medium.density);
-                    if (d < (surface ? hit.dist : D_INF)) {
+                    if (!tracked && (!INT || medium.density > 0.0)) d = medium_free_flight(rng_f64(rng), medium.density);   // (INT: density 0 makes no draw)
+                    const double t_seg = surface ? hit.dist : D_INF;
+                    if (d < t_seg) {
                         scatter = true;
                         hit.point = ray.o + ray.d * d;
                     }
+                    // absorption over the segment travelled, before anything at this visit uses the throughput
+                    if constexpr (INT) thr = medium_absorb(load_absorption(sc, med), thr, scatter ? d : t_seg);
                 }
             }
         }
@@ -303,6 +311,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             mp = &sc.mats[hit.mat];
             tv = fetch_tex(sc, *mp, hit);
             lf = make_local_frame(*mp, hit, -ray.d);
+            if constexpr (INT) interior = mp->kind == MAT_GLASS ? (uint32_t)mp->p[0] : 0u;   // (read here: B2 stays arithmetic)
             // camera.rs:186-187 — added for every material (zero unless emissive) so that a
             // non-finite throughput poisons the sample exactly as it does in the reference
             V3 emission = mp->kind == MAT_LIGHT ? tv.color : V3{0.0, 0.0, 0.0};
@@ -421,6 +430,11 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             finished = parked = true;                                  // (ENV: a zero-density or zero-throughput bounce ends the path)
         } else {
             double e = 1e-3 * signum(dot(dir, hit.gn));                // :217-222
+            if constexpr (INT) {
+                // a glass with an interior: the bounce crossed the surface when the continued ray starts on the side the incoming ray was
+                // heading to — into the interior at a front-face hit, out of it at a back-face hit; a reflection keeps the medium
+                if (interior != 0u && signum(dot(dir, hit.gn)) == signum(dot(ray.d, hit.gn))) med = hit.front ? interior : 0u;
+            }
             ray = make_ray(hit.point + e * hit.gn, dir, ray.time);
             thr = thr * attenuation;
             ++bounce;
@@ -585,8 +599,9 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // MED: participating media (shade_slot). A slot's class says nothing certain about a path inside a medium — it may scatter before the
 // hit, or instead of leaving — so these forms do not request work items a group ahead.
 // HET: grid-density media (shade_slot)
+// INT: interior media and chromatic absorption (shade_slot)
 template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false, bool MED = false,
-          bool HET = false>
+          bool HET = false, bool INT = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
     const int lane = (int)(threadIdx.x & 63u);
@@ -602,7 +617,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -779,7 +794,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

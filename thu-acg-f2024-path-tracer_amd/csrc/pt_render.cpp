@@ -263,7 +263,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         env_on = env.z > 0.0;
     }
 
-    // participating media are in effect (pt_amd.h): a world object carries a medium material, or the camera medium is set
+    // participating media are in effect (pt_amd.h): a world object carries a medium material or a glass with an interior, or the camera medium is set
     const bool med = s->media_on();
     if (med && env_on) return set_error("pt_render: environment importance sampling together with participating media is not supported (set one of them off)");
     if (med && dc.max_depth > MEDIUM_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^20 when participating media are in effect");
@@ -318,8 +318,9 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
     const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
-    const bool het = med && s->grid_media_on();   // a grid-density medium is in effect: the HET forms of k_shade
-    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het});   // the form of k_init / k_shade that exists for it
+    const bool intr = med && s->interior_on();   // a glass interior or a tinted medium is in effect: the INT forms of k_shade, which are HET forms
+    const bool het = med && (intr || s->grid_media_on());   // a grid-density medium is in effect: the HET forms of k_shade
+    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het, intr});   // the form of k_init / k_shade that exists for it
     shade_variant = form.variant;
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
@@ -937,12 +938,12 @@ extern "C" int pt_env_probe(pt_scene* s, const pt_camera* cam, int which, const 
 extern "C" int pt_medium_probe(pt_scene* s, int mat, int which, const double* in, uint32_t n, double* out) {
     if (!s || !s->ctx) return set_error("pt_medium_probe: null scene");
     if (mat < 0 || (size_t)mat >= s->mats.size() || s->mats[mat].kind != MAT_MEDIUM) return set_error("pt_medium_probe: not a medium material");
-    if (which < 0 || which > 3) return set_error("pt_medium_probe: which must be 0, 1, 2 or 3");
-    const bool grid = which >= 2;
+    if (which < 0 || which > 4) return set_error("pt_medium_probe: which must be 0, 1, 2, 3 or 4");
+    const bool grid = which == 2 || which == 3;
     if (grid && s->mats[mat].p[6] == 0.0) return set_error("pt_medium_probe: which 2 and 3 need a grid-density medium (pt_mat_medium_grid)");
     if (n == 0) return 0;
     if (!in || !out) return set_error("pt_medium_probe: null buffer");
-    static const size_t IN_COLS[4] = {5, 1, 3, 7}, OUT_COLS[4] = {4, 1, 1, 3};
+    static const size_t IN_COLS[5] = {5, 1, 3, 7, 1}, OUT_COLS[5] = {4, 1, 1, 3, 3};
     const size_t n_in = (size_t)n * IN_COLS[which], n_out = (size_t)n * OUT_COLS[which];
     if (which == 3)   // the loop's expected trip count is bounded for unit directions (pt_mat_medium_grid): longer ones are refused
         for (uint32_t i = 0; i < n; ++i) {
@@ -964,6 +965,7 @@ extern "C" int pt_medium_probe(pt_scene* s, int mat, int which, const double* in
     }
     if (ok) {
         if (grid) launch_grid_probe(which, d_g, d_v, d_i, n, d_o, ctx->stream);
+        else if (which == 4) launch_absorb_probe(s->mats[mat].p + 7, d_i, n, d_o, ctx->stream);
         else launch_medium_probe(which, s->mats[mat].p[0], s->mats[mat].p[1], d_i, n, d_o, ctx->stream);
         ok = hip_ok(hipGetLastError(), "kernel launch") &&
              hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&

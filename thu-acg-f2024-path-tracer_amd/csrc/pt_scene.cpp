@@ -185,6 +185,8 @@ extern "C" int pt_mat_principled(pt_scene* s, int color_tex, const double p[11])
 extern "C" int pt_mat_mix(pt_scene* s, double t, int m1, int m2) {   // MixBxDf::new mix.rs:14-20
     if (!MAT_OK(s, m1) || !MAT_OK(s, m2)) return set_error("pt_mat_mix: bad material handle");
     if (s->mats[m1].kind == MAT_MEDIUM || s->mats[m2].kind == MAT_MEDIUM) return set_error("pt_mat_mix: a medium cannot be mixed (it is a volume, not a BxDF)");
+    for (int c : {m1, m2})   // (a mix child is never a glass with an interior, so neither is a child's child)
+        if (s->mats[c].kind == MAT_GLASS && s->mats[c].p[0] != 0.0) return set_error("pt_mat_mix: a glass with an interior medium cannot be mixed");
     // a child may be a mix (MixBxDf::new takes any Arc<dyn BxDFMaterial>, mix.rs:14-20) — of leaves: the kernels evaluate two levels
     for (int c : {m1, m2})
         if (s->mats[c].kind == MAT_MIX && (s->mats[s->mats[c].color_tex].kind == MAT_MIX || s->mats[s->mats[c].rough_tex].kind == MAT_MIX))
@@ -218,6 +220,45 @@ extern "C" int pt_mat_medium(pt_scene* s, double density, double r, double g, do
     m.p[1] = hg_g;
     m.p[2] = r; m.p[3] = g; m.p[4] = b;
     return push_mat(s, m);
+}
+// A homogeneous medium with an absorption coefficient per channel on top of its scattering (the rule is in pt_amd.h): the same material
+// kind, with the coefficients in p[7..9] and p[10] = 1 (what makes a medium "tinted", whatever its coefficients)
+extern "C" int pt_mat_medium_tinted(pt_scene* s, double density, double r, double g, double b, double hg_g, const double absorption[3]) {
+    if (!s) return set_error("pt_mat_medium_tinted: null scene");
+    if (!absorption) return set_error("pt_mat_medium_tinted: null argument");
+    if (!(density >= 0.0) || !std::isfinite(density)) return set_error("pt_mat_medium_tinted: density must be finite and >= 0");
+    for (double a : {r, g, b})
+        if (!(a >= 0.0 && a <= 1.0)) return set_error("pt_mat_medium_tinted: each albedo channel must be in [0, 1]");
+    if (!(std::fabs(hg_g) < 1.0)) return set_error("pt_mat_medium_tinted: |hg_g| must be below 1");
+    double amax = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        if (!(absorption[c] >= 0.0) || !std::isfinite(absorption[c])) return set_error("pt_mat_medium_tinted: each absorption coefficient must be finite and >= 0");
+        amax = std::max(amax, absorption[c]);
+    }
+    if (!(density + amax > 0.0)) return set_error("pt_mat_medium_tinted: density and absorption are all 0 (no medium)");
+    if (s->mats.size() >= MEDIUM_MAX_MATS) return set_error("pt_mat_medium_tinted: a medium's material handle must be below 4094 (create media before other materials)");
+    MatD m = blank_mat(MAT_MEDIUM);
+    m.p[0] = density;
+    m.p[1] = hg_g;
+    m.p[2] = r; m.p[3] = g; m.p[4] = b;
+    for (int c = 0; c < 3; ++c) m.p[7 + c] = absorption[c];
+    m.p[10] = 1.0;
+    return push_mat(s, m);
+}
+// The medium that fills a glass object (the rule is in pt_amd.h): its handle + 1 in the glass's p[0], which glass does not use otherwise
+extern "C" int pt_mat_glass_set_interior(pt_scene* s, int glass_mat, int medium_mat) {
+    if (!s) return set_error("pt_mat_glass_set_interior: null scene");
+    if (!MAT_OK(s, glass_mat) || s->mats[glass_mat].kind != MAT_GLASS) return set_error("pt_mat_glass_set_interior: not a glass material");
+    if (medium_mat != -1 && (!MAT_OK(s, medium_mat) || s->mats[medium_mat].kind != MAT_MEDIUM)) return set_error("pt_mat_glass_set_interior: not a medium material (-1 = detach)");
+    for (const MatD& m : s->mats)
+        if (m.kind == MAT_MIX && (m.color_tex == glass_mat || m.rough_tex == glass_mat)) return set_error("pt_mat_glass_set_interior: the glass is a child of a mix");
+    s->mats[glass_mat].p[0] = (double)(medium_mat + 1);
+    s->built = false;
+    return 0;
+}
+extern "C" int pt_mat_glass_interior(pt_scene* s, int glass_mat) {
+    if (!s || !MAT_OK(s, glass_mat) || s->mats[glass_mat].kind != MAT_GLASS) return -1;
+    return (int)s->mats[glass_mat].p[0] - 1;
 }
 // A medium whose extinction is scale * V(x), V trilinear in a grid of f32 samples (the rule is in pt_amd.h): the same material kind,
 // with its row of the grid table in p[6] and its majorant in p[0]
@@ -811,11 +852,13 @@ int pt::scene_build(pt_scene* s) {
     }
     if (prims.size() >= (size_t)HIT_ID_MASK - 4) return set_error("pt_world_build: too many primitives (28-bit ids)");
     // (a medium's boundary sorts with glass — the other kind that sends the ray on — so that K2's result word keeps its classes: pt_types.h)
-    s->world_has_medium = s->world_has_grid_medium = false;
+    s->world_has_medium = s->world_has_grid_medium = s->world_has_interior = false;
     for (PrimRef& pr : prims) {
         const uint32_t kind = s->mats[pr.mat].kind;
         s->world_has_medium = s->world_has_medium || kind == MAT_MEDIUM;
         s->world_has_grid_medium = s->world_has_grid_medium || (kind == MAT_MEDIUM && s->mats[pr.mat].p[6] != 0.0);
+        // a glass with an interior, or a tinted medium's boundary
+        s->world_has_interior = s->world_has_interior || (kind == MAT_GLASS && s->mats[pr.mat].p[0] != 0.0) || (kind == MAT_MEDIUM && s->mats[pr.mat].p[10] != 0.0);
         pr.kind |= (kind == MAT_MEDIUM ? MEDIUM_SORT_KIND : kind) << PRIM_MAT_KIND_SHIFT;
     }
     std::vector<Box> entry_boxes(tlas_items.size());
@@ -852,6 +895,7 @@ int pt::scene_build(pt_scene* s) {
     std::vector<MatD> mats = s->mats;   // solid textures' values into the material records (MatD::color_solid)
     for (const PrimRef& pr : prims)   // a medium that bounds something in the world (MatD::p[5], pt_dev_medium.h)
         if (mats[pr.mat].kind == MAT_MEDIUM) mats[pr.mat].p[5] = 1.0;
+        else if (mats[pr.mat].kind == MAT_GLASS && mats[pr.mat].p[0] != 0.0) mats[(size_t)mats[pr.mat].p[0] - 1].p[5] = 1.0;   // ... or fills a glass object
     for (MatD& m : mats) {
         m.color_solid = m.rough_solid = 0u;
         const bool has_color = m.kind == MAT_DIFFUSE || m.kind == MAT_METAL || m.kind == MAT_PRINCIPLED || m.kind == MAT_LIGHT;

@@ -99,7 +99,14 @@ struct pt_scene {
     // world_has_medium (set by scene_build): some world object's material is a medium.
     int camera_medium = -1;
     bool world_has_medium = false;
-    bool media_on() const { return world_has_medium || camera_medium >= 0; }   // "in effect": the kernels' MED forms run
+    // interior media and chromatic absorption (pt_mat_glass_set_interior, pt_mat_medium_tinted): MatD::p[0] of a glass = its
+    // interior's handle + 1, p[7..9] of a medium = its absorption, p[10] = 1 for a tinted one. world_has_interior (set by scene_build): some
+    // world object's material is a glass with an interior or a tinted medium.
+    bool world_has_interior = false;
+    bool interior_on() const {   // "in effect": the kernels' INT forms run (and with them MED and HET)
+        return world_has_interior || (camera_medium >= 0 && mats[camera_medium].p[10] != 0.0);
+    }
+    bool media_on() const { return world_has_medium || camera_medium >= 0 || world_has_interior; }   // "in effect": the kernels' MED forms run
     // grid-density media (pt_mat_medium_grid): MatD::p[6] of a medium = its index here + 1. world_has_grid_medium (set by
     // scene_build): some world object's material is one.
     std::vector<pt::HostGrid> grids;

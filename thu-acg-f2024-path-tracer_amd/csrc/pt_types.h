@@ -113,6 +113,9 @@ enum MatKind : uint32_t { MAT_DIFFUSE = 0, MAT_METAL = 1, MAT_GLASS = 2, MAT_PRI
                           // and the default k_shade forms' sort stay what they were; only k_shade's MED forms look at MatD::kind.
                           // A grid-density medium (pt_mat_medium_grid) is the same kind with p[6] = its row of SceneD::grids + 1
                           // (0 = homogeneous) and p[0] = its majorant mu; only k_shade's HET forms and the probe read p[6].
+                          // A tinted medium (pt_mat_medium_tinted) keeps its absorption coefficients in p[7..9] (zero for every
+                          // other medium) and p[10] = 1; a MAT_GLASS keeps its interior medium's index + 1 in p[0] (pt_mat_glass_set_interior,
+                          // 0 = none). Only k_shade's INT forms and the probe read these.
                           MAT_MEDIUM = 9 };
 constexpr uint32_t MEDIUM_SORT_KIND = MAT_GLASS;
 // The medium a path is in travels in the upper bits of its record's bounce word (RayRec's in the compact layout, else PathRec's):

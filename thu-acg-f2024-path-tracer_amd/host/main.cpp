@@ -7,7 +7,9 @@
 // --fog DENSITY[,R,G,B[,G]] (the built world's bounds, grown by 1 %, become the boundary of a homogeneous medium of that density,
 // albedo (default 1,1,1) and Henyey-Greenstein g (default 0); the camera starts inside it when look_from lies inside),
 // --smoke SCALE[,R,G,B[,G]] (a fixed closed-form plume, smoke_plume below, sampled into a 64^3 grid over the box --fog would build, as an
-// unbounded grid-density camera medium of extinction SCALE * V).
+// unbounded grid-density camera medium of extinction SCALE * V),
+// --interior DENSITY[,R,G,B[,G[,AR,AG,AB]]] (every glass material of the scene script is filled with a homogeneous medium of that density,
+// albedo, g and absorption per channel; density 0 with an absorption > 0 is a clear tinted body).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -47,6 +49,28 @@ static bool parse_medium(const std::string& v, double out[5]) {
     for (int k = 1; k <= 3; ++k) ok = ok && out[k] >= 0.0 && out[k] <= 1.0;
     return ok;
 }
+// DENSITY[,R,G,B[,G[,AR,AG,AB]]] of --interior: one, four, five or eight numbers, each parsed whole; density >= 0, albedo in [0, 1], |G| < 1,
+// absorption >= 0, density + the largest absorption > 0
+static bool parse_interior(const std::string& v, double out[8]) {
+    std::vector<double> f;
+    bool ok = !v.empty();
+    for (size_t pos = 0; ok && pos <= v.size();) {
+        const size_t comma = std::min(v.find(',', pos), v.size());
+        const std::string tok = v.substr(pos, comma - pos);
+        char* end = nullptr;
+        const double x = strtod(tok.c_str(), &end);
+        ok = !tok.empty() && end == tok.c_str() + tok.size();
+        f.push_back(x);
+        pos = comma + 1;
+    }
+    ok = ok && (f.size() == 1 || f.size() == 4 || f.size() == 5 || f.size() == 8);
+    for (size_t k = 0; ok && k < f.size(); ++k) out[k] = f[k];
+    const double inf = std::numeric_limits<double>::infinity();
+    ok = ok && out[0] >= 0.0 && out[0] < inf && std::fabs(out[4]) < 1.0;
+    for (int k = 1; k <= 3; ++k) ok = ok && out[k] >= 0.0 && out[k] <= 1.0;
+    for (int k = 5; k <= 7; ++k) ok = ok && out[k] >= 0.0 && out[k] < inf;
+    return ok && out[0] + std::max(out[5], std::max(out[6], out[7])) > 0.0;
+}
 
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
@@ -59,6 +83,8 @@ int main(int argc, char** argv) {
     double fog_v[5] = {0.0, 1.0, 1.0, 1.0, 0.0};   // density, albedo r g b, g
     bool smoke = false;
     double smoke_v[5] = {0.0, 1.0, 1.0, 1.0, 0.0};   // scale, albedo r g b, g
+    bool interior = false;
+    double interior_v[8] = {0.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};   // density, albedo r g b, g, absorption r g b
     long aov_spp = 16;
     uint64_t seed = 1;
     std::string out, assets = "assets";
@@ -95,12 +121,19 @@ int main(int argc, char** argv) {
             if (!parse_medium(next(), smoke_v)) { std::cerr << "--smoke must be SCALE[,R,G,B[,G]]: scale > 0, albedo channels in [0, 1], |G| < 1\n"; return 2; }
             smoke = true;
         }
+        else if (a == "--interior") {
+            if (!parse_interior(next(), interior_v)) {
+                std::cerr << "--interior must be DENSITY[,R,G,B[,G[,AR,AG,AB]]]: density >= 0, albedo channels in [0, 1], |G| < 1, absorption >= 0, density or an absorption > 0\n";
+                return 2;
+            }
+            interior = true;
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n"
                          "  --smoke: an unbounded grid-density camera medium of extinction SCALE * V over the world's bounds grown by 1 % (the box --fog fills),\n"
                          "           V sampled at the centres of 64^3 cells; at the normalised position (x, y, z) of the box, y up:\n"
                          "           cx = 0.5 + 0.08 sin(3 pi y), cz = 0.5 + 0.08 cos(2 pi y), r = 0.06 + 0.22 y,\n"
@@ -117,6 +150,8 @@ int main(int argc, char** argv) {
     if (fog && env_sampling > 0.0) { std::cerr << "--fog and --env-sampling cannot be combined\n"; return 2; }
     if (smoke && env_sampling > 0.0) { std::cerr << "--smoke and --env-sampling cannot be combined\n"; return 2; }
     if (smoke && fog) { std::cerr << "--smoke and --fog cannot be combined\n"; return 2; }
+    if (interior && env_sampling > 0.0) { std::cerr << "--interior and --env-sampling cannot be combined\n"; return 2; }
+    if (interior && (fog || smoke)) { std::cerr << "--interior cannot be combined with --fog or --smoke (that would nest media)\n"; return 2; }
     if (scene < 1 || scene > 7) return 0;   // `_ => ()` main.rs:643
     pt_ctx* ctx = nullptr;
     if (pt_ctx_create(device, &ctx) != 0) {
@@ -149,6 +184,9 @@ int main(int argc, char** argv) {
                 setup.world.camera_medium = HeterogeneousVolume::from_grid(nullptr, smoke_v[0], Vec3{smoke_v[1], smoke_v[2], smoke_v[3]}, smoke_v[4], N, N, N, std::move(v), lo, hi);
             }
         }
+        if (interior)
+            setup.world.glass_interior = HomogeneousVolume::tinted(nullptr, interior_v[0], Vec3{interior_v[1], interior_v[2], interior_v[3]}, interior_v[4],
+                                                                   Vec3{interior_v[5], interior_v[6], interior_v[7]});
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();
         std::cerr << "rendering production\n";   // camera.rs:101

@@ -41,11 +41,13 @@ inline const Vec3 Vec3::ZERO{0, 0, 0}, Vec3::ONE{1, 1, 1}, Vec3::X{1, 0, 0}, Vec
 [[noreturn]] inline void panic(const std::string& what) { throw std::runtime_error(what + ": " + pt_last_error()); }
 
 // One replay of the description graph onto a pt_scene; memoises shared nodes (Arc sharing).
+struct Volume;
 struct Emitter {
     pt_scene* scene;
     std::string asset_dir;
     std::map<const void*, int> done;
     int override_mat = -1;   // >= 0: the primitives emitted now carry this material instead of their own (HomogeneousVolume's boundary)
+    const Volume* glass_interior = nullptr;   // the interior of every GlassBSDF without one of its own (World::glass_interior)
 };
 
 // ---- textures (src/texture.rs) ---------------------------------------------------------
@@ -155,13 +157,15 @@ struct GlassBSDF : BxDFMaterial {   // glass.rs:28-49
         return m;
     }
     static std::shared_ptr<GlassBSDF> basic(double ior) { return new_(SolidTexture<Vec3>::new_(Vec3::ONE), SolidTexture<double>::new_(0.001), 0.0, ior); }
-    int emit(Emitter& e) const override {
-        auto it = e.done.find(this);
-        if (it != e.done.end()) return it->second;
-        int h = pt_mat_glass(e.scene, base_color->emit(e), roughness->emit(e), anisotropic, ior);
-        if (h < 0) panic("GlassBSDF");
-        return e.done[this] = h;
+    // this build's addition: the medium that fills objects of this glass (pt_mat_glass_set_interior); the volume's
+    // boundary, if it has one, is not used
+    std::shared_ptr<Volume> interior;
+    std::shared_ptr<GlassBSDF> with_interior(std::shared_ptr<Volume> v) const {
+        auto m = std::make_shared<GlassBSDF>(*this);
+        m->interior = v;
+        return m;
     }
+    int emit(Emitter& e) const override;   // (below Volume)
 };
 struct PrincipledBSDF : BxDFMaterial {   // principled.rs:45-73, same argument order
     TexPtr<Vec3> base_color;
@@ -396,6 +400,15 @@ struct Volume : Hittable {
     }
     void bounds(Vec3& lo, Vec3& hi) const override { if (boundary) boundary->bounds(lo, hi); }
 };
+inline int GlassBSDF::emit(Emitter& e) const {
+    auto it = e.done.find(this);
+    if (it != e.done.end()) return it->second;
+    int h = pt_mat_glass(e.scene, base_color->emit(e), roughness->emit(e), anisotropic, ior);
+    if (h < 0) panic("GlassBSDF");
+    const Volume* v = interior ? interior.get() : e.glass_interior;
+    if (v && pt_mat_glass_set_interior(e.scene, h, v->medium(e)) != 0) panic("GlassBSDF::interior");
+    return e.done[this] = h;
+}
 // HomogeneousVolume of the reference's commented-out volume.rs:15-41: a boundary filled with a medium of constant density and
 // albedo. `g` (Henyey-Greenstein) is this build's addition; 0 is the isotropic phase function the stub names (pt_mat_medium).
 struct HomogeneousVolume : Volume {
@@ -406,7 +419,18 @@ struct HomogeneousVolume : Volume {
         v->boundary = boundary; v->density = density; v->albedo = albedo; v->g = g;
         return v;
     }
-    int create(Emitter& e) const override { return pt_mat_medium(e.scene, density, albedo.x, albedo.y, albedo.z, g); }
+    // this build's addition: an absorption coefficient per channel on top of the scattering; density may then be 0 (pt_mat_medium_tinted)
+    bool is_tinted = false;
+    Vec3 absorption;
+    static std::shared_ptr<HomogeneousVolume> tinted(HitPtr boundary, double density, Vec3 albedo, double g, Vec3 absorption) {
+        auto v = from_albedo(boundary, density, albedo, g);
+        v->is_tinted = true; v->absorption = absorption;
+        return v;
+    }
+    int create(Emitter& e) const override {
+        const double a[3] = {absorption.x, absorption.y, absorption.z};
+        return is_tinted ? pt_mat_medium_tinted(e.scene, density, albedo.x, albedo.y, albedo.z, g, a) : pt_mat_medium(e.scene, density, albedo.x, albedo.y, albedo.z, g);
+    }
     const char* name() const override { return "HomogeneousVolume"; }
 };
 // No counterpart in the reference: a medium whose density is scale * V(x), V trilinear in an nx x ny x nz grid of samples at the cell
@@ -445,6 +469,7 @@ struct World {
     // flatten + BVH + upload into an existing scene
     void emit_into(pt_scene* s, std::shared_ptr<ImageTexture> env = nullptr) {
         Emitter e{s, asset_dir, {}};
+        e.glass_interior = glass_interior.get();
         for (auto& o : objects) if (pt_world_add_object(s, o->emit(e)) != 0) panic("World::add_object");
         for (auto& l : lights) if (pt_world_add_light(s, l->emit(e)) != 0) panic("World::add_light");
         if (env) env->emit(e);
@@ -454,6 +479,7 @@ struct World {
         handles = e.done;
     }
     std::shared_ptr<Volume> camera_medium;   // the medium camera rays start in (pt_scene_set_camera_medium); null = none
+    std::shared_ptr<Volume> glass_interior;   // this build's option: the interior of every GlassBSDF that has none of its own (pt_render --interior)
     void bounds(Vec3& lo, Vec3& hi) const {             // of objects and lights
         for (auto& o : objects) o->bounds(lo, hi);
         for (auto& l : lights) l->bounds(lo, hi);
