@@ -142,6 +142,35 @@ double pt_scene_env_sampling(pt_scene*);
  * 2^-q x 2^-(m-q). */
 int pt_scene_set_sampler(pt_scene*, int kind);
 int pt_scene_sampler(pt_scene*);
+/* Light sampling: how lights.sample / lights.pdf treat the mesh and sphere entries of the lights list. kind 0 (default) = the
+ * reference's (mesh.rs:122-141, sphere.rs:110-135: a uniformly chosen triangle with u, v drawn in the unit square, the whole sphere
+ * surface; O(n) triangle tests per pdf); kind 1 = exact; any other kind returns -1 and leaves the setting. Changing it needs no
+ * pt_world_build. Kind 1 is IN EFFECT for a render when kind == 1 and the lights list holds at least one mesh or sphere entry,
+ * directly or under instances; otherwise every entry point launches exactly the kernels it launches without the setting and
+ * produces the same bits. In effect for pt_render, pt_render_pixels, pt_render_adaptive and pt_render_multi; pt_render_aovs does
+ * not change. With kind 1 in effect a render returns -1 when environment importance sampling or participating media are in effect
+ * too, when a light mesh's area A is 0 or not finite, or when a light mesh's BVH is deeper than 24 levels. The rule of kind 1:
+ *   The light-index draw (gen_range(0..n_lights)) and the instance chain (origin, and for the pdf the direction, into the entry's
+ *   local space, the sampled direction back out) are made exactly as with kind 0; quad and cuboid entries keep kind 0's rule.
+ *   Mesh entry of n faces in pt_mesh's face order, vertices v0, v1, v2 in the mesh's local space (instance chains are rigid, so one
+ *   table serves every placement). Table, built by pt_world_build for every mesh in the lights list: c_i = cross(v1 - v0, v2 - v0),
+ *   A_i = 0.5 * length(c_i), C[0] = 0, C[i+1] = C[i] + A_i summed in order in f64, A = C[n].
+ *     sample: one single draw u0, x = u0 * A (if x >= A: the largest double below A); face j = the smallest j with x < C[j+1] (a
+ *       zero-area face is never chosen); one two-value draw (u1, u2) (pair-aligned under the Sobol sampler); s = sqrt(u1),
+ *       b0 = 1 - s, b1 = s * (1 - u2), b2 = s * u2; point = v0 * b0 + v1 * b1 + v2 * b2 (left to right); dir = normalize(point - origin).
+ *     pdf: r = Ray::new(origin, direction, time) in local space; over EVERY face f that the triangle test of mesh.rs:50-82 accepts
+ *       with t_min = 0, at distance t: term = (t * t) / (|dot(r.d, normalize(c_f))| * A) — the geometric normal; the entry's pdf is
+ *       the sum of the terms, in the order the mesh's BVH yields them (two trees agree to rounding). All hits count, not only the
+ *       first: a direction towards any point of the mesh has that density whether the point is occluded or not.
+ *   Sphere entry, centre c at `time`, radius r: L = c - origin, d2 = length_squared(L), r2 = r * r; one two-value draw (u1, u2).
+ *     d2 <= r2 (origin inside or on the sphere): cos_t = 1 - 2 u1, sin_t = sqrt(max(0, 1 - cos_t^2)), phi = (2 pi) u2,
+ *       dir = (sin_t cos phi, sin_t sin phi, cos_t); pdf = 1 / (4 pi) for every direction.
+ *     d2 > r2: x = r2 / d2, cm = sqrt(1 - x), k = x / (1 + cm) (= 1 - cm without the cancellation); cos_t = 1 - u1 * k, sin_t and
+ *       phi as above; dir = that vector rotated from +z onto normalize(L) (the shortest-arc frame the medium's phase sampling uses);
+ *       pdf = 1 / ((2 pi) * k) when the sphere test of sphere.rs:64-87 accepts Ray::new(origin, direction, time) with t_min = 0, else 0.
+ *   lights.pdf averages the entries' pdfs over the list as with kind 0. */
+int pt_scene_set_light_sampling(pt_scene*, int kind);
+int pt_scene_light_sampling(pt_scene*);
 /* ---- materials: src/bsdf/, src/material.rs ---------------------------------------------- */
 int pt_mat_diffuse(pt_scene*, int color_tex, int normal_map_tex);       /* DiffuseBRDF::{new,from_rgb,from_textures} diffuse.rs:21-47; -1 = no map */
 int pt_mat_metal(pt_scene*, int color_tex, int rough_tex);              /* MetalBRDF::new metal.rs:23-35 */
@@ -449,6 +478,12 @@ int pt_sampler_probe(pt_ctx*, int kind, uint64_t seed, uint32_t pixel, uint32_t 
  * pixel i, sample 0) from draw 0; out = n x (collided 0 / 1, s or 0, draws consumed). which = 4 (any medium; pt_mat_medium_tinted's
  * rule): in = n segment lengths, out = n x 3 factors exp(-(a_c * l)), exactly 1 where a_c == 0. The world need not be built. */
 int pt_medium_probe(pt_scene*, int mat, int which, const double* in, uint32_t n, double* out);
+/* lights.sample / lights.pdf as k_shade calls them, of the scene's current light-sampling kind (pt_scene_set_light_sampling's rule).
+ * The world must be built; -1 without a lights list. which = 0: in = n x (origin.xyz, time); row i runs lights.sample with the
+ * independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0; out = n x (dir.xyz, light index, face index or -1 for a
+ * non-mesh entry (and always under kind 0), draws consumed). which = 1: in = n x (origin.xyz, direction.xyz, time), out = n
+ * lights.pdf values. */
+int pt_light_probe(pt_scene*, int which, const double* in, uint32_t n, double* out);
 
 #ifdef __cplusplus
 }

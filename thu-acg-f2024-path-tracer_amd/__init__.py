@@ -126,6 +126,7 @@ ABI_SYMBOLS = [
     "pt_mat_medium", "pt_scene_set_camera_medium", "pt_scene_camera_medium", "pt_medium_probe",
     "pt_mat_medium_grid",
     "pt_mat_medium_tinted", "pt_mat_glass_set_interior", "pt_mat_glass_interior",
+    "pt_scene_set_light_sampling", "pt_scene_light_sampling", "pt_light_probe",
 ]
 
 
@@ -173,6 +174,10 @@ def _load():
         lib.pt_mat_medium_tinted.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
         lib.pt_mat_glass_set_interior.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.pt_mat_glass_interior.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(lib, "pt_scene_set_light_sampling"):   # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
+        lib.pt_scene_light_sampling.argtypes = [C.c_void_p]
+        lib.pt_light_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -250,6 +255,7 @@ lib = _load()
 
 
 SAMPLERS = {"independent": 0, "sobol": 1}   # pt_scene_set_sampler's kinds
+LIGHT_SAMPLING = {"reference": 0, "exact": 1}   # pt_scene_set_light_sampling's kinds
 
 
 def _check(rc, what="pt call"):
@@ -434,6 +440,29 @@ class Scene:
 
     def sampler(self) -> int:
         return lib.pt_scene_sampler(self.handle)
+
+    def set_light_sampling(self, kind):
+        """How mesh and sphere lights are sampled: "reference" (0, the default: the reference's lights.sample / lights.pdf) or "exact"
+        (1: area-weighted mesh lights whose pdf walks the mesh's BVH, cone-sampled sphere lights; the rule is in include/pt_amd.h,
+        DESIGN.md §15). Needs no world_build."""
+        kind = LIGHT_SAMPLING.get(kind, kind)
+        if isinstance(kind, bool) or not isinstance(kind, int):
+            raise PtError(f"set_light_sampling: unknown kind {kind!r}")
+        return _check(lib.pt_scene_set_light_sampling(self.handle, kind), "set_light_sampling")
+
+    def light_sampling(self) -> int:
+        return lib.pt_scene_light_sampling(self.handle)
+
+    def light_probe(self, which: int, arr: np.ndarray) -> np.ndarray:
+        """lights.sample / lights.pdf as the kernels call them, of the current light-sampling kind. which 0: arr = (n, 4) (origin.xyz,
+        time) -> (n, 6) {dir.xyz, light index, face index or -1, draws consumed}, row i with the independent sampler's draws of (seed 0,
+        pixel i, sample 0) from draw 0; which 1: arr = (n, 7) (origin.xyz, direction.xyz, time) -> (n,) lights.pdf values."""
+        if which not in (0, 1):
+            raise PtError("light_probe: which must be 0 or 1")
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, 4 if which == 0 else 7))
+        out = np.empty((len(arr), 6) if which == 0 else (len(arr),), dtype=np.float64)
+        _check(lib.pt_light_probe(self.handle, which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_light_probe")
+        return out
 
     def mat_medium(self, density: float, albedo=(1.0, 1.0, 1.0), g: float = 0.0):
         """A homogeneous participating medium (fog, smoke) as a material: the object that carries it is the medium's invisible

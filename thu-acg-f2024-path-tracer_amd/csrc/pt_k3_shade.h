@@ -2,6 +2,7 @@
 // K3: k_shade — one bounce of every path of the pool (shade_slot), its windowed class sort and the LDS staging of the next group's records.
 #pragma once
 #include "pt_k_common.h"
+#include "pt_dev_lights.h"
 
 namespace pt {
 
@@ -193,14 +194,18 @@ struct NoPrefetch {
 // attenuates the throughput of a path inside a tinted medium over the segment it has just travelled, and makes no free-flight draw in a
 // medium of density 0; B2 sets the medium of a bounce that crossed a glass surface with an interior. Every other lane is the HET form bit
 // for bit.
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false>
+// LSE (only with LIGHTS, never with ENV or MED): exact light sampling is in effect (the rule in pt_amd.h). B1's light direction
+// and B2's light density come from pt_dev_lights.h: area-weighted mesh lights whose pdf walks the mesh's BVH with the lane's stack in LDS
+// (lstk = &stack[0][thread] of k_shade's LSE_KB-lane stack), cone-sampled sphere lights. Everything else is the bounce above bit for bit.
+constexpr int LSE_KB = 512;                                            // threads per block of every shape that has LSE forms (pt_forms.h)
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false, bool LSE = false>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
 // bounce_out at o_base + lane, its position in the window's sorted order; without reorder they are written in place, at `s`.
 PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, uint32_t s, uint32_t o_base, int lane, const SlotIn& in,
                        uint32_t& shard, uint32_t& n_done, uint32_t& n_died, Prefetch&& prefetch, unsigned long long pre_mask = 0ull,
-                       unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u, const EnvTabD* env = nullptr) {
+                       unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u, const EnvTabD* env = nullptr, uint32_t* lstk = nullptr) {
     PT_STAMP(1);
     uint32_t bounce = in.bounce;
     uint32_t med = 0u;                                                 // MED: the path's medium (material index + 1), 0 = none
@@ -363,8 +368,10 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 }
             } else if constexpr (LIGHTS) {
                 rsel = rng_f64(rng);
-                if (rsel < p_light) dir = lights_sample(sc, hit.point, ray.time, rng);
-                else ok = mat_sample(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir);
+                if (rsel < p_light) {
+                    if constexpr (LSE) dir = lights_sample_exact(sc, hit.point, ray.time, rng);
+                    else dir = lights_sample(sc, hit.point, ray.time, rng);
+                } else ok = mat_sample(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir);
             } else {
                 ++rng.draw;
                 ok = mat_sample(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir);
@@ -404,7 +411,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         V3 brdf;
         mat_pdf_eval(sc, *mp, hit, wo, dir, tv, lf, bsdf_pdf, brdf);
         double light_pdf = 0.0;
-        if constexpr (LIGHTS) light_pdf = lights_pdf(sc, hit.point, dir, ray.time);
+        if constexpr (LSE) light_pdf = lights_pdf_exact<LSE_KB>(sc, hit.point, dir, ray.time, lstk);
+        else if constexpr (LIGHTS) light_pdf = lights_pdf(sc, hit.point, dir, ray.time);
         double pdf = p_bsdf * bsdf_pdf + p_light * light_pdf;
         V3 attenuation = brdf / pdf;
         bool env_end = false;
@@ -600,9 +608,13 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // hit, or instead of leaving — so these forms do not request work items a group ahead.
 // HET: grid-density media (shade_slot)
 // INT: interior media and chromatic absorption (shade_slot)
+// LSE: exact light sampling (shade_slot); these forms hold the per-lane stack of the light meshes' all-hits walk, LIGHT_STACK levels x KB lanes in LDS
 template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false, bool MED = false,
-          bool HET = false, bool INT = false>
+          bool HET = false, bool INT = false, bool LSE = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
+    static_assert(!LSE || (SORT && LIGHTS && !ENV && !MED && KB == LSE_KB), "k_shade: the LSE forms are sorted 512-thread forms with lights, without ENV and MED");
+    __shared__ uint32_t s_lstack[LSE ? LIGHT_STACK * KB : 1];   // 48 KB: stack[level][thread] of lights_pdf_exact's mesh walk
+    uint32_t* const lstk = LSE ? &s_lstack[threadIdx.x] : nullptr;
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
     const int lane = (int)(threadIdx.x & 63u);
 #ifdef PT_STAMPS
@@ -617,7 +629,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env);
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT, LSE>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -794,8 +806,8 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
-                                                             n_died, prefetch, pre_mask, pre_base, pre_shard, &env);
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT, LSE>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                                                             n_died, prefetch, pre_mask, pre_base, pre_shard, &env, lstk);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;
                 pre_shard = pre_shard_next;

@@ -1,5 +1,5 @@
 // Host-callable launchers of the HIP kernels: one per stage. K2 is in pt_k2.hip, K1 / K3 / the AOV walk in pt_k3.hip (their Sobol forms in
-// pt_k3_qmc.hip, their media forms in pt_k3_med.hip, K3's grid-media forms in pt_k3_het.hip, its interior-media forms in pt_k3_int.hip), the small
+// pt_k3_qmc.hip, their media forms in pt_k3_med.hip, K3's grid-media forms in pt_k3_het.hip, its interior-media forms in pt_k3_int.hip, its exact-light-sampling forms in pt_k3_lse.hip), the small
 // kernels in pt_kernels.hip.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -10,8 +10,9 @@ namespace pt {
 // What a render asks of K1 / K3 / the AOV walk. variant: k_shade's shape code (pt_forms.h SHADE_SHAPES; PT_SHADE_VARIANT); lights: the scene
 // has a lights list; list: pixel-list render (PoolD::list); env: environment sampling; qmc: the Sobol sampler
 // (pt_scene_set_sampler, §11); med: participating media are in effect (§12); het: one of them is a grid-density medium (§13), or intr is set;
-// intr: a glass interior or a tinted medium is in effect (§14). Which combinations exist: pt_forms.h shade_form_exists.
-struct ShadeForm { int variant; bool lights, list, env, qmc, med, het = false, intr = false; };
+// intr: a glass interior or a tinted medium is in effect (§14); lse: exact light sampling is in effect (§15). Which combinations exist:
+// pt_forms.h shade_form_exists.
+struct ShadeForm { int variant; bool lights, list, env, qmc, med, het = false, intr = false, lse = false; };
 // The form a render gets: pixel lists, env, qmc and med exist for the default variant's shapes only — any other variant becomes 42.
 // The launchers and queries below take the form this returns.
 ShadeForm shade_form(ShadeForm asked);
@@ -37,6 +38,10 @@ void launch_medium_probe(int which, double density, double g, const double* in, 
 void launch_grid_probe(int which, const GridD* grid, const float* vals, const double* in, uint32_t n, double* out, hipStream_t st);
 // ... and the attenuation the INT forms apply (which 4: n lengths -> n x 3 factors exp(-(a_c * l)), exactly 1 where a_c == 0)
 void launch_absorb_probe(const double absorption[3], const double* in, uint32_t n, double* out, hipStream_t st);
+// pt_light_probe: lights.sample / lights.pdf as k_shade calls them (exact: the LSE forms' functions, else the reference's; which 0: n x
+// (origin.xyz, time) -> n x (dir.xyz, light index, face or -1, draws consumed), row i with the independent sampler's draws of (seed 0,
+// pixel i, sample 0) from draw 0; which 1: n x (origin.xyz, direction.xyz, time) -> n lights.pdf values); in / out: device
+void launch_light_probe(const SceneD& sc, bool exact, int which, const double* in, uint32_t n, double* out, hipStream_t st);
 // pt_sampler_probe: the 64-bit values of single draws, by the draw functions the kernels call (kind 0: Rng, 1: RngQ); out: device
 void launch_sampler_probe(int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin, uint32_t n_draws, uint64_t* out,
                           hipStream_t st);

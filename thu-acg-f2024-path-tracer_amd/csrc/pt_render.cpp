@@ -268,6 +268,13 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     if (med && env_on) return set_error("pt_render: environment importance sampling together with participating media is not supported (set one of them off)");
     if (med && dc.max_depth > MEDIUM_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^20 when participating media are in effect");
 
+    // exact light sampling is in effect (pt_amd.h): kind 1 and a mesh or sphere entry in the lights list; otherwise no new code runs
+    const bool lse = s->light_sampling_on();
+    if (lse && env_on) return set_error("pt_render: exact light sampling together with environment importance sampling is not supported (set one of them off)");
+    if (lse && med) return set_error("pt_render: exact light sampling together with participating media is not supported (set light sampling to 0 or take the media out)");
+    if (lse && s->light_mesh_bad_area) return set_error("pt_render: exact light sampling needs light meshes of finite, positive area (a mesh in the lights list has area 0 or a non-finite one)");
+    if (lse && s->light_blas_depth > (uint32_t)LIGHT_STACK) return set_error("pt_render: exact light sampling: a light mesh's BVH is deeper than the 24 levels its pdf walk's stack holds");
+
     // pool sizing. slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
     // the machine several times over; finished paths pull the next (pixel, sample) from a global
     // counter. slots_per_pixel = k >= 1: STATIC ownership (deterministic; k = 1 is the reference's
@@ -320,7 +327,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
     const bool intr = med && s->interior_on();   // a glass interior or a tinted medium is in effect: the INT forms of k_shade, which are HET forms
     const bool het = med && (intr || s->grid_media_on());   // a grid-density medium is in effect: the HET forms of k_shade
-    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het, intr});   // the form of k_init / k_shade that exists for it
+    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het, intr, lse});   // the form of k_init / k_shade that exists for it
     shade_variant = form.variant;
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
@@ -975,6 +982,32 @@ extern "C" int pt_medium_probe(pt_scene* s, int mat, int which, const double* in
     if (d_o) (void)hipFree(d_o);
     if (d_g) (void)hipFree(d_g);
     if (d_v) (void)hipFree(d_v);
+    return ok ? 0 : -1;
+}
+
+extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t n, double* out) {
+    if (!s || !s->built) return set_error("pt_light_probe: world not built");
+    if (which != 0 && which != 1) return set_error("pt_light_probe: which must be 0 or 1");
+    if (s->dev.view.n_lights == 0u) return set_error("pt_light_probe: the world has no lights list");
+    const bool exact = s->light_sampling == 1;
+    if (exact && s->light_mesh_bad_area) return set_error("pt_light_probe: exact light sampling needs light meshes of finite, positive area");
+    if (exact && s->light_blas_depth > (uint32_t)LIGHT_STACK) return set_error("pt_light_probe: exact light sampling: a light mesh's BVH is deeper than the 24 levels its pdf walk's stack holds");
+    if (n == 0) return 0;
+    if (!in || !out) return set_error("pt_light_probe: null buffer");
+    const size_t n_in = (size_t)n * (which == 0 ? 4 : 7), n_out = (size_t)n * (which == 0 ? 6 : 1);
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    double *d_i = nullptr, *d_o = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double)), "hipMalloc") &&
+              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    if (ok) {
+        launch_light_probe(s->dev.view, exact, which, d_i, n, d_o, ctx->stream);
+        ok = hip_ok(hipGetLastError(), "kernel launch") &&
+             hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    if (d_i) (void)hipFree(d_i);
+    if (d_o) (void)hipFree(d_o);
     return ok ? 0 : -1;
 }
 

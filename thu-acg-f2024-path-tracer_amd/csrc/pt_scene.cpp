@@ -122,6 +122,13 @@ extern "C" int pt_scene_set_sampler(pt_scene* s, int kind) {
     return 0;
 }
 extern "C" int pt_scene_sampler(pt_scene* s) { return s ? s->sampler : 0; }
+extern "C" int pt_scene_set_light_sampling(pt_scene* s, int kind) {
+    if (!s) return set_error("pt_scene_set_light_sampling: null scene");
+    if (kind != 0 && kind != 1) return set_error("pt_scene_set_light_sampling: kind must be 0 (reference) or 1 (exact)");
+    s->light_sampling = kind;
+    return 0;
+}
+extern "C" int pt_scene_light_sampling(pt_scene* s) { return s ? s->light_sampling : 0; }
 extern "C" int pt_register_image(pt_scene* s, const char* name, uint32_t w, uint32_t h, const uint8_t* rgb) {
     int t = pt_tex_image_rgb8(s, w, h, rgb);
     if (t < 0) return -1;
@@ -686,6 +693,9 @@ int pt::scene_build(pt_scene* s) {
     std::vector<uint32_t> tri_gid;
     std::vector<InstD> insts;
     std::vector<uint32_t> lights;
+    std::vector<double> light_cdf;   // the light meshes' running area sums (SceneD::light_cdf), one table per mesh object
+    s->lights_have_mesh_or_sphere = s->light_mesh_bad_area = false;
+    s->light_blas_depth = 0;
     std::vector<BuildItem> tlas_items;
     bool any_attr = false;
     for (auto& o : s->objs) any_attr = any_attr || !o.tri_attr.empty();
@@ -701,6 +711,8 @@ int pt::scene_build(pt_scene* s) {
         float extent;
         Box local;
         std::vector<uint32_t> face_pos;   // face -> position in BLAS (leaf) order
+        int depth = 0;                    // of the tree
+        uint32_t cdf_ofs = 0xFFFFFFFFu;   // its area table in light_cdf, once a placement of it is a light
     };
     std::map<int, SharedBlas> blas_of;
     for (size_t wi = 0; wi < order.size(); ++wi) {
@@ -729,6 +741,7 @@ int pt::scene_build(pt_scene* s) {
         };
         const bool is_light = wi < s->world_lights.size();
         if (is_light) lights.push_back((uint32_t)entries.size());   // any hittable may be a light (world.rs:18-20)
+        if (is_light && (o->kind == OBJ_MESH || o->kind == OBJ_SPHERE)) s->lights_have_mesh_or_sphere = true;
         Entry e{};
         memset(&e, 0, sizeof e);
         e.first_prim = (uint32_t)prims.size();
@@ -799,6 +812,7 @@ int pt::scene_build(pt_scene* s) {
                         sb.root = REF_NODE | node_base;
                         perm = db.order;
                         max_blas_depth = std::max(max_blas_depth, db.depth);
+                        sb.depth = db.depth;
                         ++s->n_device_blas;
                         s->device_blas_depth = std::max<uint32_t>(s->device_blas_depth, (uint32_t)db.depth);
                         on_device = true;
@@ -810,6 +824,7 @@ int pt::scene_build(pt_scene* s) {
                     if (const char* ev = exp_env("PT_SAH_SWEEP")) bl.sweep_below = (size_t)std::max(0, atoi(ev));
                     sb.root = bl.build(0, items.size(), 0, bb);
                     max_blas_depth = std::max(max_blas_depth, bl.depth_reached);
+                    sb.depth = bl.depth_reached;
                 }
                 sb.extent = box_extent(bb);
                 sb.face_pos.resize(perm.size());
@@ -822,7 +837,26 @@ int pt::scene_build(pt_scene* s) {
                 }
                 it = blas_of.emplace(oi, std::move(sb)).first;
             }
-            const SharedBlas& sb = it->second;
+            SharedBlas& sb = it->second;
+            if (is_light) {
+                // exact light sampling's table (the rule in pt_amd.h), built whatever the kind: C[0] = 0, C[i + 1] = C[i] + A_i in face order,
+                // A_i = 0.5 |cross(v1 - v0, v2 - v0)| of the local-space vertices — instance chains are rigid, so every placement shares it
+                if (sb.cdf_ofs == 0xFFFFFFFFu) {
+                    if (light_cdf.size() + o->tris.size() + 1 > 0xFFFFFFF0ull) return set_error("pt_world_build: too many light triangles");
+                    sb.cdf_ofs = (uint32_t)light_cdf.size();
+                    double c = 0.0;
+                    light_cdf.push_back(c);
+                    for (const TriD& t : o->tris) {
+                        const D3 v0 = d3(t.v0);
+                        c = c + 0.5 * length(cross(d3(t.v1) - v0, d3(t.v2) - v0));
+                        light_cdf.push_back(c);
+                    }
+                }
+                const double A = light_cdf[sb.cdf_ofs + o->tris.size()];
+                s->light_mesh_bad_area = s->light_mesh_bad_area || !(A > 0.0 && std::isfinite(A));
+                s->light_blas_depth = std::max<uint32_t>(s->light_blas_depth, (uint32_t)sb.depth);
+                e.pad[0] = sb.cdf_ofs;
+            }
             e.blas_root = sb.root;
             e.extent = sb.extent;
             local = sb.local;
@@ -959,7 +993,8 @@ int pt::scene_build(pt_scene* s) {
     bool ok = upload(dev, nodes, v.nodes) && upload(dev, entries, v.entries) && upload(dev, prims, v.prims) &&
               upload(dev, spheres, v.spheres) && upload(dev, quads, v.quads) && upload(dev, tris, v.tris) &&
               upload(dev, tri_gid, v.tri_gid) && upload(dev, insts, v.insts) && upload(dev, tex, v.tex) &&
-              upload(dev, mats, v.mats) && upload(dev, atlas, v.atlas) && upload(dev, atlas_f, v.atlas_f) && upload(dev, lights, v.lights) && upload(dev, entry_box, v.entry_box) && upload(dev, cuboid_box, v.cuboid_box);
+              upload(dev, mats, v.mats) && upload(dev, atlas, v.atlas) && upload(dev, atlas_f, v.atlas_f) && upload(dev, lights, v.lights) && upload(dev, entry_box, v.entry_box) && upload(dev, cuboid_box, v.cuboid_box) &&
+              upload(dev, light_cdf, v.light_cdf);
     if (ok && any_attr) ok = upload(dev, tri_attr, v.tri_attr);
     if (ok && !grids.empty()) ok = upload(dev, grids, v.grids) && upload(dev, grid_vals, v.grid_vals);
     if (!ok) {

@@ -114,6 +114,12 @@ struct pt_scene {
     bool grid_media_on() const {   // "in effect": the kernels' HET forms run
         return world_has_grid_medium || (camera_medium >= 0 && mats[camera_medium].p[6] != 0.0);
     }
+    // exact light sampling (pt_scene_set_light_sampling): the kind, and what scene_build found in the lights list — a mesh or
+    // sphere entry (kind 1 is then in effect), a light mesh whose area is 0 or not finite, the deepest light mesh tree
+    int light_sampling = 0;        // 0 the reference's lights.sample / lights.pdf, 1 exact (the kernels' LSE forms)
+    bool lights_have_mesh_or_sphere = false, light_mesh_bad_area = false;
+    uint32_t light_blas_depth = 0;
+    bool light_sampling_on() const { return light_sampling == 1 && lights_have_mesh_or_sphere; }   // "in effect"
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned

@@ -51,7 +51,7 @@ struct Entry {           // one per world-level object (lights list first, then 
     uint32_t blas_root;  // node index (ENTRY_MESH); several placements of one mesh share the tree and its triangles
     float extent;        // ENTRY_MESH: max |coordinate| of the mesh's (local-space) BVH boxes
     uint32_t n_prims;    // 1 (sphere, quad), 6 (cuboid) or the triangle count (mesh)
-    uint32_t pad[2];
+    uint32_t pad[2];     // pad[0]: a MESH entry of the lights list: first element of its area table in SceneD::light_cdf
 };
 // Flat top-level walk (SceneD::tlas_flat): everything a step of the walk needs in ONE 64-byte record, i.e. one scalar load — the
 // entry's world-space box (padded and rounded outward like the node boxes), a copy of its Entry, and for spheres / quads /
@@ -200,7 +200,10 @@ struct SceneD {
     uint32_t flat_pairs;         // tlas_flat and the scene has cuboids: the batch K2 runs its (ray, primitive) pair passes
     const GridD* grids;          // grid-density media (MatD::p[6] - 1 indexes it); read by k_shade's HET forms and the medium probe only
     const float* grid_vals;      // their f32 samples, one array (GridD::ofs)
+    const double* light_cdf;     // exact light sampling (pt_scene_set_light_sampling): per light mesh of n faces the n + 1 running
+                                 // area sums C[0] = 0 .. C[n] = A in face order, at Entry::pad[0]; read by k_shade's LSE forms and the light probe only
 };
+constexpr int LIGHT_STACK = 24;          // LDS entries per lane of the LSE forms' all-hits mesh walk (pt_dev_lights.h): the deepest light mesh tree they take
 constexpr uint32_t TLAS_FLAT_MAX = 24;   // round 1 (vector loads): 8-10 entries -26 % / -7 % K2 time, 17 entries (scene 5) +20 % -> limit 12;
                                           // round 2 (scalar loads, ldu): 17 entries -20 % -> limit raised
 

@@ -72,6 +72,57 @@ static bool parse_interior(const std::string& v, double out[8]) {
     return ok && out[0] + std::max(out[5], std::max(out[6], out[7])) > 0.0;
 }
 
+// X,Y,Z,RADIUS[,R,G,B] of --mesh-light: four or seven numbers, each parsed whole; radius > 0, emission >= 0
+static bool parse_mesh_light(const std::string& v, double out[7]) {
+    std::vector<double> x;
+    size_t pos = 0;
+    while (pos <= v.size()) {
+        const size_t comma = std::min(v.find(',', pos), v.size());
+        const std::string tok = v.substr(pos, comma - pos);
+        char* end = nullptr;
+        const double d = strtod(tok.c_str(), &end);
+        if (tok.empty() || !end || *end != 0 || !std::isfinite(d)) return false;
+        x.push_back(d);
+        pos = comma + 1;
+    }
+    if (x.size() != 4 && x.size() != 7) return false;
+    if (!(x[3] > 0.0)) return false;
+    for (size_t i = 4; i < x.size(); ++i)
+        if (!(x[i] >= 0.0)) return false;
+    for (size_t i = 0; i < x.size(); ++i) out[i] = x[i];
+    return true;
+}
+// A unit icosahedron subdivided `level` times (20 * 4^level triangles), its vertices pushed out to `radius` around `centre`
+static Mesh icosphere(int level, Vec3 centre, double radius) {
+    const double t = (1.0 + std::sqrt(5.0)) / 2.0;
+    std::vector<Vec3> v = {{-1, t, 0}, {1, t, 0}, {-1, -t, 0}, {1, -t, 0}, {0, -1, t}, {0, 1, t}, {0, -1, -t}, {0, 1, -t}, {t, 0, -1}, {t, 0, 1}, {-t, 0, -1}, {-t, 0, 1}};
+    std::vector<uint32_t> f = {0, 11, 5, 0, 5, 1, 0, 1, 7, 0, 7, 10, 0, 10, 11, 1, 5, 9, 5, 11, 4, 11, 10, 2, 10, 7, 6, 7, 1, 8,
+                               3, 9, 4, 3, 4, 2, 3, 2, 6, 3, 6, 8, 3, 8, 9, 4, 9, 5, 2, 4, 11, 6, 2, 10, 8, 6, 7, 9, 8, 1};
+    auto unit = [](Vec3 p) { const double l = std::sqrt(p.x * p.x + p.y * p.y + p.z * p.z); return Vec3{p.x / l, p.y / l, p.z / l}; };
+    for (Vec3& p : v) p = unit(p);
+    for (int l = 0; l < level; ++l) {
+        std::map<uint64_t, uint32_t> cache;
+        auto mid = [&](uint32_t a, uint32_t b) {
+            const uint64_t key = ((uint64_t)std::min(a, b) << 32) | std::max(a, b);
+            auto it = cache.find(key);
+            if (it != cache.end()) return it->second;
+            v.push_back(unit(Vec3{v[a].x + v[b].x, v[a].y + v[b].y, v[a].z + v[b].z}));
+            return cache[key] = (uint32_t)v.size() - 1;
+        };
+        std::vector<uint32_t> nf;
+        for (size_t i = 0; i < f.size(); i += 3) {
+            const uint32_t a = f[i], b = f[i + 1], c = f[i + 2], ab = mid(a, b), bc = mid(b, c), ca = mid(c, a);
+            for (uint32_t k : {a, ab, ca, b, bc, ab, c, ca, bc, ab, bc, ca}) nf.push_back(k);
+        }
+        f = nf;
+    }
+    Mesh m;
+    for (const Vec3& p : v)
+        for (double c : {centre.x + radius * p.x, centre.y + radius * p.y, centre.z + radius * p.z}) m.positions.push_back((float)c);
+    m.indices = f;
+    return m;
+}
+
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
@@ -85,6 +136,9 @@ int main(int argc, char** argv) {
     double smoke_v[5] = {0.0, 1.0, 1.0, 1.0, 0.0};   // scale, albedo r g b, g
     bool interior = false;
     double interior_v[8] = {0.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};   // density, albedo r g b, g, absorption r g b
+    int light_sampling = -1;   // -1: not given (--mesh-light then implies exact)
+    bool mesh_light = false;
+    double mesh_light_v[7] = {0.0, 0.0, 0.0, 0.0, 10.0, 10.0, 10.0};   // centre x y z, radius, emission r g b
     long aov_spp = 16;
     uint64_t seed = 1;
     std::string out, assets = "assets";
@@ -128,12 +182,22 @@ int main(int argc, char** argv) {
             }
             interior = true;
         }
+        else if (a == "--light-sampling") {
+            const std::string v = next();
+            if (v == "reference") light_sampling = 0;
+            else if (v == "exact") light_sampling = 1;
+            else { std::cerr << "--light-sampling must be reference or exact\n"; return 2; }
+        }
+        else if (a == "--mesh-light") {
+            if (!parse_mesh_light(next(), mesh_light_v)) { std::cerr << "--mesh-light must be X,Y,Z,RADIUS[,R,G,B]: radius > 0, emission >= 0\n"; return 2; }
+            mesh_light = true;
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n"
                          "  --smoke: an unbounded grid-density camera medium of extinction SCALE * V over the world's bounds grown by 1 % (the box --fog fills),\n"
                          "           V sampled at the centres of 64^3 cells; at the normalised position (x, y, z) of the box, y up:\n"
                          "           cx = 0.5 + 0.08 sin(3 pi y), cz = 0.5 + 0.08 cos(2 pi y), r = 0.06 + 0.22 y,\n"
@@ -152,6 +216,11 @@ int main(int argc, char** argv) {
     if (smoke && fog) { std::cerr << "--smoke and --fog cannot be combined\n"; return 2; }
     if (interior && env_sampling > 0.0) { std::cerr << "--interior and --env-sampling cannot be combined\n"; return 2; }
     if (interior && (fog || smoke)) { std::cerr << "--interior cannot be combined with --fog or --smoke (that would nest media)\n"; return 2; }
+    if (mesh_light && (env_sampling > 0.0 || fog || smoke || interior)) {
+        std::cerr << "--mesh-light cannot be combined with --env-sampling, --fog, --smoke or --interior (exact light sampling runs without them)\n";
+        return 2;
+    }
+    if (light_sampling < 0) light_sampling = mesh_light ? 1 : 0;
     if (scene < 1 || scene > 7) return 0;   // `_ => ()` main.rs:643
     pt_ctx* ctx = nullptr;
     if (pt_ctx_create(device, &ctx) != 0) {
@@ -163,6 +232,13 @@ int main(int argc, char** argv) {
         setup.world.float_hdr = float_hdr;
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;
+        setup.world.light_sampling = light_sampling;
+        if (mesh_light) {   // an emissive level-4 icosphere (5120 triangles), in the world and in the lights list
+            auto ball = TriangleMesh::from_obj(1.0, icosphere(4, Vec3{mesh_light_v[0], mesh_light_v[1], mesh_light_v[2]}, mesh_light_v[3]),
+                                               DiffuseLight::from_rgb(Vec3{mesh_light_v[4], mesh_light_v[5], mesh_light_v[6]}));
+            setup.world.add_object(ball);
+            setup.world.add_light(ball);
+        }
         if (fog || smoke) {
             const double inf = std::numeric_limits<double>::infinity();
             Vec3 lo{inf, inf, inf}, hi{-inf, -inf, -inf};

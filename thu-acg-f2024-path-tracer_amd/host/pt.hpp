@@ -487,6 +487,7 @@ struct World {
     bool float_hdr = false;   // this build's option: Radiance .hdr images keep their f32 samples (no .to_rgb8(), texture.rs:67)
     int sampler = 0;             // this build's option: 0 independent draws (the reference's), 1 Owen-scrambled Sobol (pt_scene_set_sampler)
     double env_sampling = 0.0;   // this build's option: environment importance sampling weight (pt_scene_set_env_sampling; 0 = off)
+    int light_sampling = 0;      // this build's option: 0 the reference's lights.sample / lights.pdf, 1 exact (pt_scene_set_light_sampling)
     void build_bvh(pt_ctx* ctx, std::shared_ptr<ImageTexture> env = nullptr) {
         pt_scene* s = pt_scene_create(ctx);
         if (!s) panic("pt_scene_create");
@@ -494,6 +495,7 @@ struct World {
         if (float_hdr) pt_scene_set_float_hdr(s, 1);
         if (env_sampling != 0.0 && pt_scene_set_env_sampling(s, env_sampling) != 0) panic("set_env_sampling");
         if (sampler != 0 && pt_scene_set_sampler(s, sampler) != 0) panic("set_sampler");
+        if (light_sampling != 0 && pt_scene_set_light_sampling(s, light_sampling) != 0) panic("set_light_sampling");
         emit_into(s, env);
     }
     void release() {
