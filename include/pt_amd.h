@@ -296,6 +296,51 @@ int pt_scene_camera_medium(pt_scene*);
 int pt_mat_medium_tinted(pt_scene*, double density, double r, double g, double b, double hg_g, const double absorption[3]);
 int pt_mat_glass_set_interior(pt_scene*, int glass_mat, int medium_mat);
 int pt_mat_glass_interior(pt_scene*, int glass_mat);
+/* ---- spectral dispersion of glass: prisms, diamonds, the coloured rim of a lens (no counterpart in the reference, whose glass has one
+ * index of refraction for all light) ----
+ * pt_mat_glass_set_dispersion: the ior given to pt_mat_glass is read as n_d, the index at lambda_d = 587.56 nm; abbe is the Abbe number
+ * V_d = (n_d - 1) / (n_F - n_C), lambda_F = 486.13 nm, lambda_C = 656.27 nm; 0 = off (the default). Two-term Cauchy, wavelengths in um,
+ * all f64, the operations in the order written:
+ *   inv2(l) = 1.0 / (l * l);  b = (n_d - 1) / (abbe * (inv2(0.48613) - inv2(0.65627)));
+ *   n(lambda) = n_d + b * (inv2(lambda_nm * 1e-3) - inv2(0.58756))      (the host computes b and inv2(0.58756), the device the rest)
+ * Returns -1 and leaves the setting when glass_mat is not a pt_mat_glass handle, when abbe is negative or not finite, when abbe > 0 and
+ * n(380) or n(730) is not finite or is <= 1, or when the glass is a child of a mix; pt_mat_mix with a dispersive child returns -1. The
+ * world must be (re)built after the call. pt_mat_glass_dispersion: V_d, 0 when off, -1 on a bad handle.
+ * Dispersion is IN EFFECT for a render when some world object's own material is a glass with abbe > 0; otherwise every entry point
+ * launches exactly the kernels it launches without this setting and produces the same bits (a dispersive glass nothing uses, or a
+ * dispersion set and cleared again, does not count). In effect for pt_render, pt_render_pixels, pt_render_adaptive and pt_render_multi;
+ * pt_render_aovs and pt_intersect do not change. With dispersion in effect a render returns -1 when environment importance sampling,
+ * participating media (a glass interior among them) or exact light sampling are in effect too, or when max_depth >= 2^31.
+ *
+ * The wavelength of a path is a function of (seed, pixel, global sample index s) alone — no draw of the path's own stream is made; draw
+ * indices and Sobol pair alignment do not move:
+ *   sampler kind 0: K = Philox4x32-10(counter = (0, s, seed_hi, 2), key = (seed_lo, pixel));  v = (uint64(K[0]) << 32) | K[1]
+ *   sampler kind 1: K = Philox4x32-10(counter = (0, 0, seed_hi, 2), key = (seed_lo, pixel));  x = owen(sobol0(s), K[0]);
+ *                   v = (uint64(x) << 32) | lk(x, K[1])   (owen, sobol0, lk: pt_scene_set_sampler's rule) — so the 2^m samples of an
+ *                   aligned block of one pixel put one wavelength into every stratum of width 2^-m
+ *   (counter word 3 = 2 is a stream of its own: 0 and 1 are the two samplers')
+ *   u = (v >> 11) * 2^-53;  lambda = 380 + u * 350 (nm);  bin j = min(floor(u * 64), 63)
+ * The weight table W[64][3], the same for every scene, built on the host in f64. At the centre of bin j, l_j = 380 + (j + 0.5) * (350 / 64),
+ * with the piecewise Gaussian g(l; mu, s1, s2) = exp(-0.5 * ((l - mu) / s)^2), s = s1 for l < mu, else s2:
+ *   x = 1.056 g(599.8, 37.9, 31.0) + 0.362 g(442.0, 16.0, 26.7) - 0.065 g(501.1, 20.4, 26.2)
+ *   y = 0.821 g(568.8, 46.9, 40.5) + 0.286 g(530.9, 16.3, 31.1)
+ *   z = 1.217 g(437.0, 11.8, 36.0) + 0.681 g(459.0, 26.0, 13.8)
+ *   r =  3.2404542 x - 1.5371385 y - 0.4985314 z;  g = -0.9692660 x + 1.8760108 y + 0.0415560 z;  b = 0.0556434 x - 0.2040259 y + 1.0572252 z
+ *   raw_c(j) = max(0, .);  W[j][c] = raw_c(j) * 64 / (sum of raw_c(k), k = 0 .. 63 in order) — the mean of every channel over the bins is 1.
+ * (The numbers follow the multi-lobe fit of Wyman, Sloan and Shirley 2013 to the CIE 1931 observer and the XYZ -> linear sRGB matrix;
+ * this text defines them.)
+ * The estimator: one addition to the surface bounce. Every path carries one flag, MONO, clear on a camera ray. At a surface hit whose
+ * own material is a glass with abbe > 0 the bounce is processed exactly as without dispersion (roulette, selector, light or BSDF
+ * direction, pdf, eval, offset) except that every read of the glass's ior at this bounce — eta_i / eta_o in sample, pdf and eval — takes
+ * n(lambda) of the path's wavelength. If the bounce continues the path and MONO is clear: MONO is set and the new throughput is
+ * (thr * attenuation) * W[j], componentwise, in that order. A path whose MONO is set is not weighted again. Every other hit, every miss,
+ * roulette, emission and the environment are unchanged; the principled material's glass lobe is not dispersive. With all V_d -> infinity
+ * the expectation is the one without dispersion: lambda is independent of everything the path does before its first dispersive visit and
+ * the mean of W is (1, 1, 1).
+ * Not supported: dispersion together with an interior, with media, environment sampling or exact light sampling; dispersive principled or
+ * mix materials; wavelength-dependent emission or textures; more than the two Cauchy terms. */
+int pt_mat_glass_set_dispersion(pt_scene*, int glass_mat, double abbe);
+double pt_mat_glass_dispersion(pt_scene*, int glass_mat);
 /* the three bsdf/ materials no reference scene instantiates */
 int pt_mat_mix(pt_scene*, double t, int mat1, int mat2);                /* MixBxDf::new mix.rs:14-20; a child may itself be a mix of non-mix materials (two levels) */
 int pt_mat_sheen(pt_scene*, double r, double g, double b, double sheen_tint);   /* SheenBRDF::new sheen.rs:17-22 */
@@ -484,6 +529,11 @@ int pt_medium_probe(pt_scene*, int mat, int which, const double* in, uint32_t n,
  * non-mesh entry (and always under kind 0), draws consumed). which = 1: in = n x (origin.xyz, direction.xyz, time), out = n
  * lights.pdf values. */
 int pt_light_probe(pt_scene*, int which, const double* in, uint32_t n, double* out);
+/* the device functions of dispersion that k_shade calls (pt_mat_glass_set_dispersion's rule), for dispersive glass `glass_mat` (-1 when it
+ * is not one), under the scene's current sampler kind. which = 0: in = n x (pixel, sample) as doubles (32-bit unsigned integers), out =
+ * n x (u, lambda, j, W_r, W_g, W_b, n(lambda)) of a path of `seed`; which = 1: in = n wavelengths in nm, out = n values n(lambda).
+ * The world need not be built. */
+int pt_dispersion_probe(pt_scene*, int glass_mat, int which, uint64_t seed, const double* in, uint32_t n, double* out);
 
 #ifdef __cplusplus
 }

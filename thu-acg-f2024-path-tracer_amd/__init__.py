@@ -127,6 +127,7 @@ ABI_SYMBOLS = [
     "pt_mat_medium_grid",
     "pt_mat_medium_tinted", "pt_mat_glass_set_interior", "pt_mat_glass_interior",
     "pt_scene_set_light_sampling", "pt_scene_light_sampling", "pt_light_probe",
+    "pt_mat_glass_set_dispersion", "pt_mat_glass_dispersion", "pt_dispersion_probe",
 ]
 
 
@@ -178,6 +179,11 @@ def _load():
         lib.pt_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         lib.pt_scene_light_sampling.argtypes = [C.c_void_p]
         lib.pt_light_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "pt_mat_glass_set_dispersion"):   # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_mat_glass_set_dispersion.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        lib.pt_mat_glass_dispersion.argtypes = [C.c_void_p, C.c_int]
+        lib.pt_mat_glass_dispersion.restype = C.c_double
+        lib.pt_dispersion_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -499,6 +505,28 @@ class Scene:
 
     def mat_glass_interior(self, glass_mat: int) -> int:
         return lib.pt_mat_glass_interior(self.handle, int(glass_mat))
+
+    def mat_glass_set_dispersion(self, glass_mat: int, abbe: float):
+        """Spectral dispersion of glass material `glass_mat`: its ior is read as n_d (587.56 nm) and `abbe` is the Abbe number V_d of a
+        two-term Cauchy law (crown glass about 60, flint 30; smaller = more colour; 0 = off, the default). Every path then carries one
+        wavelength, drawn per (seed, pixel, sample) and stratified under the Sobol sampler (the rule is in include/pt_amd.h, DESIGN.md
+        §16). Rebuild the world after."""
+        return _check(lib.pt_mat_glass_set_dispersion(self.handle, int(glass_mat), float(abbe)), "mat_glass_set_dispersion")
+
+    def mat_glass_dispersion(self, glass_mat: int) -> float:
+        """The Abbe number set with mat_glass_set_dispersion, 0.0 when off, -1.0 for a handle that is not a glass."""
+        return lib.pt_mat_glass_dispersion(self.handle, int(glass_mat))
+
+    def dispersion_probe(self, glass_mat: int, which: int, arr: np.ndarray, seed: int = 0) -> np.ndarray:
+        """The device functions of dispersion that the kernels call, for dispersive glass `glass_mat`, under the scene's sampler kind.
+        which 0: arr = (n, 2) (pixel, sample) -> (n, 7) {u, lambda in nm, bin, W_r, W_g, W_b, n(lambda)} of a path of `seed`;
+        which 1: arr = (n,) wavelengths in nm -> (n,) n(lambda). The world need not be built."""
+        if which not in (0, 1):
+            raise PtError("dispersion_probe: which must be 0 or 1")
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, 2) if which == 0 else (-1,))
+        out = np.empty((len(arr), 7) if which == 0 else (len(arr),), dtype=np.float64)
+        _check(lib.pt_dispersion_probe(self.handle, int(glass_mat), which, int(seed), arr.ctypes.data, len(arr), out.ctypes.data), "pt_dispersion_probe")
+        return out
 
     def set_camera_medium(self, mat: int):
         """The medium camera rays start in (a mat_medium / mat_medium_tinted / mat_medium_grid handle; -1 = none, the default)."""

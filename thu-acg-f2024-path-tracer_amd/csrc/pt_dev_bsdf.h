@@ -222,8 +222,11 @@ PT_DEV TexVals fetch_tex(const SceneD& sc, const MatD& m, const HitD& h) {
 
 // ---- BxDFMaterial::sample (bsdf/mod.rs:23) ----------------------------------------------
 // wo = -ray.direction. Returns false where the reference returns None.
-template <class R>
-PT_DEV bool mat_sample(const SceneD& sc, const MatD& mat, const HitD& h, V3 wo, R& rng, double two_pi_scale, const TexVals& tv, const LocalFrame& lf, V3& dir) {
+// DSP (k_shade's dispersion forms): `ior_l` = n(lambda) of the path's wavelength when the hit's own material is a dispersive
+// glass — every read of that glass's ior takes it — else 0: the material's own ior. The other forms compile the argument out.
+template <class R, bool DSP = false>
+PT_DEV bool mat_sample(const SceneD& sc, const MatD& mat, const HitD& h, V3 wo, R& rng, double two_pi_scale, const TexVals& tv, const LocalFrame& lf, V3& dir,
+                       double ior_l = 0.0) {
     const MatD* leaf = &mat;
     double rough = tv.rough;
     const bool own = mat.kind == MAT_MIX;   // a mix's child builds its own frame; everything else uses the bounce's (make_local_frame)
@@ -255,6 +258,9 @@ PT_DEV bool mat_sample(const SceneD& sc, const MatD& mat, const HitD& h, V3 wo, 
     case MAT_GLASS: {     // glass.rs:66-90
         V3 hv = ggx_sample_microfacet_normal(v, rough, rng);
         double eta_i = h.front ? 1.0 : m.ior, eta_o = h.front ? m.ior : 1.0;
+        if constexpr (DSP) {
+            if (ior_l > 0.0) { eta_i = h.front ? 1.0 : ior_l; eta_o = h.front ? ior_l : 1.0; }
+        }
         dir = to_world(f, sample_dielectric(v, hv, eta_i, eta_o, rng));
         return true;
     }
@@ -302,7 +308,8 @@ PT_DEV bool mat_sample(const SceneD& sc, const MatD& mat, const HitD& h, V3 wo, 
 }
 
 // ---- BxDFMaterial::pdf + eval (cosine included in eval) -----------------------------------
-PT_DEV void leaf_pdf_eval(const SceneD& sc, const MatD& m, const HitD& h, V3 wo, V3 wi, const TexVals& tv, const LocalFrame& lf, double& pdf, V3& brdf) {
+template <bool DSP = false>   // DSP, ior_l: as in mat_sample
+PT_DEV void leaf_pdf_eval(const SceneD& sc, const MatD& m, const HitD& h, V3 wo, V3 wi, const TexVals& tv, const LocalFrame& lf, double& pdf, V3& brdf, double ior_l = 0.0) {
     const Frame f = lf.f;     // the leaf's frame and local view vector (make_local_frame)
     const V3 v = lf.v;
     switch (m.kind) {
@@ -330,6 +337,9 @@ PT_DEV void leaf_pdf_eval(const SceneD& sc, const MatD& m, const HitD& h, V3 wo,
         V3 l = to_local(f, wi);
         bool is_reflect = l.z * v.z > 0.0;
         double eta_i = h.front ? 1.0 : m.ior, eta_o = h.front ? m.ior : 1.0;
+        if constexpr (DSP) {
+            if (ior_l > 0.0) { eta_i = h.front ? 1.0 : ior_l; eta_o = h.front ? ior_l : 1.0; }
+        }
         V3 hv = generalized_half(v, l, is_reflect, eta_i, eta_o);
         double rough = tv.rough;
         double g1v = ggx_G1(v, rough), d = ggx_D(hv, rough);
@@ -428,7 +438,8 @@ PT_DEV void leaf_pdf_eval(const SceneD& sc, const MatD& m, const HitD& h, V3 wo,
 // two products and their sum separately, so the weights are NOT multiplied through: the (at most four) leaves are visited in
 // the recursion's order by ONE non-unrolled loop (the leaf code above is instantiated once), an inner accumulator holding the
 // current child's value while its second leaf is evaluated and an outer one holding the first child's weighted value.
-PT_DEV void mat_pdf_eval(const SceneD& sc, const MatD& m, const HitD& h, V3 wo, V3 wi, const TexVals& tv, const LocalFrame& lf, double& pdf, V3& brdf) {
+template <bool DSP = false>   // DSP, ior_l: as in mat_sample (a dispersive glass is never a mix's child, so ior_l is 0 on every pass of the loop but a lone leaf's)
+PT_DEV void mat_pdf_eval(const SceneD& sc, const MatD& m, const HitD& h, V3 wo, V3 wi, const TexVals& tv, const LocalFrame& lf, double& pdf, V3& brdf, double ior_l = 0.0) {
     const bool mix = m.kind == MAT_MIX;
     pdf = 0.0;
     brdf = V3{0.0, 0.0, 0.0};
@@ -446,7 +457,7 @@ PT_DEV void mat_pdf_eval(const SceneD& sc, const MatD& m, const HitD& h, V3 wo, 
         V3 lfv;
         const TexVals ltv = mix ? fetch_tex(sc, lm, h) : tv;
         const LocalFrame llf = mix ? make_local_frame(lm, h, wo) : lf;
-        leaf_pdf_eval(sc, lm, h, wo, wi, ltv, llf, lp, lfv);
+        leaf_pdf_eval<DSP>(sc, lm, h, wo, wi, ltv, llf, lp, lfv, ior_l);
         if (!mix) {
             pdf = lp;
             brdf = lfv;

@@ -29,17 +29,18 @@ constexpr int shade_row(int variant, int i = N_SHADE_SHAPES - 1) { return i == 0
 // THE list of feature combinations: pixel list / ENV / QMC / MED exist only for the default variant's shapes, ENV never with MED,
 // HET (grid-density media) only with MED, INT (interior media and chromatic absorption, §14) only with MED and HET — HET
 // renders homogeneous media with MED's bits, so the INT forms need not exist without it; LSE (exact light sampling, §15) only for the default variant's shapes, only
-// with a lights list, never with ENV or MED
-constexpr bool shade_form_exists(const ShadeShape& s, bool list, bool env, bool qmc, bool med, bool het = false, bool intr = false, bool lse = false, bool lights = true) {
-    return (s.variant == 22 || s.variant == 32 || s.variant == 42 || !(list || env || qmc || med || lse)) && !(env && med) && (med || !het) && ((med && het) || !intr) &&
-           (!lse || (lights && !env && !med));
+// with a lights list, never with ENV or MED; DSP (spectral dispersion, §16) only for the default variant's shapes, never with ENV, MED or LSE
+constexpr bool shade_form_exists(const ShadeShape& s, bool list, bool env, bool qmc, bool med, bool het = false, bool intr = false, bool lse = false, bool lights = true,
+                                 bool dsp = false) {
+    return (s.variant == 22 || s.variant == 32 || s.variant == 42 || !(list || env || qmc || med || lse || dsp)) && !(env && med) && (med || !het) && ((med && het) || !intr) &&
+           (!lse || (lights && !env && !med)) && (!dsp || !(env || med || lse));
 }
 // the unit that compiles a form: pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip (§12), pt_k3_het.hip (§13) or pt_k3_int.hip
-// (§14), or pt_k3_lse.hip (§15: every LSE form, with or without QMC). K1 has no HET, INT or LSE form — a camera ray's bounce word is the MED form's — so such a render's k_init is the one of the form
-// without het, intr and lse (form_kernels).
-enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED, UNIT_HET, UNIT_INT, UNIT_LSE };
-constexpr FormUnit form_unit(bool qmc, bool med, bool het = false, bool intr = false, bool lse = false) {
-    return lse ? UNIT_LSE : intr ? UNIT_INT : het ? UNIT_HET : med ? UNIT_MED : qmc ? UNIT_QMC : UNIT_PLAIN;
+// (§14), or pt_k3_lse.hip (§15: every LSE form, with or without QMC), or pt_k3_dsp.hip (§16: every DSP form, with or without QMC). K1 has no HET, INT, LSE or DSP form — a camera ray's
+// bounce word is the MED form's, or 0 — so such a render's k_init is the one of the form without het, intr, lse and dsp (form_kernels).
+enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED, UNIT_HET, UNIT_INT, UNIT_LSE, UNIT_DSP };
+constexpr FormUnit form_unit(bool qmc, bool med, bool het = false, bool intr = false, bool lse = false, bool dsp = false) {
+    return dsp ? UNIT_DSP : lse ? UNIT_LSE : intr ? UNIT_INT : het ? UNIT_HET : med ? UNIT_MED : qmc ? UNIT_QMC : UNIT_PLAIN;
 }
 
 // run-time bools -> template arguments: f is called with one std::bool_constant per bool
@@ -52,15 +53,15 @@ template <class F, class... Rest> auto expand_bools(F&& f, bool b, Rest... rest)
 // The kernels of unit U for a form; null where the form does not exist or belongs to another unit. Every unit instantiates exactly the
 // forms it owns by compiling unit_forms<its U>.
 struct FormKernels { shade_fn shade; init_fn init; aov_fn aov; };   // (k_aov / k_aov_qmc are not templates: the unit's accessor names its own)
-template <FormUnit U, int ROW, bool LIGHTS, bool LIST, bool ENV, bool QMC, bool MED, bool HET, bool INT, bool LSE> shade_fn shade_kernel() {
+template <FormUnit U, int ROW, bool LIGHTS, bool LIST, bool ENV, bool QMC, bool MED, bool HET, bool INT, bool LSE, bool DSP> shade_fn shade_kernel() {
     constexpr ShadeShape S = SHADE_SHAPES[ROW];
-    if constexpr (shade_form_exists(S, LIST, ENV, QMC, MED, HET, INT, LSE, LIGHTS) && form_unit(QMC, MED, HET, INT, LSE) == U)
-        return k_shade<S.sort, S.minw, LIGHTS, S.kb, S.per, LIST, ENV, QMC, MED, HET, INT, LSE>;
+    if constexpr (shade_form_exists(S, LIST, ENV, QMC, MED, HET, INT, LSE, LIGHTS, DSP) && form_unit(QMC, MED, HET, INT, LSE, DSP) == U)
+        return k_shade<S.sort, S.minw, LIGHTS, S.kb, S.per, LIST, ENV, QMC, MED, HET, INT, LSE, DSP>;
     else return nullptr;
 }
 template <FormUnit U, size_t... ROW> shade_fn shade_of(const ShadeForm& f, std::index_sequence<ROW...>) {
     shade_fn k = nullptr;
-    ((shade_row(f.variant) == (int)ROW ? k = expand_bools([](auto... b) { return shade_kernel<U, (int)ROW, decltype(b)::value...>(); }, f.lights, f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse) : k), ...);
+    ((shade_row(f.variant) == (int)ROW ? k = expand_bools([](auto... b) { return shade_kernel<U, (int)ROW, decltype(b)::value...>(); }, f.lights, f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse, f.dsp) : k), ...);
     return k;
 }
 template <FormUnit U> FormKernels unit_forms(const ShadeForm& f, aov_fn aov) {
@@ -68,8 +69,8 @@ template <FormUnit U> FormKernels unit_forms(const ShadeForm& f, aov_fn aov) {
                        expand_bools([](auto list, auto qmc, auto med) -> init_fn { if constexpr (form_unit(qmc, med) == U) return k_init<list, qmc, med>; else return nullptr; },
                                     f.list, f.qmc, f.med), aov};
 }
-// the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip, pt_k3_het.hip, pt_k3_int.hip, pt_k3_lse.hip) — the only calls from one kernel unit into another
+// the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip, pt_k3_het.hip, pt_k3_int.hip, pt_k3_lse.hip, pt_k3_dsp.hip) — the only calls from one kernel unit into another
 FormKernels forms_plain(const ShadeForm& f), forms_qmc(const ShadeForm& f), forms_med(const ShadeForm& f), forms_het(const ShadeForm& f), forms_int(const ShadeForm& f),
-    forms_lse(const ShadeForm& f);
+    forms_lse(const ShadeForm& f), forms_dsp(const ShadeForm& f);
 
 }  // namespace pt

@@ -31,10 +31,10 @@ __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t see
 
 FormKernels forms_plain(const ShadeForm& f) { return unit_forms<UNIT_PLAIN>(f, k_aov); }
 static FormKernels form_kernels(const ShadeForm& f) {   // asks the unit that owns the form
-    if (f.het || f.lse) {   // k_shade from the grid-media, interior or light-sampling unit, k_init from the form without het, intr and lse (K1 has no such form: pt_forms.h)
+    if (f.het || f.lse || f.dsp) {   // k_shade from the grid-media, interior, light-sampling or dispersion unit, k_init from the form without het, intr, lse and dsp (K1 has no such form: pt_forms.h)
         ShadeForm g = f;
-        g.het = g.intr = g.lse = false;
-        FormKernels k = f.lse ? forms_lse(f) : f.intr ? forms_int(f) : forms_het(f);
+        g.het = g.intr = g.lse = g.dsp = false;
+        FormKernels k = f.dsp ? forms_dsp(f) : f.lse ? forms_lse(f) : f.intr ? forms_int(f) : forms_het(f);
         k.init = k.shade ? form_kernels(g).init : nullptr;
         return k;
     }
@@ -42,8 +42,9 @@ static FormKernels form_kernels(const ShadeForm& f) {   // asks the unit that ow
 }
 
 ShadeForm shade_form(ShadeForm f) {
-    return shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse, f.lights) ? f
-                                                                                                                            : ShadeForm{42, f.lights, f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse};
+    return shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse, f.lights, f.dsp)
+               ? f
+               : ShadeForm{42, f.lights, f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse, f.dsp};
 }
 bool shade_form_sorts(const ShadeForm& f) { return SHADE_SHAPES[shade_row(f.variant)].sort; }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "pt_k_common.h"
 #include "pt_dev_lights.h"
+#include "pt_dev_dispersion.h"
 
 namespace pt {
 
@@ -197,8 +198,13 @@ struct NoPrefetch {
 // LSE (only with LIGHTS, never with ENV or MED): exact light sampling is in effect (the rule in pt_amd.h). B1's light direction
 // and B2's light density come from pt_dev_lights.h: area-weighted mesh lights whose pdf walks the mesh's BVH with the lane's stack in LDS
 // (lstk = &stack[0][thread] of k_shade's LSE_KB-lane stack), cone-sampled sphere lights. Everything else is the bounce above bit for bit.
+// DSP (never with ENV, MED or LSE): spectral dispersion is in effect (the rule in pt_amd.h). The path's MONO flag rides in bit 31 of its
+// bounce word. Phase A: a lane at a dispersive glass computes its path's wavelength — a function of (seed, pixel, sample), no draw — the Cauchy
+// index n(lambda) and reads its row of the weight table (`env->col`: these forms have no environment tables); B1 / B2 hand n(lambda) to the glass
+// case of mat_sample / mat_pdf_eval; a continued bounce of a path whose flag is clear multiplies the new throughput by the row and sets the flag.
+// Every other lane is the bounce above bit for bit.
 constexpr int LSE_KB = 512;                                            // threads per block of every shape that has LSE forms (pt_forms.h)
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false, bool LSE = false>
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false, bool LSE = false, bool DSP = false>
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
@@ -213,6 +219,13 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         if (bounce < SLOT_IDLE) {
             med = bounce >> MEDIUM_SHIFT;
             bounce &= MEDIUM_BOUNCE_MASK;
+        }
+    }
+    bool mono = false;                                                 // DSP: the path has been weighted by its wavelength
+    if constexpr (DSP) {
+        if (bounce < SLOT_IDLE) {
+            mono = (bounce & DSP_MONO_BIT) != 0u;
+            bounce &= DSP_BOUNCE_MASK;
         }
     }
     const bool alive = bounce != SLOT_DEAD;
@@ -261,6 +274,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     MediumD medium{};
     uint32_t interior = 0u;                                            // INT: the hit is on a glass with an interior: that medium (material index + 1)
     HitD hit{};
+    double ior_l = 0.0;                                                // DSP: the hit is on a dispersive glass: n(lambda) of the path's wavelength, else 0
+    V3 w_l{1.0, 1.0, 1.0};                                             // ... and the wavelength's row of the weight table
     const MatD* mp = nullptr;
     TexVals tv{};
     LocalFrame lf{};
@@ -317,6 +332,14 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             tv = fetch_tex(sc, *mp, hit);
             lf = make_local_frame(*mp, hit, -ray.d);
             if constexpr (INT) interior = mp->kind == MAT_GLASS ? (uint32_t)mp->p[0] : 0u;   // (read here: B2 stays arithmetic)
+            if constexpr (DSP) {
+                if (dsp_is_dispersive(*mp)) {
+                    const WavelengthD wl = dsp_wavelength<QMC>((uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample);
+                    ior_l = dsp_ior(mp->ior, mp->p[1], mp->p[2], wl.lambda);
+                    const double* row = env->col + 3u * wl.bin;
+                    w_l = V3{row[0], row[1], row[2]};
+                }
+            }
             // camera.rs:186-187 — added for every material (zero unless emissive) so that a
             // non-finite throughput poisons the sample exactly as it does in the reference
             V3 emission = mp->kind == MAT_LIGHT ? tv.color : V3{0.0, 0.0, 0.0};
@@ -371,10 +394,10 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 if (rsel < p_light) {
                     if constexpr (LSE) dir = lights_sample_exact(sc, hit.point, ray.time, rng);
                     else dir = lights_sample(sc, hit.point, ray.time, rng);
-                } else ok = mat_sample(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir);
+                } else ok = mat_sample<RngT, DSP>(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir, ior_l);
             } else {
                 ++rng.draw;
-                ok = mat_sample(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir);
+                ok = mat_sample<RngT, DSP>(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir, ior_l);
             }
             if (!ok) finished = parked = true;                         // :209-211
             else have_dir = true;
@@ -409,7 +432,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     if (have_dir) {
         double bsdf_pdf;
         V3 brdf;
-        mat_pdf_eval(sc, *mp, hit, wo, dir, tv, lf, bsdf_pdf, brdf);
+        mat_pdf_eval<DSP>(sc, *mp, hit, wo, dir, tv, lf, bsdf_pdf, brdf, ior_l);
         double light_pdf = 0.0;
         if constexpr (LSE) light_pdf = lights_pdf_exact<LSE_KB>(sc, hit.point, dir, ray.time, lstk);
         else if constexpr (LIGHTS) light_pdf = lights_pdf(sc, hit.point, dir, ray.time);
@@ -445,6 +468,12 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             }
             ray = make_ray(hit.point + e * hit.gn, dir, ray.time);
             thr = thr * attenuation;
+            if constexpr (DSP) {
+                if (ior_l > 0.0 && !mono) {                            // the path's first continued bounce at a dispersive glass: weighted once
+                    thr = thr * w_l;
+                    mono = true;
+                }
+            }
             ++bounce;
             if (bounce >= cam.max_depth) finished = parked = true;     // loop bound :177
         }
@@ -540,6 +569,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             thr = V3{1.0, 1.0, 1.0};
             rad = V3{0.0, 0.0, 0.0};
             bounce = 0;
+            if constexpr (DSP) mono = false;
             if constexpr (MED) med = cam.medium;
             sample = next_sample;
             pixel = next_pixel;
@@ -555,7 +585,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         const uint32_t state_new = bounce < SLOT_IDLE ? 0u : bounce, state_old = was_idle ? SLOT_IDLE : 0u;
         if (reorder || state_new != state_old) pool.bounce_out[o] = state_new;
         if (bounce < SLOT_IDLE) {
-            const uint32_t bounce_word = MED ? bounce | (med << MEDIUM_SHIFT) : bounce;
+            const uint32_t bounce_word = MED ? bounce | (med << MEDIUM_SHIFT) : DSP && mono ? bounce | DSP_MONO_BIT : bounce;
             store_ray(pool, pool.ray_out, o, ray, sample, rng.draw, pixel, bounce_word);
             if (!pool.compact || bounce != 0u) store_path(pool.path_out, o, thr, pixel, bounce_word);
             if (!pool.dynamic) { pool.rx[s] = rad.x; pool.ry[s] = rad.y; pool.rz[s] = rad.z; }
@@ -609,9 +639,11 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // HET: grid-density media (shade_slot)
 // INT: interior media and chromatic absorption (shade_slot)
 // LSE: exact light sampling (shade_slot); these forms hold the per-lane stack of the light meshes' all-hits walk, LIGHT_STACK levels x KB lanes in LDS
+// DSP: spectral dispersion (shade_slot); `env.col` is the weight table of these forms
 template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false, bool MED = false,
-          bool HET = false, bool INT = false, bool LSE = false>
+          bool HET = false, bool INT = false, bool LSE = false, bool DSP = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
+    static_assert(!DSP || (SORT && !ENV && !MED && !LSE && KB == 512), "k_shade: the DSP forms are sorted 512-thread forms without ENV, MED and LSE");
     static_assert(!LSE || (SORT && LIGHTS && !ENV && !MED && KB == LSE_KB), "k_shade: the LSE forms are sorted 512-thread forms with lights, without ENV and MED");
     __shared__ uint32_t s_lstack[LSE ? LIGHT_STACK * KB : 1];   // 48 KB: stack[level][thread] of lights_pdf_exact's mesh walk
     uint32_t* const lstk = LSE ? &s_lstack[threadIdx.x] : nullptr;
@@ -629,7 +661,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT, LSE>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT, LSE, DSP>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -806,7 +838,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT, LSE>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT, LSE, DSP>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env, lstk);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

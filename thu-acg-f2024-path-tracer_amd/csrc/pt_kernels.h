@@ -1,5 +1,5 @@
 // Host-callable launchers of the HIP kernels: one per stage. K2 is in pt_k2.hip, K1 / K3 / the AOV walk in pt_k3.hip (their Sobol forms in
-// pt_k3_qmc.hip, their media forms in pt_k3_med.hip, K3's grid-media forms in pt_k3_het.hip, its interior-media forms in pt_k3_int.hip, its exact-light-sampling forms in pt_k3_lse.hip), the small
+// pt_k3_qmc.hip, their media forms in pt_k3_med.hip, K3's grid-media forms in pt_k3_het.hip, its interior-media forms in pt_k3_int.hip, its exact-light-sampling forms in pt_k3_lse.hip, its dispersion forms in pt_k3_dsp.hip), the small
 // kernels in pt_kernels.hip.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -10,9 +10,9 @@ namespace pt {
 // What a render asks of K1 / K3 / the AOV walk. variant: k_shade's shape code (pt_forms.h SHADE_SHAPES; PT_SHADE_VARIANT); lights: the scene
 // has a lights list; list: pixel-list render (PoolD::list); env: environment sampling; qmc: the Sobol sampler
 // (pt_scene_set_sampler, §11); med: participating media are in effect (§12); het: one of them is a grid-density medium (§13), or intr is set;
-// intr: a glass interior or a tinted medium is in effect (§14); lse: exact light sampling is in effect (§15). Which combinations exist:
-// pt_forms.h shade_form_exists.
-struct ShadeForm { int variant; bool lights, list, env, qmc, med, het = false, intr = false, lse = false; };
+// intr: a glass interior or a tinted medium is in effect (§14); lse: exact light sampling is in effect (§15); dsp: spectral dispersion is in
+// effect (§16). Which combinations exist: pt_forms.h shade_form_exists.
+struct ShadeForm { int variant; bool lights, list, env, qmc, med, het = false, intr = false, lse = false, dsp = false; };
 // The form a render gets: pixel lists, env, qmc and med exist for the default variant's shapes only — any other variant becomes 42.
 // The launchers and queries below take the form this returns.
 ShadeForm shade_form(ShadeForm asked);
@@ -24,7 +24,7 @@ bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_bloc
 // flat-top-level instantiation without / with pair passes), -(stack*10 + blocks) = two-phase kernel k_extend2<stack, blocks> for stack in {16, 20, 24}.
 void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st);
 // wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
-// env: the environment-sampling tables of a form with `env`, else null
+// env: the environment-sampling tables of a form with `env`; of a form with `dsp`: its `col` = the dispersion weight table (device, DSP_BINS x 3); else null
 bool launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, const ShadeForm& form, hipStream_t st,
                   uint32_t wide_window_min = 16, const EnvTabD* env = nullptr);
 // resident blocks per CU of the K2 / K3 kernel a render launches (shade: 0 when no kernel of that form exists)
@@ -42,6 +42,9 @@ void launch_absorb_probe(const double absorption[3], const double* in, uint32_t 
 // (origin.xyz, time) -> n x (dir.xyz, light index, face or -1, draws consumed), row i with the independent sampler's draws of (seed 0,
 // pixel i, sample 0) from draw 0; which 1: n x (origin.xyz, direction.xyz, time) -> n lights.pdf values); in / out: device
 void launch_light_probe(const SceneD& sc, bool exact, int which, const double* in, uint32_t n, double* out, hipStream_t st);
+// pt_dispersion_probe: the device functions k_shade's DSP forms call (which 0: n x (pixel, sample) -> n x (u, lambda, bin, W_r, W_g, W_b, n(lambda)) under
+// sampler `kind`; 1: n wavelengths in nm -> n values n(lambda)); n_d, b, inv2_d: the glass's MatD::ior, p[1], p[2]; w: the weight table; in / out / w: device
+void launch_dispersion_probe(int kind, int which, uint64_t seed, double n_d, double b, double inv2_d, const double* w, const double* in, uint32_t n, double* out, hipStream_t st);
 // pt_sampler_probe: the 64-bit values of single draws, by the draw functions the kernels call (kind 0: Rng, 1: RngQ); out: device
 void launch_sampler_probe(int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin, uint32_t n_draws, uint64_t* out,
                           hipStream_t st);

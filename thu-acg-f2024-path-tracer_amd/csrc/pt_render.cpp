@@ -275,6 +275,17 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     if (lse && s->light_mesh_bad_area) return set_error("pt_render: exact light sampling needs light meshes of finite, positive area (a mesh in the lights list has area 0 or a non-finite one)");
     if (lse && s->light_blas_depth > (uint32_t)LIGHT_STACK) return set_error("pt_render: exact light sampling: a light mesh's BVH is deeper than the 24 levels its pdf walk's stack holds");
 
+    // spectral dispersion is in effect (pt_amd.h): some world object's material is a glass with an Abbe number; otherwise no new code runs
+    const bool dsp = s->dispersion_on();
+    if (dsp && env_on) return set_error("pt_render: spectral dispersion together with environment importance sampling is not supported (set one of them off)");
+    if (dsp && med) return set_error("pt_render: spectral dispersion together with participating media or a glass interior is not supported (clear the dispersion or take the media out)");
+    if (dsp && lse) return set_error("pt_render: spectral dispersion together with exact light sampling is not supported (set one of them off)");
+    if (dsp && dc.max_depth > DSP_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^31 when spectral dispersion is in effect");
+    if (dsp) {   // the DSP forms read the weight table where the ENV forms read their tables (pt_types.h)
+        env.col = dispersion_table(s, st);
+        if (!env.col) return -1;
+    }
+
     // pool sizing. slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
     // the machine several times over; finished paths pull the next (pixel, sample) from a global
     // counter. slots_per_pixel = k >= 1: STATIC ownership (deterministic; k = 1 is the reference's
@@ -327,7 +338,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
     const bool intr = med && s->interior_on();   // a glass interior or a tinted medium is in effect: the INT forms of k_shade, which are HET forms
     const bool het = med && (intr || s->grid_media_on());   // a grid-density medium is in effect: the HET forms of k_shade
-    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het, intr, lse});   // the form of k_init / k_shade that exists for it
+    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het, intr, lse, dsp});   // the form of k_init / k_shade that exists for it
     shade_variant = form.variant;
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
@@ -499,7 +510,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             launch_extend(s->dev.view, pool, s->d_counters, grid_extend, extend_code, st);
             timer.end(st);
             timer.begin(1, st);
-            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, form, st, wide_window_min, env_on ? &env : nullptr)) return set_error("pt_render: no k_shade form for this render");
+            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, form, st, wide_window_min, env_on || dsp ? &env : nullptr)) return set_error("pt_render: no k_shade form for this render");
             timer.end(st);
             if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
                 std::swap(pool.ray, pool.ray_out);
@@ -1002,6 +1013,36 @@ extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t
               hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
     if (ok) {
         launch_light_probe(s->dev.view, exact, which, d_i, n, d_o, ctx->stream);
+        ok = hip_ok(hipGetLastError(), "kernel launch") &&
+             hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    if (d_i) (void)hipFree(d_i);
+    if (d_o) (void)hipFree(d_o);
+    return ok ? 0 : -1;
+}
+
+extern "C" int pt_dispersion_probe(pt_scene* s, int glass_mat, int which, uint64_t seed, const double* in, uint32_t n, double* out) {
+    if (!s || !s->ctx) return set_error("pt_dispersion_probe: null scene");
+    if (glass_mat < 0 || (size_t)glass_mat >= s->mats.size() || s->mats[glass_mat].kind != MAT_GLASS || s->mats[glass_mat].p[3] == 0.0)
+        return set_error("pt_dispersion_probe: not a dispersive glass material (pt_mat_glass_set_dispersion)");
+    if (which != 0 && which != 1) return set_error("pt_dispersion_probe: which must be 0 or 1");
+    if (n == 0) return 0;
+    if (!in || !out) return set_error("pt_dispersion_probe: null buffer");
+    if (which == 0)
+        for (size_t i = 0; i < 2 * (size_t)n; ++i)
+            if (!(in[i] >= 0.0 && in[i] <= 4294967295.0) || in[i] != std::floor(in[i])) return set_error("pt_dispersion_probe: which 0 takes (pixel, sample) pairs of 32-bit unsigned integers");
+    const size_t n_in = (size_t)n * (which == 0 ? 2 : 1), n_out = (size_t)n * (which == 0 ? 7 : 1);
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    const double* d_w = dispersion_table(s, ctx->stream);
+    if (!d_w) return -1;
+    const MatD& m = s->mats[glass_mat];
+    double *d_i = nullptr, *d_o = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double)), "hipMalloc") &&
+              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    if (ok) {
+        launch_dispersion_probe(s->sampler, which, seed, m.ior, m.p[1], m.p[2], d_w, d_i, n, d_o, ctx->stream);
         ok = hip_ok(hipGetLastError(), "kernel launch") &&
              hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
              hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");

@@ -47,6 +47,7 @@ pt_scene::~pt_scene() {
     if (compact_scratch) (void)hipFree(compact_scratch);
     if (pixel_list) (void)hipFree(pixel_list);
     if (env_tab) (void)hipFree(env_tab);
+    if (disp_w) (void)hipFree(disp_w);
     if (d_counters) (void)hipFree(d_counters);
     if (h_counters) (void)hipHostFree(h_counters);
 }
@@ -194,6 +195,8 @@ extern "C" int pt_mat_mix(pt_scene* s, double t, int m1, int m2) {   // MixBxDf:
     if (s->mats[m1].kind == MAT_MEDIUM || s->mats[m2].kind == MAT_MEDIUM) return set_error("pt_mat_mix: a medium cannot be mixed (it is a volume, not a BxDF)");
     for (int c : {m1, m2})   // (a mix child is never a glass with an interior, so neither is a child's child)
         if (s->mats[c].kind == MAT_GLASS && s->mats[c].p[0] != 0.0) return set_error("pt_mat_mix: a glass with an interior medium cannot be mixed");
+    for (int c : {m1, m2})
+        if (s->mats[c].kind == MAT_GLASS && s->mats[c].p[3] != 0.0) return set_error("pt_mat_mix: a dispersive glass cannot be mixed");
     // a child may be a mix (MixBxDf::new takes any Arc<dyn BxDFMaterial>, mix.rs:14-20) — of leaves: the kernels evaluate two levels
     for (int c : {m1, m2})
         if (s->mats[c].kind == MAT_MIX && (s->mats[s->mats[c].color_tex].kind == MAT_MIX || s->mats[s->mats[c].rough_tex].kind == MAT_MIX))
@@ -266,6 +269,71 @@ extern "C" int pt_mat_glass_set_interior(pt_scene* s, int glass_mat, int medium_
 extern "C" int pt_mat_glass_interior(pt_scene* s, int glass_mat) {
     if (!s || !MAT_OK(s, glass_mat) || s->mats[glass_mat].kind != MAT_GLASS) return -1;
     return (int)s->mats[glass_mat].p[0] - 1;
+}
+// Spectral dispersion of a glass (the rule is in pt_amd.h): the two-term Cauchy law through (n_d, V_d). b in the glass's p[1], inv2(0.58756) in
+// p[2], the Abbe number in p[3] — slots glass does not use otherwise (p[0] is the interior).
+namespace pt {
+static double inv2(double l) { return 1.0 / (l * l); }
+double dispersion_ior(const MatD& m, double lambda_nm) { return m.ior + m.p[1] * (inv2(lambda_nm * 1e-3) - m.p[2]); }
+void dispersion_weights(double w[DSP_BINS][3]) {
+    auto g = [](double l, double mu, double s1, double s2) {
+        const double t = (l - mu) / (l < mu ? s1 : s2);
+        return std::exp(-0.5 * (t * t));
+    };
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < DSP_BINS; ++j) {
+        const double l = 380.0 + ((double)j + 0.5) * (350.0 / (double)DSP_BINS);
+        const double x = 1.056 * g(l, 599.8, 37.9, 31.0) + 0.362 * g(l, 442.0, 16.0, 26.7) - 0.065 * g(l, 501.1, 20.4, 26.2);
+        const double y = 0.821 * g(l, 568.8, 46.9, 40.5) + 0.286 * g(l, 530.9, 16.3, 31.1);
+        const double z = 1.217 * g(l, 437.0, 11.8, 36.0) + 0.681 * g(l, 459.0, 26.0, 13.8);
+        const double rgb[3] = {3.2404542 * x - 1.5371385 * y - 0.4985314 * z, -0.9692660 * x + 1.8760108 * y + 0.0415560 * z,
+                               0.0556434 * x - 0.2040259 * y + 1.0572252 * z};
+        for (int c = 0; c < 3; ++c) {
+            w[j][c] = std::max(0.0, rgb[c]);
+            sum[c] += w[j][c];
+        }
+    }
+    for (int j = 0; j < DSP_BINS; ++j)
+        for (int c = 0; c < 3; ++c) w[j][c] = w[j][c] * (double)DSP_BINS / sum[c];
+}
+double* dispersion_table(pt_scene* s, hipStream_t st) {
+    if (s->disp_w) return s->disp_w;
+    double w[DSP_BINS][3];
+    dispersion_weights(w);
+    double* d = nullptr;
+    if (!hip_ok(hipMalloc((void**)&d, sizeof w), "hipMalloc(dispersion weights)")) return nullptr;
+    if (!hip_ok(hipMemcpyAsync(d, w, sizeof w, hipMemcpyHostToDevice, st), "hipMemcpy(dispersion weights)") ||
+        !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(dispersion weights)")) {   // (`w` is on this stack)
+        (void)hipFree(d);
+        return nullptr;
+    }
+    return s->disp_w = d;
+}
+}  // namespace pt
+extern "C" int pt_mat_glass_set_dispersion(pt_scene* s, int glass_mat, double abbe) {
+    if (!s) return set_error("pt_mat_glass_set_dispersion: null scene");
+    if (!MAT_OK(s, glass_mat) || s->mats[glass_mat].kind != MAT_GLASS) return set_error("pt_mat_glass_set_dispersion: not a glass material");
+    if (!(abbe >= 0.0) || !std::isfinite(abbe)) return set_error("pt_mat_glass_set_dispersion: the Abbe number must be finite and >= 0 (0 = off)");
+    for (const MatD& m : s->mats)
+        if (m.kind == MAT_MIX && (m.color_tex == glass_mat || m.rough_tex == glass_mat)) return set_error("pt_mat_glass_set_dispersion: the glass is a child of a mix");
+    MatD m = s->mats[glass_mat];
+    m.p[1] = m.p[2] = m.p[3] = 0.0;
+    if (abbe > 0.0) {
+        m.p[1] = (m.ior - 1.0) / (abbe * (inv2(0.48613) - inv2(0.65627)));
+        m.p[2] = inv2(0.58756);
+        m.p[3] = abbe;
+        for (double l : {380.0, 730.0}) {
+            const double n = dispersion_ior(m, l);
+            if (!std::isfinite(n) || !(n > 1.0)) return set_error("pt_mat_glass_set_dispersion: the index of refraction must be finite and above 1 over 380..730 nm");
+        }
+    }
+    s->mats[glass_mat] = m;
+    s->built = false;
+    return 0;
+}
+extern "C" double pt_mat_glass_dispersion(pt_scene* s, int glass_mat) {
+    if (!s || !MAT_OK(s, glass_mat) || s->mats[glass_mat].kind != MAT_GLASS) return -1.0;
+    return s->mats[glass_mat].p[3];
 }
 // A medium whose extinction is scale * V(x), V trilinear in a grid of f32 samples (the rule is in pt_amd.h): the same material kind,
 // with its row of the grid table in p[6] and its majorant in p[0]
@@ -886,13 +954,14 @@ int pt::scene_build(pt_scene* s) {
     }
     if (prims.size() >= (size_t)HIT_ID_MASK - 4) return set_error("pt_world_build: too many primitives (28-bit ids)");
     // (a medium's boundary sorts with glass — the other kind that sends the ray on — so that K2's result word keeps its classes: pt_types.h)
-    s->world_has_medium = s->world_has_grid_medium = s->world_has_interior = false;
+    s->world_has_medium = s->world_has_grid_medium = s->world_has_interior = s->world_has_dispersion = false;
     for (PrimRef& pr : prims) {
         const uint32_t kind = s->mats[pr.mat].kind;
         s->world_has_medium = s->world_has_medium || kind == MAT_MEDIUM;
         s->world_has_grid_medium = s->world_has_grid_medium || (kind == MAT_MEDIUM && s->mats[pr.mat].p[6] != 0.0);
         // a glass with an interior, or a tinted medium's boundary
         s->world_has_interior = s->world_has_interior || (kind == MAT_GLASS && s->mats[pr.mat].p[0] != 0.0) || (kind == MAT_MEDIUM && s->mats[pr.mat].p[10] != 0.0);
+        s->world_has_dispersion = s->world_has_dispersion || (kind == MAT_GLASS && s->mats[pr.mat].p[3] != 0.0);   // a dispersive glass
         pr.kind |= (kind == MAT_MEDIUM ? MEDIUM_SORT_KIND : kind) << PRIM_MAT_KIND_SHIFT;
     }
     std::vector<Box> entry_boxes(tlas_items.size());

@@ -120,6 +120,12 @@ struct pt_scene {
     bool lights_have_mesh_or_sphere = false, light_mesh_bad_area = false;
     uint32_t light_blas_depth = 0;
     bool light_sampling_on() const { return light_sampling == 1 && lights_have_mesh_or_sphere; }   // "in effect"
+    // spectral dispersion (pt_mat_glass_set_dispersion): MatD::p[1..3] of a glass = the Cauchy b, inv2(0.58756) and its Abbe
+    // number (0 = off). world_has_dispersion (set by scene_build): some world object's material is a glass with an Abbe number > 0.
+    // disp_w: the weight table W[DSP_BINS][3] on the device, uploaded at the first render or probe that needs it and kept until destroy.
+    bool world_has_dispersion = false;
+    bool dispersion_on() const { return world_has_dispersion; }   // "in effect": the kernels' DSP forms run
+    double* disp_w = nullptr;
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned
@@ -128,4 +134,7 @@ struct pt_scene {
 
 namespace pt {
 int scene_build(pt_scene* s);   // flatten + BVH + upload
+void dispersion_weights(double w[DSP_BINS][3]);   // the weight table of pt_mat_glass_set_dispersion's rule (host, f64)
+double dispersion_ior(const MatD& glass, double lambda_nm);   // n(lambda) of a dispersive glass as the device computes it
+double* dispersion_table(pt_scene* s, hipStream_t st);   // pt_scene::disp_w, uploaded if need be; null (error set) when that fails
 }

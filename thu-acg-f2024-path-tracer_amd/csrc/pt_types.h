@@ -123,6 +123,14 @@ constexpr uint32_t MEDIUM_SORT_KIND = MAT_GLASS;
 // without media in effect the field is zero and the word is the bounce number, as before. The host refuses a medium material whose
 // index does not fit and a max_depth that reaches into the field (pt_mat_medium, pt_render).
 constexpr uint32_t MEDIUM_SHIFT = 20, MEDIUM_BOUNCE_MASK = (1u << MEDIUM_SHIFT) - 1u, MEDIUM_MAX_MATS = 4094;
+// Spectral dispersion (pt_mat_glass_set_dispersion): a dispersive MAT_GLASS keeps the Cauchy coefficient b in p[1], inv2(0.58756)
+// in p[2] and its Abbe number in p[3] (0 = not dispersive; glass uses none of them otherwise, and p[0] is the interior). A path's MONO flag —
+// it has been weighted by its wavelength's row of the weight table — is bit 31 of its bounce word, which the non-MED forms leave free. Only
+// the DSP forms of k_shade pack and unpack it; a camera ray's word is 0, so K1 has no DSP form. The host refuses a max_depth that reaches
+// the bit (pt_render). The weight table W[DSP_BINS][3] (f64, the same for every scene) reaches the DSP forms through the `col` pointer of
+// their EnvTabD argument, which no form without ENV reads otherwise — DSP never comes with ENV.
+constexpr uint32_t DSP_MONO_BIT = 1u << 31, DSP_BOUNCE_MASK = DSP_MONO_BIT - 1u;
+constexpr int DSP_BINS = 64;
 constexpr uint32_t CLASS_MISS = 0u, CLASS_IDLE = 1u + MAT_KINDS, CLASS_DEAD = 2u + MAT_KINDS, N_CLASSES = 3u + MAT_KINDS;
 // MAT_SHEEN: p[0..2] = base colour, p[3] = sheen_tint (sheen.rs). MAT_CLEARCOAT: alpha_g (clearcoat.rs).
 // MAT_MIX: p[0] = t, color_tex / rough_tex hold the two child MATERIAL indices (mix.rs; children are leaves).

@@ -48,6 +48,7 @@ struct Emitter {
     std::map<const void*, int> done;
     int override_mat = -1;   // >= 0: the primitives emitted now carry this material instead of their own (HomogeneousVolume's boundary)
     const Volume* glass_interior = nullptr;   // the interior of every GlassBSDF without one of its own (World::glass_interior)
+    double glass_dispersion = 0.0;            // the Abbe number of every GlassBSDF without one of its own (World::glass_dispersion), 0 = none
 };
 
 // ---- textures (src/texture.rs) ---------------------------------------------------------
@@ -163,6 +164,13 @@ struct GlassBSDF : BxDFMaterial {   // glass.rs:28-49
     std::shared_ptr<GlassBSDF> with_interior(std::shared_ptr<Volume> v) const {
         auto m = std::make_shared<GlassBSDF>(*this);
         m->interior = v;
+        return m;
+    }
+    // this build's addition: spectral dispersion — `ior` is then n_d and `abbe` the Abbe number V_d (pt_mat_glass_set_dispersion); 0 = none
+    double abbe = 0.0;
+    std::shared_ptr<GlassBSDF> with_dispersion(double v_d) const {
+        auto m = std::make_shared<GlassBSDF>(*this);
+        m->abbe = v_d;
         return m;
     }
     int emit(Emitter& e) const override;   // (below Volume)
@@ -407,6 +415,8 @@ inline int GlassBSDF::emit(Emitter& e) const {
     if (h < 0) panic("GlassBSDF");
     const Volume* v = interior ? interior.get() : e.glass_interior;
     if (v && pt_mat_glass_set_interior(e.scene, h, v->medium(e)) != 0) panic("GlassBSDF::interior");
+    const double v_d = abbe != 0.0 ? abbe : e.glass_dispersion;
+    if (v_d != 0.0 && pt_mat_glass_set_dispersion(e.scene, h, v_d) != 0) panic("GlassBSDF::dispersion");
     return e.done[this] = h;
 }
 // HomogeneousVolume of the reference's commented-out volume.rs:15-41: a boundary filled with a medium of constant density and
@@ -470,6 +480,7 @@ struct World {
     void emit_into(pt_scene* s, std::shared_ptr<ImageTexture> env = nullptr) {
         Emitter e{s, asset_dir, {}};
         e.glass_interior = glass_interior.get();
+        e.glass_dispersion = glass_dispersion;
         for (auto& o : objects) if (pt_world_add_object(s, o->emit(e)) != 0) panic("World::add_object");
         for (auto& l : lights) if (pt_world_add_light(s, l->emit(e)) != 0) panic("World::add_light");
         if (env) env->emit(e);
@@ -480,6 +491,7 @@ struct World {
     }
     std::shared_ptr<Volume> camera_medium;   // the medium camera rays start in (pt_scene_set_camera_medium); null = none
     std::shared_ptr<Volume> glass_interior;   // this build's option: the interior of every GlassBSDF that has none of its own (pt_render --interior)
+    double glass_dispersion = 0.0;            // this build's option: the Abbe number of every GlassBSDF that has none of its own (pt_render --dispersion), 0 = none
     void bounds(Vec3& lo, Vec3& hi) const {             // of objects and lights
         for (auto& o : objects) o->bounds(lo, hi);
         for (auto& l : lights) l->bounds(lo, hi);

@@ -25,7 +25,7 @@ for u in $UNITS; do
   echo "== $n"
   [ -s "$TMP/$n.s" ] || { cat "$TMP/$n.log"; exit 1; }
   grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size" "$TMP/$n.log" | sed -e 's/.*remark: //' -e 's/ \[-Rpass.*//' | paste - - - - - \
-   | sed -e 's/Function Name: _ZN2pt//' -e 's/    */ /g' | cut -c1-200
+   | sed -e 's/Function Name: _ZN2pt//' -e 's/    */ /g' | cut -c1-230
 done
 [ -z "$ISA" ] && exit 0
 python3 - "$ISA" "$TMP"/*.s <<'EOF'
