@@ -53,8 +53,27 @@ PT_DEV V3 tex_image(const SceneD& sc, const TexD& T, double u, double v) {   // 
     const double s = 1.0 / 255.0;
     return V3{s * (double)p[0], s * (double)p[1], s * (double)p[2]};
 }
-PT_DEV V3 tex_rgb(const SceneD& sc, int32_t t, double u, double v, V3 p) {
-    for (int depth = 0; depth < 16; ++depth) {
+// U (tex_rgb, tex_f, fetch_tex): the texture / material index is wave-uniform (k_shade's single-primitive groups) — the descriptor's
+// fields arrive by scalar loads (ldu) instead of per-lane gathers of the same bytes. A checker whose children are textures of their
+// own sends every lane to ITS child: the walk goes on per lane from there (depth0 = the levels already walked).
+template <bool U, class T> PT_DEV T ldf(const T* p) {
+    if constexpr (U) return ldu(p); else return *p;
+}
+PT_DEV V3 ldu3(const double* p) { return V3{ldu(p), ldu(p + 1), ldu(p + 2)}; }
+template <bool U = false>
+PT_DEV V3 tex_rgb(const SceneD& sc, int32_t t, double u, double v, V3 p, int depth0 = 0) {
+    if constexpr (U) {
+        const TexD* T = &sc.tex[t];
+        const uint32_t kind = ldu(&T->kind);
+        if (kind == TEX_CHECKER) {
+            const bool first = checker_is_first(ldu(&T->inv_scale), p);
+            if (ldu(&T->flat)) return first ? ldu3(T->c1) : ldu3(T->c2);
+            return tex_rgb<false>(sc, (int32_t)(first ? ldu(&T->t1) : ldu(&T->t2)), u, v, p, 1);
+        }
+        if (kind == TEX_IMAGE || kind == TEX_IMAGE_F32) return tex_image(sc, ldu(T), u, v);
+        return ldu3(T->v);
+    } else {
+    for (int depth = depth0; depth < 16; ++depth) {
         const TexD& T = sc.tex[t];
         if (T.kind == TEX_CHECKER) {
             const bool first = checker_is_first(T.inv_scale, p);
@@ -66,9 +85,20 @@ PT_DEV V3 tex_rgb(const SceneD& sc, int32_t t, double u, double v, V3 p) {
         return V3{T.v[0], T.v[1], T.v[2]};
     }
     return V3{0.0, 0.0, 0.0};
+    }
 }
-PT_DEV double tex_f(const SceneD& sc, int32_t t, V3 p) {
-    for (int depth = 0; depth < 16; ++depth) {
+template <bool U = false>
+PT_DEV double tex_f(const SceneD& sc, int32_t t, V3 p, int depth0 = 0) {
+    if constexpr (U) {
+        const TexD* T = &sc.tex[t];
+        if (ldu(&T->kind) == TEX_CHECKER) {
+            const bool first = checker_is_first(ldu(&T->inv_scale), p);
+            if (ldu(&T->flat)) return first ? ldu(&T->c1[0]) : ldu(&T->c2[0]);
+            return tex_f<false>(sc, (int32_t)(first ? ldu(&T->t1) : ldu(&T->t2)), p, 1);
+        }
+        return ldu(&T->v[0]);
+    } else {
+    for (int depth = depth0; depth < 16; ++depth) {
         const TexD& T = sc.tex[t];
         if (T.kind == TEX_CHECKER) {
             const bool first = checker_is_first(T.inv_scale, p);
@@ -79,6 +109,7 @@ PT_DEV double tex_f(const SceneD& sc, int32_t t, V3 p) {
         return T.v[0];
     }
     return 0.0;
+    }
 }
 
 // ---- microfacet helpers (bsdf/mod.rs:61-97, sampling.rs) --------------------------------
@@ -203,20 +234,23 @@ struct LocalFrame {
     Frame f;
     V3 v;
 };
-PT_DEV LocalFrame make_local_frame(const MatD& m, const HitD& h, V3 wo) {
+PT_DEV LocalFrame make_local_frame(uint32_t k, const HitD& h, V3 wo) {            // k: the material's kind
     LocalFrame lf{};
-    const uint32_t k = m.kind;
     if (k == MAT_MIX || k == MAT_LIGHT) return lf;
     lf.f = frame_to_z((k == MAT_PRINCIPLED || k == MAT_SHEEN) ? h.gn : h.sn);    // principled.rs / sheen.rs use the geometric normal
     if (k != MAT_DIFFUSE) lf.v = to_local(lf.f, wo);                              // (Lambert needs no view vector)
     return lf;
 }
+PT_DEV LocalFrame make_local_frame(const MatD& m, const HitD& h, V3 wo) { return make_local_frame(m.kind, h, wo); }
+template <bool U = false>   // U: `m` is the same record for every lane
 PT_DEV TexVals fetch_tex(const SceneD& sc, const MatD& m, const HitD& h) {
     TexVals tv{V3{0.0, 0.0, 0.0}, 0.0};
-    const uint32_t k = m.kind;
-    if (k == MAT_DIFFUSE || k == MAT_METAL || k == MAT_PRINCIPLED || k == MAT_LIGHT)
-        tv.color = m.color_solid ? V3{m.color_v[0], m.color_v[1], m.color_v[2]} : tex_rgb(sc, m.color_tex, h.u, h.v, h.point);
-    if (k == MAT_METAL || k == MAT_GLASS) tv.rough = m.rough_solid ? m.rough_v : tex_f(sc, m.rough_tex, h.point);
+    const uint32_t k = ldf<U>(&m.kind);
+    if (k == MAT_DIFFUSE || k == MAT_METAL || k == MAT_PRINCIPLED || k == MAT_LIGHT) {
+        if constexpr (U) tv.color = ldu(&m.color_solid) ? ldu3(m.color_v) : tex_rgb<true>(sc, ldu(&m.color_tex), h.u, h.v, h.point);
+        else tv.color = m.color_solid ? V3{m.color_v[0], m.color_v[1], m.color_v[2]} : tex_rgb(sc, m.color_tex, h.u, h.v, h.point);
+    }
+    if (k == MAT_METAL || k == MAT_GLASS) tv.rough = ldf<U>(&m.rough_solid) ? ldf<U>(&m.rough_v) : tex_f<U>(sc, ldf<U>(&m.rough_tex), h.point);
     return tv;   // MAT_MIX: its children fetch their own (mat_sample / mat_pdf_eval)
 }
 

@@ -120,28 +120,46 @@ PT_DEV void finish_hit(const SceneD& sc, const RayD& r, V3 point, V3 normal, dou
     h.v = v;
 }
 
-// Rebuilds the reference's HitInfo for primitive `gid` known to be hit by `world_ray`.
+// Rebuilds the reference's HitInfo for the primitive of record `pr`, known to be hit by `world_ray`.
 // Re-runs that one primitive's intersection (same arithmetic as the traversal kernel, so the
 // same t/u/v bits), then applies Instance::intersects' world transform (instance.rs:43-53, Q1).
-PT_DEV bool reconstruct_hit(const SceneD& sc, const RayD& world_ray, uint32_t gid, double t_min, HitD& h) {
-    const PrimRef pr = sc.prims[gid];
+// UV = false (k_shade): a sphere whose record lacks PRIM_NEEDS_UV gets u = v = 0 — the host has proved that nothing reads them
+// (pt_types.h) — and neither dev_acos, dev_atan2 nor the two divisions are computed. UV = true (probe, AOV walk): always computed.
+// U: `pr` is wave-uniform and no triangle (k_shade's single-primitive groups): the instance chain, the sphere / quad record and the
+// material's normal-map handle arrive by scalar loads instead of a chain of dependent per-lane gathers of the same bytes.
+template <bool UV = true, bool U = false>
+PT_DEV bool reconstruct_hit_prim(const SceneD& sc, const RayD& world_ray, const PrimRef& pr, double t_min, HitD& h) {
     int32_t innermost = -1;
-    const RayD r = ray_to_local_chain(sc, pr.inst, world_ray, &innermost);
+    const RayD r = ray_to_local_chain<U>(sc, pr.inst, world_ray, &innermost);
     const uint32_t kind = pr.kind & 0xFFu;
     if (kind == PRIM_SPHERE) {
         double t;
         V3 c;
-        if (!hit_sphere(sc.spheres[pr.index], r, t_min, t, c)) return false;
+        bool ok;
+        if constexpr (U) ok = hit_sphere(ldu(&sc.spheres[pr.index]), r, t_min, t, c);
+        else ok = hit_sphere(sc.spheres[pr.index], r, t_min, t, c);
+        if (!ok) return false;
         V3 point = ray_at(r, t);
         V3 normal = normalize(point - c);
-        double theta = dev_acos(-normal.y);                       // sphere.rs:52-56
-        double phi = dev_atan2(-normal.z, normal.x) + D_PI;
-        finish_hit(sc, r, point, normal, t, pr.mat, phi / (2.0 * D_PI), theta / D_PI, h);
-    } else if (kind == PRIM_QUAD) {
+        double u = 0.0, v = 0.0;
+        if (UV || (pr.kind & PRIM_NEEDS_UV)) {
+            double theta = dev_acos(-normal.y);                   // sphere.rs:52-56
+            double phi = dev_atan2(-normal.z, normal.x) + D_PI;
+            u = phi / (2.0 * D_PI);
+            v = theta / D_PI;
+        }
+        finish_hit<U>(sc, r, point, normal, t, pr.mat, u, v, h);
+    } else if (U || kind == PRIM_QUAD) {
         double t, a, b;
-        const QuadD& q = sc.quads[pr.index];
-        if (!hit_quad(q, r, t_min, t, a, b)) return false;
-        finish_hit(sc, r, ray_at(r, t), ld3(q.n), t, pr.mat, a, b, h);
+        if constexpr (U) {
+            const QuadD q = ldu(&sc.quads[pr.index]);
+            if (!hit_quad(q, r, t_min, t, a, b)) return false;
+            finish_hit<true>(sc, r, ray_at(r, t), ld3(q.n), t, pr.mat, a, b, h);
+        } else {
+            const QuadD& q = sc.quads[pr.index];
+            if (!hit_quad(q, r, t_min, t, a, b)) return false;
+            finish_hit(sc, r, ray_at(r, t), ld3(q.n), t, pr.mat, a, b, h);
+        }
     } else {
         double t, u, v;
         const TriD& tr = sc.tris[pr.index];
@@ -165,12 +183,25 @@ PT_DEV bool reconstruct_hit(const SceneD& sc, const RayD& world_ray, uint32_t gi
         finish_hit(sc, r, ray_at(r, t), normal, t, pr.mat, tu, tv, h);
     }
     for (int32_t i = innermost; i >= 0;) {                                       // instance.rs:43-53, innermost instance first
-        const InstD& m = sc.insts[i];
-        h.point = xform_point(m.c0, m.c1, m.c2, m.t, h.point);
-        h.gn = normalize(xform_vector(m.c0, m.c1, m.c2, h.gn));
-        i = m.outer;
+        if constexpr (U) {
+            const InstD m = ldu(&sc.insts[i]);
+            h.point = xform_point(m.c0, m.c1, m.c2, m.t, h.point);
+            h.gn = normalize(xform_vector(m.c0, m.c1, m.c2, h.gn));
+            i = m.outer;
+        } else {
+            const InstD& m = sc.insts[i];
+            h.point = xform_point(m.c0, m.c1, m.c2, m.t, h.point);
+            h.gn = normalize(xform_vector(m.c0, m.c1, m.c2, h.gn));
+            i = m.outer;
+        }
     }
     return true;
+}
+// ... for primitive `gid`, each lane its own
+template <bool UV = true>
+PT_DEV bool reconstruct_hit(const SceneD& sc, const RayD& world_ray, uint32_t gid, double t_min, HitD& h) {
+    const PrimRef pr = sc.prims[gid];
+    return reconstruct_hit_prim<UV, false>(sc, world_ray, pr, t_min, h);
 }
 
 // ---- lights list: Hittable::sample / pdf for every kind of object (list.rs:78-96, quad.rs:80-98,

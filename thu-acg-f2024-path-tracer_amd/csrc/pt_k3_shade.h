@@ -118,6 +118,9 @@ PT_DEV SlotIn load_slot_global(const PoolD& pool, uint32_t s, bool enable, const
 // wave-uniform base + lane * 16, as the instruction writes — is then simply the records in lane order: RayRec of lane l at
 // stage[4 l .. 4 l + 3], PathRec at stage[256 + 2 l ..]. The slots of the other lanes come by ds_bpermute.
 // Must be executed by ALL 64 lanes (wave-uniform control flow).
+#ifndef PT_UNIFORM_GROUPS
+#define PT_UNIFORM_GROUPS 3         // bit 0: the hit of a single-primitive group by scalar loads, bit 1: its material fields and texture descriptor too; 0: every group per lane (for A/B)
+#endif
 #ifndef PT_STAGE_AUX
 #define PT_STAGE_AUX 0             // cache policy of the record stream: 0 default, 2 = nt (MI355X_MICROARCH.md row "nt-weights")
 #endif
@@ -204,7 +207,9 @@ struct NoPrefetch {
 // case of mat_sample / mat_pdf_eval; a continued bounce of a path whose flag is clear multiplies the new throughput by the row and sets the flag.
 // Every other lane is the bounce above bit for bit.
 constexpr int LSE_KB = 512;                                            // threads per block of every shape that has LSE forms (pt_forms.h)
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false, bool LSE = false, bool DSP = false>
+template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false, bool LSE = false, bool DSP = false,
+          bool UNI = true>
+// UNI: the form may take the single-primitive path of phase A (k_shade: every two-wave shape).
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
@@ -280,6 +285,34 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     TexVals tv{};
     LocalFrame lf{};
     PT_STAMP_VAR(a1);
+    // A group whose surface lanes all hit ONE primitive, a sphere or a quad (k_shade's sort makes groups of one class, and a class is
+    // often dominated by one primitive: a ground quad, a big sphere): every lane would gather the same PrimRef, instance chain,
+    // sphere / quad record, material fields and texture descriptor, each gather waiting for the one before. Decided here, at a
+    // wave-uniform point; such a group reads them through the scalar cache (reconstruct_hit_prim<.., true>, fetch_tex<true>). Any
+    // other group runs the per-lane code. The operands are the same bytes either way: no result changes.
+    // Forms whose register allocation pays for the second copy of phase A with more scratch than they had (tools/regs.sh against the
+    // same form without it: the MED forms with lights, the pixel-list ENV forms with lights, the three-wave shapes) keep the per-lane path.
+    constexpr int UG = UNI && !(MED && LIGHTS) && !(LIGHTS && LIST && ENV) ? PT_UNIFORM_GROUPS : 0;
+    bool uni = false;                                                  // wave-uniform
+    PrimRef pr0{};
+    {
+        const uint32_t id = in.hw & HIT_ID_MASK;
+        const bool on_surface = live && (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS;
+        const unsigned long long sm = __ballot(on_surface);
+        if (UG != 0 && sm != 0ull) {
+            const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane((int)id, __ffsll((long long)sm) - 1);
+            if (__ballot(on_surface && id != g0) == 0ull) {
+                pr0 = ldu(&sc.prims[g0]);
+                uni = (pr0.kind & 0xFFu) != PRIM_TRI;
+#ifdef PT_STAMPS
+                if (lane == 0) {
+                    atomicAdd(&g_prof[prof_class][12], 1ull);          // groups of one primitive ...
+                    if (uni) atomicAdd(&g_prof[prof_class][13], 1ull); // ... that is no triangle
+                }
+#endif
+            }
+        }
+    }
     if (live) {
         if (!pool.dynamic) {
             pixel = slot_pixel<LIST>(pool, s);
@@ -287,7 +320,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         }
         rng = RngT{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, in.draw};
         const uint32_t gid = in.hw & HIT_ID_MASK;
-        const bool surface = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS && reconstruct_hit(sc, ray, gid, 1e-3, hit);
+        const bool surface = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS &&
+                             (uni ? reconstruct_hit_prim<false, true>(sc, ray, pr0, 1e-3, hit) : reconstruct_hit<false>(sc, ray, gid, 1e-3, hit));
         PT_STAMP_SET(a1);
         if constexpr (MED) {
             if (med != 0u) {                                           // free flight: one draw, d = -log(1 - u) / density
@@ -324,26 +358,43 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         } else if (!surface) {
             add_radiance(pool, pixel, rad, thr * sample_environment(sc, cam, ray.d));   // camera.rs:180-183
             finished = true;
-        } else if (MED && sc.mats[hit.mat].kind == MAT_MEDIUM) {
-            boundary = true;                                           // a medium's boundary: invisible, no emission
         } else {
-            is_hit = true;
+            // the material fields phase A reads: of the group's one material by scalar loads, else per lane (B1 / B2 read *mp as before)
             mp = &sc.mats[hit.mat];
-            tv = fetch_tex(sc, *mp, hit);
-            lf = make_local_frame(*mp, hit, -ray.d);
-            if constexpr (INT) interior = mp->kind == MAT_GLASS ? (uint32_t)mp->p[0] : 0u;   // (read here: B2 stays arithmetic)
+            uint32_t mkind;
+            double m_p0 = 0.0, m_p1 = 0.0, m_p2 = 0.0, m_p3 = 0.0, m_ior = 0.0;   // INT: p[0]; DSP: p[1..3], ior
+            if ((UG & 2) != 0 && uni) {
+                const MatD* um = &sc.mats[pr0.mat];
+                mkind = ldu(&um->kind);
+                if (!MED || mkind != MAT_MEDIUM) tv = fetch_tex<true>(sc, *um, hit);
+                if constexpr (INT) m_p0 = ldu(&um->p[0]);
+                if constexpr (DSP) { m_p1 = ldu(&um->p[1]); m_p2 = ldu(&um->p[2]); m_p3 = ldu(&um->p[3]); m_ior = ldu(&um->ior); }
+            } else {
+                mkind = mp->kind;
+                if (!MED || mkind != MAT_MEDIUM) tv = fetch_tex(sc, *mp, hit);
+                if constexpr (INT) m_p0 = mp->p[0];
+                if constexpr (DSP) { m_p1 = mp->p[1]; m_p2 = mp->p[2]; m_p3 = mp->p[3]; m_ior = mp->ior; }
+            }
+            if (MED && mkind == MAT_MEDIUM) {
+                boundary = true;                                       // a medium's boundary: invisible, no emission
+                mp = nullptr;
+            } else {
+            is_hit = true;
+            lf = make_local_frame(mkind, hit, -ray.d);
+            if constexpr (INT) interior = mkind == MAT_GLASS ? (uint32_t)m_p0 : 0u;   // (read here: B2 stays arithmetic)
             if constexpr (DSP) {
-                if (dsp_is_dispersive(*mp)) {
+                if (mkind == MAT_GLASS && m_p3 != 0.0) {               // dsp_is_dispersive
                     const WavelengthD wl = dsp_wavelength<QMC>((uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample);
-                    ior_l = dsp_ior(mp->ior, mp->p[1], mp->p[2], wl.lambda);
+                    ior_l = dsp_ior(m_ior, m_p1, m_p2, wl.lambda);
                     const double* row = env->col + 3u * wl.bin;
                     w_l = V3{row[0], row[1], row[2]};
                 }
             }
             // camera.rs:186-187 — added for every material (zero unless emissive) so that a
             // non-finite throughput poisons the sample exactly as it does in the reference
-            V3 emission = mp->kind == MAT_LIGHT ? tv.color : V3{0.0, 0.0, 0.0};
+            V3 emission = mkind == MAT_LIGHT ? tv.color : V3{0.0, 0.0, 0.0};
             add_radiance(pool, pixel, rad, thr * emission);
+            }
         }
     }
     PT_STAMP(a2);
@@ -661,7 +712,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT, LSE, DSP>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
+            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT, LSE, DSP, MINW == 2>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -838,7 +889,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT, LSE, DSP>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT, LSE, DSP, MINW == 2>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env, lstk);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

@@ -588,7 +588,12 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                         names[c], p[0], (double)p[2] / p[0], (double)p[1] / p[0], (double)p[6] / p[0], (double)p[7] / p[0], (double)(p[2] - p[1] - p[6] - p[7]) / p[0],
                         (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]),
                 fprintf(stderr, "[pt prof] %-10s   lanes per group: live %5.1f  on a surface %5.1f  with a next direction %5.1f  regenerated %5.1f\n", names[c], (double)p[8] / p[0],
-                        (double)p[9] / p[0], (double)p[10] / p[0], (double)p[11] / p[0]);
+                        (double)p[9] / p[0], (double)p[10] / p[0], (double)p[11] / p[0])
+#ifdef PT_STAMPS
+                , fprintf(stderr, "[pt prof] %-10s   groups of one primitive %10llu (%5.1f %%), of one sphere / quad %10llu (%5.1f %%)\n", names[c], p[12], 100.0 * (double)p[12] / p[0],
+                          p[13], 100.0 * (double)p[13] / p[0])
+#endif
+                ;
             else if (p[0])
                 fprintf(stderr, "[pt prof] WINDOW     n %10llu  sort %8.0f  shade %8.0f  barrier wait %8.0f  groups %8.0f  record wait %8.0f (cycles per window and wave)\n", p[0],
                         (double)p[1] / p[0], (double)p[2] / p[0], (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]);

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 #include "../../include/pt_amd.h"
 
@@ -955,8 +956,25 @@ int pt::scene_build(pt_scene* s) {
     if (prims.size() >= (size_t)HIT_ID_MASK - 4) return set_error("pt_world_build: too many primitives (28-bit ids)");
     // (a medium's boundary sorts with glass — the other kind that sends the ray on — so that K2's result word keeps its classes: pt_types.h)
     s->world_has_medium = s->world_has_grid_medium = s->world_has_interior = s->world_has_dispersion = false;
+    // PRIM_NEEDS_UV (pt_types.h): can this material read HitD::u / v? A normal map, an image texture in the colour texture's tree
+    // (through checker children), or a mix with such a child, at both nesting levels. An index out of range counts as "can".
+    std::function<bool(int32_t, int)> tex_reads_uv = [&](int32_t t, int depth) -> bool {
+        if (t < 0) return false;
+        if ((size_t)t >= s->tex.size() || depth > 16) return true;
+        const TexD& T = s->tex[t].d;
+        if (T.kind == TEX_IMAGE || T.kind == TEX_IMAGE_F32) return true;
+        return T.kind == TEX_CHECKER && (tex_reads_uv((int32_t)T.t1, depth + 1) || tex_reads_uv((int32_t)T.t2, depth + 1));
+    };
+    std::function<bool(int32_t, int)> mat_reads_uv = [&](int32_t mi, int depth) -> bool {
+        if (mi < 0 || (size_t)mi >= s->mats.size() || depth > 2) return true;   // (pt_mat_mix admits two levels)
+        const MatD& m = s->mats[mi];
+        if (m.nmap_tex >= 0) return true;
+        if (m.kind == MAT_MIX) return mat_reads_uv(m.color_tex, depth + 1) || mat_reads_uv(m.rough_tex, depth + 1);   // (a mix keeps its children there)
+        return tex_reads_uv(m.color_tex, 0);
+    };
     for (PrimRef& pr : prims) {
         const uint32_t kind = s->mats[pr.mat].kind;
+        if ((pr.kind & 0xFFu) == PRIM_SPHERE && mat_reads_uv((int32_t)pr.mat, 0)) pr.kind |= PRIM_NEEDS_UV;
         s->world_has_medium = s->world_has_medium || kind == MAT_MEDIUM;
         s->world_has_grid_medium = s->world_has_grid_medium || (kind == MAT_MEDIUM && s->mats[pr.mat].p[6] != 0.0);
         // a glass with an interior, or a tinted medium's boundary

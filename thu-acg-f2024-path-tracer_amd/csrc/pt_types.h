@@ -36,6 +36,13 @@ constexpr int MAX_TLAS_DEPTH = 10;
 enum PrimKind : uint32_t { PRIM_SPHERE = 0, PRIM_QUAD = 1, PRIM_TRI = 2 };
 enum EntryKind : uint32_t { ENTRY_SPHERE = 0, ENTRY_QUAD = 1, ENTRY_CUBOID = 2, ENTRY_MESH = 3 };
 constexpr uint32_t PRIM_HAS_NORMALS = 1u << 8, PRIM_HAS_UVS = 1u << 9;
+// A SPHERE whose material can read HitD::u / v. The scene build sets it when the material has a normal map (nmap_tex >= 0), when its
+// colour texture tree — through checker children — holds an image texture (TEX_IMAGE, TEX_IMAGE_F32), or when it is a mix with such a
+// child at either nesting level. Nothing else in k_shade reads a hit's (u, v) (fetch_tex's colour lookup and finish_hit's normal
+// map are the two places), so k_shade computes a sphere's (u, v) — dev_acos, dev_atan2, two divisions — only where the bit is set and
+// passes zeros elsewhere: the host proves the value unused, as it does for the Philox blocks nobody reads (CamD::motionless).
+// Quads and triangles have their (u, v) from the intersection itself; the bit is not set for them.
+constexpr uint32_t PRIM_NEEDS_UV = 1u << 10;
 constexpr uint32_t PRIM_MAT_KIND_SHIFT = 16;   // PrimRef::kind bits 16..23: MatKind of the primitive's material (k_shade's class sort)
 
 struct PrimRef {         // indexed by GLOBAL primitive id (lights list first, then objects)
@@ -309,7 +316,11 @@ struct PoolD {
 // (65k per launch at 4M resident paths), which alone would cost ~0.75 ms per launch. Shard s hands
 // out the work items w with w % WORK_SHARDS == s; a block always uses shard blockIdx.x % WORK_SHARDS.
 constexpr uint32_t WORK_SHARDS = 64;
-constexpr int PROF_COLS = 12;   // diagnostic build (-DPT_STAMPS): columns of the per-class profile
+#ifdef PT_STAMPS
+constexpr int PROF_COLS = 14;   // diagnostic build (-DPT_STAMPS): columns of the per-class profile
+#else
+constexpr int PROF_COLS = 12;   // (the last two — single-primitive groups — exist in the diagnostic build only)
+#endif
 struct CountersD {
     unsigned long long alive;        // slots still rendering
     unsigned long long segments;     // extend() calls on live paths
@@ -320,7 +331,8 @@ struct CountersD {
     unsigned long long win_extend, win_shade;
     unsigned long long pad[11];
     // diagnostic builds only (-DPT_STAMPS, tools/build_variant.sh): wave-cycle sums per k_shade class
-    // [class][0 groups, 1 record-load wait, 2 body, 3 work dequeue, 4 regeneration + stores, 5 whole], [N_CLASSES][..] = window phases
+    // [class][0 groups, 1 record-load wait, 2 body, 3 work dequeue, 4 regeneration + stores, 5 whole, .., 12 groups whose surface lanes hit one
+    // primitive, 13 those whose primitive is no triangle], [N_CLASSES][..] = window phases
     unsigned long long prof[N_CLASSES + 1][PROF_COLS];
     struct alignas(128) Shard { unsigned long long next; unsigned long long pad[15]; } work[WORK_SHARDS];
 };

@@ -1,6 +1,6 @@
 import importlib, os, sys
 import numpy as np
-ROOT = "/root/repo"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from common import random_scene
 pt = importlib.import_module("thu-acg-f2024-path-tracer_amd")
