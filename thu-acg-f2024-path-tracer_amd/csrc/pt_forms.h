@@ -1,6 +1,7 @@
 // Which forms of k_shade and k_init exist, which translation unit compiles them, and how a run-time ShadeForm (pt_kernels.h) becomes a
-// kernel pointer. A new feature flag is one more bool in ShadeForm, one clause in shade_form_exists and, if its forms want a unit of
-// their own, one more value of form_unit with its accessor.
+// kernel pointer. A form is a shape (SHADE_SHAPES), three orthogonal bools (lights, list, qmc) and the shading mode (pt_types.h ShadeMode,
+// which says what the modes are and how they nest). A new exclusive feature is one more ShadeMode and, if its forms want a unit of their
+// own, one more FormUnit with its accessor.
 #pragma once
 #include <utility>
 
@@ -26,21 +27,20 @@ constexpr ShadeShape SHADE_SHAPES[] = {
 };
 constexpr int N_SHADE_SHAPES = sizeof(SHADE_SHAPES) / sizeof(SHADE_SHAPES[0]);
 constexpr int shade_row(int variant, int i = N_SHADE_SHAPES - 1) { return i == 0 || SHADE_SHAPES[i].variant == variant ? i : shade_row(variant, i - 1); }
-// THE list of feature combinations: pixel list / ENV / QMC / MED exist only for the default variant's shapes, ENV never with MED,
-// HET (grid-density media) only with MED, INT (interior media and chromatic absorption, §14) only with MED and HET — HET
-// renders homogeneous media with MED's bits, so the INT forms need not exist without it; LSE (exact light sampling, §15) only for the default variant's shapes, only
-// with a lights list, never with ENV or MED; DSP (spectral dispersion, §16) only for the default variant's shapes, never with ENV, MED or LSE
-constexpr bool shade_form_exists(const ShadeShape& s, bool list, bool env, bool qmc, bool med, bool het = false, bool intr = false, bool lse = false, bool lights = true,
-                                 bool dsp = false) {
-    return (s.variant == 22 || s.variant == 32 || s.variant == 42 || !(list || env || qmc || med || lse || dsp)) && !(env && med) && (med || !het) && ((med && het) || !intr) &&
-           (!lse || (lights && !env && !med)) && (!dsp || !(env || med || lse));
+// Which forms exist: a shape other than the default variant's three has the plain mode only, without pixel list and Sobol sampler; the
+// LSE forms need a lights list.
+constexpr bool shade_form_exists(const ShadeShape& s, bool lights, bool list, bool qmc, ShadeMode mode) {
+    return (s.variant == 22 || s.variant == 32 || s.variant == 42 || !(list || qmc || mode != MODE_PLAIN)) && (mode != MODE_LSE || lights);
 }
-// the unit that compiles a form: pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip (§12), pt_k3_het.hip (§13) or pt_k3_int.hip
-// (§14), or pt_k3_lse.hip (§15: every LSE form, with or without QMC), or pt_k3_dsp.hip (§16: every DSP form, with or without QMC). K1 has no HET, INT, LSE or DSP form — a camera ray's
-// bounce word is the MED form's, or 0 — so such a render's k_init is the one of the form without het, intr, lse and dsp (form_kernels).
+// the unit that compiles a form: pt_k3.hip, pt_k3_qmc.hip, or the mode's own — pt_k3_med.hip (§12), pt_k3_het.hip (§13),
+// pt_k3_int.hip (§14), pt_k3_lse.hip (§15), pt_k3_dsp.hip (§16), each with and without QMC. K1 has a plain and a MED form only — a camera
+// ray's bounce word is the MED forms', or 0 — so a render's k_init comes from the unit of (its mode has media ? MED : PLAIN, qmc).
 enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED, UNIT_HET, UNIT_INT, UNIT_LSE, UNIT_DSP };
-constexpr FormUnit form_unit(bool qmc, bool med, bool het = false, bool intr = false, bool lse = false, bool dsp = false) {
-    return dsp ? UNIT_DSP : lse ? UNIT_LSE : intr ? UNIT_INT : het ? UNIT_HET : med ? UNIT_MED : qmc ? UNIT_QMC : UNIT_PLAIN;
+constexpr FormUnit form_unit(ShadeMode mode, bool qmc) {
+    switch (mode) {
+    case MODE_MED: return UNIT_MED; case MODE_HET: return UNIT_HET; case MODE_INT: return UNIT_INT; case MODE_LSE: return UNIT_LSE; case MODE_DSP: return UNIT_DSP;
+    default: return qmc ? UNIT_QMC : UNIT_PLAIN;   // PLAIN, ENV
+    }
 }
 
 // run-time bools -> template arguments: f is called with one std::bool_constant per bool
@@ -53,21 +53,20 @@ template <class F, class... Rest> auto expand_bools(F&& f, bool b, Rest... rest)
 // The kernels of unit U for a form; null where the form does not exist or belongs to another unit. Every unit instantiates exactly the
 // forms it owns by compiling unit_forms<its U>.
 struct FormKernels { shade_fn shade; init_fn init; aov_fn aov; };   // (k_aov / k_aov_qmc are not templates: the unit's accessor names its own)
-template <FormUnit U, int ROW, bool LIGHTS, bool LIST, bool ENV, bool QMC, bool MED, bool HET, bool INT, bool LSE, bool DSP> shade_fn shade_kernel() {
+template <FormUnit U, int ROW, ShadeMode M, bool LIGHTS, bool LIST, bool QMC> shade_fn shade_kernel() {
     constexpr ShadeShape S = SHADE_SHAPES[ROW];
-    if constexpr (shade_form_exists(S, LIST, ENV, QMC, MED, HET, INT, LSE, LIGHTS, DSP) && form_unit(QMC, MED, HET, INT, LSE, DSP) == U)
-        return k_shade<S.sort, S.minw, LIGHTS, S.kb, S.per, LIST, ENV, QMC, MED, HET, INT, LSE, DSP>;
+    if constexpr (shade_form_exists(S, LIGHTS, LIST, QMC, M) && form_unit(M, QMC) == U) return k_shade<S.sort, S.minw, LIGHTS, S.kb, S.per, LIST, M, QMC>;
     else return nullptr;
 }
-template <FormUnit U, size_t... ROW> shade_fn shade_of(const ShadeForm& f, std::index_sequence<ROW...>) {
+template <FormUnit U, size_t... I> shade_fn shade_of(const ShadeForm& f, std::index_sequence<I...>) {   // I = shape row * N_SHADE_MODES + mode
     shade_fn k = nullptr;
-    ((shade_row(f.variant) == (int)ROW ? k = expand_bools([](auto... b) { return shade_kernel<U, (int)ROW, decltype(b)::value...>(); }, f.lights, f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse, f.dsp) : k), ...);
+    ((shade_row(f.variant) * N_SHADE_MODES + f.mode == (int)I ? k = expand_bools([](auto... b) { return shade_kernel<U, (int)I / N_SHADE_MODES, (ShadeMode)(I % N_SHADE_MODES), decltype(b)::value...>(); }, f.lights, f.list, f.qmc) : k), ...);
     return k;
 }
 template <FormUnit U> FormKernels unit_forms(const ShadeForm& f, aov_fn aov) {
-    return FormKernels{shade_of<U>(f, std::make_index_sequence<N_SHADE_SHAPES>{}),
-                       expand_bools([](auto list, auto qmc, auto med) -> init_fn { if constexpr (form_unit(qmc, med) == U) return k_init<list, qmc, med>; else return nullptr; },
-                                    f.list, f.qmc, f.med), aov};
+    return FormKernels{shade_of<U>(f, std::make_index_sequence<N_SHADE_SHAPES * N_SHADE_MODES>{}),
+                       expand_bools([](auto list, auto qmc, auto med) -> init_fn { if constexpr (form_unit(med ? MODE_MED : MODE_PLAIN, qmc) == U) return k_init<list, qmc, med>; else return nullptr; },
+                                    f.list, f.qmc, mode_has_media(f.mode)), aov};
 }
 // the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip, pt_k3_het.hip, pt_k3_int.hip, pt_k3_lse.hip, pt_k3_dsp.hip) — the only calls from one kernel unit into another
 FormKernels forms_plain(const ShadeForm& f), forms_qmc(const ShadeForm& f), forms_med(const ShadeForm& f), forms_het(const ShadeForm& f), forms_int(const ShadeForm& f),

@@ -1,4 +1,4 @@
-// K1 / K3 forms without the Sobol sampler and without media (unit_forms<UNIT_PLAIN>: k_init<LIST>, k_shade's shapes x LIGHTS and the
+// K1 / K3 forms of the plain and ENV modes without the Sobol sampler (unit_forms<UNIT_PLAIN>: k_init<LIST>, k_shade's shapes x LIGHTS and the
 // LIST / ENV forms of the default shapes), k_probe, k_aov, and the launchers of K1, K3 and the AOV walk, which pick a form's kernel from the unit that owns it.
 #include "pt_forms.h"
 #include "pt_k_trace.h"
@@ -30,21 +30,17 @@ __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t see
 }
 
 FormKernels forms_plain(const ShadeForm& f) { return unit_forms<UNIT_PLAIN>(f, k_aov); }
-static FormKernels form_kernels(const ShadeForm& f) {   // asks the unit that owns the form
-    if (f.het || f.lse || f.dsp) {   // k_shade from the grid-media, interior, light-sampling or dispersion unit, k_init from the form without het, intr, lse and dsp (K1 has no such form: pt_forms.h)
-        ShadeForm g = f;
-        g.het = g.intr = g.lse = g.dsp = false;
-        FormKernels k = f.dsp ? forms_dsp(f) : f.lse ? forms_lse(f) : f.intr ? forms_int(f) : forms_het(f);
-        k.init = k.shade ? form_kernels(g).init : nullptr;
-        return k;
-    }
-    return form_unit(f.qmc, f.med) == UNIT_MED ? forms_med(f) : form_unit(f.qmc, f.med) == UNIT_QMC ? forms_qmc(f) : forms_plain(f);
+static FormKernels form_kernels(const ShadeForm& f) {   // asks the unit that owns the form's k_shade, and the one that owns its k_init (pt_forms.h)
+    constexpr FormKernels (*unit[])(const ShadeForm&) = {forms_plain, forms_qmc, forms_med, forms_het, forms_int, forms_lse, forms_dsp};   // in FormUnit's order
+    const FormUnit k3 = form_unit(f.mode, f.qmc), k1 = form_unit(mode_has_media(f.mode) ? MODE_MED : MODE_PLAIN, f.qmc);   // K1 has a plain and a MED form only
+    FormKernels k = unit[k3](f);
+    if (k1 != k3) k.init = k.shade ? unit[k1](f).init : nullptr;
+    return k;
 }
 
 ShadeForm shade_form(ShadeForm f) {
-    return shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse, f.lights, f.dsp)
-               ? f
-               : ShadeForm{42, f.lights, f.list, f.env, f.qmc, f.med, f.het, f.intr, f.lse, f.dsp};
+    if (!shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.lights, f.list, f.qmc, f.mode)) f.variant = 42;
+    return f;
 }
 bool shade_form_sorts(const ShadeForm& f) { return SHADE_SHAPES[shade_row(f.variant)].sort; }
 

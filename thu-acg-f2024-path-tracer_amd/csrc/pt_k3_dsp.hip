@@ -1,4 +1,4 @@
-// The spectral-dispersion forms of K3 (unit_forms<UNIT_DSP>: DSP with or without LIGHTS, LIST and QMC, never ENV, MED or LSE)
+// The spectral-dispersion forms of K3 (unit_forms<UNIT_DSP>: the mode DSP, with or without LIGHTS, LIST and QMC)
 // and the dispersion probe.
 #include "pt_forms.h"
 

@@ -1,4 +1,4 @@
-// The grid-density-media forms of K3 (unit_forms<UNIT_HET>: MED and HET, with or without QMC, never ENV) and the grid probe.
+// The grid-density-media forms of K3 (unit_forms<UNIT_HET>: the mode HET, with or without QMC) and the grid probe.
 #include "pt_forms.h"
 
 namespace pt {

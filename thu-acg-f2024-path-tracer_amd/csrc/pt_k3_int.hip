@@ -1,4 +1,4 @@
-// The interior-media forms of K3 (unit_forms<UNIT_INT>: MED, HET and INT, with or without QMC, never ENV) and the
+// The interior-media forms of K3 (unit_forms<UNIT_INT>: the mode INT, with or without QMC) and the
 // absorption probe.
 #include "pt_forms.h"
 

@@ -1,4 +1,4 @@
-// The exact-light-sampling forms of K3 (unit_forms<UNIT_LSE>: LSE with LIGHTS, with or without LIST and QMC, never ENV or MED)
+// The exact-light-sampling forms of K3 (unit_forms<UNIT_LSE>: the mode LSE, with or without LIST and QMC)
 // and the light probe.
 #include "pt_forms.h"
 

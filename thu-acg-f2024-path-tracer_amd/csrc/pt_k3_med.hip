@@ -1,4 +1,4 @@
-// The participating-media forms of K1 / K3 (unit_forms<UNIT_MED>: MED with or without QMC, never ENV) and the medium probe.
+// The participating-media forms of K1 / K3 (unit_forms<UNIT_MED>: the mode MED, with or without QMC) and the medium probe.
 #include "pt_forms.h"
 
 namespace pt {

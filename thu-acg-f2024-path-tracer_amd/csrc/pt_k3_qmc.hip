@@ -1,4 +1,4 @@
-// The Sobol sampler's forms of K1 / K3 (unit_forms<UNIT_QMC>: QMC without MED), k_aov_qmc and the sampler probe.
+// The Sobol sampler's forms of K1 / K3 (unit_forms<UNIT_QMC>: the plain and ENV modes with QMC), k_aov_qmc and the sampler probe.
 #include "pt_forms.h"
 #include "pt_k_trace.h"
 

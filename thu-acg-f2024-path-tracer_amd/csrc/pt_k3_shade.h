@@ -179,6 +179,8 @@ struct NoPrefetch {
 //   D  regeneration (arithmetic), stores
 // vmcnt counts loads, stores, atomics and LDS-DMA in issue order, so a fetch can only hide behind a stretch in which no
 // younger load is waited for — hence the phase discipline (tex values fetched up front, pt_dev_bsdf.h fetch_tex).
+// The template arguments. M is the shading mode (pt_types.h ShadeMode, which says what combines with what); ENV / MED / HET / INT / LSE / DSP
+// below are the constants the body derives from it, and "the X forms" the modes that have X.
 // LIGHTS: the scene has a lights list (World::lights non-empty). The instantiation without compiles lights.sample / lights.pdf, the
 // selector draw and the later prefetch point out: p_light = 0 there (camera.rs:199-200), so no result changes.
 // ENV: environment importance sampling is in effect (the rule in pt_amd.h; `env` holds the tables). At a hit in the env
@@ -190,25 +192,24 @@ struct NoPrefetch {
 // word. Phase A makes the free-flight draw of a path inside a medium: a lane whose distance falls short of the hit (or whose ray left
 // the scene) is at a MEDIUM VERTEX — no surface code runs for it; B1 draws roulette, selector and a light or Henyey-Greenstein
 // direction, B2 the phase function, the MIS density and the next ray. A lane that reached a medium's BOUNDARY toggles its medium and
-// continues straight on. Every other lane is the bounce above bit for bit. Never together with ENV (pt_render refuses it).
-// HET (only with MED): a grid-density medium is in effect (the rule in pt_amd.h). A path whose medium has a grid makes
+// continues straight on. Every other lane is the bounce above bit for bit.
+// HET: a grid-density medium is in effect (the rule in pt_amd.h). A path whose medium has a grid makes
 // phase A's free flight by delta tracking (grid_track: a lane-divergent loop, nothing sorts around it); a homogeneous medium and every
 // other lane are the MED form bit for bit.
-// INT (only with MED and HET): interior media or chromatic absorption are in effect (the rule in pt_amd.h). Phase A
+// INT: interior media or chromatic absorption are in effect (the rule in pt_amd.h). Phase A
 // attenuates the throughput of a path inside a tinted medium over the segment it has just travelled, and makes no free-flight draw in a
 // medium of density 0; B2 sets the medium of a bounce that crossed a glass surface with an interior. Every other lane is the HET form bit
 // for bit.
-// LSE (only with LIGHTS, never with ENV or MED): exact light sampling is in effect (the rule in pt_amd.h). B1's light direction
+// LSE (only with LIGHTS): exact light sampling is in effect (the rule in pt_amd.h). B1's light direction
 // and B2's light density come from pt_dev_lights.h: area-weighted mesh lights whose pdf walks the mesh's BVH with the lane's stack in LDS
 // (lstk = &stack[0][thread] of k_shade's LSE_KB-lane stack), cone-sampled sphere lights. Everything else is the bounce above bit for bit.
-// DSP (never with ENV, MED or LSE): spectral dispersion is in effect (the rule in pt_amd.h). The path's MONO flag rides in bit 31 of its
+// DSP: spectral dispersion is in effect (the rule in pt_amd.h). The path's MONO flag rides in bit 31 of its
 // bounce word. Phase A: a lane at a dispersive glass computes its path's wavelength — a function of (seed, pixel, sample), no draw — the Cauchy
 // index n(lambda) and reads its row of the weight table (`env->col`: these forms have no environment tables); B1 / B2 hand n(lambda) to the glass
 // case of mat_sample / mat_pdf_eval; a continued bounce of a path whose flag is clear multiplies the new throughput by the row and sets the flag.
 // Every other lane is the bounce above bit for bit.
 constexpr int LSE_KB = 512;                                            // threads per block of every shape that has LSE forms (pt_forms.h)
-template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = false, bool MED = false, bool HET = false, bool INT = false, bool LSE = false, bool DSP = false,
-          bool UNI = true>
+template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true>
 // UNI: the form may take the single-primitive path of phase A (k_shade: every two-wave shape).
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
@@ -217,6 +218,7 @@ template <bool LIGHTS, bool LIST, class Prefetch, bool ENV = false, bool QMC = f
 PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, uint32_t s, uint32_t o_base, int lane, const SlotIn& in,
                        uint32_t& shard, uint32_t& n_done, uint32_t& n_died, Prefetch&& prefetch, unsigned long long pre_mask = 0ull,
                        unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u, const EnvTabD* env = nullptr, uint32_t* lstk = nullptr) {
+    constexpr bool ENV = M == MODE_ENV, MED = mode_has_media(M), HET = mode_has_grid(M), INT = M == MODE_INT, LSE = M == MODE_LSE, DSP = M == MODE_DSP;
     PT_STAMP(1);
     uint32_t bounce = in.bounce;
     uint32_t med = 0u;                                                 // MED: the path's medium (material index + 1), 0 = none
@@ -683,19 +685,16 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // waves of the block (work stealing), and every slot's records are moved whole by its own lane.
 // KB: threads per block (256, or [r3] 512 with a 4096-slot window: the sort's barriers and the window's end are paid once per twice
 // as many slots and eight waves level a window's end better than four; one block per CU then).
-// ENV: environment importance sampling (shade_slot; `env` is read by these forms only)
+// M: the shading mode (pt_types.h ShadeMode; shade_slot says what each of the constants derived from it changes). Of `env`, the ENV
+// forms read the tables and the DSP forms `col`, their weight table; no other form reads it.
 // QMC: the Sobol sampler (shade_slot)
 // MED: participating media (shade_slot). A slot's class says nothing certain about a path inside a medium — it may scatter before the
 // hit, or instead of leaving — so these forms do not request work items a group ahead.
-// HET: grid-density media (shade_slot)
-// INT: interior media and chromatic absorption (shade_slot)
-// LSE: exact light sampling (shade_slot); these forms hold the per-lane stack of the light meshes' all-hits walk, LIGHT_STACK levels x KB lanes in LDS
-// DSP: spectral dispersion (shade_slot); `env.col` is the weight table of these forms
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, bool ENV = false, bool QMC = false, bool MED = false,
-          bool HET = false, bool INT = false, bool LSE = false, bool DSP = false>
+// LSE: these forms hold the per-lane stack of the light meshes' all-hits walk, LIGHT_STACK levels x KB lanes in LDS
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, ShadeMode M = MODE_PLAIN, bool QMC = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
-    static_assert(!DSP || (SORT && !ENV && !MED && !LSE && KB == 512), "k_shade: the DSP forms are sorted 512-thread forms without ENV, MED and LSE");
-    static_assert(!LSE || (SORT && LIGHTS && !ENV && !MED && KB == LSE_KB), "k_shade: the LSE forms are sorted 512-thread forms with lights, without ENV and MED");
+    constexpr bool ENV = M == MODE_ENV, MED = mode_has_media(M), LSE = M == MODE_LSE, DSP = M == MODE_DSP;   // (HET and INT change nothing here)
+    static_assert((!LSE || LIGHTS) && (!(LSE || DSP) || (SORT && KB == LSE_KB)), "k_shade: the LSE forms need a lights list; the LSE and DSP forms are sorted 512-thread forms");
     __shared__ uint32_t s_lstack[LSE ? LIGHT_STACK * KB : 1];   // 48 KB: stack[level][thread] of lights_pdf_exact's mesh walk
     uint32_t* const lstk = LSE ? &s_lstack[threadIdx.x] : nullptr;
     uint32_t n_done = 0, n_died = 0;   // per thread and launch: far below 2^32 (64-bit counters here were the kernel's only spills)
@@ -712,7 +711,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, ENV, QMC, MED, HET, INT, LSE, DSP, MINW == 2>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
+            shade_slot<LIGHTS, LIST, NoPrefetch, M, QMC, MINW == 2>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -889,7 +888,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, ENV, QMC, MED, HET, INT, LSE, DSP, MINW == 2>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, M, QMC, MINW == 2>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env, lstk);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

@@ -1,6 +1,5 @@
-// Host-callable launchers of the HIP kernels: one per stage. K2 is in pt_k2.hip, K1 / K3 / the AOV walk in pt_k3.hip (their Sobol forms in
-// pt_k3_qmc.hip, their media forms in pt_k3_med.hip, K3's grid-media forms in pt_k3_het.hip, its interior-media forms in pt_k3_int.hip, its exact-light-sampling forms in pt_k3_lse.hip, its dispersion forms in pt_k3_dsp.hip), the small
-// kernels in pt_kernels.hip.
+// Host-callable launchers of the HIP kernels: one per stage. K2 is in pt_k2.hip, K1 / K3 / the AOV walk in pt_k3.hip and the units
+// pt_forms.h form_unit names (pt_k3_*.hip: the Sobol sampler's forms and one unit per shading mode), the small kernels in pt_kernels.hip.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -8,12 +7,10 @@
 
 namespace pt {
 // What a render asks of K1 / K3 / the AOV walk. variant: k_shade's shape code (pt_forms.h SHADE_SHAPES; PT_SHADE_VARIANT); lights: the scene
-// has a lights list; list: pixel-list render (PoolD::list); env: environment sampling; qmc: the Sobol sampler
-// (pt_scene_set_sampler, §11); med: participating media are in effect (§12); het: one of them is a grid-density medium (§13), or intr is set;
-// intr: a glass interior or a tinted medium is in effect (§14); lse: exact light sampling is in effect (§15); dsp: spectral dispersion is in
-// effect (§16). Which combinations exist: pt_forms.h shade_form_exists.
-struct ShadeForm { int variant; bool lights, list, env, qmc, med, het = false, intr = false, lse = false, dsp = false; };
-// The form a render gets: pixel lists, env, qmc and med exist for the default variant's shapes only — any other variant becomes 42.
+// has a lights list; list: pixel-list render (PoolD::list); qmc: the Sobol sampler (pt_scene_set_sampler); mode: the
+// shading mode (pt_types.h ShadeMode). Which forms exist: pt_forms.h shade_form_exists.
+struct ShadeForm { int variant = 0; bool lights = false, list = false, qmc = false; ShadeMode mode = MODE_PLAIN; };
+// The form a render gets: pixel lists, qmc and every mode but the plain one exist for the default variant's shapes only — any other variant becomes 42.
 // The launchers and queries below take the form this returns.
 ShadeForm shade_form(ShadeForm asked);
 // whether the form's k_shade sorts its windows by class (the shading-order output, PoolD::reorder, needs the sort's positions)
@@ -24,7 +21,7 @@ bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_bloc
 // flat-top-level instantiation without / with pair passes), -(stack*10 + blocks) = two-phase kernel k_extend2<stack, blocks> for stack in {16, 20, 24}.
 void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st);
 // wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
-// env: the environment-sampling tables of a form with `env`; of a form with `dsp`: its `col` = the dispersion weight table (device, DSP_BINS x 3); else null
+// env: the table argument of a mode that has one (pt_types.h mode_has_table) — the ENV forms' tables; the DSP forms' weight table (device, DSP_BINS x 3) in `col` — else null
 bool launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, const ShadeForm& form, hipStream_t st,
                   uint32_t wide_window_min = 16, const EnvTabD* env = nullptr);
 // resident blocks per CU of the K2 / K3 kernel a render launches (shade: 0 when no kernel of that form exists)

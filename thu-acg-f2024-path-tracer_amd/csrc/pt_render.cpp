@@ -232,6 +232,37 @@ static int env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e) {
     return 0;
 }
 
+// The shading mode of a render (pt_types.h ShadeMode), or an error: which of the exclusive features is in effect (the rules: pt_amd.h),
+// the refusal of two of them at once and of what a mode's path records or kernels cannot hold. env: the table argument of a mode that
+// has one (pt_types.h mode_has_table), zeroed by the caller.
+static int render_mode(pt_scene* s, const CamD& dc, hipStream_t st, ShadeMode& mode, EnvTabD& env) {
+    // environment sampling is in effect: f > 0, the environment is a map and its weight Z > 0 (pt_amd.h); otherwise no new code runs
+    if (s->env_f > 0.0 && dc.env_is_map && env_tables(s, dc, st, env) != 0) return -1;
+    const bool env_on = env.z > 0.0;   // (env arrives zeroed: only env_tables sets a weight)
+
+    // participating media are in effect (pt_amd.h): a world object carries a medium material or a glass with an interior, or the camera medium is set
+    const bool med = s->media_on();
+    if (med && env_on) return set_error("pt_render: environment importance sampling together with participating media is not supported (set one of them off)");
+    if (med && dc.max_depth > MEDIUM_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^20 when participating media are in effect");
+
+    // exact light sampling is in effect (pt_amd.h): kind 1 and a mesh or sphere entry in the lights list; otherwise no new code runs
+    const bool lse = s->light_sampling_on();
+    if (lse && env_on) return set_error("pt_render: exact light sampling together with environment importance sampling is not supported (set one of them off)");
+    if (lse && med) return set_error("pt_render: exact light sampling together with participating media is not supported (set light sampling to 0 or take the media out)");
+    if (lse && s->light_mesh_bad_area) return set_error("pt_render: exact light sampling needs light meshes of finite, positive area (a mesh in the lights list has area 0 or a non-finite one)");
+    if (lse && s->light_blas_depth > (uint32_t)LIGHT_STACK) return set_error("pt_render: exact light sampling: a light mesh's BVH is deeper than the 24 levels its pdf walk's stack holds");
+
+    // spectral dispersion is in effect (pt_amd.h): some world object's material is a glass with an Abbe number; otherwise no new code runs
+    const bool dsp = s->dispersion_on();
+    if (dsp && env_on) return set_error("pt_render: spectral dispersion together with environment importance sampling is not supported (set one of them off)");
+    if (dsp && med) return set_error("pt_render: spectral dispersion together with participating media or a glass interior is not supported (clear the dispersion or take the media out)");
+    if (dsp && lse) return set_error("pt_render: spectral dispersion together with exact light sampling is not supported (set one of them off)");
+    if (dsp && dc.max_depth > DSP_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^31 when spectral dispersion is in effect");
+    if (dsp && !(env.col = dispersion_table(s, st))) return -1;   // the DSP forms read the weight table where the ENV forms read their tables (pt_types.h)
+    mode = dsp ? MODE_DSP : lse ? MODE_LSE : !med ? (env_on ? MODE_ENV : MODE_PLAIN) : s->interior_on() ? MODE_INT : s->grid_media_on() ? MODE_HET : MODE_MED;
+    return 0;
+}
+
 // The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
 // pixels) / n_list: a pixel-list render (PoolD::list; d_list sorted by tiled index, n_list > 0), or null: the whole frame — then the
 // path below is exactly pt_render's.
@@ -255,36 +286,9 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
     const uint32_t spp = spp_end - spp_begin;
     const bool list = d_list != nullptr;
     const uint32_t n_items = list ? n_list : n_pixels;   // pixels rendered
-    // environment sampling is in effect: f > 0, the environment is a map and its weight Z > 0 (pt_amd.h); otherwise no new code runs
-    EnvTabD env{};
-    bool env_on = false;
-    if (s->env_f > 0.0 && dc.env_is_map) {
-        if (env_tables(s, dc, st, env) != 0) return -1;
-        env_on = env.z > 0.0;
-    }
-
-    // participating media are in effect (pt_amd.h): a world object carries a medium material or a glass with an interior, or the camera medium is set
-    const bool med = s->media_on();
-    if (med && env_on) return set_error("pt_render: environment importance sampling together with participating media is not supported (set one of them off)");
-    if (med && dc.max_depth > MEDIUM_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^20 when participating media are in effect");
-
-    // exact light sampling is in effect (pt_amd.h): kind 1 and a mesh or sphere entry in the lights list; otherwise no new code runs
-    const bool lse = s->light_sampling_on();
-    if (lse && env_on) return set_error("pt_render: exact light sampling together with environment importance sampling is not supported (set one of them off)");
-    if (lse && med) return set_error("pt_render: exact light sampling together with participating media is not supported (set light sampling to 0 or take the media out)");
-    if (lse && s->light_mesh_bad_area) return set_error("pt_render: exact light sampling needs light meshes of finite, positive area (a mesh in the lights list has area 0 or a non-finite one)");
-    if (lse && s->light_blas_depth > (uint32_t)LIGHT_STACK) return set_error("pt_render: exact light sampling: a light mesh's BVH is deeper than the 24 levels its pdf walk's stack holds");
-
-    // spectral dispersion is in effect (pt_amd.h): some world object's material is a glass with an Abbe number; otherwise no new code runs
-    const bool dsp = s->dispersion_on();
-    if (dsp && env_on) return set_error("pt_render: spectral dispersion together with environment importance sampling is not supported (set one of them off)");
-    if (dsp && med) return set_error("pt_render: spectral dispersion together with participating media or a glass interior is not supported (clear the dispersion or take the media out)");
-    if (dsp && lse) return set_error("pt_render: spectral dispersion together with exact light sampling is not supported (set one of them off)");
-    if (dsp && dc.max_depth > DSP_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^31 when spectral dispersion is in effect");
-    if (dsp) {   // the DSP forms read the weight table where the ENV forms read their tables (pt_types.h)
-        env.col = dispersion_table(s, st);
-        if (!env.col) return -1;
-    }
+    ShadeMode mode;
+    EnvTabD env{};   // the table argument of a mode that has one
+    if (render_mode(s, dc, st, mode, env) != 0) return -1;
 
     // pool sizing. slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
     // the machine several times over; finished paths pull the next (pixel, sample) from a global
@@ -335,10 +339,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
                               // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
                               // windows per block launched, else 22)
     if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
-    const bool qmc = s->sampler == 1;   // the Sobol sampler: the QMC forms of k_init / k_shade
-    const bool intr = med && s->interior_on();   // a glass interior or a tinted medium is in effect: the INT forms of k_shade, which are HET forms
-    const bool het = med && (intr || s->grid_media_on());   // a grid-density medium is in effect: the HET forms of k_shade
-    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, env_on, qmc, med, het, intr, lse, dsp});   // the form of k_init / k_shade that exists for it
+    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, mode});   // the form of k_init / k_shade that exists for it
     shade_variant = form.variant;
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
@@ -510,7 +511,7 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             launch_extend(s->dev.view, pool, s->d_counters, grid_extend, extend_code, st);
             timer.end(st);
             timer.begin(1, st);
-            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, form, st, wide_window_min, env_on || dsp ? &env : nullptr)) return set_error("pt_render: no k_shade form for this render");
+            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, form, st, wide_window_min, mode_has_table(mode) ? &env : nullptr)) return set_error("pt_render: no k_shade form for this render");
             timer.end(st);
             if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
                 std::swap(pool.ray, pool.ray_out);
@@ -848,7 +849,9 @@ extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, 
         d_aov = own.p;
         if (!opts.overwrite && !hip_ok(hipMemcpyAsync(d_aov, aov, bytes, hipMemcpyHostToDevice, st), "hipMemcpy(aov)")) return -1;
     }
-    if (!launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, ShadeForm{0, false, false, false, s->sampler == 1, false}))
+    ShadeForm aov_form;   // of a form, the AOV walk looks at the sampler only
+    aov_form.qmc = s->sampler == 1;
+    if (!launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, aov_form))
         return set_error("pt_render_aovs: no k_aov form for this sampler");
     if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
     if (!opts.accum_on_device && !hip_ok(hipMemcpyAsync(aov, d_aov, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(aov)")) return -1;

@@ -135,9 +135,24 @@ constexpr uint32_t MEDIUM_SHIFT = 20, MEDIUM_BOUNCE_MASK = (1u << MEDIUM_SHIFT) 
 // it has been weighted by its wavelength's row of the weight table — is bit 31 of its bounce word, which the non-MED forms leave free. Only
 // the DSP forms of k_shade pack and unpack it; a camera ray's word is 0, so K1 has no DSP form. The host refuses a max_depth that reaches
 // the bit (pt_render). The weight table W[DSP_BINS][3] (f64, the same for every scene) reaches the DSP forms through the `col` pointer of
-// their EnvTabD argument, which no form without ENV reads otherwise — DSP never comes with ENV.
+// their EnvTabD argument, which only the ENV forms read otherwise.
 constexpr uint32_t DSP_MONO_BIT = 1u << 31, DSP_BOUNCE_MASK = DSP_MONO_BIT - 1u;
 constexpr int DSP_BINS = 64;
+// THE shading mode of a render: which of the mutually exclusive features is in effect (the rules: pt_amd.h; which one a scene gets, or why
+// it gets none: pt_render.cpp render_mode). k_shade and shade_slot are compiled once per mode; "the X forms" are the kernels whose mode has X:
+//   PLAIN  none of them
+//   ENV    environment importance sampling; the kernel's EnvTabD argument holds its tables
+//   MED    participating media (§12)
+//   HET    MED, and grid-density media (§13): a homogeneous medium is rendered with MED's bits
+//   INT    MED and HET, and interior media / chromatic absorption (§14)
+//   LSE    exact light sampling (§15); needs a lights list
+//   DSP    spectral dispersion (§16); the `col` pointer of the kernel's EnvTabD argument is the weight table
+// Nothing else combines: MED < HET < INT nest, every other pair excludes each other. The pixel list, the Sobol sampler and the lights list
+// are orthogonal to the mode (ShadeForm, pt_kernels.h).
+enum ShadeMode { MODE_PLAIN, MODE_ENV, MODE_MED, MODE_HET, MODE_INT, MODE_LSE, MODE_DSP, N_SHADE_MODES /* their number, not a mode */ };
+constexpr bool mode_has_media(ShadeMode m) { return m == MODE_MED || m == MODE_HET || m == MODE_INT; }
+constexpr bool mode_has_grid(ShadeMode m) { return m == MODE_HET || m == MODE_INT; }
+constexpr bool mode_has_table(ShadeMode m) { return m == MODE_ENV || m == MODE_DSP; }
 constexpr uint32_t CLASS_MISS = 0u, CLASS_IDLE = 1u + MAT_KINDS, CLASS_DEAD = 2u + MAT_KINDS, N_CLASSES = 3u + MAT_KINDS;
 // MAT_SHEEN: p[0..2] = base colour, p[3] = sheen_tint (sheen.rs). MAT_CLEARCOAT: alpha_g (clearcoat.rs).
 // MAT_MIX: p[0] = t, color_tex / rough_tex hold the two child MATERIAL indices (mix.rs; children are leaves).

@@ -7,9 +7,12 @@
 #                              unit (.LBB<N>_, .Lfunc_begin<N> / _end<N>, .Ltmp<N>, ...) renumbered, the kernel's descriptor appended — and
 #                              DIR/MANIFEST: "<sha256> <kernel|func> <symbol> <unit>" sorted by symbol. Two trees hold the same code when
 #                              `cut -d' ' -f1-3 MANIFEST | sort -u` of both are equal (the order of functions and units does not enter).
+#                              And DIR/MANIFEST.anon: "<sha256> <kernel|func> <unit>" of the same text with every occurrence of the
+#                              function's own symbol replaced by one token. Two trees hold the same code up to the renaming of functions
+#                              (a template's arguments respelt) when `cut -d' ' -f1-2 MANIFEST.anon | sort` of both are equal.
 set -e
 ISA=
-[ "$1" = "--isa" ] && { ISA=$(mkdir -p "$2" && cd "$2" && pwd); rm -f "$ISA"/*.s "$ISA/MANIFEST"; }
+[ "$1" = "--isa" ] && { ISA=$(mkdir -p "$2" && cd "$2" && pwd); rm -f "$ISA"/*.s "$ISA"/MANIFEST "$ISA"/MANIFEST.anon; }
 cd "${PKG:-$(dirname "$0")/../thu-acg-f2024-path-tracer_amd}"
 UNITS=${UNITS:-$(sed -n 's/^CSRC *= *//p' Makefile | tr ' ' '\n' | grep '\.hip$')}
 TMP=$(mktemp -d)
@@ -30,7 +33,7 @@ done
 [ -z "$ISA" ] && exit 0
 python3 - "$ISA" "$TMP"/*.s <<'EOF'
 import hashlib, os, re, sys
-out, manifest = sys.argv[1], []
+out, manifest, anon = sys.argv[1], [], []
 label = re.compile(r"\.L([A-Za-z_]+?)(\d+)(_\d+)?\b")
 for path in sys.argv[2:]:
     unit = os.path.basename(path)[:-2]
@@ -63,8 +66,11 @@ for path in sys.argv[2:]:
             return ".L%s#%d" % (m.group(1), tmp.setdefault(m.group(0), len(tmp)))   # .Ltmp<N>: by first appearance
         norm = "\n".join(label.sub(renumber, l) for l in body) + "\n"
         per_unit.write("== %s\n%s" % (sym, norm))
-        manifest.append("%s %s %s %s" % (hashlib.sha256(norm.encode()).hexdigest(), "kernel" if sym in kernels else "func", sym, unit))
+        kind = "kernel" if sym in kernels else "func"
+        manifest.append("%s %s %s %s" % (hashlib.sha256(norm.encode()).hexdigest(), kind, sym, unit))
+        anon.append("%s %s %s" % (hashlib.sha256(norm.replace(sym, "@SELF").encode()).hexdigest(), kind, unit))
 manifest.sort(key=lambda m: m.split()[2:])
 open(os.path.join(out, "MANIFEST"), "w").write("\n".join(manifest) + "\n")
+open(os.path.join(out, "MANIFEST.anon"), "w").write("\n".join(sorted(anon)) + "\n")
 print("%d kernels, %d device functions -> %s/MANIFEST" % (sum(" kernel " in m for m in manifest), sum(" func " in m for m in manifest), out))
 EOF
