@@ -337,3 +337,79 @@ def white_furnace_scene(width=256, aspect=1.0):
     spec.camera = default_camera(width=width, aspect=aspect, look_from=(0.0, 1.8, -5.5), look_at=(0.0, 0.9, 0.0), vfov=50.0,
                                  env_color=(0.7, 0.8, 0.9))
     return spec
+
+
+# ---- every compiled form of k_shade on one scene (tests/test_k3_forms_gpu.py) -----------------------------------------------------------
+def _with_env(env, fn):
+    """fn() under the environment variables `env`, restored after (the experiment switches are read at every render)."""
+    import os
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return fn()
+    finally:
+        for k, v in old.items():
+            if v is None: os.environ.pop(k, None)
+            else: os.environ[k] = v
+
+
+def window_slots(st, wide_window_min=16):
+    """The window size of the render's first k_shade launch (launch_shade's rule for variant 42)."""
+    n_alloc = (st.n_slots + 8191) // 8192 * 8192
+    return 8192 if n_alloc // 8192 >= st.blocks_shade * wide_window_min else 4096
+
+
+FORMS_MODES = ("PLAIN", "ENV", "MED", "HET", "INT", "LSE", "DSP")      # ShadeMode (csrc/pt_types.h), in its order
+FORMS_W, FORMS_H = 160, 120                                            # 19 200 slots in static mode: 24 576 allocated (three 8192-slot windows)
+
+
+def forms_scene(mode="PLAIN", lights=True):
+    """One small scene in which every ShadeMode can be put in effect, with many material classes in every window: a checker floor,
+    spheres of metal, glass, principled and a mix, a diffuse cuboid under a rotated instance and an icosphere mesh under an instance (the
+    two-phase K2), under a small float environment map; `lights`: a lights list of a quad and a small emissive mesh (no sphere light:
+    the reference's Sphere::pdf yields NaN). `mode` adds what puts that mode in effect and nothing else, so the PLAIN scenes replay on
+    the oracle. A new ShadeMode needs its entry here."""
+    assert mode in FORMS_MODES and (lights or mode != "LSE")
+    rng = np.random.default_rng(42)
+    s = SceneSpec()
+    rgb = lambda r, g, b: s.add("tex_solid_rgb", r, g, b)
+    env = s.add("tex_image_rgbf32", rng.uniform(0.05, 1.6 if not lights else 0.5, size=(4, 8, 3)).astype(np.float32))
+    floor = s.add("mat_diffuse", s.add("tex_checker", 0.7, rgb(0.2, 0.3, 0.1), rgb(0.9, 0.9, 0.9)), -1)
+    metal = s.add("mat_metal", rgb(0.85, 0.75, 0.5), s.add("tex_solid_f", 0.15))
+    glass = s.add("mat_glass", rgb(1.0, 1.0, 1.0), s.add("tex_solid_f", 0.05), 0.0, 1.5)
+    prin = s.add("mat_principled", rgb(0.7, 0.35, 0.3), [0.3, 0.4, 0.5, 0.2, 0.3, 1.45, 0.4, 0.3, 0.2, 0.5, 0.1])
+    mix = s.add("mat_mix", 0.45, s.add("mat_sheen", (0.6, 0.5, 0.8), 0.4), s.add("mat_metal", rgb(0.6, 0.8, 0.9), s.add("tex_solid_f", 0.3)))
+    red = s.add("mat_diffuse", rgb(0.8, 0.2, 0.15), -1)
+    blue = s.add("mat_diffuse", rgb(0.2, 0.3, 0.8), -1)
+    s.add("world_add_object", s.add("quad", (-20.0, 0.0, -20.0), (0.0, 0.0, 40.0), (40.0, 0.0, 0.0), floor))
+    for r, c, m in ((0.6, (-2.3, 0.6, 0.3), metal), (0.9, (0.0, 0.9, -1.5), glass), (0.5, (1.7, 0.5, -1.9), prin), (0.55, (2.5, 0.55, 0.8), mix)):
+        s.add("world_add_object", s.add("sphere", r, c, c, m))
+    box = s.add("cuboid", (0.0, 0.0, 0.0), (0.8, 1.2, 0.8), red)
+    s.add("world_add_object", s.add("instance", box, (0.0, 1.0, 0.0), 0.6, (-1.4, 0.0, 1.6)))
+    P, I = icosphere(1)
+    s.add("world_add_object", s.add("instance", s.add("mesh", 0.6, P, I, None, None, blue), (0.3, 0.9, 0.2), 0.8, (1.1, 0.6, 1.4)))
+    if lights:
+        s.add("world_add_light", s.add("quad", (-1.0, 4.0, -1.0), (2.0, 0.0, 0.0), (0.0, 0.0, 2.0), s.add("mat_light", rgb(8.0, 8.0, 7.0))))
+        P0, I0 = icosphere(0)
+        P0 = (np.asarray(P0, dtype=np.float64) + np.array([-6.0, 9.0, 2.0])).astype(np.float32)        # (scaled by 0.3 below: centre (-1.8, 2.7, 0.6))
+        s.add("world_add_light", s.add("mesh", 0.3, P0, I0, None, None, s.add("mat_light", rgb(5.0, 9.0, 12.0))))
+    if mode == "ENV":
+        s.add("set_env_sampling", 0.5)
+    elif mode == "MED":
+        fog = s.add("mat_medium", 0.04, (0.9, 0.9, 0.9), 0.3)           # a fog box with the camera and everything else inside: paths leave it to the environment
+        s.add("world_add_object", s.add("cuboid", (-12.0, -1.0, -12.0), (12.0, 10.0, 12.0), fog))
+        s.add("set_camera_medium", fog)
+        s.add("world_add_object", s.add("sphere", 0.7, (-0.9, 2.2, 0.4), (-0.9, 2.2, 0.4), s.add("mat_medium", 1.5, (0.6, 0.7, 0.8), -0.3)))
+    elif mode == "HET":
+        lo, hi = (-3.4, -0.5, -2.9), (3.4, 3.3, 3.0)                  # around the objects; the camera and the quad light are outside
+        smoke = s.add("mat_medium_grid", 0.5, (0.9, 0.8, 0.7), 0.3, rng.uniform(0.0, 1.0, size=(4, 4, 4)).astype(np.float32), lo, hi)
+        s.add("world_add_object", s.add("cuboid", lo, hi, smoke))
+    elif mode == "INT":
+        s.add("mat_glass_set_interior", glass, s.add("mat_medium_tinted", 0.8, (0.9, 0.8, 0.7), 0.2, (0.3, 0.1, 0.6)))
+    elif mode == "LSE":
+        s.add("set_light_sampling", "exact")
+    elif mode == "DSP":
+        s.add("mat_glass_set_dispersion", glass, 30.0)
+    s.add("world_build")
+    s.camera = default_camera(width=FORMS_W, aspect=FORMS_W / FORMS_H, spp=4, env_is_map=1, env_tex=env)
+    return s
