@@ -474,6 +474,56 @@ typedef struct pt_denoise_opts {
 int pt_denoise(pt_ctx*, uint32_t width, uint32_t height, const double* sum_a, uint32_t n_a, const double* sum_b, uint32_t n_b,
                const double* aov, uint32_t n_aov, const pt_denoise_opts* opts, double* out);
 
+/* ---- the film stage: exposure, glare, tone mapping and HDR output (no counterpart in the reference, whose camera.rs:109-130 is the
+ * default options' case) ----
+ * pt_film_develop turns W*H*3 sample SUMS (row-major, as pt_render leaves them) into the scene-linear image hdr_out (W*H*3 f64) and / or
+ * the display image rgb8_out (W*H*3 bytes); either may be null, not both. n = counts ? counts[p] : total_spp per pixel p. Host buffers,
+ * or with opts->on_device device pointers (a torch tensor, the accumulator of pt_render with accum_on_device). Like pt_denoise the call
+ * returns when the work is done; sums is not written. With default options (opts NULL) rgb8_out holds pt_resolve_u8's bytes, or
+ * pt_resolve_u8_counts's when counts is given.
+ * The rule. f64, one IEEE rounding per written operation; lum(c) = 0.2126 r + 0.7152 g + 0.0722 b.
+ *  1 Mean and exposure: m_c = sum_c * (1.0 / n), as pt_resolve_u8 / pt_resolve_u8_counts form it; k = exp2(exposure_ev), computed on the
+ *    host; x_c = fmax(m_c * k, 0.0): NaN and negative values become 0, +inf stays.
+ *  2 Bright part: Y = lum(x); w = (Y > T and Y is finite) ? (Y - T) / Y : 0, T = bloom_threshold; B_c = x_c * w.
+ *  3 Glare, only when s = bloom_strength > 0. For level l = 0 .. L-1 (L = bloom_levels): sigma_l = bloom_sigma * 2^l, r_l = ceil(3 sigma_l),
+ *    k_l[i] = exp(-(i * i) / (2 sigma_l^2)) for i = -r_l .. r_l, divided by their sum taken in that order (host).
+ *    H_l[y][x] = sum_i k_l[i] B[y][x + i], then V_l[y][x] = sum_i k_l[i] H_l[y + i][x]; taps outside the image contribute 0 and the weights
+ *    are NOT renormalised: light scattered past the frame is lost and none comes in. G = sum_l (1 / L) V_l. The order of the sums is the
+ *    implementation's: every term is non-negative, so any order agrees to about (2 r + 1) * 2^-53 relative.
+ *    o_c = (x_c - s * B_c) + s * G_c. With s == 0: o = x, no kernel of this step runs and no scratch for it is allocated.
+ *  4 hdr_out = o: scene-linear, after exposure and glare, before the tone curve.
+ *  5 Tone curve. For tonemap 1-3 first o_c = fmin(o_c, 1e150). oetf(t) = t <= 0.0031308 ? 12.92 t : 1.055 * pow(t, 1 / 2.4) - 0.055 (the
+ *    deterministic pow of pt_detmath.h).
+ *      0 reference: v_c = sqrt(o_c)                          1 srgb: v_c = oetf(fmin(o_c, 1))
+ *      2 reinhard (extended, on luminance): Y = lum(o), sc = (1 + Y / (white * white)) / (1 + Y), v_c = oetf(fmin(o_c * sc, 1))
+ *      3 aces (Narkowicz's fit): t = (o (2.51 o + 0.03)) / (o (2.43 o + 0.59) + 0.14), v_c = oetf(clamp(t, 0, 1))
+ *  6 Quantiser, every mode: rgb8 = (uint8)(clamp(v_c, 0, 0.999) * 256) (NaN -> 0), pt_resolve_u8's.
+ * Returns -1, writing nothing, for a null context or sums, both outputs null, W or H = 0, counts null and total_spp = 0, a host-side count
+ * of 0 (device counts are not inspected), an option outside the range its field states (NaN included; pt_film_opts_check is that test
+ * alone: 0, or -1 and pt_last_error; NULL = the defaults), or, with s > 0, a W or H above 524280 (the convolution's launch grid).
+ * Device memory for the call's duration: with s > 0, 72 B per pixel of scratch (B, the transposed row pass, G: three f64 planes each)
+ * plus the weights (8 B per tap); with s == 0 none. Host buffers add their device copies: 55 B per pixel. */
+typedef struct pt_film_opts {
+    double   exposure_ev;      /* image is scaled by 2^ev first. Default 0. Finite, |ev| <= 100 */
+    uint32_t tonemap;          /* 0 reference (sqrt), 1 srgb, 2 reinhard, 3 aces. Default 0 */
+    double   white;            /* tonemap 2: the luminance that maps to 1. Default 4. Finite, >= 1e-3 */
+    double   bloom_strength;   /* s in [0, 1]; 0 = no glare (default) */
+    double   bloom_threshold;  /* T >= 0, finite: luminance above which light spreads. Default 1 */
+    double   bloom_sigma;      /* sigma_0 in pixels, in [0.5, 64]. Default 2 */
+    uint32_t bloom_levels;     /* L in 1..6, sigma_0 * 2^(L-1) <= 128. Default 5 */
+    uint32_t on_device;        /* sums, counts, hdr_out, rgb8_out are device pointers */
+    void*    stream;           /* hipStream_t; NULL = the context's */
+} pt_film_opts;
+int pt_film_opts_check(const pt_film_opts* /* NULL = defaults */);
+int pt_film_develop(pt_ctx*, uint32_t width, uint32_t height, const double* sums, uint32_t total_spp, const uint32_t* counts /* or NULL */,
+                    const pt_film_opts* /* NULL = defaults */, double* hdr_out /* W*H*3 or NULL */, uint8_t* rgb8_out /* W*H*3 or NULL */);
+/* Float image files (host). pt_save_hdr: Radiance RGBE, readable by pt_load_hdr_rgbf32: the "#?RADIANCE" / "FORMAT=32-bit_rle_rgbe" /
+ * "-Y h +X w" header and flat scanlines; per pixel the shared exponent comes from its largest channel by frexp, mantissas are truncated;
+ * negative, NaN and below-1e-38 values encode as 0. pt_save_pfm: "PF", little-endian (scale -1.0), rows bottom to top, the f32 bits as they
+ * are. Both return -1 for a null pointer, a zero size or a file that cannot be written. */
+int pt_save_hdr(const char* path, uint32_t w, uint32_t h, const float* rgb);
+int pt_save_pfm(const char* path, uint32_t w, uint32_t h, const float* rgb);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

@@ -106,6 +106,30 @@ class DenoiseOpts(C.Structure):
     ]
 
 
+TONEMAPS = {"reference": 0, "srgb": 1, "reinhard": 2, "aces": 3}   # pt_film_opts.tonemap
+
+
+class FilmOpts(C.Structure):
+    """pt_film_opts: exposure, tone curve and glare of the film stage (include/pt_amd.h has the rule). A fresh instance holds the defaults."""
+
+    _fields_ = [
+        ("exposure_ev", C.c_double),
+        ("tonemap", C.c_uint32),
+        ("white", C.c_double),
+        ("bloom_strength", C.c_double),
+        ("bloom_threshold", C.c_double),
+        ("bloom_sigma", C.c_double),
+        ("bloom_levels", C.c_uint32),
+        ("on_device", C.c_uint32),
+        ("stream", C.c_void_p),
+    ]
+
+    def __init__(self, exposure_ev=0.0, tonemap=0, white=4.0, bloom_strength=0.0, bloom_threshold=1.0, bloom_sigma=2.0, bloom_levels=5,
+                 on_device=0, stream=None):
+        super().__init__(exposure_ev, TONEMAPS.get(tonemap, tonemap), white, bloom_strength, bloom_threshold, bloom_sigma, bloom_levels,
+                         on_device, stream)
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -123,6 +147,7 @@ ABI_SYMBOLS = [
     "pt_bootstrap_exchange", "pt_render_multi",
     "pt_render_pixels", "pt_adaptive_schedule", "pt_render_adaptive", "pt_resolve_u8_counts",
     "pt_render_aovs", "pt_denoise",
+    "pt_film_opts_check", "pt_film_develop", "pt_save_hdr", "pt_save_pfm",
     "pt_mat_medium", "pt_scene_set_camera_medium", "pt_scene_camera_medium", "pt_medium_probe",
     "pt_mat_medium_grid",
     "pt_mat_medium_tinted", "pt_mat_glass_set_interior", "pt_mat_glass_interior",
@@ -240,6 +265,11 @@ def _load():
         lib.pt_render_aovs.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(RenderOpts)]
         lib.pt_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                    C.POINTER(DenoiseOpts), C.c_void_p]
+    if hasattr(lib, "pt_film_develop"):            # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_film_develop.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(FilmOpts), C.c_void_p, C.c_void_p]
+        lib.pt_film_opts_check.argtypes = [C.POINTER(FilmOpts)]
+        lib.pt_save_hdr.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.pt_save_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -344,6 +374,32 @@ class Context:
         _check(lib.pt_denoise(self.handle, w, h, sum_a.ctypes.data, n_a, sum_b.ctypes.data, n_b, aov.ctypes.data, n_aov, C.byref(opts),
                               out.ctypes.data), "pt_denoise")
         return out
+
+    def film(self, sums, total_spp: Optional[int] = None, counts=None, *, device_ptrs=None, **opts):
+        """pt_film_develop: (hdr, rgb8) of a frame of sample SUMS: hdr the scene-linear (H, W, 3) f64 image after exposure and glare,
+        rgb8 the (H, W, 3) bytes after the tone curve. `sums`: (H, W, 3) sums of `total_spp` samples, or with `counts` (H, W) of each
+        pixel's own count. `opts`: the fields of FilmOpts (tonemap by name or number); none = pt_resolve_u8's bytes.
+        device_ptrs = (width, height, sums, counts or None, hdr or None, rgb8 or None) as device addresses (e.g. tensor.data_ptr())
+        runs on device buffers instead (on_device): `sums` is then ignored and None is returned."""
+        o = FilmOpts(**opts)
+        if device_ptrs is not None:
+            w, h, d_sums, d_counts, d_hdr, d_rgb = device_ptrs
+            o.on_device = 1
+            _check(lib.pt_film_develop(self.handle, w, h, d_sums, total_spp or 0, d_counts, C.byref(o), d_hdr, d_rgb), "pt_film_develop")
+            return None
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        h, w = sums.shape[0], sums.shape[1]
+        assert sums.shape == (h, w, 3)
+        cnt = None
+        if counts is not None:
+            cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+            assert cnt.size == h * w
+        o.on_device = 0
+        hdr = np.empty((h, w, 3), dtype=np.float64)
+        rgb8 = np.empty((h, w, 3), dtype=np.uint8)
+        _check(lib.pt_film_develop(self.handle, w, h, sums.ctypes.data, total_spp or 0, cnt.ctypes.data if cnt is not None else None, C.byref(o),
+                                   hdr.ctypes.data, rgb8.ctypes.data), "pt_film_develop")
+        return hdr, rgb8
 
 
 def adaptive_schedule(min_spp: int, max_spp: int):
@@ -785,3 +841,20 @@ def save_png(path: str, rgb8: np.ndarray):
     rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
     h, w = rgb8.shape[:2]
     _check(lib.pt_save_png(path.encode(), w, h, rgb8.ctypes.data), "pt_save_png")
+
+
+def _save_f32(fn, what: str, path: str, rgb: np.ndarray):
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = rgb.shape[:2]
+    assert rgb.shape == (h, w, 3)
+    _check(fn(path.encode(), w, h, rgb.ctypes.data), what)
+
+
+def save_hdr(path: str, rgb: np.ndarray):
+    """(H, W, 3) float image -> Radiance RGBE .hdr (pt_save_hdr; load_hdr_rgbf32 reads it back)."""
+    _save_f32(lib.pt_save_hdr, "pt_save_hdr", path, rgb)
+
+
+def save_pfm(path: str, rgb: np.ndarray):
+    """(H, W, 3) float image -> little-endian colour .pfm, the f32 bits as they are (pt_save_pfm)."""
+    _save_f32(lib.pt_save_pfm, "pt_save_pfm", path, rgb)

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -365,4 +366,56 @@ extern "C" int pt_save_png(const char* path, uint32_t w, uint32_t h, const uint8
     size_t n = fwrite(png.data(), 1, png.size(), f);
     fclose(f);
     return n == png.size() ? 0 : set_error("pt_save_png: short write");
+}
+
+// The float writers of the film stage (pt_film_develop's hdr_out narrowed to f32). Radiance RGBE with flat scanlines: the largest
+// mantissa of a non-zero pixel is >= 128, so no scanline can start with the run-length marker (2, 2, w >> 8, w & 255).
+static int write_file(const char* who, const char* path, const std::vector<uint8_t>& bytes) {
+    FILE* f = fopen(path, "wb");
+    if (!f) return set_error(std::string(who) + ": cannot open " + path);
+    const size_t n = fwrite(bytes.data(), 1, bytes.size(), f);
+    return (fclose(f) == 0 && n == bytes.size()) ? 0 : set_error(std::string(who) + ": short write");
+}
+extern "C" int pt_save_hdr(const char* path, uint32_t w, uint32_t h, const float* rgb) {
+    if (!path || !rgb) return set_error("pt_save_hdr: null pointer");
+    if (w == 0 || h == 0) return set_error("pt_save_hdr: width and height must be positive");
+    return guarded("pt_save_hdr", [&]() {
+        const std::string head = "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y " + std::to_string(h) + " +X " + std::to_string(w) + "\n";
+        std::vector<uint8_t> out(head.begin(), head.end());
+        out.reserve(out.size() + (size_t)w * h * 4);
+        for (size_t p = 0; p < (size_t)w * h; ++p) {
+            double c[3], m = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                const double v = (double)rgb[3 * p + k];
+                c[k] = v >= 1e-38 ? v : 0.0;   // negative, NaN, below 1e-38
+                m = std::max(m, c[k]);
+            }
+            uint8_t px[4] = {0, 0, 0, 0};
+            if (m > 0.0) {
+                int e = 0;
+                (void)std::frexp(m, &e);   // m = f * 2^e, f in [0.5, 1); +inf leaves e unspecified
+                if (!(m < std::numeric_limits<double>::infinity()) || e > 127) e = 127;
+                for (int k = 0; k < 3; ++k) px[k] = (uint8_t)std::min(255.0, std::ldexp(c[k], 8 - e));
+                px[3] = (uint8_t)(e + 128);
+            }
+            out.insert(out.end(), px, px + 4);
+        }
+        return write_file("pt_save_hdr", path, out);
+    });
+}
+extern "C" int pt_save_pfm(const char* path, uint32_t w, uint32_t h, const float* rgb) {
+    if (!path || !rgb) return set_error("pt_save_pfm: null pointer");
+    if (w == 0 || h == 0) return set_error("pt_save_pfm: width and height must be positive");
+    return guarded("pt_save_pfm", [&]() {
+        const std::string head = "PF\n" + std::to_string(w) + " " + std::to_string(h) + "\n-1.0\n";
+        std::vector<uint8_t> out(head.begin(), head.end());
+        out.reserve(out.size() + (size_t)w * h * 12);
+        for (uint32_t y = h; y-- > 0;)
+            for (size_t i = 0; i < (size_t)w * 3; ++i) {
+                uint32_t bits;
+                memcpy(&bits, &rgb[(size_t)y * w * 3 + i], 4);
+                for (int b = 0; b < 4; ++b) out.push_back((uint8_t)(bits >> (8 * b)));
+            }
+        return write_file("pt_save_pfm", path, out);
+    });
 }

@@ -68,5 +68,12 @@ bool launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_b
 // pt_denoise.hip: the a-trous denoiser (see there). Device buffers; tmp: 12 doubles per pixel of scratch
 void launch_denoise(uint32_t width, uint32_t height, const double* sum_a, double n_a, const double* sum_b, double n_b, const double* aov, double n_aov,
                     uint32_t iterations, double sigma_l, double sigma_z, double* tmp, double* out, hipStream_t st);
+// pt_film.hip: the film stage (see there). Device buffers. bright / glare: 3 planes of n_pixels doubles; counts: per-pixel sample counts or
+// null (then scale = 1 / total_spp); launch_film_conv: one transposing pass (in: 3 planes rows x cols, out: 3 planes cols x rows, taps: 2 r + 1
+// weights), false when the radius needs more LDS than a CU has; launch_film_develop: glare null = no glare, hdr or rgb8 may be null
+void launch_film_prepare(const double* sums, uint32_t n_pixels, double scale, const uint32_t* counts, double k, double thr, double* bright, hipStream_t st);
+bool launch_film_conv(const double* in, double* out, uint32_t rows, uint32_t cols, uint32_t r, const double* taps, double scale, bool accumulate, hipStream_t st);
+void launch_film_develop(const double* sums, uint32_t n_pixels, double scale, const uint32_t* counts, double k, double thr, double s, const double* glare,
+                         uint32_t tonemap, double white, double* hdr, uint8_t* rgb8, hipStream_t st);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);
 }  // namespace pt

@@ -10,7 +10,11 @@
 // unbounded grid-density camera medium of extinction SCALE * V),
 // --interior DENSITY[,R,G,B[,G[,AR,AG,AB]]] (every glass material of the scene script is filled with a homogeneous medium of that density,
 // albedo, g and absorption per channel; density 0 with an absorption > 0 is a clear tinted body),
-// --dispersion ABBE (every glass material of the scene script disperses: its ior is n_d, ABBE > 0 its Abbe number V_d).
+// --dispersion ABBE (every glass material of the scene script disperses: its ior is n_d, ABBE > 0 its Abbe number V_d),
+// --exposure EV, --tonemap reference|srgb|reinhard|aces, --white W, --bloom S[,THRESHOLD[,SIGMA[,LEVELS]]] (the film stage between the
+// accumulator and the PNG: the image scaled by 2^EV, glare of strength S around pixels brighter than THRESHOLD, a tone curve; pt_film_develop,
+// DESIGN.md §17; without them the PNG is the reference's) and --out-hdr FILE (the scene-linear image after exposure and glare as f32:
+// .pfm, or Radiance .hdr for any other extension).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -73,6 +77,32 @@ static bool parse_interior(const std::string& v, double out[8]) {
     return ok && out[0] + std::max(out[5], std::max(out[6], out[7])) > 0.0;
 }
 
+// S[,THRESHOLD[,SIGMA[,LEVELS]]] of --bloom: one to four numbers, each parsed whole (LEVELS a whole number); the ranges are pt_film_opts_check's
+static bool parse_bloom(const std::string& v, Film& film) {
+    std::vector<double> f;
+    for (size_t pos = 0; pos <= v.size();) {
+        const size_t comma = std::min(v.find(',', pos), v.size());
+        const std::string tok = v.substr(pos, comma - pos);
+        char* end = nullptr;
+        const double x = strtod(tok.c_str(), &end);
+        if (tok.empty() || end != tok.c_str() + tok.size()) return false;
+        f.push_back(x);
+        pos = comma + 1;
+    }
+    if (f.empty() || f.size() > 4) return false;
+    if (f.size() > 3 && !(f[3] >= 0.0 && f[3] <= 1e6 && f[3] == std::floor(f[3]))) return false;
+    film.bloom_strength = f[0];
+    if (f.size() > 1) film.bloom_threshold = f[1];
+    if (f.size() > 2) film.bloom_sigma = f[2];
+    if (f.size() > 3) film.bloom_levels = (uint32_t)f[3];
+    return true;
+}
+// a whole-string number, any value: the film options' ranges are checked once, by pt_film_opts_check
+static bool parse_number(const std::string& v, double& out) {
+    char* end = nullptr;
+    out = strtod(v.c_str(), &end);
+    return !v.empty() && end == v.c_str() + v.size();
+}
 // X,Y,Z,RADIUS[,R,G,B] of --mesh-light: four or seven numbers, each parsed whole; radius > 0, emission >= 0
 static bool parse_mesh_light(const std::string& v, double out[7]) {
     std::vector<double> x;
@@ -142,6 +172,7 @@ int main(int argc, char** argv) {
     bool mesh_light = false;
     double mesh_light_v[7] = {0.0, 0.0, 0.0, 0.0, 10.0, 10.0, 10.0};   // centre x y z, radius, emission r g b
     long aov_spp = 16;
+    Film film;   // --exposure, --tonemap, --white, --bloom, --out-hdr
     uint64_t seed = 1;
     std::string out, assets = "assets";
     for (int i = 1; i < argc; ++i) {
@@ -203,12 +234,33 @@ int main(int argc, char** argv) {
             if (!parse_mesh_light(next(), mesh_light_v)) { std::cerr << "--mesh-light must be X,Y,Z,RADIUS[,R,G,B]: radius > 0, emission >= 0\n"; return 2; }
             mesh_light = true;
         }
+        else if (a == "--exposure") {
+            if (!parse_number(next(), film.exposure_ev)) { std::cerr << "--exposure must be a number (EV)\n"; return 2; }
+        }
+        else if (a == "--tonemap") {
+            const std::string v = next();
+            if (v == "reference") film.tonemap = 0;
+            else if (v == "srgb") film.tonemap = 1;
+            else if (v == "reinhard") film.tonemap = 2;
+            else if (v == "aces") film.tonemap = 3;
+            else { std::cerr << "--tonemap must be reference, srgb, reinhard or aces\n"; return 2; }
+        }
+        else if (a == "--white") {
+            if (!parse_number(next(), film.white)) { std::cerr << "--white must be a number\n"; return 2; }
+        }
+        else if (a == "--bloom") {
+            if (!parse_bloom(next(), film)) { std::cerr << "--bloom must be S[,THRESHOLD[,SIGMA[,LEVELS]]]: numbers, LEVELS a whole one\n"; return 2; }
+        }
+        else if (a == "--out-hdr") film.hdr_filename = next();
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
+                         "  --exposure, --tonemap, --white, --bloom: the film stage between the accumulator and the PNG: the image is scaled by 2^EV, light above the\n"
+                         "           luminance THRESHOLD (default 1) spreads as glare of strength S (LEVELS Gaussians of SIGMA, 2 SIGMA, ... pixels; defaults 5 and 2),\n"
+                         "           then the tone curve (reinhard maps the luminance W, default 4, to white). --out-hdr: the linear image after exposure and glare, f32\n"
                          "  --dispersion ABBE: every glass of the scene disperses light; its ior is read as n_d (587.56 nm), ABBE = V_d = (n_d - 1) / (n_F - n_C)\n"
                          "           (crown glass about 60, flint 30, diamond 55; smaller = more colour). Not with --env-sampling, --fog, --smoke, --interior,\n"
                          "           --light-sampling exact or --mesh-light\n"
@@ -238,6 +290,13 @@ int main(int argc, char** argv) {
     if (dispersion > 0.0 && (env_sampling > 0.0 || fog || smoke || interior || light_sampling == 1)) {
         std::cerr << "--dispersion cannot be combined with --env-sampling, --fog, --smoke, --interior, --light-sampling exact or --mesh-light\n";
         return 2;
+    }
+    {   // the film options' ranges: the library's own test, before anything is rendered
+        const pt_film_opts fo = film.to_c();
+        if (pt_film_opts_check(&fo) != 0) {
+            std::cerr << "--exposure / --tonemap / --white / --bloom: " << pt_last_error() << "\n";
+            return 2;
+        }
     }
     if (scene < 1 || scene > 7) return 0;   // `_ => ()` main.rs:643
     pt_ctx* ctx = nullptr;
@@ -284,6 +343,7 @@ int main(int argc, char** argv) {
                                                                    Vec3{interior_v[5], interior_v[6], interior_v[7]});
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();
+        setup.camera.film = film;
         std::cerr << "rendering production\n";   // camera.rs:101
         if (use_adaptive) {
             const uint32_t m = (uint32_t)std::max(2L, std::min(min_spp, (long)s));

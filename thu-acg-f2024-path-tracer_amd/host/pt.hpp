@@ -525,6 +525,22 @@ struct EnvironmentType {
     static EnvironmentType Color(Vec3 c) { EnvironmentType e; e.color = c; return e; }
     static EnvironmentType Map(std::shared_ptr<ImageTexture> t) { EnvironmentType e; e.is_map = true; e.map = t; return e; }
 };
+// not in the reference: the film stage between the accumulator and the files (pt_film_develop; include/pt_amd.h has the rule). The default
+// is the reference's mean / sqrt gamma / quantise (camera.rs:109-130), so a default Film writes the PNG bytes written before it existed.
+struct Film {
+    double exposure_ev = 0.0;
+    uint32_t tonemap = 0;   // 0 reference (sqrt), 1 srgb, 2 reinhard, 3 aces
+    double white = 4.0, bloom_strength = 0.0, bloom_threshold = 1.0, bloom_sigma = 2.0;
+    uint32_t bloom_levels = 5;
+    std::string hdr_filename;   // if set: the scene-linear image (after exposure and glare), narrowed to f32, as .pfm or (any other extension) Radiance .hdr
+    pt_film_opts to_c() const {
+        pt_film_opts o;
+        std::memset(&o, 0, sizeof o);
+        o.exposure_ev = exposure_ev; o.tonemap = tonemap; o.white = white;
+        o.bloom_strength = bloom_strength; o.bloom_threshold = bloom_threshold; o.bloom_sigma = bloom_sigma; o.bloom_levels = bloom_levels;
+        return o;
+    }
+};
 struct Camera {
     double aspect_ratio = 0;
     size_t image_width = 0, samples_per_pixel = 0, max_depth = 0;
@@ -534,6 +550,7 @@ struct Camera {
     EnvironmentType environment = EnvironmentType::Color(Vec3::ZERO);
     size_t image_height = 0;
     double derived[18] = {0};   // forward,right,up,pixel00,pixel_du,pixel_dv
+    Film film;                  // not in the reference (after its fields, so that aggregate initialisation in its order still holds)
     static Camera new_() { return Camera(); }
 
     pt_camera to_c(const World* world) const {
@@ -568,6 +585,26 @@ struct Camera {
         if (pt_camera_init(&c, derived, &h) != 0) panic("Camera::init");
         image_height = h;
     }
+    // camera.rs:109-130 generalised: sums (of total_spp samples, or of counts[p] each) through the film stage into the PNG and, if asked
+    // for, the float file
+    void develop(World& world, const std::string& filename, const std::vector<double>& sums, uint32_t total_spp, const uint32_t* counts, const char* who) const {
+        const size_t n = image_width * image_height;
+        const pt_film_opts fo = film.to_c();
+        std::vector<uint8_t> rgb(n * 3);
+        std::vector<double> hdr(film.hdr_filename.empty() ? 0 : n * 3);
+        if (pt_film_develop(pt_scene_ctx(world.scene), (uint32_t)image_width, (uint32_t)image_height, sums.data(), total_spp, counts, &fo,
+                            hdr.empty() ? nullptr : hdr.data(), rgb.data()) != 0)
+            panic(std::string(who) + ": " + pt_last_error());
+        if (pt_save_png(filename.c_str(), (uint32_t)image_width, (uint32_t)image_height, rgb.data()) != 0)
+            std::fprintf(stderr, "Failed to save image %s\n", pt_last_error());
+        if (!hdr.empty()) {
+            const std::vector<float> f(hdr.begin(), hdr.end());
+            const std::string& name = film.hdr_filename;
+            const bool pfm = name.size() >= 4 && name.compare(name.size() - 4, 4, ".pfm") == 0;
+            if ((pfm ? pt_save_pfm : pt_save_hdr)(name.c_str(), (uint32_t)image_width, (uint32_t)image_height, f.data()) != 0)
+                std::fprintf(stderr, "Failed to save image %s\n", pt_last_error());
+        }
+    }
     // camera.rs:79-126: render, gamma, quantise, save PNG, print the wall-clock seconds
     void render(World& world, const std::string& filename, uint64_t seed = 1, pt_render_stats* stats_out = nullptr) const {
         auto start = std::chrono::steady_clock::now();
@@ -576,10 +613,7 @@ struct Camera {
         std::vector<double> accum(n * 3, 0.0);
         pt_render_stats st;
         if (pt_render(world.scene, &c, seed, 0, (uint32_t)samples_per_pixel, accum.data(), nullptr, &st) != 0) panic("Camera::render");
-        std::vector<uint8_t> rgb(n * 3);
-        if (pt_resolve_u8(pt_scene_ctx(world.scene), accum.data(), (uint32_t)n, (uint32_t)samples_per_pixel, rgb.data()) != 0) panic("Camera::render");
-        if (pt_save_png(filename.c_str(), (uint32_t)image_width, (uint32_t)image_height, rgb.data()) != 0)
-            std::fprintf(stderr, "Failed to save image %s\n", pt_last_error());
+        develop(world, filename, accum, (uint32_t)samples_per_pixel, nullptr, "Camera::render");
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         std::fprintf(stderr, "[camera.rs:125] start.elapsed().as_secs_f64() = %.6f (render kernel time %.3f s, %.2f Msamples/s)\n", secs,
                      st.ms_total * 1e-3, (double)st.samples / (st.ms_total * 1e-3) * 1e-6);
@@ -600,10 +634,7 @@ struct Camera {
         ao.threshold = threshold;
         pt_render_stats st;
         if (pt_render_adaptive(world.scene, &c, seed, &ao, accum.data(), counts.data(), &st) != 0) panic(std::string("Camera::render_adaptive: ") + pt_last_error());
-        std::vector<uint8_t> rgb(n * 3);
-        if (pt_resolve_u8_counts(pt_scene_ctx(world.scene), accum.data(), (uint32_t)n, counts.data(), rgb.data()) != 0) panic("Camera::render_adaptive");
-        if (pt_save_png(filename.c_str(), (uint32_t)image_width, (uint32_t)image_height, rgb.data()) != 0)
-            std::fprintf(stderr, "Failed to save image %s\n", pt_last_error());
+        develop(world, filename, accum, 0, counts.data(), "Camera::render_adaptive");
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         std::fprintf(stderr, "adaptive: threshold %g, min spp %u, max spp %u: mean spp %.2f (%llu samples) in %.6f s\n", threshold, min_spp,
                      (uint32_t)samples_per_pixel, (double)st.samples / (double)n, (unsigned long long)st.samples, secs);
@@ -625,10 +656,7 @@ struct Camera {
         if (pt_denoise(ctx, (uint32_t)image_width, (uint32_t)image_height, sum_a.data(), half, sum_b.data(), s - half, aov.data(), n_aov, nullptr,
                        out.data()) != 0)
             panic(std::string("Camera::render_denoised: ") + pt_last_error());
-        std::vector<uint8_t> rgb(n * 3);
-        if (pt_resolve_u8(ctx, out.data(), (uint32_t)n, 1, rgb.data()) != 0) panic("Camera::render_denoised");
-        if (pt_save_png(filename.c_str(), (uint32_t)image_width, (uint32_t)image_height, rgb.data()) != 0)
-            std::fprintf(stderr, "Failed to save image %s\n", pt_last_error());
+        develop(world, filename, out, 1, nullptr, "Camera::render_denoised");   // out holds means: n = 1
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         std::fprintf(stderr, "denoise: %u spp as %u + %u, aov %u spp: %.6f s (render kernel time %.3f s)\n", s, half, s - half, n_aov, secs,
                      (sa.ms_total + sb.ms_total) * 1e-3);
