@@ -171,6 +171,36 @@ int pt_scene_sampler(pt_scene*);
  *   lights.pdf averages the entries' pdfs over the list as with kind 0. */
 int pt_scene_set_light_sampling(pt_scene*, int kind);
 int pt_scene_light_sampling(pt_scene*);
+/* The projection: how a (pixel, sample) becomes a camera ray. kind 0 (default) = perspective, the reference's pinhole / thin-lens camera
+ * (camera.rs:153-168): every entry point is then the code it was before this setting existed, bit for bit. 1 = orthographic, 2 = fisheye
+ * (equidistant), 3 = panorama (equirectangular lat-long); any other kind returns -1 and leaves the setting. Changing it needs no
+ * pt_world_build. In effect for pt_render, pt_render_pixels, pt_render_adaptive, pt_render_multi and pt_render_aovs (and so for the
+ * denoiser's features), in every shading mode, under both samplers, in static and dynamic pools. pt_camera and pt_camera_init do not
+ * change. The rule. forward, right, up, pixel00, pixel_du, pixel_dv, center are pt_camera_init's; W, H the image size; F = focal_length;
+ * dof_right, dof_up = right, up times the lens radius tan((defocus_angle / 2) * (PI / 180)) * F. f64, one IEEE rounding per written
+ * operation; (sin, cos) are the deterministic ones of the kernels (pt_math_probe which 3 / 4).
+ *   Every kind makes exactly the draws kind 0 makes, in its order: the two-value pixel draw (u0, u1): radius = sqrt(u0), angle =
+ *   u1 * 2 * PI, bx = (radius * cos(angle)) * blur_strength, by = (radius * sin(angle)) * blur_strength; the two-value lens draw, the
+ *   same way without the factor: (px, py), made and not used when the lens radius is zero; the time draw (made by index only when
+ *   nothing in the scene moves). So draw indices, the Sobol sampler's pair alignment and dispersion's wavelength stream do not move.
+ *   fy = row + bx, fx = col + by: continuous pixel coordinates, integer at a pixel centre (bx belongs to rows, as in the reference).
+ *   1 orthographic: S = pixel00 + pixel_dv * fy + pixel_du * fx (kind 0's sample location); O = S + forward * F, a point of the plane
+ *     through center; with a non-zero lens O = (O + dof_right * px) + dof_up * py; ray = Ray::new(O, S - O, time). The camera frames the
+ *     rectangle kind 0 sees on its focal plane: an object at distance F keeps its size, the focal plane is sharp, defocus works as in kind 0.
+ *   2 fisheye: vfov is the full angle across the image HEIGHT. xn = (2 * (fx + 0.5) - W) / H, yn = (H - 2 * (fy + 0.5)) / H,
+ *     rho = sqrt(xn * xn + yn * yn); theta = fmin(rho * th, PI), th = (vfov * (PI / 180)) / 2 formed on the host; a = rho > 0 ?
+ *     sin(theta) / rho : 0; w = (right * (xn * a) + up * (yn * a)) - forward * cos(theta); ray = Ray::new(center, w, time).
+ *   3 panorama, in WORLD axes (look_at, vup and vfov must be valid for pt_camera_init and are otherwise not read; only look_from
+ *     matters): phi = -PI + ((2 * PI) * (fx + 0.5)) / W; theta = fmin(fmax((PI * (fy + 0.5)) / H, 0), PI);
+ *     w = (sin(theta) * cos(phi), cos(theta), sin(theta) * sin(phi)); ray = Ray::new(center, w, time). This is the direction
+ *     convention of the environment lookup (camera.rs:140-151) and of pt_scene_set_env_sampling's table: pixel (i, j) looks along the
+ *     centre of texel (i, j) of an environment map of the same size, so the image IS an environment map of the scene around look_from,
+ *     at any aspect ratio.
+ * A render (and pt_render_aovs, pt_camera_probe) returns -1, writing nothing: kinds 2 and 3 with defocus_angle != 0 (a lens disc has no
+ * natural plane there); kind 2 when vfov is not finite or not > 0, or when sqrt((W / H)^2 + 1) * th > PI: the image circle must cover
+ * the frame, so that no sample is without a ray. Jitter beyond the frame is covered by the clamps. */
+int pt_scene_set_projection(pt_scene*, int kind);
+int pt_scene_projection(pt_scene*);
 /* ---- materials: src/bsdf/, src/material.rs ---------------------------------------------- */
 int pt_mat_diffuse(pt_scene*, int color_tex, int normal_map_tex);       /* DiffuseBRDF::{new,from_rgb,from_textures} diffuse.rs:21-47; -1 = no map */
 int pt_mat_metal(pt_scene*, int color_tex, int rough_tex);              /* MetalBRDF::new metal.rs:23-35 */
@@ -584,6 +614,10 @@ int pt_light_probe(pt_scene*, int which, const double* in, uint32_t n, double* o
  * n x (u, lambda, j, W_r, W_g, W_b, n(lambda)) of a path of `seed`; which = 1: in = n wavelengths in nm, out = n values n(lambda).
  * The world need not be built. */
 int pt_dispersion_probe(pt_scene*, int glass_mat, int which, uint64_t seed, const double* in, uint32_t n, double* out);
+/* generate_ray as k_init calls it, under the scene's projection (pt_scene_set_projection's rule) and sampler: in = n x (pixel, sample) as
+ * doubles (pixel < W * H, sample a 32-bit unsigned integer, else -1); out = n x (origin.xyz, direction.xyz, time, draws consumed) of the
+ * sample's stream of `seed` from draw 0. The camera's refusals are the renders'. The world need not be built (time is then drawn). */
+int pt_camera_probe(pt_scene*, const pt_camera*, uint64_t seed, const double* in, uint32_t n, double* out);
 
 #ifdef __cplusplus
 }

@@ -153,6 +153,7 @@ ABI_SYMBOLS = [
     "pt_mat_medium_tinted", "pt_mat_glass_set_interior", "pt_mat_glass_interior",
     "pt_scene_set_light_sampling", "pt_scene_light_sampling", "pt_light_probe",
     "pt_mat_glass_set_dispersion", "pt_mat_glass_dispersion", "pt_dispersion_probe",
+    "pt_scene_set_projection", "pt_scene_projection", "pt_camera_probe",
 ]
 
 
@@ -209,6 +210,10 @@ def _load():
         lib.pt_mat_glass_dispersion.argtypes = [C.c_void_p, C.c_int]
         lib.pt_mat_glass_dispersion.restype = C.c_double
         lib.pt_dispersion_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "pt_scene_set_projection"):   # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_scene_set_projection.argtypes = [C.c_void_p, C.c_int]
+        lib.pt_scene_projection.argtypes = [C.c_void_p]
+        lib.pt_camera_probe.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -292,6 +297,7 @@ lib = _load()
 
 SAMPLERS = {"independent": 0, "sobol": 1}   # pt_scene_set_sampler's kinds
 LIGHT_SAMPLING = {"reference": 0, "exact": 1}   # pt_scene_set_light_sampling's kinds
+PROJECTIONS = {"perspective": 0, "orthographic": 1, "fisheye": 2, "panorama": 3}   # pt_scene_set_projection's kinds
 
 
 def _check(rc, what="pt call"):
@@ -524,6 +530,27 @@ class Scene:
         arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, 4 if which == 0 else 7))
         out = np.empty((len(arr), 6) if which == 0 else (len(arr),), dtype=np.float64)
         _check(lib.pt_light_probe(self.handle, which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_light_probe")
+        return out
+
+    def set_projection(self, kind):
+        """How a pixel becomes a camera ray: "perspective" (0, the default: the reference's pinhole / thin-lens camera), "orthographic"
+        (1: parallel rays framing the perspective camera's focal plane), "fisheye" (2: equidistant, vfov across the image height) or
+        "panorama" (3: an equirectangular image of everything around look_from, usable as an environment map; the rule is in
+        include/pt_amd.h). Needs no world_build."""
+        kind = PROJECTIONS.get(kind, kind)
+        if isinstance(kind, bool) or not isinstance(kind, int):
+            raise PtError(f"set_projection: unknown projection {kind!r}")
+        return _check(lib.pt_scene_set_projection(self.handle, kind), "set_projection")
+
+    def projection(self) -> int:
+        return lib.pt_scene_projection(self.handle)
+
+    def camera_probe(self, cam: "Camera", seed: int, pixels_samples: np.ndarray) -> np.ndarray:
+        """The camera rays the kernels generate, under the scene's projection and sampler: pixels_samples = (n, 2) (pixel, sample) ->
+        (n, 8) {origin.xyz, direction.xyz, time, draws consumed} of the sample's stream of `seed`. The world need not be built."""
+        arr = np.ascontiguousarray(pixels_samples, dtype=np.float64).reshape(-1, 2)
+        out = np.empty((len(arr), 8), dtype=np.float64)
+        _check(lib.pt_camera_probe(self.handle, C.byref(cam), int(seed), arr.ctypes.data, len(arr), out.ctypes.data), "pt_camera_probe")
         return out
 
     def mat_medium(self, density: float, albedo=(1.0, 1.0, 1.0), g: float = 0.0):

@@ -376,6 +376,30 @@ PT_DEV void random_offsets(R& rng, double& ox, double& oy) {
     ox = radius * cs;
     oy = radius * sn;
 }
+// The directions of the fisheye and panorama projections (pt_scene_set_projection kinds 2 and 3; the rule is in include/pt_amd.h,
+// DESIGN.md §18) for the continuous pixel coordinates fy = row + bx, fx = col + by.
+// z: a zero the compiler cannot see through. The CamD fields that only kinds 1-3 read are loaded at field[z]: a plain load of a kernel
+// argument is hoisted to the kernel's entry, and 30 more SGPRs live across every call of K1 / K3 cost the perspective camera's kernels
+// registers and scratch; a load whose address depends on an instruction of the cold branch stays in it.
+PT_DEV V3 projected_direction(const CamD& cam, double fy, double fx) {
+    uint32_t z;
+    asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+    const double W = (&cam.fw)[z], H = (&cam.fh)[z];
+    if (cam.projection == PROJ_FISHEYE) {
+        const double xn = (2.0 * (fx + 0.5) - W) / H, yn = (H - 2.0 * (fy + 0.5)) / H;
+        const double rho = sqrt((xn * xn) + (yn * yn));
+        const SinCos t = dev_sincos(fmin(rho * (&cam.th)[z], D_PI));
+        const double a = rho > 0.0 ? t.s / rho : 0.0;
+        return (ld3(cam.right + z) * (xn * a)) + (ld3(cam.up + z) * (yn * a)) - (ld3(cam.forward + z) * t.c);
+    }
+    // PROJ_PANORAMA: sample_environment's convention, in world axes
+    const double phi = -D_PI + ((2.0 * D_PI) * (fx + 0.5)) / W;
+    const double theta = fmin(fmax((D_PI * (fy + 0.5)) / H, 0.0), D_PI);
+    const SinCos t = dev_sincos(theta), p = dev_sincos(phi);
+    return V3{t.s * p.c, t.c, t.s * p.s};
+}
+// The branches on cam.projection are wave-uniform (cam is a kernel argument) and not taken by the perspective camera (kind 0), whose
+// arithmetic below is the reference's; every kind makes kind 0's draws in kind 0's order.
 template <class R>
 PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, R& rng) {
     double bx, by;
@@ -383,7 +407,14 @@ PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, R& rng) {
     bx = bx * cam.blur_strength;
     by = by * cam.blur_strength;
     V3 sample_location = ld3(cam.pixel00) + (ld3(cam.pixel_dv) * ((double)row + bx)) + (ld3(cam.pixel_du) * ((double)col + by));
+    if (cam.projection >= PROJ_FISHEYE)   // fisheye, panorama: the ray's direction w takes the sample location's place
+        sample_location = projected_direction(cam, (double)row + bx, (double)col + by);
     V3 origin = ld3(cam.center);
+    if (cam.projection == PROJ_ORTHOGRAPHIC) {   // O = S + forward * F, in the plane through center (z: see projected_direction)
+        uint32_t z;
+        asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+        origin = sample_location + (ld3(cam.forward + z) * (&cam.focal_length)[z]);
+    }
     if (cam.lens_zero) {
         rng_skip2(rng);   // the two lens draws are made all the same (camera.rs:160); their products with a zero radius add nothing
     } else {
@@ -394,7 +425,7 @@ PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, R& rng) {
     double time = 0.0;
     if (cam.motionless) ++rng.draw;   // drawn all the same (camera.rs:165); no result depends on it (CamD::motionless), so its Philox block is not computed
     else time = rng_f64(rng);
-    return make_ray(origin, sample_location - origin, time);
+    return make_ray(origin, cam.projection >= PROJ_FISHEYE ? sample_location : sample_location - origin, time);
 }
 // camera.rs:140-151
 PT_DEV V3 sample_environment(const SceneD& sc, const CamD& cam, V3 d) {

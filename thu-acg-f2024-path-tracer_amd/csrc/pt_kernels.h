@@ -75,5 +75,7 @@ void launch_film_prepare(const double* sums, uint32_t n_pixels, double scale, co
 bool launch_film_conv(const double* in, double* out, uint32_t rows, uint32_t cols, uint32_t r, const double* taps, double scale, bool accumulate, hipStream_t st);
 void launch_film_develop(const double* sums, uint32_t n_pixels, double scale, const uint32_t* counts, double k, double thr, double s, const double* glare,
                          uint32_t tonemap, double white, double* hdr, uint8_t* rgb8, hipStream_t st);
+// pt_camera_probe: generate_ray as k_init calls it under sampler `kind` (n x (pixel, sample) -> n x (origin.xyz, direction.xyz, time, draws consumed)); in / out: device
+void launch_camera_probe(const CamD& cam, int kind, uint64_t seed, const double* in, uint32_t n, double* out, hipStream_t st);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);
 }  // namespace pt

@@ -190,6 +190,21 @@ static int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
         if (cam->env_tex < 0 || (size_t)cam->env_tex >= s->tex.size() || (s->tex[cam->env_tex].d.kind != TEX_IMAGE && s->tex[cam->env_tex].d.kind != TEX_IMAGE_F32))
             return set_error("pt_render: env_tex must be an image texture of this scene");
     }
+    // the projection (pt_scene_set_projection's rule): what kinds 1-3 read on top of the above, and their refusals
+    dc.projection = (uint32_t)s->projection;
+    dc.th = (cam->vfov * (PI / 180.0)) / 2.0;
+    dc.focal_length = cam->focal_length;
+    dc.fw = (double)dc.width;
+    dc.fh = (double)dc.height;
+    st3(dc.forward, cd.forward); st3(dc.right, cd.right); st3(dc.up, cd.up);
+    if ((dc.projection == PROJ_FISHEYE || dc.projection == PROJ_PANORAMA) && cam->defocus_angle != 0.0)
+        return set_error("camera: the fisheye and panorama projections have no lens (defocus_angle must be 0)");
+    if (dc.projection == PROJ_FISHEYE) {
+        if (!std::isfinite(cam->vfov) || !(cam->vfov > 0.0)) return set_error("camera: the fisheye projection needs a finite vfov > 0");
+        const double a = (double)dc.width / (double)dc.height;
+        if (std::sqrt(a * a + 1.0) * dc.th > PI)
+            return set_error("camera: the fisheye image circle must cover the frame: sqrt((W/H)^2 + 1) * vfov / 2 may not exceed 180 degrees (lower vfov)");
+    }
     return 0;
 }
 
@@ -1169,6 +1184,36 @@ extern "C" int pt_dispersion_probe(pt_scene* s, int glass_mat, int which, uint64
         launch_dispersion_probe(s->sampler, which, seed, m.ior, m.p[1], m.p[2], d_w, d_i, n, d_o, ctx->stream);
         ok = hip_ok(hipGetLastError(), "kernel launch") &&
              hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
+             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
+    }
+    if (d_i) (void)hipFree(d_i);
+    if (d_o) (void)hipFree(d_o);
+    return ok ? 0 : -1;
+}
+
+extern "C" int pt_camera_probe(pt_scene* s, const pt_camera* cam, uint64_t seed, const double* in, uint32_t n, double* out) {
+    if (!s || !s->ctx) return set_error("pt_camera_probe: null scene");
+    if (!cam) return set_error("pt_camera_probe: null camera");
+    CamD dc;
+    if (make_camd(s, cam, dc) != 0) return -1;
+    const uint64_t n_pixels = (uint64_t)dc.width * dc.height;
+    if (n_pixels > 0x7FFFFFFFull) return set_error("pt_camera_probe: bad image size");
+    if (n == 0) return 0;
+    if (!in || !out) return set_error("pt_camera_probe: null buffer");
+    for (uint32_t i = 0; i < n; ++i) {
+        const double p = in[2 * (size_t)i], sm = in[2 * (size_t)i + 1];
+        if (!(p >= 0.0 && p < (double)n_pixels) || p != std::floor(p) || !(sm >= 0.0 && sm <= 4294967295.0) || sm != std::floor(sm))
+            return set_error("pt_camera_probe: takes (pixel, sample) pairs: pixel < width * height, sample a 32-bit unsigned integer");
+    }
+    pt_ctx* ctx = s->ctx;
+    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
+    double *d_i = nullptr, *d_o = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&d_i, (size_t)n * 2 * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, (size_t)n * 8 * sizeof(double)), "hipMalloc") &&
+              hip_ok(hipMemcpyAsync(d_i, in, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
+    if (ok) {
+        launch_camera_probe(dc, s->sampler, seed, d_i, n, d_o, ctx->stream);
+        ok = hip_ok(hipGetLastError(), "kernel launch") &&
+             hip_ok(hipMemcpyAsync(out, d_o, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
              hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
     }
     if (d_i) (void)hipFree(d_i);

@@ -131,6 +131,13 @@ extern "C" int pt_scene_set_light_sampling(pt_scene* s, int kind) {
     return 0;
 }
 extern "C" int pt_scene_light_sampling(pt_scene* s) { return s ? s->light_sampling : 0; }
+extern "C" int pt_scene_set_projection(pt_scene* s, int kind) {
+    if (!s) return set_error("pt_scene_set_projection: null scene");
+    if (kind < 0 || kind > 3) return set_error("pt_scene_set_projection: kind must be 0 (perspective), 1 (orthographic), 2 (fisheye) or 3 (panorama)");
+    s->projection = kind;
+    return 0;
+}
+extern "C" int pt_scene_projection(pt_scene* s) { return s ? s->projection : 0; }
 extern "C" int pt_register_image(pt_scene* s, const char* name, uint32_t w, uint32_t h, const uint8_t* rgb) {
     int t = pt_tex_image_rgb8(s, w, h, rgb);
     if (t < 0) return -1;

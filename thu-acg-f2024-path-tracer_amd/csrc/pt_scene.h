@@ -126,6 +126,7 @@ struct pt_scene {
     bool world_has_dispersion = false;
     bool dispersion_on() const { return world_has_dispersion; }   // "in effect": the kernels' DSP forms run
     double* disp_w = nullptr;
+    int projection = 0;            // pt_scene_set_projection: 0 perspective, 1 orthographic, 2 fisheye, 3 panorama (CamD::projection)
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;
     pt::CountersD* h_counters = nullptr;   // pinned

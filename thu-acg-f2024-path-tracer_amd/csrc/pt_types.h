@@ -193,7 +193,15 @@ struct CamD {
     uint32_t lens_zero;      // defocus radius 0 (dof_right = dof_up = 0, no -0.0 in center): the lens point is `center` exactly
     uint32_t motionless;     // no moving sphere in the scene: Ray::time is drawn (camera.rs:165) but its value is never used
     uint32_t medium;         // the medium camera rays start in: material index + 1, 0 = none (pt_scene_set_camera_medium; read by the MED forms only)
+    // the projection (pt_scene_set_projection; the rule is in include/pt_amd.h). Everything below is read by kinds 1-3 only:
+    // kind 0 (PROJ_PERSPECTIVE) reads `projection` and then what it read before the setting existed (generate_ray, pt_dev_geom.h).
+    uint32_t projection;     // PROJ_*
+    double th;               // fisheye: half of vfov in radians, (vfov * (PI / 180)) / 2, formed on the host
+    double focal_length;
+    double fw, fh;           // width and height as doubles (converted on the host: see generate_ray)
+    double forward[3], right[3], up[3];   // Camera::init's basis (pt_camera_init)
 };
+enum Projection : uint32_t { PROJ_PERSPECTIVE = 0, PROJ_ORTHOGRAPHIC = 1, PROJ_FISHEYE = 2, PROJ_PANORAMA = 3 };
 
 // Environment importance sampling (pt_scene_set_env_sampling): the f64 tables of the camera's environment map,
 // built by pt_envmap.hip, and the mixture weight. A separate kernel argument of k_shade's ENV forms and of k_env_probe — CamD and

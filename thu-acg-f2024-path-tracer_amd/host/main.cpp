@@ -168,6 +168,7 @@ int main(int argc, char** argv) {
     bool interior = false;
     double interior_v[8] = {0.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};   // density, albedo r g b, g, absorption r g b
     double dispersion = 0.0;   // the Abbe number of --dispersion, 0: not given
+    int projection = 0;        // --projection: pt_scene_set_projection's kind
     int light_sampling = -1;   // -1: not given (--mesh-light then implies exact)
     bool mesh_light = false;
     double mesh_light_v[7] = {0.0, 0.0, 0.0, 0.0, 10.0, 10.0, 10.0};   // centre x y z, radius, emission r g b
@@ -230,6 +231,14 @@ int main(int argc, char** argv) {
             else if (v == "exact") light_sampling = 1;
             else { std::cerr << "--light-sampling must be reference or exact\n"; return 2; }
         }
+        else if (a == "--projection") {
+            const std::string v = next();
+            if (v == "perspective") projection = 0;
+            else if (v == "orthographic") projection = 1;
+            else if (v == "fisheye") projection = 2;
+            else if (v == "panorama") projection = 3;
+            else { std::cerr << "--projection must be perspective, orthographic, fisheye or panorama\n"; return 2; }
+        }
         else if (a == "--mesh-light") {
             if (!parse_mesh_light(next(), mesh_light_v)) { std::cerr << "--mesh-light must be X,Y,Z,RADIUS[,R,G,B]: radius > 0, emission >= 0\n"; return 2; }
             mesh_light = true;
@@ -257,7 +266,11 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
+                         "  --projection: orthographic frames the rectangle the scene's camera sees on its focal plane; fisheye is equidistant with the scene's vfov\n"
+                         "           across the image height; panorama is an equirectangular image of everything around the camera position, in world axes: loaded as\n"
+                         "           an environment map (--out-hdr, then --float-hdr) it lights another scene. fisheye and panorama have no lens: the scene's\n"
+                         "           defocus_angle is set to 0 for them\n"
                          "  --exposure, --tonemap, --white, --bloom: the film stage between the accumulator and the PNG: the image is scaled by 2^EV, light above the\n"
                          "           luminance THRESHOLD (default 1) spreads as glare of strength S (LEVELS Gaussians of SIGMA, 2 SIGMA, ... pixels; defaults 5 and 2),\n"
                          "           then the tone curve (reinhard maps the luminance W, default 4, to white). --out-hdr: the linear image after exposure and glare, f32\n"
@@ -310,6 +323,8 @@ int main(int argc, char** argv) {
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;
         setup.world.light_sampling = light_sampling;
+        setup.world.projection = projection;
+        if (projection >= 2) setup.camera.defocus_angle = 0.0;   // the library refuses a lens there (pt_scene_set_projection's rule)
         if (mesh_light) {   // an emissive level-4 icosphere (5120 triangles), in the world and in the lights list
             auto ball = TriangleMesh::from_obj(1.0, icosphere(4, Vec3{mesh_light_v[0], mesh_light_v[1], mesh_light_v[2]}, mesh_light_v[3]),
                                                DiffuseLight::from_rgb(Vec3{mesh_light_v[4], mesh_light_v[5], mesh_light_v[6]}));

@@ -500,6 +500,7 @@ struct World {
     int sampler = 0;             // this build's option: 0 independent draws (the reference's), 1 Owen-scrambled Sobol (pt_scene_set_sampler)
     double env_sampling = 0.0;   // this build's option: environment importance sampling weight (pt_scene_set_env_sampling; 0 = off)
     int light_sampling = 0;      // this build's option: 0 the reference's lights.sample / lights.pdf, 1 exact (pt_scene_set_light_sampling)
+    int projection = 0;          // this build's option: 0 perspective (the reference's camera), 1 orthographic, 2 fisheye, 3 panorama (pt_scene_set_projection)
     void build_bvh(pt_ctx* ctx, std::shared_ptr<ImageTexture> env = nullptr) {
         pt_scene* s = pt_scene_create(ctx);
         if (!s) panic("pt_scene_create");
@@ -508,6 +509,7 @@ struct World {
         if (env_sampling != 0.0 && pt_scene_set_env_sampling(s, env_sampling) != 0) panic("set_env_sampling");
         if (sampler != 0 && pt_scene_set_sampler(s, sampler) != 0) panic("set_sampler");
         if (light_sampling != 0 && pt_scene_set_light_sampling(s, light_sampling) != 0) panic("set_light_sampling");
+        if (projection != 0 && pt_scene_set_projection(s, projection) != 0) panic("set_projection");
         emit_into(s, env);
     }
     void release() {
