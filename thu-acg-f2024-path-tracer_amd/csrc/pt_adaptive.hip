@@ -1,4 +1,4 @@
-// Adaptive sampling (pt_render_adaptive, pt_render.cpp): the kernels that run between the render passes of a round schedule.
+// Adaptive sampling (pt_render_adaptive, pt_render.cpp; its resolve pt_resolve_u8_counts, pt_post.cpp): the kernels that run between the render passes of a round schedule.
 //
 // Every round renders the sample range [b_i, b_{i+1}) of the ACTIVE pixels (one pixel-list pass of the render core) into one of
 // two device accumulators: E takes the even rounds, O the odd ones. Two independent sample sets of one pixel estimate its noise

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "pt_bvh_device.h"
+#include "pt_devmem.h"
 
 namespace pt {
 namespace {
@@ -153,13 +154,6 @@ __global__ void k_fit_level(const uint32_t* child, uint32_t level_first, uint32_
     out[id] = nd;
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    bool alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess; }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 bool build_blas_device(const TriD* host_tris, uint32_t n, const double mesh_lo[3], const double mesh_hi[3], uint32_t leaf_max, uint32_t max_depth,
@@ -169,29 +163,28 @@ bool build_blas_device(const TriD* host_tris, uint32_t n, const double mesh_lo[3
     out.depth = 0;
     if (n <= leaf_max || n < 2 || n > 0x07FFFFFFu || leaf_max < 1 || leaf_max > 8 || max_depth < 1 || max_depth > 40) return false;   // a single leaf: nothing to build
     if (((unsigned long long)leaf_max << max_depth) < (unsigned long long)n) return false;      // cannot fit into max_depth levels at all
-    DevBuf<TriD> tris;
-    DevBuf<Box64> tri_box, node_box;
-    DevBuf<uint64_t> keys, keys_sorted;
-    DevBuf<uint32_t> vals, vals_sorted, child, node_first, node_last, counter;
-    DevBuf<BvhNode> nodes;
-    DevBuf<char> tmp;
-    if (!tris.alloc(n) || !tri_box.alloc(n) || !node_box.alloc(n) || !keys.alloc(n) || !keys_sorted.alloc(n) || !vals.alloc(n) || !vals_sorted.alloc(n) ||
-        !child.alloc(2 * (size_t)n) || !node_first.alloc(n) || !node_last.alloc(n) || !counter.alloc(1) || !nodes.alloc(n))
+    DevMem tris, tri_box, node_box, keys, keys_sorted, vals, vals_sorted, child, node_first, node_last, counter, nodes, tmp;
+    auto get = [](DevMem& m, size_t bytes) { return m.alloc(bytes, "hipMalloc(device BVH build)"); };
+    const size_t n_ = n;
+    if (!get(tris, n_ * sizeof(TriD)) || !get(tri_box, n_ * sizeof(Box64)) || !get(node_box, n_ * sizeof(Box64)) || !get(keys, n_ * sizeof(uint64_t)) ||
+        !get(keys_sorted, n_ * sizeof(uint64_t)) || !get(vals, n_ * sizeof(uint32_t)) || !get(vals_sorted, n_ * sizeof(uint32_t)) ||
+        !get(child, 2 * n_ * sizeof(uint32_t)) || !get(node_first, n_ * sizeof(uint32_t)) || !get(node_last, n_ * sizeof(uint32_t)) ||
+        !get(counter, sizeof(uint32_t)) || !get(nodes, n_ * sizeof(BvhNode)))
         return false;
     Box64 mesh;
     for (int k = 0; k < 3; ++k) { mesh.lo[k] = mesh_lo[k]; mesh.hi[k] = mesh_hi[k]; }
     const dim3 grid((n + BT - 1) / BT), block(BT);
-    if (hipMemcpyAsync(tris.p, host_tris, (size_t)n * sizeof(TriD), hipMemcpyHostToDevice, st) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_keys, grid, block, 0, st, tris.p, n, mesh, tri_box.p, keys.p, vals.p);
+    if (hipMemcpyAsync(tris.as<TriD>(), host_tris, (size_t)n * sizeof(TriD), hipMemcpyHostToDevice, st) != hipSuccess) return false;
+    hipLaunchKernelGGL(k_keys, grid, block, 0, st, tris.as<TriD>(), n, mesh, tri_box.as<Box64>(), keys.as<uint64_t>(), vals.as<uint32_t>());
     size_t tmp_bytes = 0;
-    if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys_sorted.p, vals.p, vals_sorted.p, (int)n, 0, 63, st) != hipSuccess) return false;
-    if (!tmp.alloc(tmp_bytes)) return false;
-    if (hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.p, keys_sorted.p, vals.p, vals_sorted.p, (int)n, 0, 63, st) != hipSuccess) return false;
+    if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), vals.as<uint32_t>(), vals_sorted.as<uint32_t>(), (int)n, 0, 63, st) != hipSuccess) return false;
+    if (!get(tmp, tmp_bytes)) return false;
+    if (hipcub::DeviceRadixSort::SortPairs(tmp.as<char>(), tmp_bytes, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), vals.as<uint32_t>(), vals_sorted.as<uint32_t>(), (int)n, 0, 63, st) != hipSuccess) return false;
     // root = node 0 over the whole sorted range; then one launch per level (a host round trip each: <= max_depth of them)
     const uint32_t root_range[2] = {0u, n - 1u}, one = 1u;
-    bool ok = hipMemcpyAsync(node_first.p, &root_range[0], sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(node_last.p, &root_range[1], sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(counter.p, &one, sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
+    bool ok = hipMemcpyAsync(node_first.as<uint32_t>(), &root_range[0], sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(node_last.as<uint32_t>(), &root_range[1], sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(counter.as<uint32_t>(), &one, sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
     if (!ok) return false;
     std::vector<uint32_t> level_start{0u};          // level L = node ids [level_start[L], level_start[L + 1])
     uint32_t created = 1;
@@ -200,22 +193,22 @@ bool build_blas_device(const TriD* host_tris, uint32_t n, const double mesh_lo[3
         const uint32_t first = level_start.back(), end = created;
         level_start.push_back(end);
         const unsigned long long child_cap = (unsigned long long)leaf_max << (max_depth - level - 1u);   // what a child's subtree may hold
-        hipLaunchKernelGGL(k_split_level, dim3((end - first + BT - 1) / BT), block, 0, st, keys_sorted.p, first, end, leaf_max, child_cap, median_below, node_first.p,
-                           node_last.p, child.p, counter.p);
-        if (hipMemcpyAsync(&created, counter.p, sizeof created, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
+        hipLaunchKernelGGL(k_split_level, dim3((end - first + BT - 1) / BT), block, 0, st, keys_sorted.as<uint64_t>(), first, end, leaf_max, child_cap, median_below, node_first.as<uint32_t>(),
+                           node_last.as<uint32_t>(), child.as<uint32_t>(), counter.as<uint32_t>());
+        if (hipMemcpyAsync(&created, counter.as<uint32_t>(), sizeof created, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
         if (created > n) return false;
     }
     const uint32_t n_levels = (uint32_t)level_start.size() - 1u;               // level_start = {0, .., created}
     for (uint32_t level = n_levels; level-- > 0;) {
         const uint32_t first = level_start[level], end = level_start[level + 1];
-        hipLaunchKernelGGL(k_fit_level, dim3((end - first + BT - 1) / BT), block, 0, st, child.p, first, end, tri_box.p, vals_sorted.p, node_box.p, nodes.p);
+        hipLaunchKernelGGL(k_fit_level, dim3((end - first + BT - 1) / BT), block, 0, st, child.as<uint32_t>(), first, end, tri_box.as<Box64>(), vals_sorted.as<uint32_t>(), node_box.as<Box64>(), nodes.as<BvhNode>());
     }
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return false;
     out.depth = (int)n_levels;          // depth of the deepest leaf (root = 0), counted like the host builder's depth_reached
     out.nodes.resize(created);
     out.order.resize(n);
-    ok = hipMemcpy(out.nodes.data(), nodes.p, (size_t)created * sizeof(BvhNode), hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(out.order.data(), vals_sorted.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+    ok = hipMemcpy(out.nodes.data(), nodes.as<BvhNode>(), (size_t)created * sizeof(BvhNode), hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(out.order.data(), vals_sorted.as<uint32_t>(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
     return ok;
 }
 

@@ -27,11 +27,9 @@ struct pt_comm {
     pt_ctx* ctx = nullptr;
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
-    double* d_scratch = nullptr;     // small device buffer for host-value collectives
-    double* d_accum = nullptr;       // frame accumulator of pt_render_multi (grown on demand)
-    size_t accum_bytes = 0;
-    double* h_stage = nullptr;       // rank 0: pinned landing buffer of the reduced frame (grown on demand)
-    size_t stage_bytes = 0;
+    DevMem d_scratch;                // small device buffer for host-value collectives
+    GrowBuf d_accum;                 // frame accumulator of pt_render_multi (grown on demand)
+    GrowBuf h_stage{true};           // rank 0: pinned landing buffer of the reduced frame (grown on demand)
     bool aborted = false;            // ncclCommAbort was called after a local failure: every later collective fails at once
 };
 
@@ -136,7 +134,7 @@ extern "C" int pt_comm_create(pt_ctx* ctx, int rank, int world, const char* id_p
     c->rank = rank;
     c->world = world;
     if (!nccl_ok(ncclCommInitRank(&c->comm, world, id, rank), "ncclCommInitRank") ||
-        !hip_ok(hipMalloc((void**)&c->d_scratch, 64 * sizeof(double)), "hipMalloc(comm scratch)")) {
+        !c->d_scratch.alloc(64 * sizeof(double), "hipMalloc(comm scratch)")) {
         if (c->comm) (void)ncclCommDestroy(c->comm);
         delete c;
         return -1;
@@ -148,11 +146,8 @@ extern "C" void pt_comm_destroy(pt_comm* c) {
     if (!c) return;
     (void)hipSetDevice(c->ctx->device);
     (void)hipStreamSynchronize(c->ctx->stream);
-    if (c->d_accum) (void)hipFree(c->d_accum);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    delete c;
+    delete c;   // (frees the buffers: pt_devmem.h)
 }
 extern "C" int pt_comm_rank(pt_comm* c) { return c ? c->rank : -1; }
 extern "C" int pt_comm_world(pt_comm* c) { return c ? c->world : -1; }
@@ -177,10 +172,11 @@ extern "C" int pt_comm_allreduce_f64(pt_comm* c, double* values, uint32_t n, int
     if (!comm_usable(c, "pt_comm_allreduce_f64")) return -1;
     if (!values || n == 0 || n > 64) return set_error("pt_comm_allreduce_f64: bad arguments (1..64 values)");
     hipStream_t st = c->ctx->stream;
+    double* d = c->d_scratch.as<double>();
     const bool ok = hip_ok(hipSetDevice(c->ctx->device), "hipSetDevice") &&
-                    hip_ok(hipMemcpyAsync(c->d_scratch, values, n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(allreduce in)") &&
-                    nccl_ok(ncclAllReduce(c->d_scratch, c->d_scratch, n, ncclDouble, op == 1 ? ncclMax : ncclSum, c->comm, st), "ncclAllReduce") &&
-                    hip_ok(hipMemcpyAsync(values, c->d_scratch, n * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(allreduce out)") &&
+                    hip_ok(hipMemcpyAsync(d, values, n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(allreduce in)") &&
+                    nccl_ok(ncclAllReduce(d, d, n, ncclDouble, op == 1 ? ncclMax : ncclSum, c->comm, st), "ncclAllReduce") &&
+                    hip_ok(hipMemcpyAsync(values, d, n * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(allreduce out)") &&
                     hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(allreduce)");
     if (!ok && c->world > 1) return abort_comm(c, std::string("pt_comm_allreduce_f64: ") + pt::last_error());
     return ok ? 0 : -1;
@@ -212,28 +208,16 @@ extern "C" int pt_render_multi(pt_scene* s, const pt_camera* cam, uint64_t seed,
         if (pt_camera_init(cam, v, &height) != 0) return -1;
         n = (size_t)cam->image_width * height * 3;
         bytes = n * sizeof(double);
-        if (bytes > c->accum_bytes) {
-            if (c->d_accum) (void)hipFree(c->d_accum);
-            c->d_accum = nullptr;
-            c->accum_bytes = 0;
-            if (!hip_ok(hipMalloc((void**)&c->d_accum, bytes), "hipMalloc(frame accumulator)")) return -1;
-            c->accum_bytes = bytes;
-        }
-        if (c->rank == 0 && bytes > c->stage_bytes) {
-            if (c->h_stage) (void)hipHostFree(c->h_stage);
-            c->h_stage = nullptr;
-            c->stage_bytes = 0;
-            if (!hip_ok(hipHostMalloc((void**)&c->h_stage, bytes, hipHostMallocDefault), "hipHostMalloc(frame staging)")) return -1;
-            c->stage_bytes = bytes;
-        }
-        if (!hip_ok(hipMemsetAsync(c->d_accum, 0, bytes, st), "hipMemset(frame accumulator)")) return -1;
+        if (!c->d_accum.reserve(bytes, "hipMalloc(frame accumulator)")) return -1;
+        if (c->rank == 0 && !c->h_stage.reserve(bytes, "hipHostMalloc(frame staging)")) return -1;
+        if (!hip_ok(hipMemsetAsync(c->d_accum.as<double>(), 0, bytes, st), "hipMemset(frame accumulator)")) return -1;
         pt_render_opts o = opts;
         o.accum_on_device = 1;
         o.overwrite = 0;                 // the device accumulator was just cleared
         o.stream = (void*)st;
         uint32_t lo, hi;
         pt_shard_range(spp_total, c->rank, c->world, &lo, &hi);
-        return pt_render(s, cam, seed, lo, hi, c->d_accum, &o, stats);
+        return pt_render(s, cam, seed, lo, hi, c->d_accum.as<double>(), &o, stats);
     };
     const int rc = local();
     if (c->world > 1) {
@@ -243,17 +227,18 @@ extern "C" int pt_render_multi(pt_scene* s, const pt_camera* cam, uint64_t seed,
         if (rc != 0) return set_error(own);
         if (failed != 0.0) return set_error("pt_render_multi: the render failed on another rank; no frame was reduced");
         // the frame's single collective: sum of the per-rank sample SUMS, in place on the root, on the render stream
-        if (!nccl_ok(ncclReduce(c->d_accum, c->d_accum, n, ncclDouble, ncclSum, 0, c->comm, st), "ncclReduce"))
+        if (!nccl_ok(ncclReduce(c->d_accum.as<double>(), c->d_accum.as<double>(), n, ncclDouble, ncclSum, 0, c->comm, st), "ncclReduce"))
             return abort_comm(c, std::string("pt_render_multi: ") + pt::last_error());
     } else if (rc != 0) {
         return -1;
     }
     if (c->rank == 0) {
         // one DMA into the pinned landing buffer, then one pass over the caller's (pageable) frame
-        if (!hip_ok(hipMemcpyAsync(c->h_stage, c->d_accum, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(frame)")) return -1;
+        double* staged = c->h_stage.as<double>();
+        if (!hip_ok(hipMemcpyAsync(staged, c->d_accum.as<double>(), bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(frame)")) return -1;
         if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(frame)")) return -1;
-        if (overwrite) memcpy(accum_root, c->h_stage, bytes);
-        else for (size_t i = 0; i < n; ++i) accum_root[i] += c->h_stage[i];
+        if (overwrite) memcpy(accum_root, staged, bytes);
+        else for (size_t i = 0; i < n; ++i) accum_root[i] += staged[i];
     } else if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(reduce)")) {
         return -1;
     }

@@ -1,4 +1,4 @@
-// The a-trous denoiser behind pt_denoise (pt_render.cpp; no counterpart in the reference). The rule is written out in
+// The a-trous denoiser behind pt_denoise (pt_post.cpp; no counterpart in the reference). The rule is written out in
 // include/pt_amd.h; in short:
 //   k_dn_prepare  per pixel: demodulated colour c = mu / max(albedo, 1e-3) and its variance v from the two disjoint sample sets
 //                 (A, B) the frame was rendered as; the guides N (unit shading normal) and z (mean first-hit depth). Background

@@ -1,4 +1,4 @@
-// The film stage behind pt_film_develop (pt_render.cpp; no counterpart in the reference, whose camera.rs:109-130 is the default
+// The film stage behind pt_film_develop (pt_post.cpp; no counterpart in the reference, whose camera.rs:109-130 is the default
 // options' special case). The rule is written out in include/pt_amd.h; in short:
 //   k_film_prepare  per pixel: x = max(mean * 2^ev, 0) and the bright part B = x * (Y - T) / Y for Y = lum(x) > T, as three planes.
 //   k_film_conv     one separable pass of one glare level: out[c][x][y] (+)= scale * sum_i k[i] in[c][y][x + i], i = -r .. r, zero

@@ -1,6 +1,8 @@
 // Context management and the wavefront render loop (host side of Camera::render,
 // camera.rs:79-126): size the path pool, launch init -> {extend, shade}* -> resolve on one HIP
 // stream, poll the live-slot counter every few iterations, report per-kernel HIP-event times.
+// The render core is a short list of steps (render_core, below); the pixel-list, adaptive and AOV drivers follow it. The probes are
+// in pt_probe.cpp, the post stage (resolve, denoise, film) in pt_post.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -154,7 +156,7 @@ struct EventTimer {   // per-launch HIP-event timing, drained at the polling syn
 
 // The device camera of a render (CamD) from the public one: Camera::init's derived vectors plus what K1 and K3 read per sample.
 // pt_render's core and pt_render_aovs both start here, so an AOV sample traces the same camera ray as the render sample.
-static int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
+int pt::make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
     CamDerived cd;
     if (derive_camera(cam, cd) != 0) return -1;
     memset(&dc, 0, sizeof dc);
@@ -211,27 +213,25 @@ static int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
 // Environment importance sampling: the tables of the camera's environment map, built once per (scene, texture) at the
 // first call that needs them — from the device atlas, by pt_envmap.hip — and kept until pt_scene_destroy (one texture's at a time).
 // `e` gets the tables and Z; e.z > 0 (finite) is the map's half of the in-effect rule. The caller has checked dc.env_is_map.
-static int env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e) {
+int pt::env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e) {
     memset(&e, 0, sizeof e);
     if (s->env_tab_tex != dc.env_tex) {
         TexD T;
         if (!hip_ok(hipMemcpyAsync(&T, s->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, st), "hipMemcpy(env texture)") ||
             !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(env texture)"))
             return -1;
-        if (s->env_tab) (void)hipFree(s->env_tab);
-        s->env_tab = nullptr;
-        s->env_tab_bytes = 0;
+        s->env_tab.release();   // the tables are forgotten before they are rebuilt: a failed rebuild leaves none
         s->env_tab_tex = -1;
         s->env_tab_w = T.w;
         s->env_tab_h = T.h;
         s->env_tab_z = 0.0;
         if (T.w != 0 && T.h != 0) {
             const size_t n_col = (size_t)T.h * (T.w + 1), bytes = (n_col + T.h + 1) * sizeof(double);
-            if (!hip_ok(hipMalloc((void**)&s->env_tab, bytes), "hipMalloc(env tables)")) return -1;
-            s->env_tab_bytes = bytes;
-            launch_env_tables(s->dev.view, T, s->env_tab, s->env_tab + n_col, st);
+            if (!s->env_tab.reserve(bytes, "hipMalloc(env tables)")) return -1;
+            double* tab = s->env_tab.as<double>();
+            launch_env_tables(s->dev.view, T, tab, tab + n_col, st);
             if (!hip_ok(hipGetLastError(), "env tables") ||
-                !hip_ok(hipMemcpyAsync(&s->env_tab_z, s->env_tab + n_col + T.h, sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(env Z)") ||
+                !hip_ok(hipMemcpyAsync(&s->env_tab_z, tab + n_col + T.h, sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(env Z)") ||
                 !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(env tables)"))
                 return -1;
         }
@@ -241,8 +241,8 @@ static int env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e) {
     e.h = s->env_tab_h;
     e.f = s->env_f;
     if (s->env_tab && std::isfinite(s->env_tab_z) && s->env_tab_z > 0.0) {
-        e.col = s->env_tab;
-        e.row = s->env_tab + (size_t)e.h * (e.w + 1);
+        e.col = s->env_tab.as<double>();
+        e.row = e.col + (size_t)e.h * (e.w + 1);
         e.z = s->env_tab_z;
     }
     return 0;
@@ -279,47 +279,91 @@ static int render_mode(pt_scene* s, const CamD& dc, hipStream_t st, ShadeMode& m
     return 0;
 }
 
-// The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
-// pixels) / n_list: a pixel-list render (PoolD::list; d_list sorted by tiled index, n_list > 0), or null: the whole frame — then the
-// path below is exactly pt_render's.
-static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum,
-                       const pt_render_opts* opts_in, pt_render_stats* stats, const uint32_t* d_list, const uint32_t* h_list, uint32_t n_list) {
-    if (!s || !s->built) return set_error("pt_render: world not built (call pt_world_build)");
-    if (!accum) return set_error("pt_render: null accumulator");
-    if (spp_end < spp_begin) return set_error("pt_render: spp_end < spp_begin");
+
+// ---- the render core, step by step (render_core, at the end, calls them in this order) ------------------------------------------------
+namespace {
+
+// What one call renders: the caller's arguments and what the camera and the scene make of them.
+struct Job {
     pt_render_opts opts;
-    memset(&opts, 0, sizeof opts);
-    if (opts_in) opts = *opts_in;
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    hipStream_t st = opts.stream ? (hipStream_t)opts.stream : ctx->stream;
-
+    hipStream_t st;
+    uint64_t seed;
+    uint32_t spp_begin, spp_end, spp;
+    const uint32_t *d_list, *h_list;   // a pixel-list render (PoolD::list): the device list, sorted by tiled index, and the same pixels on the host
+    uint32_t n_list;
+    bool list;
+    uint32_t n_pixels, n_items;   // of the frame; rendered (the list's, or all)
     CamD dc;
-    if (make_camd(s, cam, dc) != 0) return -1;
-    const uint64_t n_pixels64 = (uint64_t)dc.width * dc.height;
-    if (n_pixels64 == 0 || n_pixels64 > 0x7FFFFFFFull) return set_error("pt_render: bad image size");
-    const uint32_t n_pixels = (uint32_t)n_pixels64;
-    const uint32_t spp = spp_end - spp_begin;
-    const bool list = d_list != nullptr;
-    const uint32_t n_items = list ? n_list : n_pixels;   // pixels rendered
     ShadeMode mode;
-    EnvTabD env{};   // the table argument of a mode that has one
-    if (render_mode(s, dc, st, mode, env) != 0) return -1;
+    EnvTabD env;   // the table argument of a mode that has one
+};
 
-    // pool sizing. slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
-    // the machine several times over; finished paths pull the next (pixel, sample) from a global
-    // counter. slots_per_pixel = k >= 1: STATIC ownership (deterministic; k = 1 is the reference's
-    // exact per-pixel sample order).
-    uint32_t k = opts.slots_per_pixel;
-    if (k == 0)   // an explicit option wins over the experiment switch
-        if (const char* e = exp_env("PT_SLOTS_PER_PIXEL")) k = (uint32_t)atoi(e);
-    const bool dynamic = k == 0;
-    const uint32_t tiles_x = (dc.width + 7) / 8, tiles_y = (dc.height + 7) / 8;
-    const uint64_t n_tile_pixels64 = (uint64_t)tiles_x * tiles_y * 64;
+// Every experiment switch of a render (exp_env: read under PT_EXPERIMENT=1 only), read once. An explicit option wins over its switch.
+struct Switches {
+    uint32_t slots_per_pixel = 0;   // opts.slots_per_pixel, else PT_SLOTS_PER_PIXEL
+    bool pool_slots_set = false;    // PT_POOL_SLOTS: the dynamic pool's size (plan_pool refuses 0)
+    uint64_t pool_slots = 0;
+    int shade_variant = 42;   // k_shade<sort, min waves/SIMD>: sort*10 + waves (12 = windowed material sort with 256 threads / 2048-slot windows, 2 = plain;
+                              // [r3] 22 = the same with 512 threads / 4096-slot windows: K3 -2 % on scenes 6, 3 and 5; 32 = 8192-slot windows: another
+                              // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
+                              // windows per block launched, else 22)
+    bool pool_in_place = false, no_defer_regen = false, no_compact_records = false, init_shuffle = false, accum_linear = false, no_compact_pool = false,
+         prof = false;
+    int grid_mult = 1;   // persistent grids: resident blocks per CU x CUs x this
+    uint32_t wide_window_min = 16;
+    int ext2 = 0;        // PT_EXT2 = stack*10 + blocks per CU picks the two-phase K2's instantiation (0: not set)
+    enum { K2_AUTO, K2_BATCH, K2_TWOPHASE } k2 = K2_AUTO;   // PT_K2=batch forces the batch kernel, twophase the two-phase one where it can run
+    uint64_t compact_num = 1, compact_den = 2;   // compact when live <= num/den of the slots still covered (25 % .. 85 % measured level: within 0.5 %)
+    uint32_t poll_cap = 8;
+};
+Switches read_switches(const pt_render_opts& opts) {
+    Switches sw;
+    sw.slots_per_pixel = opts.slots_per_pixel;
+    if (sw.slots_per_pixel == 0)
+        if (const char* e = exp_env("PT_SLOTS_PER_PIXEL")) sw.slots_per_pixel = (uint32_t)atoi(e);
+    if (const char* e = exp_env("PT_POOL_SLOTS")) {
+        sw.pool_slots_set = true;
+        sw.pool_slots = strtoull(e, nullptr, 10);
+    }
+    if (const char* e = exp_env("PT_SHADE_VARIANT")) sw.shade_variant = atoi(e);
+    sw.pool_in_place = exp_env("PT_POOL_IN_PLACE") != nullptr;
+    sw.no_defer_regen = exp_env("PT_NO_DEFER_REGEN") != nullptr;
+    sw.no_compact_records = exp_env("PT_NO_COMPACT_RECORDS") != nullptr;
+    sw.init_shuffle = exp_env("PT_INIT_SHUFFLE") != nullptr;
+    if (const char* e = exp_env("PT_GRID_MULT")) sw.grid_mult = std::max(1, atoi(e));
+    if (const char* e = exp_env("PT_WIDE_WINDOW_MIN")) sw.wide_window_min = (uint32_t)std::max(1, atoi(e));
+    if (const char* e = exp_env("PT_EXT2")) sw.ext2 = atoi(e);
+    if (const char* e = exp_env("PT_K2")) sw.k2 = !strcmp(e, "batch") ? Switches::K2_BATCH : !strcmp(e, "twophase") ? Switches::K2_TWOPHASE : Switches::K2_AUTO;
+    sw.accum_linear = exp_env("PT_ACCUM_LINEAR") != nullptr;
+    sw.no_compact_pool = exp_env("PT_NO_COMPACT_POOL") != nullptr;
+    if (const char* e = exp_env("PT_COMPACT_AT")) { sw.compact_num = (uint64_t)std::max(1, atoi(e)); sw.compact_den = 100; }   // per cent
+    if (const char* e = exp_env("PT_POLL_CAP")) sw.poll_cap = (uint32_t)std::max(1, atoi(e));
+    sw.prof = exp_env("PT_PROF") != nullptr;
+    return sw;
+}
+
+// Pool sizing (arithmetic only). slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
+// the machine several times over; finished paths pull the next (pixel, sample) from a global
+// counter. slots_per_pixel = k >= 1: STATIC ownership (deterministic; k = 1 is the reference's
+// exact per-pixel sample order).
+struct PoolPlan {
+    bool dynamic;
+    uint32_t k;   // static mode: slots per pixel as clamped here
+    uint32_t tiles_x, n_tile_pixels;
+    uint64_t total_work;
+    uint32_t n_slots;
+};
+int plan_pool(const Switches& sw, const Job& job, int n_cus, PoolPlan& p) {
+    uint32_t k = sw.slots_per_pixel;
+    p.dynamic = k == 0;
+    const uint32_t tiles_y = (job.dc.height + 7) / 8;
+    p.tiles_x = (job.dc.width + 7) / 8;
+    const uint64_t n_tile_pixels64 = (uint64_t)p.tiles_x * tiles_y * 64;
     if (n_tile_pixels64 > 0x7FFFFFFFull) return set_error("pt_render: image too large");
-    const uint64_t total_work = dynamic ? (list ? (uint64_t)n_list : n_tile_pixels64) * spp : (uint64_t)n_items * spp;
+    p.n_tile_pixels = (uint32_t)n_tile_pixels64;
+    p.total_work = p.dynamic ? (job.list ? (uint64_t)job.n_list : n_tile_pixels64) * job.spp : (uint64_t)job.n_items * job.spp;
     uint64_t n_slots64;
-    if (dynamic) {
+    if (p.dynamic) {
         // Resident paths: enough that per-launch fixed costs and kernel tails amortise (16.8M slots are 9% faster than
         // 4.2M on the 4000-spp frame, 33.6M another 2%), few enough that the frame's end — when the sample budget is
         // handed out and slots die — stays short: between 16K and 128K slots per CU (3.5 GB of path state at 33.6M).
@@ -332,67 +376,101 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
         // 67 M 2836, 134 M 2752; @ 500: 16.8 M 2688, 33.6 M 2750, 67 M 2694; @ 250: 8.4 M 2484, 16.8 M 2574; scene 3 1920x1920 @ 4000:
         // 1314 / 1328 / 1359; scene 5 4K @ 1000: 4355 / 4431 / 4499 (profiles/r03_pool_sweep.txt). 134 M slots are 14 GB of path records.
         uint64_t per_cu = 16384;   // a power of two (the tile-ordered work items and the 64 counter shards divide it evenly)
-        while (per_cu < 524288 && per_cu * 2 * (uint64_t)std::max(1, ctx->n_cus) * 30 <= total_work) per_cu *= 2;
+        while (per_cu < 524288 && per_cu * 2 * (uint64_t)std::max(1, n_cus) * 30 <= p.total_work) per_cu *= 2;
         // one more doubling (268 M slots, 28 GB) only from 48 samples per slot: scene 3 1920x1920 @ 4000 spp (55 per slot) 1335 -> 1362,
         // while at 31 per slot scene 6 FHD @ 4000 loses 0.7 % and scene 5 4K @ 1000 0.5 % (initialising and compacting the pool costs 58 ms there)
-        if (per_cu == 524288 && per_cu * 2 * (uint64_t)std::max(1, ctx->n_cus) * 48 <= total_work) per_cu *= 2;
-        uint64_t target = (uint64_t)ctx->n_cus * per_cu;
-        if (const char* e = exp_env("PT_POOL_SLOTS")) {
-            target = strtoull(e, nullptr, 10);
+        if (per_cu == 524288 && per_cu * 2 * (uint64_t)std::max(1, n_cus) * 48 <= p.total_work) per_cu *= 2;
+        uint64_t target = (uint64_t)n_cus * per_cu;
+        if (sw.pool_slots_set) {
+            target = sw.pool_slots;
             if (target == 0) return set_error("pt_render: PT_POOL_SLOTS must be positive");
         }
-        n_slots64 = std::min<uint64_t>(target, std::max<uint64_t>(total_work, 1));
+        n_slots64 = std::min<uint64_t>(target, std::max<uint64_t>(p.total_work, 1));
     } else {
-        if (k > spp) k = spp;
+        if (k > job.spp) k = job.spp;
         if (k == 0) k = 1;
-        while ((uint64_t)k * n_items > 0x40000000ull && k > 1) --k;
-        n_slots64 = (uint64_t)k * n_items;
+        while ((uint64_t)k * job.n_items > 0x40000000ull && k > 1) --k;
+        n_slots64 = (uint64_t)k * job.n_items;
     }
     if (n_slots64 > 0x7FFFFFC0ull) return set_error("pt_render: image too large for the path pool");
-    const uint32_t n_slots = (uint32_t)n_slots64;
-    int shade_variant = 42;   // k_shade<sort, min waves/SIMD>: sort*10 + waves (12 = windowed material sort with 256 threads / 2048-slot windows, 2 = plain;
-                              // [r3] 22 = the same with 512 threads / 4096-slot windows: K3 -2 % on scenes 6, 3 and 5; 32 = 8192-slot windows: another
-                              // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
-                              // windows per block launched, else 22)
-    if (const char* e = exp_env("PT_SHADE_VARIANT")) shade_variant = atoi(e);
-    const ShadeForm form = shade_form(ShadeForm{shade_variant, s->dev.view.n_lights != 0u, list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, mode});   // the form of k_init / k_shade that exists for it
-    shade_variant = form.variant;
+    p.k = k;
+    p.n_slots = (uint32_t)n_slots64;
+    return 0;
+}
+
+// The kernels of a render: the form of k_init / k_shade that exists for it, K2's variant, the persistent grids.
+struct Kernels {
+    ShadeForm form;
+    bool ordered;      // shading-order output (PoolD::reorder)
+    int extend_code;   // -1 = batch, -(stack*10 + blocks) = two-phase
+    int blocks_shade;  // resident blocks per CU of the form's k_shade; 0: there is no such kernel (render_core refuses)
+    int grid_extend, grid_shade;
+};
+// the two-phase K2's instantiation for this scene's BVHs (stack*10 + blocks per CU), 0 when its LDS stack does not cover them
+int extend2_code(const pt_scene* s, const Switches& sw) {
+    const int need = (int)s->stack_need_extend2;
+    if (need > 32) return 0;
+    // four blocks per CU where the LDS allows it (stacks of 16 and 20 entries): the kernel then runs at 128 registers with
+    // 64 B of spills per lane and is still 7.5 % faster than at three blocks and 149 registers (round 2; in round 1, at
+    // 166 registers, the same bound meant 168 B of spills and lost 11 %)
+    // [r3, last] stacks of <= 16 entries: blocks of 128 threads over 1024-slot windows (code 2164, eight blocks per CU) — with the
+    // queue's end in half windows the smaller block's shorter barrier waits win on every pool size: K2 -1.0 % (16.8 M slots), -1.8 %
+    // (67 M, 134 M) against 256 threads; 64 threads: +1 % / -2.0 % / -2.5 % (worse on shallow pools); 512 threads: +5 %
+    int code = need <= 16 ? 2164 : need <= 20 ? 204 : need <= 24 ? 243 : need <= 28 ? 283 : 323;
+    if (const int c = sw.ext2) {
+        if (c / 10 >= need && (c == 163 || c == 164 || c == 204 || c == 243 || c == 283 || c == 323)) code = c;
+        if ((c == 1164 || c == 2164 || c == 8164) && need <= 16) code = c;
+    }
+    return code;
+}
+Kernels choose_kernels(const Switches& sw, const pt_scene* s, const Job& job, const PoolPlan& p) {
+    Kernels kn;
+    kn.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode});
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
     // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
-    const bool ordered = dynamic && !list && shade_form_sorts(form) && !exp_env("PT_POOL_IN_PLACE");
+    kn.ordered = p.dynamic && !job.list && shade_form_sorts(kn.form) && !sw.pool_in_place;
+    // K2 variant: two-phase kernel when there are meshes to defer and its LDS stack covers the scene's BVHs, else the
+    // batch kernel (the experiment switches: Switches::k2, ext2)
+    const int two_phase = extend2_code(s, sw);
+    kn.extend_code = (s->n_mesh_entries > 0 && two_phase != 0) ? -two_phase : -1;
+    if (sw.k2 == Switches::K2_BATCH) kn.extend_code = -1;
+    else if (sw.k2 == Switches::K2_TWOPHASE && two_phase != 0) kn.extend_code = -two_phase;
+    const int blocks_extend = extend_occupancy_blocks(kn.extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : kn.extend_code);
+    kn.blocks_shade = shade_occupancy_blocks(kn.form);
+    kn.grid_extend = s->ctx->n_cus * blocks_extend * sw.grid_mult;
+    kn.grid_shade = s->ctx->n_cus * kn.blocks_shade * sw.grid_mult;
+    return kn;
+}
+
+// The pool's memory: the scene's cached buffer grown to what THIS render needs and carved from this render's n_al (never from the cached
+// capacity: a small render after a large one lays its arrays out as a fresh scene would), the scene's counters, PoolD's scalar fields.
+int bind_pool(pt_scene* s, const Switches& sw, const Job& job, const PoolPlan& p, const Kernels& kn, PoolD& pool) {
     // one allocation: the two record arrays (RayRec, PathRec), the static mode's f64 arrays, the two u32 state arrays (+ the output area)
-    const size_t n_al = ((size_t)n_slots + 8191) & ~(size_t)8191;   // whole windows: 2048 slots (k_extend2, k_shade) / 4096 (k_shade with 512 threads)
-    const size_t n_f64 = dynamic ? 0 : 6;   // the per-slot sample sums and radiances exist in the static mode only (the dynamic mode adds into the frame)
+    const size_t n_al = ((size_t)p.n_slots + 8191) & ~(size_t)8191;   // whole windows: 2048 slots (k_extend2, k_shade) / 4096 (k_shade with 512 threads)
+    const size_t n_f64 = p.dynamic ? 0 : 6;   // the per-slot sample sums and radiances exist in the static mode only (the dynamic mode adds into the frame)
     const size_t bytes = n_al * (sizeof(RayRec) + sizeof(PathRec) + n_f64 * sizeof(double) + 2 * sizeof(uint32_t)) +
-                         (ordered ? n_al * (sizeof(RayRec) + sizeof(PathRec) + sizeof(uint32_t)) : 0);
-    if (bytes > s->pool_bytes) {
-        if (s->pool_mem) (void)hipFree(s->pool_mem);
-        s->pool_mem = nullptr;
-        s->pool_bytes = 0;
-        if (!hip_ok(hipMalloc(&s->pool_mem, bytes), "hipMalloc(path pool)")) return -1;
-        s->pool_bytes = bytes;
-    }
+                         (kn.ordered ? n_al * (sizeof(RayRec) + sizeof(PathRec) + sizeof(uint32_t)) : 0);
+    if (!s->pool_mem.reserve(bytes, "hipMalloc(path pool)")) return -1;
     if (!s->d_counters) {
         if (!hip_ok(hipMalloc((void**)&s->d_counters, sizeof(CountersD)), "hipMalloc(counters)")) return -1;
         if (!hip_ok(hipHostMalloc((void**)&s->h_counters, sizeof(CountersD), hipHostMallocDefault), "hipHostMalloc(counters)")) return -1;
     }
-    PoolD pool;
     memset(&pool, 0, sizeof pool);
     {
-        char* m = (char*)s->pool_mem;   // hipMalloc memory is 256-B aligned; records first (64-B aligned)
+        char* m = s->pool_mem.as<char>();   // hipMalloc memory is 256-B aligned; records first (64-B aligned)
         pool.ray = (RayRec*)m; m += n_al * sizeof(RayRec);
         pool.path = (PathRec*)m; m += n_al * sizeof(PathRec);
         double* d = (double*)m;
         double** f64s[6] = {&pool.ax, &pool.ay, &pool.az, &pool.rx, &pool.ry, &pool.rz};
-        for (auto p : f64s) { *p = n_f64 ? d : nullptr; d += n_f64 ? n_al : 0; }
+        for (auto f : f64s) { *f = n_f64 ? d : nullptr; d += n_f64 ? n_al : 0; }
         uint32_t* u = (uint32_t*)d;
         uint32_t** u32s[2] = {&pool.hit_prim, &pool.bounce};
-        for (auto p : u32s) { *p = u; u += n_al; }
+        for (auto f : u32s) { *f = u; u += n_al; }
         pool.ray_out = pool.ray;
         pool.path_out = pool.path;
         pool.bounce_out = pool.bounce;
-        if (ordered) {   // (u is 64-B aligned: n_al is a multiple of 8192)
+        if (kn.ordered) {   // (u is 64-B aligned: n_al is a multiple of 8192)
             m = (char*)u;
             pool.ray_out = (RayRec*)m; m += n_al * sizeof(RayRec);
             pool.path_out = (PathRec*)m; m += n_al * sizeof(PathRec);
@@ -400,244 +478,274 @@ static int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_
             pool.reorder = 1u;
         }
     }
-    pool.n_slots = n_slots;
+    pool.n_slots = p.n_slots;
     pool.n_alloc = (uint32_t)n_al;
-    pool.n_pixels = n_pixels;
-    pool.k = dynamic ? 0u : k;
-    pool.spp_begin = spp_begin;
-    pool.spp_end = spp_end;
-    pool.dynamic = dynamic ? 1u : 0u;
-    pool.defer_regen = (dynamic && !exp_env("PT_NO_DEFER_REGEN")) ? 1u : 0u;
-    pool.compact = (dc.motionless && !exp_env("PT_NO_COMPACT_RECORDS")) ? 1u : 0u;
-    pool.total_work = total_work;
-    pool.width = dc.width;
-    pool.height = dc.height;
-    pool.tiles_x = tiles_x;
-    pool.n_tile_pixels = (uint32_t)n_tile_pixels64;
-    pool.list = d_list;
-    pool.n_list = list ? n_list : 0u;
-    pool.list_store = list && opts.accum_on_device && opts.overwrite ? 1u : 0u;   // (a host accumulator is written below, pixel by pixel)
+    pool.n_pixels = job.n_pixels;
+    pool.k = p.dynamic ? 0u : p.k;
+    pool.spp_begin = job.spp_begin;
+    pool.spp_end = job.spp_end;
+    pool.dynamic = p.dynamic ? 1u : 0u;
+    pool.defer_regen = (p.dynamic && !sw.no_defer_regen) ? 1u : 0u;
+    pool.compact = (job.dc.motionless && !sw.no_compact_records) ? 1u : 0u;
+    pool.total_work = p.total_work;
+    pool.width = job.dc.width;
+    pool.height = job.dc.height;
+    pool.inv_width = 1.0 / (double)job.dc.width;
+    pool.tiles_x = p.tiles_x;
+    pool.n_tile_pixels = p.n_tile_pixels;
+    pool.list = job.d_list;
+    pool.n_list = job.list ? job.n_list : 0u;
+    pool.list_store = job.list && job.opts.accum_on_device && job.opts.overwrite ? 1u : 0u;   // (a host accumulator is written by copy_back, pixel by pixel)
     // experiment (PT_INIT_SHUFFLE=1): k_init hands the initial items out permuted inside each 8192-slot granule (an odd multiplier), so
     // that the first K2 launch traces incoherent chunks — the measure of what tile-ordered chunks are worth
-    if (dynamic && !list && exp_env("PT_INIT_SHUFFLE")) pool.init_perm = 0x9E3779B1u;
+    if (p.dynamic && !job.list && sw.init_shuffle) pool.init_perm = 0x9E3779B1u;
+    return 0;
+}
 
-    // accumulator on the device (freed on every return path when it is ours)
+// The frame accumulator on the device: the caller's, or one of this call's (`own` frees it on every return path), cleared where the
+// render is to overwrite. d_accum is null when this fails.
+double* device_accum(const Job& job, double* accum, DevMem& own) {
+    const size_t bytes = (size_t)job.n_pixels * 3 * sizeof(double);
     double* d_accum = accum;
-    const size_t accum_bytes = (size_t)n_pixels * 3 * sizeof(double);
-    struct AccumGuard {
-        double* p = nullptr;
-        ~AccumGuard() { if (p) (void)hipFree(p); }
-    } own_accum;
-    if (!opts.accum_on_device) {
-        if (!hip_ok(hipMalloc((void**)&d_accum, accum_bytes), "hipMalloc(accum)")) return -1;
-        own_accum.p = d_accum;
-        if (!hip_ok(hipMemsetAsync(d_accum, 0, accum_bytes, st), "hipMemset(accum)")) return -1;
-    } else if (opts.overwrite && !list) {   // (a list render stores its pixels instead: the others are not written)
-        if (!hip_ok(hipMemsetAsync(d_accum, 0, accum_bytes, st), "hipMemset(accum)")) return -1;
+    if (!job.opts.accum_on_device) {
+        if (!own.alloc(bytes, "hipMalloc(accum)")) return nullptr;
+        d_accum = own.as<double>();
+        if (!hip_ok(hipMemsetAsync(d_accum, 0, bytes, job.st), "hipMemset(accum)")) return nullptr;
+    } else if (job.opts.overwrite && !job.list) {   // (a list render stores its pixels instead: the others are not written)
+        if (!hip_ok(hipMemsetAsync(d_accum, 0, bytes, job.st), "hipMemset(accum)")) return nullptr;
     }
-
-    // persistent grids: resident blocks per CU x CUs
-    int mult = 1;
-    if (const char* e = exp_env("PT_GRID_MULT")) mult = std::max(1, atoi(e));
-    uint32_t wide_window_min = 16;
-    if (const char* e = exp_env("PT_WIDE_WINDOW_MIN")) wide_window_min = (uint32_t)std::max(1, atoi(e));
-    // K2 variant: two-phase kernel when there are meshes to defer and its LDS stack covers the scene's BVHs, else the
-    // batch kernel. Experiment switches: PT_K2=batch forces the batch kernel; PT_EXT2 = stack*10 + blocks per CU picks
-    // the instantiation. extend_code: -1 = batch, -(stack*10 + blocks) = two-phase.
-    auto extend2_code = [&]() -> int {
-        const int need = (int)s->stack_need_extend2;
-        if (need > 32) return 0;
-        // four blocks per CU where the LDS allows it (stacks of 16 and 20 entries): the kernel then runs at 128 registers with
-        // 64 B of spills per lane and is still 7.5 % faster than at three blocks and 149 registers (round 2; in round 1, at
-        // 166 registers, the same bound meant 168 B of spills and lost 11 %)
-        // [r3, last] stacks of <= 16 entries: blocks of 128 threads over 1024-slot windows (code 2164, eight blocks per CU) — with the
-        // queue's end in half windows the smaller block's shorter barrier waits win on every pool size: K2 -1.0 % (16.8 M slots), -1.8 %
-        // (67 M, 134 M) against 256 threads; 64 threads: +1 % / -2.0 % / -2.5 % (worse on shallow pools); 512 threads: +5 %
-        int code = need <= 16 ? 2164 : need <= 20 ? 204 : need <= 24 ? 243 : need <= 28 ? 283 : 323;
-        if (const char* e = exp_env("PT_EXT2")) {
-            const int c = atoi(e);
-            if (c / 10 >= need && (c == 163 || c == 164 || c == 204 || c == 243 || c == 283 || c == 323)) code = c;
-            if ((c == 1164 || c == 2164 || c == 8164) && need <= 16) code = c;
-        }
-        return code;
-    };
-    int extend_code = (s->n_mesh_entries > 0 && extend2_code() != 0) ? -extend2_code() : -1;
-    if (const char* e = exp_env("PT_K2")) {
-        if (!strcmp(e, "batch")) extend_code = -1;
-        else if (!strcmp(e, "twophase") && extend2_code() != 0) extend_code = -extend2_code();
-    }
-    const int blocks_extend = extend_occupancy_blocks(extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : extend_code), blocks_shade = shade_occupancy_blocks(form);
-    if (blocks_shade < 1) return set_error("pt_render: no k_shade form for this combination of pixel list, environment sampling, sampler and media");
-    const int grid_extend = ctx->n_cus * blocks_extend * mult, grid_shade = ctx->n_cus * blocks_shade * mult;
-
-    pool.accum = d_accum;
-    // dynamic mode: the kernels add into channel planes in work-item (tile) order (PoolD::accum_tiled); k_detile adds them to d_accum
-    const bool tiled = dynamic && !exp_env("PT_ACCUM_LINEAR");
-    if (tiled) {
-        const size_t tb = (size_t)n_tile_pixels64 * 3 * sizeof(double);
-        if (tb > s->tile_accum_bytes) {
-            if (s->tile_accum) (void)hipFree(s->tile_accum);
-            s->tile_accum = nullptr;
-            s->tile_accum_bytes = 0;
-            if (!hip_ok(hipMalloc((void**)&s->tile_accum, tb), "hipMalloc(tiled accumulator)")) return -1;
-            s->tile_accum_bytes = tb;
-        }
-        if (!hip_ok(hipMemsetAsync(s->tile_accum, 0, tb, st), "hipMemset(tiled accumulator)")) return -1;
-        pool.accum = s->tile_accum;
-        pool.accum_tiled = 1u;
-    }
-    pool.inv_width = 1.0 / (double)dc.width;
-    CountersD init_cnt;
+    return d_accum;
+}
+// dynamic mode: the kernels add into channel planes in work-item (tile) order (PoolD::accum_tiled); k_detile adds them to d_accum
+int tiled_accum(pt_scene* s, const Job& job, PoolD& pool) {
+    const size_t tb = (size_t)pool.n_tile_pixels * 3 * sizeof(double);
+    if (!s->tile_accum.reserve(tb, "hipMalloc(tiled accumulator)")) return -1;
+    if (!hip_ok(hipMemsetAsync(s->tile_accum.as<double>(), 0, tb, job.st), "hipMemset(tiled accumulator)")) return -1;
+    pool.accum = s->tile_accum.as<double>();
+    pool.accum_tiled = 1u;
+    return 0;
+}
+// (init_cnt is the caller's: the copy is asynchronous, so it has to live until the render's next synchronise)
+int start_counters(pt_scene* s, const Job& job, uint32_t n_slots, CountersD& init_cnt) {
     memset(&init_cnt, 0, sizeof init_cnt);
-    init_cnt.alive = spp == 0 ? 0 : n_slots;   // every slot starts with one sample (k <= spp / n_slots <= total_work)
+    init_cnt.alive = job.spp == 0 ? 0 : n_slots;   // every slot starts with one sample (k <= spp / n_slots <= total_work)
     for (uint32_t sh = 0; sh < WORK_SHARDS; ++sh) {   // dynamic mode: items 0 .. n_slots-1 were handed out by k_init
         const uint64_t row = (uint64_t)WORK_SHARDS * 64, rows = n_slots / row, rem = n_slots % row;
         const uint64_t part = rem > (uint64_t)sh * 64 ? std::min<uint64_t>(rem - (uint64_t)sh * 64, 64) : 0;
         init_cnt.work[sh].next = rows * 64 + part;
     }
-    if (!hip_ok(hipMemcpyAsync(s->d_counters, &init_cnt, sizeof init_cnt, hipMemcpyHostToDevice, st), "hipMemcpy(counters)")) return -1;
+    return hip_ok(hipMemcpyAsync(s->d_counters, &init_cnt, sizeof init_cnt, hipMemcpyHostToDevice, job.st), "hipMemcpy(counters)") ? 0 : -1;
+}
 
-    EventTimer timer;
-    timer.enabled = opts.profile != 0;
-    auto t0 = std::chrono::steady_clock::now();
+// the frame's end: once half of the slots still covered are dead the survivors move to the front and the launches shrink with them
+// (k_compact_scan / k_compact_move). The count is the last poll's — stale only towards MORE live slots, which errs on the safe side.
+int compact_pool(pt_scene* s, hipStream_t st, uint64_t n_alive, PoolD& pool, EventTimer& timer) {
+    const uint32_t new_end = (uint32_t)((n_alive + 8191) & ~(uint64_t)8191);
+    const uint32_t cap = new_end;                                  // holes and movers are both at most the live count
+    if (!s->compact_scratch.reserve((2 * (size_t)cap + 2) * sizeof(uint32_t), "hipMalloc(compaction lists)")) return -1;
+    uint32_t* scratch = s->compact_scratch.as<uint32_t>();
+    timer.begin(2, st);
+    launch_compact(pool, new_end, scratch, scratch + cap, scratch + 2 * (size_t)cap, cap, s->ctx->n_cus * 8, st);
+    timer.end(st);
+    pool.n_alloc = new_end;
+    pool.n_slots = std::min(pool.n_slots, new_end);
+    return 0;
+}
+
+struct RunResult { uint64_t iterations = 0; uint32_t compactions = 0; double ms_total = 0.0; };
+// init -> {extend, shade}* -> detile / resolve on the job's stream, with a poll of the live-slot counter every few iterations
+int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPlan& p, const Kernels& kn, PoolD& pool, double* d_accum, EventTimer& timer,
+                  RunResult& r) {
+    hipStream_t st = job.st;
+    const CamD& dc = job.dc;
     (void)hipStreamSynchronize(st);
-    t0 = std::chrono::steady_clock::now();
+    const auto t0 = std::chrono::steady_clock::now();
 
     timer.begin(2, st);
-    if (!launch_init(dc, pool, seed, grid_shade, st, form)) return set_error("pt_render: no k_init form for this render");
+    if (!launch_init(dc, pool, job.seed, kn.grid_shade, st, kn.form)) return set_error("pt_render: no k_init form for this render");
     timer.end(st);
-    uint64_t iterations = 0;
-    const uint64_t per_slot = dynamic ? (total_work + n_slots - 1) / std::max<uint64_t>(n_slots, 1) + 1 : (spp + k - 1) / k;
+    const uint64_t per_slot = p.dynamic ? (p.total_work + p.n_slots - 1) / std::max<uint64_t>(p.n_slots, 1) + 1 : (job.spp + p.k - 1) / p.k;
     const uint64_t max_iterations = per_slot * ((uint64_t)std::max(1u, dc.max_depth) + 1) + 4;   // + 1: a parked slot idles one iteration
     uint32_t poll_every = 8;
-    const bool compact_ok = dynamic && !exp_env("PT_NO_COMPACT_POOL");
-    uint32_t compactions = 0;
-    uint64_t compact_num = 1, compact_den = 2;      // compact when live <= num/den of the slots still covered (25 % .. 85 % measured level: within 0.5 %)
-    uint32_t poll_cap = 8;
-    if (const char* e = exp_env("PT_COMPACT_AT")) { compact_num = (uint64_t)std::max(1, atoi(e)); compact_den = 100; }   // per cent
-    if (const char* e = exp_env("PT_POLL_CAP")) poll_cap = (uint32_t)std::max(1, atoi(e));
-    bool alive = spp != 0 && dc.max_depth != 0;
-    if (spp != 0 && dc.max_depth == 0) {
-        // max_depth = 0: trace() returns zero radiance for every sample (camera.rs:177); nothing to launch
-        alive = false;
-    }
+    const bool compact_ok = p.dynamic && !sw.no_compact_pool;
+    // max_depth = 0: trace() returns zero radiance for every sample (camera.rs:177); nothing to launch
+    bool alive = job.spp != 0 && dc.max_depth != 0;
     while (alive) {
         for (uint32_t i = 0; i < poll_every; ++i) {
             timer.begin(0, st);
-            launch_extend(s->dev.view, pool, s->d_counters, grid_extend, extend_code, st);
+            launch_extend(s->dev.view, pool, s->d_counters, kn.grid_extend, kn.extend_code, st);
             timer.end(st);
             timer.begin(1, st);
-            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, seed, grid_shade, form, st, wide_window_min, mode_has_table(mode) ? &env : nullptr)) return set_error("pt_render: no k_shade form for this render");
+            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, job.seed, kn.grid_shade, kn.form, st, sw.wide_window_min, mode_has_table(job.mode) ? &job.env : nullptr))
+                return set_error("pt_render: no k_shade form for this render");
             timer.end(st);
-            if (ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
+            if (kn.ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
                 std::swap(pool.ray, pool.ray_out);
                 std::swap(pool.path, pool.path_out);
                 std::swap(pool.bounce, pool.bounce_out);
             }
-            ++iterations;
+            ++r.iterations;
         }
         if (!hip_ok(hipMemcpyAsync(s->h_counters, s->d_counters, sizeof(CountersD), hipMemcpyDeviceToHost, st), "hipMemcpy(counters)")) return -1;
         if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(render)")) return -1;
         timer.drain();
         const uint64_t n_alive = s->h_counters->alive;
         alive = n_alive != 0;
-        if (alive && iterations > max_iterations + 128) return set_error("pt_render: iteration bound exceeded (internal error)");
-        if (poll_every < poll_cap) poll_every *= 2;     // (a poll is a pipeline drain of some tens of microseconds: every 8 iterations costs <= 0.5 %)
-        // the frame's end: once half of the slots still covered are dead the survivors move to the front and the launches shrink with them
-        // (k_compact_scan / k_compact_move). The count is the last poll's — stale only towards MORE live slots, which errs on the safe side.
-        if (compact_ok && alive && n_alive * compact_den <= (uint64_t)pool.n_alloc * compact_num && pool.n_alloc > 4 * 8192u) {
-            const uint32_t new_end = (uint32_t)((n_alive + 8191) & ~(uint64_t)8191);
-            const uint32_t cap = new_end;                                  // holes and movers are both at most the live count
-            const size_t words = 2 * (size_t)cap + 2;
-            if (words > s->compact_scratch_words) {
-                if (s->compact_scratch) (void)hipFree(s->compact_scratch);
-                s->compact_scratch = nullptr;
-                s->compact_scratch_words = 0;
-                if (!hip_ok(hipMalloc((void**)&s->compact_scratch, words * sizeof(uint32_t)), "hipMalloc(compaction lists)")) return -1;
-                s->compact_scratch_words = words;
-            }
-            timer.begin(2, st);
-            launch_compact(pool, new_end, s->compact_scratch, s->compact_scratch + cap, s->compact_scratch + 2 * (size_t)cap, cap, ctx->n_cus * 8, st);
-            timer.end(st);
-            pool.n_alloc = new_end;
-            pool.n_slots = std::min(pool.n_slots, new_end);
-            ++compactions;
+        if (alive && r.iterations > max_iterations + 128) return set_error("pt_render: iteration bound exceeded (internal error)");
+        if (poll_every < sw.poll_cap) poll_every *= 2;     // (a poll is a pipeline drain of some tens of microseconds: every 8 iterations costs <= 0.5 %)
+        if (compact_ok && alive && n_alive * sw.compact_den <= (uint64_t)pool.n_alloc * sw.compact_num && pool.n_alloc > 4 * 8192u) {
+            if (compact_pool(s, st, n_alive, pool, timer) != 0) return -1;
+            ++r.compactions;
         }
     }
-    if (!dynamic || tiled) {
+    if (!p.dynamic || pool.accum_tiled) {
         timer.begin(2, st);
-        if (tiled) launch_detile(pool, d_accum, ctx->n_cus * 8, st);
-        else launch_resolve(pool, d_accum, ctx->n_cus * 8, st);
+        if (pool.accum_tiled) launch_detile(pool, d_accum, s->ctx->n_cus * 8, st);
+        else launch_resolve(pool, d_accum, s->ctx->n_cus * 8, st);
         timer.end(st);
     }
     if (!hip_ok(hipMemcpyAsync(s->h_counters, s->d_counters, sizeof(CountersD), hipMemcpyDeviceToHost, st), "hipMemcpy(counters)")) return -1;
     if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(resolve)")) return -1;
     timer.drain();
-    auto t1 = std::chrono::steady_clock::now();
-    if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
+    r.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return hip_ok(hipGetLastError(), "kernel launch") ? 0 : -1;
+}
 
-    if (!opts.accum_on_device && list) {   // only the listed pixels of the caller's frame are written
-        std::vector<double> tmp((size_t)n_pixels * 3);
-        if (!hip_ok(hipMemcpy(tmp.data(), d_accum, accum_bytes, hipMemcpyDeviceToHost), "hipMemcpy(accum)")) return -1;
-        for (uint32_t i = 0; i < n_list; ++i)
+// a host accumulator gets the frame back: the whole of it, or only the listed pixels of the caller's frame
+int copy_back(const Job& job, const double* d_accum, double* accum) {
+    if (job.opts.accum_on_device) return 0;
+    const size_t n = (size_t)job.n_pixels * 3, bytes = n * sizeof(double);
+    if (job.opts.overwrite && !job.list) return hip_ok(hipMemcpy(accum, d_accum, bytes, hipMemcpyDeviceToHost), "hipMemcpy(accum)") ? 0 : -1;
+    std::vector<double> tmp(n);
+    if (!hip_ok(hipMemcpy(tmp.data(), d_accum, bytes, hipMemcpyDeviceToHost), "hipMemcpy(accum)")) return -1;
+    if (job.list) {
+        for (uint32_t i = 0; i < job.n_list; ++i)
             for (uint32_t c = 0; c < 3; ++c) {
-                const size_t j = 3 * (size_t)h_list[i] + c;
-                accum[j] = opts.overwrite ? tmp[j] : accum[j] + tmp[j];
+                const size_t j = 3 * (size_t)job.h_list[i] + c;
+                accum[j] = job.opts.overwrite ? tmp[j] : accum[j] + tmp[j];
             }
-    } else if (!opts.accum_on_device) {
-        if (opts.overwrite) {
-            if (!hip_ok(hipMemcpy(accum, d_accum, accum_bytes, hipMemcpyDeviceToHost), "hipMemcpy(accum)")) return -1;
-        } else {
-            std::vector<double> tmp((size_t)n_pixels * 3);
-            if (!hip_ok(hipMemcpy(tmp.data(), d_accum, accum_bytes, hipMemcpyDeviceToHost), "hipMemcpy(accum)")) return -1;
-            for (size_t i = 0; i < tmp.size(); ++i) accum[i] += tmp[i];
-        }
-    }
-    if (exp_env("PT_PROF")) {   // diagnostic builds (-DPT_STAMPS): wave-cycle sums per k_shade class
-        static const char* names[N_CLASSES + 1] = {"miss", "diffuse", "metal", "glass", "principled", "light", "sheen", "clearcoat", "mix", "idle", "dead", "WINDOW"};
-        for (uint32_t c = 0; c <= N_CLASSES; ++c) {
-            const unsigned long long* p = s->h_counters->prof[c];
-            if (p[0] && c == CLASS_DEAD)
-                fprintf(stderr, "[pt prof] K2 window  n %10llu  phase A %8.0f  barrier %8.0f  phase B %8.0f  barrier %8.0f  candidates %6.1f (cycles per window and wave)\n", p[0],
-                        (double)p[1] / p[0], (double)p[2] / p[0], (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]);
-            else if (p[0] && c < N_CLASSES)
-                fprintf(stderr, "[pt prof] %-10s n %10llu  body %8.0f = hit %7.0f + env/tex %7.0f + direction %7.0f + pdf/eval/ray %7.0f  dequeue %8.0f  regen+store %8.0f  whole %8.0f (cycles per wave-group)\n",
-                        names[c], p[0], (double)p[2] / p[0], (double)p[1] / p[0], (double)p[6] / p[0], (double)p[7] / p[0], (double)(p[2] - p[1] - p[6] - p[7]) / p[0],
-                        (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]),
-                fprintf(stderr, "[pt prof] %-10s   lanes per group: live %5.1f  on a surface %5.1f  with a next direction %5.1f  regenerated %5.1f\n", names[c], (double)p[8] / p[0],
-                        (double)p[9] / p[0], (double)p[10] / p[0], (double)p[11] / p[0])
-#ifdef PT_STAMPS
-                , fprintf(stderr, "[pt prof] %-10s   groups of one primitive %10llu (%5.1f %%), of one sphere / quad %10llu (%5.1f %%)\n", names[c], p[12], 100.0 * (double)p[12] / p[0],
-                          p[13], 100.0 * (double)p[13] / p[0])
-#endif
-                ;
-            else if (p[0])
-                fprintf(stderr, "[pt prof] WINDOW     n %10llu  sort %8.0f  shade %8.0f  barrier wait %8.0f  groups %8.0f  record wait %8.0f (cycles per window and wave)\n", p[0],
-                        (double)p[1] / p[0], (double)p[2] / p[0], (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]);
-        }
-    }
-    if (stats) {
-        memset(stats, 0, sizeof *stats);
-        stats->samples = s->h_counters->samples;
-        stats->segments = s->h_counters->segments;
-        stats->iterations = iterations;
-        stats->n_slots = n_slots;
-        stats->slots_per_pixel = dynamic ? 0u : k;
-        stats->ms_total = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        stats->ms_extend = timer.ms[0];
-        stats->ms_shade = timer.ms[1];
-        stats->ms_other = timer.ms[2];
-        stats->launches_extend = timer.launches[0];
-        stats->launches_shade = timer.launches[1];
-        stats->extend_variant = extend_code <= -100 ? 0u : 1u;
-        stats->shade_variant = (uint32_t)shade_variant;
-        stats->blocks_extend = (uint32_t)grid_extend;
-        stats->blocks_shade = (uint32_t)grid_shade;
-        stats->compactions = compactions;
-        stats->n_alloc_end = pool.n_alloc;
+    } else {
+        for (size_t i = 0; i < n; ++i) accum[i] += tmp[i];
     }
     return 0;
 }
+
+// PT_PROF, diagnostic builds (-DPT_STAMPS): wave-cycle sums per k_shade class
+void print_prof(const CountersD* cnt) {
+    static const char* names[N_CLASSES + 1] = {"miss", "diffuse", "metal", "glass", "principled", "light", "sheen", "clearcoat", "mix", "idle", "dead", "WINDOW"};
+    for (uint32_t c = 0; c <= N_CLASSES; ++c) {
+        const unsigned long long* p = cnt->prof[c];
+        if (p[0] && c == CLASS_DEAD)
+            fprintf(stderr, "[pt prof] K2 window  n %10llu  phase A %8.0f  barrier %8.0f  phase B %8.0f  barrier %8.0f  candidates %6.1f (cycles per window and wave)\n", p[0],
+                    (double)p[1] / p[0], (double)p[2] / p[0], (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]);
+        else if (p[0] && c < N_CLASSES)
+            fprintf(stderr, "[pt prof] %-10s n %10llu  body %8.0f = hit %7.0f + env/tex %7.0f + direction %7.0f + pdf/eval/ray %7.0f  dequeue %8.0f  regen+store %8.0f  whole %8.0f (cycles per wave-group)\n",
+                    names[c], p[0], (double)p[2] / p[0], (double)p[1] / p[0], (double)p[6] / p[0], (double)p[7] / p[0], (double)(p[2] - p[1] - p[6] - p[7]) / p[0],
+                    (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]),
+            fprintf(stderr, "[pt prof] %-10s   lanes per group: live %5.1f  on a surface %5.1f  with a next direction %5.1f  regenerated %5.1f\n", names[c], (double)p[8] / p[0],
+                    (double)p[9] / p[0], (double)p[10] / p[0], (double)p[11] / p[0])
+#ifdef PT_STAMPS
+            , fprintf(stderr, "[pt prof] %-10s   groups of one primitive %10llu (%5.1f %%), of one sphere / quad %10llu (%5.1f %%)\n", names[c], p[12], 100.0 * (double)p[12] / p[0],
+                      p[13], 100.0 * (double)p[13] / p[0])
+#endif
+            ;
+        else if (p[0])
+            fprintf(stderr, "[pt prof] WINDOW     n %10llu  sort %8.0f  shade %8.0f  barrier wait %8.0f  groups %8.0f  record wait %8.0f (cycles per window and wave)\n", p[0],
+                    (double)p[1] / p[0], (double)p[2] / p[0], (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]);
+    }
+}
+
+void fill_stats(const pt_scene* s, const PoolPlan& p, const Kernels& kn, const PoolD& pool, const EventTimer& timer, const RunResult& r, pt_render_stats* stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->samples = s->h_counters->samples;
+    stats->segments = s->h_counters->segments;
+    stats->iterations = r.iterations;
+    stats->n_slots = p.n_slots;
+    stats->slots_per_pixel = p.dynamic ? 0u : p.k;
+    stats->ms_total = r.ms_total;
+    stats->ms_extend = timer.ms[0];
+    stats->ms_shade = timer.ms[1];
+    stats->ms_other = timer.ms[2];
+    stats->launches_extend = timer.launches[0];
+    stats->launches_shade = timer.launches[1];
+    stats->extend_variant = kn.extend_code <= -100 ? 0u : 1u;
+    stats->shade_variant = (uint32_t)kn.form.variant;
+    stats->blocks_extend = (uint32_t)kn.grid_extend;
+    stats->blocks_shade = (uint32_t)kn.grid_shade;
+    stats->compactions = r.compactions;
+    stats->n_alloc_end = pool.n_alloc;
+}
+// the statistics of an adaptive render: its passes' counts and times added up, the pool and the kernels of the last pass
+void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
+    sum.samples += ps.samples;
+    sum.segments += ps.segments;
+    sum.iterations += ps.iterations;
+    sum.n_slots = std::max(sum.n_slots, ps.n_slots);
+    sum.slots_per_pixel = ps.slots_per_pixel;
+    sum.ms_extend += ps.ms_extend;
+    sum.ms_shade += ps.ms_shade;
+    sum.ms_other += ps.ms_other;
+    sum.launches_extend += ps.launches_extend;
+    sum.launches_shade += ps.launches_shade;
+    sum.extend_variant = ps.extend_variant;
+    sum.shade_variant = ps.shade_variant;
+    sum.blocks_extend = ps.blocks_extend;
+    sum.blocks_shade = ps.blocks_shade;
+    sum.compactions += ps.compactions;
+    sum.n_alloc_end = ps.n_alloc_end;
+}
+
+// The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
+// pixels) / n_list: a pixel-list render (PoolD::list; d_list sorted by tiled index, n_list > 0), or null: the whole frame — then the
+// path below is exactly pt_render's. When several things are wrong at once the first refusal in this order is the one returned:
+// arguments, camera, size, mode, pool, then form.
+int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum, const pt_render_opts* opts_in,
+                pt_render_stats* stats, const uint32_t* d_list, const uint32_t* h_list, uint32_t n_list) {
+    if (!s || !s->built) return set_error("pt_render: world not built (call pt_world_build)");
+    if (!accum) return set_error("pt_render: null accumulator");
+    if (spp_end < spp_begin) return set_error("pt_render: spp_end < spp_begin");
+    Job job;
+    memset(&job.opts, 0, sizeof job.opts);
+    if (opts_in) job.opts = *opts_in;
+    if (!hip_ok(hipSetDevice(s->ctx->device), "hipSetDevice")) return -1;
+    job.st = job.opts.stream ? (hipStream_t)job.opts.stream : s->ctx->stream;
+    job.seed = seed;
+    job.spp_begin = spp_begin; job.spp_end = spp_end; job.spp = spp_end - spp_begin;
+    job.d_list = d_list; job.h_list = h_list; job.n_list = n_list; job.list = d_list != nullptr;
+    if (make_camd(s, cam, job.dc) != 0) return -1;
+    const uint64_t n_pixels64 = (uint64_t)job.dc.width * job.dc.height;
+    if (n_pixels64 == 0 || n_pixels64 > 0x7FFFFFFFull) return set_error("pt_render: bad image size");
+    job.n_pixels = (uint32_t)n_pixels64;
+    job.n_items = job.list ? n_list : job.n_pixels;
+    memset(&job.env, 0, sizeof job.env);
+    if (render_mode(s, job.dc, job.st, job.mode, job.env) != 0) return -1;
+
+    const Switches sw = read_switches(job.opts);
+    PoolPlan plan;
+    if (plan_pool(sw, job, s->ctx->n_cus, plan) != 0) return -1;
+    const Kernels kn = choose_kernels(sw, s, job, plan);
+    PoolD pool;
+    if (bind_pool(s, sw, job, plan, kn, pool) != 0) return -1;
+    DevMem own_accum;
+    double* d_accum = device_accum(job, accum, own_accum);
+    if (!d_accum) return -1;
+    // (refused here and no earlier: a failed allocation above has always been reported first)
+    if (kn.blocks_shade < 1) return set_error("pt_render: no k_shade form for this combination of pixel list, environment sampling, sampler and media");
+    pool.accum = d_accum;
+    if (plan.dynamic && !sw.accum_linear && tiled_accum(s, job, pool) != 0) return -1;
+    CountersD init_cnt;
+    if (start_counters(s, job, plan.n_slots, init_cnt) != 0) return -1;
+
+    EventTimer timer;
+    timer.enabled = job.opts.profile != 0;
+    RunResult run;
+    if (run_wavefront(s, sw, job, plan, kn, pool, d_accum, timer, run) != 0) return -1;
+    if (copy_back(job, d_accum, accum) != 0) return -1;
+    if (sw.prof) print_prof(s->h_counters);
+    if (stats) fill_stats(s, plan, kn, pool, timer, run, stats);
+    return 0;
+}
+}  // namespace
 
 extern "C" int pt_render(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* accum,
                          const pt_render_opts* opts, pt_render_stats* stats) {
@@ -648,16 +756,6 @@ namespace {
 uint32_t tiled_key(uint32_t p, uint32_t width, uint32_t tiles_x) {   // row-major pixel -> its tiled index (k_detile's tiled_index)
     const uint32_t y = p / width, x = p % width;
     return ((y >> 3) * tiles_x + (x >> 3)) * 64u + ((y & 7u) << 3) + (x & 7u);
-}
-// the scene's device pixel list (re-used like tile_accum), at least n entries
-bool pixel_list_buffer(pt_scene* s, size_t n) {
-    if (n <= s->pixel_list_words) return true;
-    if (s->pixel_list) (void)hipFree(s->pixel_list);
-    s->pixel_list = nullptr;
-    s->pixel_list_words = 0;
-    if (!hip_ok(hipMalloc((void**)&s->pixel_list, n * sizeof(uint32_t)), "hipMalloc(pixel list)")) return false;
-    s->pixel_list_words = n;
-    return true;
 }
 }  // namespace
 
@@ -684,9 +782,9 @@ extern "C" int pt_render_pixels(pt_scene* s, const pt_camera* cam, uint64_t seed
     std::vector<uint32_t> sorted(pixels, pixels + n);
     std::sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return tiled_key(a, width, tiles_x) < tiled_key(b, width, tiles_x); });
     if (!hip_ok(hipSetDevice(s->ctx->device), "hipSetDevice")) return -1;
-    if (!pixel_list_buffer(s, n)) return -1;
-    if (!hip_ok(hipMemcpy(s->pixel_list, sorted.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(pixel list)")) return -1;
-    return render_core(s, cam, seed, spp_begin, spp_end, accum, opts, stats, s->pixel_list, sorted.data(), n);
+    if (!s->pixel_list.reserve((size_t)n * sizeof(uint32_t), "hipMalloc(pixel list)")) return -1;   // (re-used like the pool)
+    if (!hip_ok(hipMemcpy(s->pixel_list.as<uint32_t>(), sorted.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(pixel list)")) return -1;
+    return render_core(s, cam, seed, spp_begin, spp_end, accum, opts, stats, s->pixel_list.as<uint32_t>(), sorted.data(), n);
 }
 
 extern "C" int pt_adaptive_schedule(uint32_t min_spp, uint32_t max_spp, uint32_t* bounds, uint32_t cap) {
@@ -733,12 +831,9 @@ extern "C" int pt_render_adaptive(pt_scene* s, const pt_camera* cam, uint64_t se
     // device state: E, O (3 f64 per pixel each), the error map, two pixel lists, the stop counts, the select kernels' block counts
     const uint32_t n_blocks = adapt_select_blocks(width, height);
     const size_t f64s = (size_t)n_pixels * 7, u32s = (size_t)n_pixels * 3 + n_blocks + 1;
-    struct Mem {
-        void* p = nullptr;
-        ~Mem() { if (p) (void)hipFree(p); }
-    } mem;
-    if (!hip_ok(hipMalloc(&mem.p, f64s * sizeof(double) + u32s * sizeof(uint32_t)), "hipMalloc(adaptive state)")) return -1;
-    double* E = (double*)mem.p;
+    DevMem mem;
+    if (!mem.alloc(f64s * sizeof(double) + u32s * sizeof(uint32_t), "hipMalloc(adaptive state)")) return -1;
+    double* E = mem.as<double>();
     double* O = E + 3 * (size_t)n_pixels;
     double* err = O + 3 * (size_t)n_pixels;
     uint32_t* list_a = (uint32_t*)(err + n_pixels);
@@ -777,22 +872,7 @@ extern "C" int pt_render_adaptive(pt_scene* s, const pt_camera* cam, uint64_t se
         const uint32_t lo = b[(size_t)i], hi = b[(size_t)i + 1];
         pt_render_stats ps;
         if (render_core(s, cam, seed, lo, hi, (i & 1) ? O : E, &po, &ps, list_a, nullptr, n_active) != 0) return -1;
-        sum.samples += ps.samples;
-        sum.segments += ps.segments;
-        sum.iterations += ps.iterations;
-        sum.n_slots = std::max(sum.n_slots, ps.n_slots);
-        sum.slots_per_pixel = ps.slots_per_pixel;
-        sum.ms_extend += ps.ms_extend;
-        sum.ms_shade += ps.ms_shade;
-        sum.ms_other += ps.ms_other;
-        sum.launches_extend += ps.launches_extend;
-        sum.launches_shade += ps.launches_shade;
-        sum.extend_variant = ps.extend_variant;
-        sum.shade_variant = ps.shade_variant;
-        sum.blocks_extend = ps.blocks_extend;
-        sum.blocks_shade = ps.blocks_shade;
-        sum.compactions += ps.compactions;
-        sum.n_alloc_end = ps.n_alloc_end;
+        add_stats(sum, ps);
         ((i & 1) ? n_o : n_e) += (double)(hi - lo);
         if (i >= 1 && hi < max_spp) {   // the test: who goes on into round i + 1
             launch_adapt_error(E, O, stop, n_pixels, n_e, n_o, err, st);
@@ -813,31 +893,6 @@ extern "C" int pt_render_adaptive(pt_scene* s, const pt_camera* cam, uint64_t se
     return 0;
 }
 
-extern "C" int pt_resolve_u8_counts(pt_ctx* ctx, const double* accum, uint32_t n_pixels, const uint32_t* spp_per_pixel, uint8_t* rgb8) {
-    if (!ctx) return set_error("pt_resolve_u8_counts: null context");
-    if (!accum || !spp_per_pixel || !rgb8) return set_error("pt_resolve_u8_counts: null buffer");
-    for (uint32_t p = 0; p < n_pixels; ++p)
-        if (spp_per_pixel[p] == 0) return set_error("pt_resolve_u8_counts: a pixel has no samples");
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    const size_t n = (size_t)n_pixels * 3;
-    double* d_in = nullptr;
-    uint32_t* d_cnt = nullptr;
-    uint8_t* d_out = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_in, n * sizeof(double) + 8), "hipMalloc") && hip_ok(hipMalloc((void**)&d_cnt, (size_t)n_pixels * 4 + 4), "hipMalloc") &&
-              hip_ok(hipMalloc((void**)&d_out, n + 1), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_in, accum, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy") &&
-              hip_ok(hipMemcpyAsync(d_cnt, spp_per_pixel, (size_t)n_pixels * 4, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_quantise_counts(d_in, n_pixels, d_cnt, d_out, ctx->stream);
-        ok = hip_ok(hipMemcpyAsync(rgb8, d_out, n, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_in) (void)hipFree(d_in);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (d_out) (void)hipFree(d_out);
-    return ok ? 0 : -1;
-}
-
 extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov,
                               const pt_render_opts* opts_in) {
     if (!s || !s->built) return set_error("pt_render_aovs: world not built (call pt_world_build)");
@@ -855,14 +910,11 @@ extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, 
     const uint64_t n_pixels = (uint64_t)dc.width * dc.height;
     if (n_pixels == 0 || n_pixels > 0x7FFFFFFFull) return set_error("pt_render_aovs: bad image size");
     const size_t bytes = (size_t)n_pixels * 8 * sizeof(double);
-    struct Mem {
-        double* p = nullptr;
-        ~Mem() { if (p) (void)hipFree(p); }
-    } own;
+    DevMem own;
     double* d_aov = aov;
     if (!opts.accum_on_device) {   // a host buffer: its sums travel to the device and back, the kernel adds to them there
-        if (!hip_ok(hipMalloc((void**)&own.p, bytes), "hipMalloc(aov)")) return -1;
-        d_aov = own.p;
+        if (!own.alloc(bytes, "hipMalloc(aov)")) return -1;
+        d_aov = own.as<double>();
         if (!opts.overwrite && !hip_ok(hipMemcpyAsync(d_aov, aov, bytes, hipMemcpyHostToDevice, st), "hipMemcpy(aov)")) return -1;
     }
     ShadeForm aov_form;   // of a form, the AOV walk looks at the sampler only
@@ -872,388 +924,4 @@ extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, 
     if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
     if (!opts.accum_on_device && !hip_ok(hipMemcpyAsync(aov, d_aov, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(aov)")) return -1;
     return hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(aov)") ? 0 : -1;
-}
-
-extern "C" int pt_denoise(pt_ctx* ctx, uint32_t width, uint32_t height, const double* sum_a, uint32_t n_a, const double* sum_b, uint32_t n_b,
-                          const double* aov, uint32_t n_aov, const pt_denoise_opts* opts_in, double* out) {
-    if (!ctx) return set_error("pt_denoise: null context");
-    if (!sum_a || !sum_b || !aov || !out) return set_error("pt_denoise: null buffer");
-    if (width == 0 || height == 0) return set_error("pt_denoise: width and height must be positive");
-    if ((uint64_t)width * height > 0x7FFFFFFFull) return set_error("pt_denoise: image too large");
-    if (n_a == 0 || n_b == 0 || n_aov == 0) return set_error("pt_denoise: n_a, n_b and n_aov must be positive");
-    pt_denoise_opts o{5u, 4.0, 0.1};
-    if (opts_in) o = *opts_in;
-    if (o.iterations > 10) return set_error("pt_denoise: at most 10 iterations");
-    if (!(o.sigma_l > 0.0) || !(o.sigma_z > 0.0)) return set_error("pt_denoise: sigma_l and sigma_z must be positive");
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    const size_t n = (size_t)width * height;
-    // scratch (12 per pixel: two colour + variance buffers and the guides, 32-B records: first), sum_a, sum_b, out (3 each), aov (8)
-    struct Mem {
-        double* p = nullptr;
-        ~Mem() { if (p) (void)hipFree(p); }
-    } mem;
-    if (!hip_ok(hipMalloc((void**)&mem.p, n * 29 * sizeof(double)), "hipMalloc(denoise)")) return -1;
-    double* d_tmp = mem.p;
-    double* d_a = d_tmp + 12 * n;
-    double* d_b = d_a + 3 * n;
-    double* d_out = d_b + 3 * n;
-    double* d_aov = d_out + 3 * n;
-    hipStream_t st = ctx->stream;
-    if (!hip_ok(hipMemcpyAsync(d_a, sum_a, 3 * n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(sum_a)") ||
-        !hip_ok(hipMemcpyAsync(d_b, sum_b, 3 * n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(sum_b)") ||
-        !hip_ok(hipMemcpyAsync(d_aov, aov, 8 * n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(aov)"))
-        return -1;
-    launch_denoise(width, height, d_a, (double)n_a, d_b, (double)n_b, d_aov, (double)n_aov, o.iterations, o.sigma_l, o.sigma_z, d_tmp, d_out, st);
-    if (!hip_ok(hipGetLastError(), "kernel launch") ||
-        !hip_ok(hipMemcpyAsync(out, d_out, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(out)") ||
-        !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(denoise)"))
-        return -1;
-    return 0;
-}
-
-// The film stage (include/pt_amd.h has the rule; the kernels: pt_film.hip). Everything that can refuse the call is checked before the
-// first device call, so a refused call writes nothing.
-static pt_film_opts film_defaults() {
-    pt_film_opts o;
-    memset(&o, 0, sizeof o);
-    o.white = 4.0; o.bloom_threshold = 1.0; o.bloom_sigma = 2.0; o.bloom_levels = 5u;
-    return o;
-}
-extern "C" int pt_film_opts_check(const pt_film_opts* opts) {
-    const pt_film_opts o = opts ? *opts : film_defaults();
-    if (!std::isfinite(o.exposure_ev) || std::fabs(o.exposure_ev) > 100.0) return set_error("pt_film_develop: exposure_ev must be finite and within +-100");
-    if (o.tonemap > 3u) return set_error("pt_film_develop: tonemap must be 0 (reference), 1 (srgb), 2 (reinhard) or 3 (aces)");
-    if (!std::isfinite(o.white) || !(o.white >= 1e-3)) return set_error("pt_film_develop: white must be finite and >= 1e-3");
-    if (!(o.bloom_strength >= 0.0 && o.bloom_strength <= 1.0)) return set_error("pt_film_develop: bloom_strength must be in [0, 1]");
-    if (!std::isfinite(o.bloom_threshold) || !(o.bloom_threshold >= 0.0)) return set_error("pt_film_develop: bloom_threshold must be finite and >= 0");
-    if (!(o.bloom_sigma >= 0.5 && o.bloom_sigma <= 64.0)) return set_error("pt_film_develop: bloom_sigma must be in [0.5, 64]");
-    if (o.bloom_levels < 1u || o.bloom_levels > 6u || !(o.bloom_sigma * (double)(1u << (o.bloom_levels - 1u)) <= 128.0))
-        return set_error("pt_film_develop: bloom_levels must be in 1..6 with bloom_sigma * 2^(levels - 1) <= 128");
-    return 0;
-}
-extern "C" int pt_film_develop(pt_ctx* ctx, uint32_t width, uint32_t height, const double* sums, uint32_t total_spp, const uint32_t* counts,
-                               const pt_film_opts* opts_in, double* hdr_out, uint8_t* rgb8_out) {
-    if (!ctx) return set_error("pt_film_develop: null context");
-    if (!sums) return set_error("pt_film_develop: null sums");
-    if (!hdr_out && !rgb8_out) return set_error("pt_film_develop: both outputs are null");
-    if (width == 0 || height == 0) return set_error("pt_film_develop: width and height must be positive");
-    if ((uint64_t)width * height > 0x7FFFFFFFull) return set_error("pt_film_develop: image too large");
-    if (!counts && total_spp == 0) return set_error("pt_film_develop: total_spp must be positive without per-pixel counts");
-    pt_film_opts o = film_defaults();
-    if (opts_in) o = *opts_in;
-    if (pt_film_opts_check(&o) != 0) return -1;
-    const bool glare = o.bloom_strength > 0.0;
-    // (the convolution's grid has one row of blocks per 8 rows of its input, which is the frame and then its transpose)
-    if (glare && std::max(width, height) > 524280u) return set_error("pt_film_develop: with glare, width and height must be at most 524280");
-    const uint32_t n = width * height;
-    if (!o.on_device && counts)
-        for (uint32_t p = 0; p < n; ++p)
-            if (counts[p] == 0) return set_error("pt_film_develop: a pixel has no samples");
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    hipStream_t st = o.stream ? (hipStream_t)o.stream : ctx->stream;
-    const uint32_t L = o.bloom_levels;
-    // the levels' weights, one after the other: k_l[i] = exp(-(i * i) / (2 sigma_l^2)) / their sum
-    std::vector<double> taps;
-    std::vector<uint32_t> radius(L), first(L);
-    if (glare)
-        for (uint32_t l = 0; l < L; ++l) {
-            const double sigma = o.bloom_sigma * (double)(1u << l);
-            const int r = (int)std::ceil(3.0 * sigma);
-            radius[l] = (uint32_t)r;
-            first[l] = (uint32_t)taps.size();
-            double sum = 0.0;
-            for (int i = -r; i <= r; ++i) {
-                const double k = std::exp(-((double)i * (double)i) / (2.0 * sigma * sigma));
-                taps.push_back(k);
-                sum += k;
-            }
-            for (size_t i = first[l]; i < taps.size(); ++i) taps[i] /= sum;
-        }
-    // device memory, doubles first: glare scratch (bright, transposed pass, G: 3 planes each) and the weights; then, for host
-    // buffers, the sums and hdr_out; then the counts and rgb8_out
-    const size_t n3 = (size_t)n * 3;
-    const size_t f64s = (glare ? 3 * n3 + taps.size() : 0) + (o.on_device ? 0 : 2 * n3);
-    const size_t tail = o.on_device ? 0 : (size_t)n * sizeof(uint32_t) + n3;
-    struct Mem {
-        void* p = nullptr;
-        ~Mem() { if (p) (void)hipFree(p); }
-    } mem;
-    if (f64s + tail > 0 && !hip_ok(hipMalloc(&mem.p, f64s * sizeof(double) + tail), "hipMalloc(film)")) return -1;
-    double* at = (double*)mem.p;
-    double *d_bright = nullptr, *d_pass = nullptr, *d_glare = nullptr, *d_taps = nullptr;
-    if (glare) {
-        d_bright = at; d_pass = at + n3; d_glare = at + 2 * n3; d_taps = at + 3 * n3;
-        at += 3 * n3 + taps.size();
-    }
-    const double* d_sums = sums;
-    const uint32_t* d_counts = counts;
-    double* d_hdr = hdr_out;
-    uint8_t* d_rgb = rgb8_out;
-    if (!o.on_device) {
-        double* in = at;
-        d_hdr = hdr_out ? at + n3 : nullptr;
-        uint32_t* cnt = (uint32_t*)(at + 2 * n3);
-        d_rgb = rgb8_out ? (uint8_t*)(cnt + n) : nullptr;
-        if (!hip_ok(hipMemcpyAsync(in, sums, n3 * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(film sums)")) return -1;
-        if (counts && !hip_ok(hipMemcpyAsync(cnt, counts, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st), "hipMemcpy(film counts)")) return -1;
-        d_sums = in;
-        d_counts = counts ? cnt : nullptr;
-    }
-    const double scale = counts ? 0.0 : 1.0 / (double)total_spp;   // pixel_sample_scale camera.rs:53
-    const double k = std::exp2(o.exposure_ev);
-    if (glare) {
-        if (!hip_ok(hipMemcpyAsync(d_taps, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy(film weights)")) return -1;
-        launch_film_prepare(d_sums, n, scale, d_counts, k, o.bloom_threshold, d_bright, st);
-        if (!hip_ok(hipGetLastError(), "k_film_prepare launch")) return -1;
-        for (uint32_t l = 0; l < L; ++l) {   // rows, written transposed; then the columns as rows, transposed back and added into G
-            if (!launch_film_conv(d_bright, d_pass, height, width, radius[l], d_taps + first[l], 1.0, false, st) ||
-                !launch_film_conv(d_pass, d_glare, width, height, radius[l], d_taps + first[l], 1.0 / (double)L, l > 0, st)) {
-                (void)hipStreamSynchronize(st);
-                return set_error("pt_film_develop: no convolution kernel for this radius");
-            }
-            if (!hip_ok(hipGetLastError(), "k_film_conv launch")) {
-                (void)hipStreamSynchronize(st);
-                return -1;
-            }
-        }
-    }
-    launch_film_develop(d_sums, n, scale, d_counts, k, o.bloom_threshold, o.bloom_strength, glare ? d_glare : nullptr, o.tonemap, o.white, d_hdr, d_rgb, st);
-    bool ok = hip_ok(hipGetLastError(), "k_film_develop launch");
-    if (ok && !o.on_device) {
-        if (hdr_out) ok = hip_ok(hipMemcpyAsync(hdr_out, d_hdr, n3 * sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(film hdr)");
-        if (ok && rgb8_out) ok = hip_ok(hipMemcpyAsync(rgb8_out, d_rgb, n3, hipMemcpyDeviceToHost, st), "hipMemcpy(film rgb8)");
-    }
-    return hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(film)") && ok ? 0 : -1;
-}
-
-extern "C" int pt_resolve_u8(pt_ctx* ctx, const double* accum, uint32_t n_pixels, uint32_t total_spp, uint8_t* rgb8) {
-    if (!ctx) return set_error("pt_resolve_u8: null context");
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    const uint32_t n = n_pixels * 3;
-    double* d_in = nullptr;
-    uint8_t* d_out = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_in, (size_t)n * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_out, n), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_in, accum, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_quantise(d_in, n, 1.0 / (double)total_spp, d_out, ctx->stream);   // pixel_sample_scale camera.rs:53
-        ok = hip_ok(hipMemcpyAsync(rgb8, d_out, n, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_intersect(pt_scene* s, const double* rays, uint32_t n, double* out) {
-    if (!s || !s->built) return set_error("pt_intersect: world not built");
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    double *d_r = nullptr, *d_o = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_r, (size_t)n * 7 * sizeof(double) + 8), "hipMalloc") &&
-              hip_ok(hipMalloc((void**)&d_o, (size_t)n * 15 * sizeof(double) + 8), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_r, rays, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_probe(s->dev.view, d_r, n, d_o, ctx->stream);
-        ok = hip_ok(hipMemcpyAsync(out, d_o, (size_t)n * 15 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_r) (void)hipFree(d_r);
-    if (d_o) (void)hipFree(d_o);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_env_probe(pt_scene* s, const pt_camera* cam, int which, const double* in, uint32_t n, double* out) {
-    if (!s || !s->built) return set_error("pt_env_probe: world not built");
-    if (!cam || (which != 0 && which != 1)) return set_error("pt_env_probe: which must be 0 or 1");
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    CamD dc;
-    if (make_camd(s, cam, dc) != 0) return -1;
-    if (!dc.env_is_map) return set_error("pt_env_probe: the camera's environment is not a map");
-    EnvTabD e;
-    if (env_tables(s, dc, ctx->stream, e) != 0) return -1;
-    if (!(e.z > 0.0)) return set_error("pt_env_probe: the environment map has no weight (Z = 0)");
-    TexD T;
-    if (!hip_ok(hipMemcpyAsync(&T, s->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") ||
-        !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
-        return -1;
-    const size_t n_in = (size_t)n * (which == 0 ? 2 : 3), n_out = (size_t)n * (which == 0 ? 4 : 1);
-    double *d_i = nullptr, *d_o = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double) + 8), "hipMalloc") &&
-              hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double) + 8), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_env_probe(s->dev.view, T, e, which, d_i, n, d_o, ctx->stream);
-        ok = hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_i) (void)hipFree(d_i);
-    if (d_o) (void)hipFree(d_o);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_medium_probe(pt_scene* s, int mat, int which, const double* in, uint32_t n, double* out) {
-    if (!s || !s->ctx) return set_error("pt_medium_probe: null scene");
-    if (mat < 0 || (size_t)mat >= s->mats.size() || s->mats[mat].kind != MAT_MEDIUM) return set_error("pt_medium_probe: not a medium material");
-    if (which < 0 || which > 4) return set_error("pt_medium_probe: which must be 0, 1, 2, 3 or 4");
-    const bool grid = which == 2 || which == 3;
-    if (grid && s->mats[mat].p[6] == 0.0) return set_error("pt_medium_probe: which 2 and 3 need a grid-density medium (pt_mat_medium_grid)");
-    if (n == 0) return 0;
-    if (!in || !out) return set_error("pt_medium_probe: null buffer");
-    static const size_t IN_COLS[5] = {5, 1, 3, 7, 1}, OUT_COLS[5] = {4, 1, 1, 3, 3};
-    const size_t n_in = (size_t)n * IN_COLS[which], n_out = (size_t)n * OUT_COLS[which];
-    if (which == 3)   // the loop's expected trip count is bounded for unit directions (pt_mat_medium_grid): longer ones are refused
-        for (uint32_t i = 0; i < n; ++i) {
-            const double* d = in + 7 * (size_t)i + 3;
-            if (!(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= 1.0 + 1e-9)) return set_error("pt_medium_probe: which 3 takes directions of length <= 1");
-        }
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    double *d_i = nullptr, *d_o = nullptr;
-    GridD* d_g = nullptr;
-    float* d_v = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double)), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok && grid) {   // the medium's own grid, uploaded for the call (the world need not be built)
-        const HostGrid& hg = s->grids[(size_t)s->mats[mat].p[6] - 1];
-        ok = hip_ok(hipMalloc((void**)&d_g, sizeof(GridD)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_v, hg.vals.size() * sizeof(float)), "hipMalloc") &&
-             hip_ok(hipMemcpyAsync(d_g, &hg.d, sizeof(GridD), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipMemcpyAsync(d_v, hg.vals.data(), hg.vals.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    }
-    if (ok) {
-        if (grid) launch_grid_probe(which, d_g, d_v, d_i, n, d_o, ctx->stream);
-        else if (which == 4) launch_absorb_probe(s->mats[mat].p + 7, d_i, n, d_o, ctx->stream);
-        else launch_medium_probe(which, s->mats[mat].p[0], s->mats[mat].p[1], d_i, n, d_o, ctx->stream);
-        ok = hip_ok(hipGetLastError(), "kernel launch") &&
-             hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_i) (void)hipFree(d_i);
-    if (d_o) (void)hipFree(d_o);
-    if (d_g) (void)hipFree(d_g);
-    if (d_v) (void)hipFree(d_v);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t n, double* out) {
-    if (!s || !s->built) return set_error("pt_light_probe: world not built");
-    if (which != 0 && which != 1) return set_error("pt_light_probe: which must be 0 or 1");
-    if (s->dev.view.n_lights == 0u) return set_error("pt_light_probe: the world has no lights list");
-    const bool exact = s->light_sampling == 1;
-    if (exact && s->light_mesh_bad_area) return set_error("pt_light_probe: exact light sampling needs light meshes of finite, positive area");
-    if (exact && s->light_blas_depth > (uint32_t)LIGHT_STACK) return set_error("pt_light_probe: exact light sampling: a light mesh's BVH is deeper than the 24 levels its pdf walk's stack holds");
-    if (n == 0) return 0;
-    if (!in || !out) return set_error("pt_light_probe: null buffer");
-    const size_t n_in = (size_t)n * (which == 0 ? 4 : 7), n_out = (size_t)n * (which == 0 ? 6 : 1);
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    double *d_i = nullptr, *d_o = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double)), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_light_probe(s->dev.view, exact, which, d_i, n, d_o, ctx->stream);
-        ok = hip_ok(hipGetLastError(), "kernel launch") &&
-             hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_i) (void)hipFree(d_i);
-    if (d_o) (void)hipFree(d_o);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_dispersion_probe(pt_scene* s, int glass_mat, int which, uint64_t seed, const double* in, uint32_t n, double* out) {
-    if (!s || !s->ctx) return set_error("pt_dispersion_probe: null scene");
-    if (glass_mat < 0 || (size_t)glass_mat >= s->mats.size() || s->mats[glass_mat].kind != MAT_GLASS || s->mats[glass_mat].p[3] == 0.0)
-        return set_error("pt_dispersion_probe: not a dispersive glass material (pt_mat_glass_set_dispersion)");
-    if (which != 0 && which != 1) return set_error("pt_dispersion_probe: which must be 0 or 1");
-    if (n == 0) return 0;
-    if (!in || !out) return set_error("pt_dispersion_probe: null buffer");
-    if (which == 0)
-        for (size_t i = 0; i < 2 * (size_t)n; ++i)
-            if (!(in[i] >= 0.0 && in[i] <= 4294967295.0) || in[i] != std::floor(in[i])) return set_error("pt_dispersion_probe: which 0 takes (pixel, sample) pairs of 32-bit unsigned integers");
-    const size_t n_in = (size_t)n * (which == 0 ? 2 : 1), n_out = (size_t)n * (which == 0 ? 7 : 1);
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    const double* d_w = dispersion_table(s, ctx->stream);
-    if (!d_w) return -1;
-    const MatD& m = s->mats[glass_mat];
-    double *d_i = nullptr, *d_o = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_i, n_in * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, n_out * sizeof(double)), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_i, in, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_dispersion_probe(s->sampler, which, seed, m.ior, m.p[1], m.p[2], d_w, d_i, n, d_o, ctx->stream);
-        ok = hip_ok(hipGetLastError(), "kernel launch") &&
-             hip_ok(hipMemcpyAsync(out, d_o, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_i) (void)hipFree(d_i);
-    if (d_o) (void)hipFree(d_o);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_camera_probe(pt_scene* s, const pt_camera* cam, uint64_t seed, const double* in, uint32_t n, double* out) {
-    if (!s || !s->ctx) return set_error("pt_camera_probe: null scene");
-    if (!cam) return set_error("pt_camera_probe: null camera");
-    CamD dc;
-    if (make_camd(s, cam, dc) != 0) return -1;
-    const uint64_t n_pixels = (uint64_t)dc.width * dc.height;
-    if (n_pixels > 0x7FFFFFFFull) return set_error("pt_camera_probe: bad image size");
-    if (n == 0) return 0;
-    if (!in || !out) return set_error("pt_camera_probe: null buffer");
-    for (uint32_t i = 0; i < n; ++i) {
-        const double p = in[2 * (size_t)i], sm = in[2 * (size_t)i + 1];
-        if (!(p >= 0.0 && p < (double)n_pixels) || p != std::floor(p) || !(sm >= 0.0 && sm <= 4294967295.0) || sm != std::floor(sm))
-            return set_error("pt_camera_probe: takes (pixel, sample) pairs: pixel < width * height, sample a 32-bit unsigned integer");
-    }
-    pt_ctx* ctx = s->ctx;
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    double *d_i = nullptr, *d_o = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_i, (size_t)n * 2 * sizeof(double)), "hipMalloc") && hip_ok(hipMalloc((void**)&d_o, (size_t)n * 8 * sizeof(double)), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_i, in, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_camera_probe(dc, s->sampler, seed, d_i, n, d_o, ctx->stream);
-        ok = hip_ok(hipGetLastError(), "kernel launch") &&
-             hip_ok(hipMemcpyAsync(out, d_o, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_i) (void)hipFree(d_i);
-    if (d_o) (void)hipFree(d_o);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_sampler_probe(pt_ctx* ctx, int kind, uint64_t seed, uint32_t pixel, uint32_t sample_begin, uint32_t n_samples, uint32_t draw_begin,
-                                uint32_t n_draws, uint64_t* out) {
-    if (!ctx) return set_error("pt_sampler_probe: null context");
-    if (kind != 0 && kind != 1) return set_error("pt_sampler_probe: kind must be 0 (independent) or 1 (Sobol)");
-    const uint64_t n = (uint64_t)n_samples * n_draws;
-    if (n == 0) return 0;
-    if (!out || n > (1ull << 28)) return set_error("pt_sampler_probe: null output or more than 2^28 values");
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    uint64_t* d_o = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_o, n * sizeof(uint64_t)), "hipMalloc");
-    if (ok) {
-        launch_sampler_probe(kind, seed, pixel, sample_begin, n_samples, draw_begin, n_draws, d_o, ctx->stream);
-        ok = hip_ok(hipGetLastError(), "kernel launch") &&
-             hip_ok(hipMemcpyAsync(out, d_o, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_o) (void)hipFree(d_o);
-    return ok ? 0 : -1;
-}
-
-extern "C" int pt_math_probe(pt_ctx* ctx, int which, const double* in, uint32_t n, double* out) {
-    if (!ctx) return set_error("pt_math_probe: null context");
-    if (!hip_ok(hipSetDevice(ctx->device), "hipSetDevice")) return -1;
-    double *d_i = nullptr, *d_o = nullptr;
-    bool ok = hip_ok(hipMalloc((void**)&d_i, (size_t)n * 2 * sizeof(double) + 8), "hipMalloc") &&
-              hip_ok(hipMalloc((void**)&d_o, (size_t)n * sizeof(double) + 8), "hipMalloc") &&
-              hip_ok(hipMemcpyAsync(d_i, in, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "hipMemcpy");
-    if (ok) {
-        launch_math_probe(which, d_i, n, d_o, ctx->stream);
-        ok = hip_ok(hipMemcpyAsync(out, d_o, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") &&
-             hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
-    }
-    if (d_i) (void)hipFree(d_i);
-    if (d_o) (void)hipFree(d_o);
-    return ok ? 0 : -1;
 }

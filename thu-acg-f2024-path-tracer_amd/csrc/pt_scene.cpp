@@ -42,12 +42,7 @@ void DeviceBuffers::release() {
 }  // namespace pt
 
 pt_scene::~pt_scene() {
-    dev.release();
-    if (pool_mem) (void)hipFree(pool_mem);
-    if (tile_accum) (void)hipFree(tile_accum);
-    if (compact_scratch) (void)hipFree(compact_scratch);
-    if (pixel_list) (void)hipFree(pixel_list);
-    if (env_tab) (void)hipFree(env_tab);
+    dev.release();   // (the cached buffers free themselves: pt_devmem.h GrowBuf)
     if (disp_w) (void)hipFree(disp_w);
     if (d_counters) (void)hipFree(d_counters);
     if (h_counters) (void)hipHostFree(h_counters);

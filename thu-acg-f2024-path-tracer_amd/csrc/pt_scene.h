@@ -3,12 +3,17 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <functional>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
 
+#include "pt_devmem.h"
 #include "pt_host_math.h"
 #include "pt_types.h"
+
+struct pt_camera;   // include/pt_amd.h
 
 struct pt_ctx {
     int device = 0;
@@ -21,7 +26,7 @@ namespace pt {
 
 int set_error(const std::string& msg);   // returns -1
 const char* last_error();
-bool hip_ok(hipError_t e, const char* what);
+bool hip_ok(hipError_t e, const char* what);   // (declared in pt_devmem.h too)
 // Experiment switches (PT_POOL_SLOTS, PT_SHADE_VARIANT, ...) are read only when PT_EXPERIMENT=1 is set: a release
 // library's behaviour does not depend on stray environment variables, and an explicit option always wins over them.
 const char* exp_env(const char* name);
@@ -78,21 +83,17 @@ struct pt_scene {
     uint32_t n_device_blas = 0, device_blas_depth = 0;   // meshes of the last build that the GPU builder handled, deepest of them
     uint32_t stack_need_extend2 = 0;   // ... for k_extend2, whose top-level walk is stackless when the entry list is walked flat
     pt::DeviceBuffers dev;
-    // path pool cache (re-used across pt_render calls of the same size)
-    void* pool_mem = nullptr;
-    size_t pool_bytes = 0;
-    double* tile_accum = nullptr;  // dynamic mode: the frame accumulator in tile order (PoolD::accum_tiled), re-used like the pool
-    size_t tile_accum_bytes = 0;
-    uint32_t* compact_scratch = nullptr;   // the end-of-frame compaction's hole / mover lists + counters (pt_render.cpp)
-    size_t compact_scratch_words = 0;
-    uint32_t* pixel_list = nullptr;   // pt_render_pixels: the device pixel list (tiled order), re-used like tile_accum
-    size_t pixel_list_words = 0;
+    // buffers cached across calls (pt_devmem.h GrowBuf: grown on demand, freed with the scene). A call sizes what it carves out of one
+    // from its own needs, never from the cached capacity.
+    pt::GrowBuf pool_mem;          // the path pool of a render (pt_render.cpp bind_pool)
+    pt::GrowBuf tile_accum;        // dynamic mode: the frame accumulator in tile order (PoolD::accum_tiled)
+    pt::GrowBuf compact_scratch;   // the end-of-frame compaction's hole / mover lists + counters (pt_render.cpp)
+    pt::GrowBuf pixel_list;        // pt_render_pixels: the device pixel list (tiled order)
     // environment importance sampling (pt_scene_set_env_sampling): the mixture weight, and the f64 tables of ONE
-    // environment texture, built at the first render that needs them (pt_render.cpp env_tables) and kept until destroy
+    // environment texture, built at the first render or probe that needs them (pt_render.cpp env_tables) and kept until destroy
     double env_f = 0.0;
     int env_tab_tex = -1;          // texture the tables below belong to (-1: none built)
-    double* env_tab = nullptr;     // H * (W + 1) row prefix sums, then H + 1 row-total prefix sums (EnvTabD)
-    size_t env_tab_bytes = 0;
+    pt::GrowBuf env_tab;           // H * (W + 1) row prefix sums, then H + 1 row-total prefix sums (EnvTabD), doubles
     uint32_t env_tab_w = 0, env_tab_h = 0;
     double env_tab_z = 0.0;
     // participating media (pt_mat_medium). camera_medium: the medium material camera rays start in, -1 = none.
@@ -138,4 +139,15 @@ int scene_build(pt_scene* s);   // flatten + BVH + upload
 void dispersion_weights(double w[DSP_BINS][3]);   // the weight table of pt_mat_glass_set_dispersion's rule (host, f64)
 double dispersion_ior(const MatD& glass, double lambda_nm);   // n(lambda) of a dispersive glass as the device computes it
 double* dispersion_table(pt_scene* s, hipStream_t st);   // pt_scene::disp_w, uploaded if need be; null (error set) when that fails
+// pt_render.cpp, shared with the probes (pt_probe.cpp): the device camera of a render, and the environment-sampling tables of its map
+int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc);
+int env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e);
+// pt_probe.cpp: the one path of the probes and the u8 resolves. Host inputs go to the device, `launch` enqueues its kernel on the
+// context's stream given the device pointers (inputs in the order listed), the launch error is checked, `out_bytes` come back and the
+// stream is synchronised. 0, or -1 with the error set. An empty output (n == 0) is no device work at all.
+struct ProbeIn {
+    const void* host;
+    size_t bytes;
+};
+int run_probe(pt_ctx* ctx, std::initializer_list<ProbeIn> in, void* out, size_t out_bytes, const std::function<void(void* const* d_in, void* d_out)>& launch);
 }
