@@ -384,6 +384,42 @@ int pt_cuboid(pt_scene*, const double a[3], const double b[3], int mat);        
 int pt_mesh(pt_scene*, double scale, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
             uint32_t n_nrm, const float* nrm, uint32_t n_uv, const float* uv, int mat);
 int pt_instance(pt_scene*, int obj, const double axis[3], double angle, const double translation[3]);   /* Instance::new instance.rs:20-30 */
+/* ---- motion blur of instances: keyframed poses and a camera shutter (not in the reference, opt-in) ----
+ * A ray's `time` is drawn per sample (camera.rs:165) and the reference reads it only in Sphere::center. pt_instance_moving makes an
+ * Instance whose pose depends on it, so that a quad, a cuboid, a mesh or a light under it blurs like a moving sphere does.
+ * The pose at `time`. Keys: axis, angle0, angle1, tr0, tr1. da = angle1 - angle0 and dtr = tr1 - tr0 (componentwise) are formed once on
+ *   the host. angle = angle0 + da * time; tr = tr0 + dtr * time, componentwise. The forward matrix and its analytic inverse are then built
+ *   by exactly pt_instance's operation sequence: (sn, cs) = the deterministic sincos(angle * 0.5) (pt_math_probe which 3 / 4), v = axis * sn,
+ *   q = (v, cs), x2 = qx + qx .. wz = qw * z2, c0 = (1 - (yy + zz), xy + wz, xz - wy), c1 = (xy - wz, 1 - (xx + zz), yz + wx),
+ *   c2 = (xz + wy, yz - wx, 1 - (xx + yy)), t = tr; i* = the transposed columns, it = -(i0 * t.x, then i1 * t.y + that, then i2 * t.z + that).
+ *   So a moving instance at time t is, bit for bit, pt_instance(obj, axis, angle, tr) of those two lerped values. An instance with
+ *   angle0 == angle1 ("translates only") keeps the rotation columns of angle0 + da * 0 and recomputes only t and it. Every level of a
+ *   chain uses the ray's one time; moving and static instances nest in any order.
+ * The shutter. pt_scene_set_shutter(scene, open, close), 0 <= open <= close <= 1, both finite; the default is (0, 1). Where motion is in
+ *   effect a camera ray's time is open + (close - open) * u, u the value generate_ray draws today (the number and order of draws are
+ *   unchanged); with (0, 1) those are u's bits, open == close freezes the scene at that instant. The shutter scales moving spheres too.
+ * In effect (pt_scene_motion, after pt_world_build): some placed object's chain holds an instance made by pt_instance_moving, even one
+ *   whose two keys are equal, or the shutter is not (0, 1) and something in the scene moves. Otherwise no new code runs.
+ * Boxes. The world box of a placement covers every time in [0, 1]. A level that translates only: the union of the transformed box at
+ *   time 0 and at time 1 (exact: the box is linear in time). A level that spins: rho = the largest corner norm of the child box, the union
+ *   of tr(0) +- rho and tr(1) +- rho (rho widened by 1e-14 relative and the box by four ulps of its largest coordinate, for rounding).
+ *   Levels above transform that box as they do a static one. (A mesh under ONE instance that translates only gets the bounds of its
+ *   transformed vertices at times 0 and 1, as a mesh under a static instance gets those of its transformed vertices.)
+ * Limits. With motion in effect a render returns -1 when environment importance sampling, any participating or interior medium, exact
+ *   light sampling or dispersion is in effect too. A moving instance in the lights list is allowed under light-sampling kind 0: its
+ *   sample / pdf (instance.rs:64-75) use the pose at the path's time. pt_intersect and pt_light_probe take the ray's time as given, with no
+ *   shutter, and are defined for time in [0, 1] (pt_light_probe under kind 1 returns -1 when an instance moves, as a render does);
+ *   pt_camera_probe and pt_render_aovs apply the shutter when motion is in effect. */
+int pt_instance_moving(pt_scene*, int obj, const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3]);
+int pt_scene_set_shutter(pt_scene*, double open, double close);
+int pt_scene_shutter(pt_scene*, double out[2]);
+int pt_scene_motion(pt_scene*);         /* 1: motion is in effect, 0: not, -1: the world is not built */
+/* Host only, no context needed. pt_motion_pose: the InstD numbers of the pose at `time` (c0, c1, c2, t, i0, i1, i2, it: 24 doubles).
+ * pt_motion_swept_box: one level of the box rule for box = (lo.xyz, hi.xyz). */
+int pt_motion_pose(const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double time, double out24[24]);
+int pt_motion_swept_box(const double box[6], const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double out[6]);
+/* test probe: the f64 world box (lo.xyz, hi.xyz) of world entry `entry` (lights list first, then objects), before the f32 rounding */
+int pt_world_entry_box(pt_scene*, uint32_t entry, double out[6]);
 /* ---- world: src/hittable/world.rs:10-29 -------------------------------------------------- */
 int pt_world_add_object(pt_scene*, int obj);
 int pt_world_add_light(pt_scene*, int obj);

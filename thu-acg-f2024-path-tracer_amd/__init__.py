@@ -154,6 +154,7 @@ ABI_SYMBOLS = [
     "pt_scene_set_light_sampling", "pt_scene_light_sampling", "pt_light_probe",
     "pt_mat_glass_set_dispersion", "pt_mat_glass_dispersion", "pt_dispersion_probe",
     "pt_scene_set_projection", "pt_scene_projection", "pt_camera_probe",
+    "pt_instance_moving", "pt_scene_set_shutter", "pt_scene_shutter", "pt_scene_motion", "pt_motion_pose", "pt_motion_swept_box", "pt_world_entry_box",
 ]
 
 
@@ -214,6 +215,14 @@ def _load():
         lib.pt_scene_set_projection.argtypes = [C.c_void_p, C.c_int]
         lib.pt_scene_projection.argtypes = [C.c_void_p]
         lib.pt_camera_probe.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "pt_instance_moving"):   # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_instance_moving.argtypes = [C.c_void_p, C.c_int, d3, C.c_double, C.c_double, d3, d3]
+        lib.pt_scene_set_shutter.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        lib.pt_scene_shutter.argtypes = [C.c_void_p, d3]
+        lib.pt_scene_motion.argtypes = [C.c_void_p]
+        lib.pt_motion_pose.argtypes = [d3, C.c_double, C.c_double, d3, d3, C.c_double, d3]
+        lib.pt_motion_swept_box.argtypes = [d3, d3, C.c_double, C.c_double, d3, d3, d3]
+        lib.pt_world_entry_box.argtypes = [C.c_void_p, C.c_uint32, d3]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -656,6 +665,29 @@ class Scene:
                                   0 if uv is None else len(uv), None if uv is None else uv.ctypes.data, mat), "mesh")
 
     def instance(self, obj, axis, angle, translation): return _check(lib.pt_instance(self.handle, obj, _d3(axis), angle, _d3(translation)), "instance")
+
+    def instance_moving(self, obj, axis, angle0, angle1, tr0, tr1):
+        """An instance whose pose is keyframed over the ray's time (pt_instance_moving): angle0 -> angle1 about `axis`, tr0 -> tr1."""
+        return _check(lib.pt_instance_moving(self.handle, obj, _d3(axis), float(angle0), float(angle1), _d3(tr0), _d3(tr1)), "instance_moving")
+
+    def set_shutter(self, open, close):
+        """The camera shutter (pt_scene_set_shutter): 0 <= open <= close <= 1; a camera ray's time is open + (close - open) * u."""
+        return _check(lib.pt_scene_set_shutter(self.handle, float(open), float(close)), "set_shutter")
+
+    def shutter(self):
+        out = (C.c_double * 2)()
+        _check(lib.pt_scene_shutter(self.handle, out), "pt_scene_shutter")
+        return (out[0], out[1])
+
+    def motion(self):
+        """True when motion is in effect for the built world (pt_scene_motion)."""
+        return _check(lib.pt_scene_motion(self.handle), "pt_scene_motion") == 1
+
+    def entry_box(self, entry):
+        """The f64 world box (lo.xyz, hi.xyz) of world entry `entry` (pt_world_entry_box)."""
+        out = (C.c_double * 6)()
+        _check(lib.pt_world_entry_box(self.handle, int(entry), out), "pt_world_entry_box")
+        return np.array(out[:], dtype=np.float64)
     def world_add_object(self, obj): return _check(lib.pt_world_add_object(self.handle, obj), "world_add_object")
     def world_add_light(self, obj): return _check(lib.pt_world_add_light(self.handle, obj), "world_add_light")
     def world_build(self): return _check(lib.pt_world_build(self.handle), "world_build")
@@ -785,6 +817,21 @@ class Scene:
 
 # every non-HDR image a scene script opens (for hosts that decode everything themselves, e.g. the test oracle via Pillow)
 SCENE_IMAGE_FILES = {2: ["earthmap.jpg"], 5: ["envmap.jpg"], 7: ["bricks/color.png", "bricks/normal.png"]}
+
+
+def motion_pose(axis, angle0, angle1, tr0, tr1, time) -> np.ndarray:
+    """The pose of a moving instance at `time` (pt_motion_pose; host only): 8 rows c0, c1, c2, t, i0, i1, i2, it."""
+    out = (C.c_double * 24)()
+    _check(lib.pt_motion_pose(_d3(axis), float(angle0), float(angle1), _d3(tr0), _d3(tr1), float(time), out), "pt_motion_pose")
+    return np.array(out[:], dtype=np.float64).reshape(8, 3)
+
+
+def motion_swept_box(box, axis, angle0, angle1, tr0, tr1) -> np.ndarray:
+    """One level of the box rule of moving instances (pt_motion_swept_box; host only): box = (lo.xyz, hi.xyz) -> its box over times [0, 1]."""
+    b = (C.c_double * 6)(*[float(x) for x in box])
+    out = (C.c_double * 6)()
+    _check(lib.pt_motion_swept_box(b, _d3(axis), float(angle0), float(angle1), _d3(tr0), _d3(tr1), out), "pt_motion_swept_box")
+    return np.array(out[:], dtype=np.float64)
 
 
 def camera_init(cam: Camera):

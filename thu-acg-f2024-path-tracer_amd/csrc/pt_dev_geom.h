@@ -18,15 +18,65 @@ PT_DEV RayD ray_to_local(const InstD& m, const RayD& r) {
     return make_ray(xform_point(m.i0, m.i1, m.i2, m.it, r.o), xform_vector(m.i0, m.i1, m.i2, r.d), r.time);
 }
 
+// The pose of a moving instance at `time` (pt_instance_moving's rule, pt_amd.h): pt_instance's operation sequence (pt_scene.cpp
+// make_pose) on angle0 + dangle * time and tr0 + dtr * time, so the record equals the static instance's of those two values bit for
+// bit. A key pair that does not spin keeps the stored rotation columns and makes no sincos call.
+PT_DEV void pose_at(const InstMotionD& k, double time, InstD& m) {
+    if (k.spins) {
+        const double angle = k.angle0 + k.dangle * time;
+        const SinCos h = dev_sincos(angle * 0.5);
+        const V3 v = ld3(k.axis) * h.s;
+        const double qx = v.x, qy = v.y, qz = v.z, qw = h.c;
+        const double x2 = qx + qx, y2 = qy + qy, z2 = qz + qz;
+        const double xx = qx * x2, xy = qx * y2, xz = qx * z2;
+        const double yy = qy * y2, yz = qy * z2, zz = qz * z2;
+        const double wx = qw * x2, wy = qw * y2, wz = qw * z2;
+        m.c0[0] = 1.0 - (yy + zz); m.c0[1] = xy + wz; m.c0[2] = xz - wy;
+        m.c1[0] = xy - wz; m.c1[1] = 1.0 - (xx + zz); m.c1[2] = yz + wx;
+        m.c2[0] = xz + wy; m.c2[1] = yz - wx; m.c2[2] = 1.0 - (xx + yy);
+        m.i0[0] = m.c0[0]; m.i0[1] = m.c1[0]; m.i0[2] = m.c2[0];
+        m.i1[0] = m.c0[1]; m.i1[1] = m.c1[1]; m.i1[2] = m.c2[1];
+        m.i2[0] = m.c0[2]; m.i2[1] = m.c1[2]; m.i2[2] = m.c2[2];
+    }
+    const V3 t = ld3(k.tr0) + ld3(k.dtr) * time;
+    const V3 it = -xform_vector(m.i0, m.i1, m.i2, t);
+    m.t[0] = t.x; m.t[1] = t.y; m.t[2] = t.z;
+    m.it[0] = it.x; m.it[1] = it.y; m.it[2] = it.z;
+}
+// Instance record `i` as a ray of time `time` sees it. MOT = false: the stored record — a scalar load when U says the index is
+// wave-uniform, else each lane's own. MOT = true (the MOT forms of K2 / K3, the probes): the pose at `time` where the instance
+// moves. The record is wave-uniform wherever it was; the pose is per lane, because `time` is.
+// Only inst_at<true, U> is ever instantiated: the chain walks below call it in their MOT forms only and keep their statements as they were
+// otherwise (MOT = false here says what those statements are: today's load, nothing else) — routed through this function's
+// by-value record, four of k_shade's and k_aov's non-MOT kernels came out with other SGPR spill counts, and a scene
+// without motion must run the kernels it ran before.
+template <bool MOT, bool U = false>
+PT_DEV InstD inst_at(const SceneD& sc, int32_t i, double time) {
+    InstD m;
+    if constexpr (U) m = ldu(&sc.insts[i]); else m = sc.insts[i];
+    if constexpr (MOT) {
+        if (sc.inst_motion) {   // (null: the scene's motion is its spheres' and the shutter's)
+            InstMotionD k;
+            if constexpr (U) k = ldu(&sc.inst_motion[i]); else k = sc.inst_motion[i];
+            if (k.moves) pose_at(k, time, m);
+        }
+    }
+    return m;
+}
+
 // Ray into the object space of a placement: Instance::intersects' transform (instance.rs:36-38, Ray::new re-normalises)
-// of every instance of the chain, outermost first. U: the chain is wave-uniform (scalar loads). `innermost` receives the
-// last index visited (the start of the way back: to_world_chain).
-template <bool U = false>
+// of every instance of the chain, outermost first, every level at the ray's time. U: the chain is wave-uniform (scalar loads).
+// `innermost` receives the last index visited (the start of the way back: to_world_chain).
+template <bool U = false, bool MOT = false>
 PT_DEV RayD ray_to_local_chain(const SceneD& sc, int32_t outermost, RayD r, int32_t* innermost = nullptr) {
     int32_t last = -1;
     for (int32_t i = outermost; i >= 0;) {
         last = i;
-        if constexpr (U) {
+        if constexpr (MOT) {
+            const InstD m = inst_at<true, U>(sc, i, r.time);
+            r = ray_to_local(m, r);
+            i = m.inner;
+        } else if constexpr (U) {
             const InstD m = ldu(&sc.insts[i]);
             r = ray_to_local(m, r);
             i = m.inner;
@@ -127,10 +177,10 @@ PT_DEV void finish_hit(const SceneD& sc, const RayD& r, V3 point, V3 normal, dou
 // (pt_types.h) — and neither dev_acos, dev_atan2 nor the two divisions are computed. UV = true (probe, AOV walk): always computed.
 // U: `pr` is wave-uniform and no triangle (k_shade's single-primitive groups): the instance chain, the sphere / quad record and the
 // material's normal-map handle arrive by scalar loads instead of a chain of dependent per-lane gathers of the same bytes.
-template <bool UV = true, bool U = false>
+template <bool UV = true, bool U = false, bool MOT = false>
 PT_DEV bool reconstruct_hit_prim(const SceneD& sc, const RayD& world_ray, const PrimRef& pr, double t_min, HitD& h) {
     int32_t innermost = -1;
-    const RayD r = ray_to_local_chain<U>(sc, pr.inst, world_ray, &innermost);
+    const RayD r = ray_to_local_chain<U, MOT>(sc, pr.inst, world_ray, &innermost);
     const uint32_t kind = pr.kind & 0xFFu;
     if (kind == PRIM_SPHERE) {
         double t;
@@ -183,7 +233,12 @@ PT_DEV bool reconstruct_hit_prim(const SceneD& sc, const RayD& world_ray, const 
         finish_hit(sc, r, ray_at(r, t), normal, t, pr.mat, tu, tv, h);
     }
     for (int32_t i = innermost; i >= 0;) {                                       // instance.rs:43-53, innermost instance first
-        if constexpr (U) {
+        if constexpr (MOT) {
+            const InstD m = inst_at<true, U>(sc, i, world_ray.time);
+            h.point = xform_point(m.c0, m.c1, m.c2, m.t, h.point);
+            h.gn = normalize(xform_vector(m.c0, m.c1, m.c2, h.gn));
+            i = m.outer;
+        } else if constexpr (U) {
             const InstD m = ldu(&sc.insts[i]);
             h.point = xform_point(m.c0, m.c1, m.c2, m.t, h.point);
             h.gn = normalize(xform_vector(m.c0, m.c1, m.c2, h.gn));
@@ -198,10 +253,10 @@ PT_DEV bool reconstruct_hit_prim(const SceneD& sc, const RayD& world_ray, const 
     return true;
 }
 // ... for primitive `gid`, each lane its own
-template <bool UV = true>
+template <bool UV = true, bool MOT = false>
 PT_DEV bool reconstruct_hit(const SceneD& sc, const RayD& world_ray, uint32_t gid, double t_min, HitD& h) {
     const PrimRef pr = sc.prims[gid];
-    return reconstruct_hit_prim<UV, false>(sc, world_ray, pr, t_min, h);
+    return reconstruct_hit_prim<UV, false, MOT>(sc, world_ray, pr, t_min, h);
 }
 
 // ---- lights list: Hittable::sample / pdf for every kind of object (list.rs:78-96, quad.rs:80-98,
@@ -227,7 +282,7 @@ PT_DEV double pdf_quad(const SceneD& sc, const QuadD& q, uint32_t mat, V3 origin
 // ONE: the lights list has a single entry (the Cornell box, scene 7): the index draw still happens (list.rs:82 draws it), but the
 // light is the same for every lane, so its entry, transform chain and quad / sphere record arrive by scalar loads instead of four
 // DEPENDENT vector gathers (lights[i] -> entries -> prims -> quads, ~700 cycles each in k_shade).
-template <bool ONE, class R>
+template <bool ONE, bool MOT, class R>
 PT_DEV V3 lights_sample_impl(const SceneD& sc, V3 origin_w, double time, R& rng) {
     uint32_t i = rng_index(rng, sc.n_lights);
     Entry e;
@@ -235,7 +290,12 @@ PT_DEV V3 lights_sample_impl(const SceneD& sc, V3 origin_w, double time, R& rng)
     V3 origin = origin_w;
     int32_t innermost = -1;
     for (int32_t k = e.inst; k >= 0;) {                                           // instance.rs:64-66, outermost instance first
-        if constexpr (ONE) {
+        if constexpr (MOT) {
+            const InstD m = inst_at<true, ONE>(sc, k, time);   // the pose at the path's time
+            origin = xform_point(m.i0, m.i1, m.i2, m.it, origin);
+            innermost = k;
+            k = m.inner;
+        } else if constexpr (ONE) {
             const InstD m = ldu(&sc.insts[k]);
             origin = xform_point(m.i0, m.i1, m.i2, m.it, origin);
             innermost = k;
@@ -278,17 +338,24 @@ PT_DEV V3 lights_sample_impl(const SceneD& sc, V3 origin_w, double time, R& rng)
         dir = normalize(point - origin);
     }
     for (int32_t k = innermost; k >= 0;) {                                        // instance.rs:67-68 (not re-normalised)
-        const InstD& m = sc.insts[k];
-        dir = xform_vector(m.c0, m.c1, m.c2, dir);
-        k = m.outer;
+        if constexpr (MOT) {
+            const InstD m = inst_at<true, false>(sc, k, time);
+            dir = xform_vector(m.c0, m.c1, m.c2, dir);
+            k = m.outer;
+        } else {
+            const InstD& m = sc.insts[k];
+            dir = xform_vector(m.c0, m.c1, m.c2, dir);
+            k = m.outer;
+        }
     }
     return dir;
 }
-template <class R>
+template <bool MOT = false, class R>
 PT_DEV V3 lights_sample(const SceneD& sc, V3 origin_w, double time, R& rng) {
-    if (sc.n_lights == 1u) return lights_sample_impl<true>(sc, origin_w, time, rng);
-    return lights_sample_impl<false>(sc, origin_w, time, rng);
+    if (sc.n_lights == 1u) return lights_sample_impl<true, MOT>(sc, origin_w, time, rng);
+    return lights_sample_impl<false, MOT>(sc, origin_w, time, rng);
 }
+template <bool MOT = false>
 PT_DEV double lights_pdf(const SceneD& sc, V3 origin_w, V3 direction_w, double time) {
     if (sc.n_lights == 0) return 0.0;
     double sum = 0.0;
@@ -296,10 +363,17 @@ PT_DEV double lights_pdf(const SceneD& sc, V3 origin_w, V3 direction_w, double t
         const Entry e = ldu(&sc.entries[ldu(&sc.lights[i])]);
         V3 origin = origin_w, direction = direction_w;
         for (int32_t k = e.inst; k >= 0;) {                                       // instance.rs:71-75, outermost instance first
-            const InstD m = ldu(&sc.insts[k]);
-            origin = xform_point(m.i0, m.i1, m.i2, m.it, origin);
-            direction = xform_vector(m.i0, m.i1, m.i2, direction);
-            k = m.inner;
+            if constexpr (MOT) {
+                const InstD m = inst_at<true, true>(sc, k, time);
+                origin = xform_point(m.i0, m.i1, m.i2, m.it, origin);
+                direction = xform_vector(m.i0, m.i1, m.i2, direction);
+                k = m.inner;
+            } else {
+                const InstD m = ldu(&sc.insts[k]);
+                origin = xform_point(m.i0, m.i1, m.i2, m.it, origin);
+                direction = xform_vector(m.i0, m.i1, m.i2, direction);
+                k = m.inner;
+            }
         }
         double pdf = 0.0;
         if (e.kind == ENTRY_QUAD) {
@@ -400,7 +474,9 @@ PT_DEV V3 projected_direction(const CamD& cam, double fy, double fx) {
 }
 // The branches on cam.projection are wave-uniform (cam is a kernel argument) and not taken by the perspective camera (kind 0), whose
 // arithmetic below is the reference's; every kind makes kind 0's draws in kind 0's order.
-template <class R>
+// MOT (the MOT forms of K1 / K3, and the probes when motion is in effect): the shutter maps the time draw u to open + span * u — with the
+// default (0, 1) those are u's bits. The number and order of draws are the same.
+template <bool MOT = false, class R>
 PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, R& rng) {
     double bx, by;
     random_offsets(rng, bx, by);
@@ -425,6 +501,7 @@ PT_DEV RayD generate_ray(const CamD& cam, uint32_t row, uint32_t col, R& rng) {
     double time = 0.0;
     if (cam.motionless) ++rng.draw;   // drawn all the same (camera.rs:165); no result depends on it (CamD::motionless), so its Philox block is not computed
     else time = rng_f64(rng);
+    if constexpr (MOT) time = cam.shutter_open + cam.shutter_span * time;
     return make_ray(origin, cam.projection >= PROJ_FISHEYE ? sample_location : sample_location - origin, time);
 }
 // camera.rs:140-151

@@ -50,6 +50,7 @@ PT_DEV void wave_lds_order() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+template <bool MOT = false>
 PT_PAIR_PASS_ATTR void pair_pass(const SceneD& sc, const RayD& r, double t_min, int lane, const PairLds& L, uint32_t head, uint32_t n) {
     wave_lds_order();
     const bool mine = (uint32_t)lane < n;
@@ -62,7 +63,7 @@ PT_PAIR_PASS_ATTR void pair_pass(const SceneD& sc, const RayD& r, double t_min, 
     double t = 0.0;
     if (mine) {
         const PrimRef pr = sc.prims[gid];
-        const RayD lr = ray_to_local_chain(sc, pr.inst, pr_ray);
+        const RayD lr = ray_to_local_chain<false, MOT>(sc, pr.inst, pr_ray);
         if ((pr.kind & 0xFFu) == PRIM_SPHERE) {
             V3 c;
             hit = hit_sphere(sc.spheres[pr.index], lr, t_min, t, c);
@@ -92,7 +93,8 @@ PT_PAIR_PASS_ATTR void pair_pass(const SceneD& sc, const RayD& r, double t_min, 
 // box of mesh entry `ei` (wave-uniform index).
 // PAIRS: cuboids few rays of the chunk enter go through the pair passes (L must be valid); false: everything on the spot.
 // CULL: compile the cuboid face culling in (the instantiation for scenes without cuboids leaves it out: its registers spilled there).
-template <bool PAIRS, bool CULL, class OnMesh>
+// MOT: instances are posed at each lane's ray time (inst_at); face culling and the pair passes use the per-lane local ray they compute anyway.
+template <bool PAIRS, bool CULL, bool MOT = false, class OnMesh>
 PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const RayF& f, double t_min, float t_min_f, int lane, const PairLds& L,
                               OnMesh&& on_mesh) {
     if constexpr (PAIRS) {
@@ -104,7 +106,7 @@ PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const
     float t_max_f = t_max_f32(best.t);
     bool pairs_open = PAIRS;                                         // wave-uniform: pair results not yet merged into `best`
     auto close_pairs = [&]() {
-        if (tail != head) pair_pass(sc, r, t_min, lane, L, head, tail - head);
+        if (tail != head) pair_pass<MOT>(sc, r, t_min, lane, L, head, tail - head);
         if (tail != 0u) {                                            // some pass ran: its results join the on-the-spot ones (same rule)
             wave_lds_order();
             const double lt = __longlong_as_double((long long)((volatile unsigned long long*)L.bt)[lane]);
@@ -139,7 +141,7 @@ PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const
                 RayD lr{};
                 uint32_t fm = 0u;
                 if (hb) {
-                    lr = ray_to_local_chain<true>(sc, bx.inst, r);
+                    lr = ray_to_local_chain<true, MOT>(sc, bx.inst, r);
                     const CuboidBox cb = ldu(&sc.cuboid_box[k]);
                     fm = cuboid_face_mask(cb.lo, cb.hi, make_rayf(lr.o, lr.d, bx.extent), t_min_f, t_max_f);
                 }
@@ -154,7 +156,7 @@ PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const
                 continue;
             }
             if (hb) {
-                const RayD lr = ray_to_local_chain<true>(sc, bx.inst, r);
+                const RayD lr = ray_to_local_chain<true, MOT>(sc, bx.inst, r);
                 if (PT_FLAT_DIRECT && bx.prim_kind == PRIM_SPHERE) {
                     const SphereD sp = ldu(&sc.spheres[bx.prim_index]);
                     double t;
@@ -178,7 +180,7 @@ PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const
             if (CULL && PT_CUBOID_CULL && bx.kind == ENTRY_CUBOID && bx.prim_kind == PRIM_QUAD) {
                 fm = 0u;
                 if (hb) {
-                    const RayD lr = ray_to_local_chain<true>(sc, bx.inst, r);
+                    const RayD lr = ray_to_local_chain<true, MOT>(sc, bx.inst, r);
                     const CuboidBox cb = ldu(&sc.cuboid_box[k]);
                     fm = cuboid_face_mask(cb.lo, cb.hi, make_rayf(lr.o, lr.d, bx.extent), t_min_f, t_max_f);
                 }
@@ -191,7 +193,7 @@ PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const
                 if (need) ((volatile uint32_t*)L.pairs)[(tail + rank) % PAIR_CAP] = ((bx.first_prim + fi) << 6) | (uint32_t)lane;
                 tail += (uint32_t)__popcll(mf);
                 if (tail - head >= 64u) {
-                    pair_pass(sc, r, t_min, lane, L, head, 64u);
+                    pair_pass<MOT>(sc, r, t_min, lane, L, head, 64u);
                     head += 64u;
                 }
             }
@@ -200,12 +202,12 @@ PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const
     if (PAIRS && pairs_open) close_pairs();
     return best;
 }
-template <bool PAIRS>
+template <bool PAIRS, bool MOT = false>
 PT_DEV Closest closest_hit_flat(const SceneD& sc, bool alive, const RayD& r, double t_min, uint32_t* stk, int lane, const PairLds& L) {
     const float t_min_f = __double2float_rd(t_min);
     const RayF f = make_rayf(r.o, r.d, sc.tlas_extent);
-    return flat_top_level<PAIRS, PAIRS>(sc, alive, r, f, t_min, t_min_f, lane, L,   // (the batch kernel's instantiation without pair passes serves scenes without cuboids)
-                                [&](uint32_t, const Entry& e, Closest& best) { blas_pass(sc, r, e, t_min, t_min_f, stk, TRAVERSAL_STACK, best); });
+    return flat_top_level<PAIRS, PAIRS, MOT>(sc, alive, r, f, t_min, t_min_f, lane, L,   // (the batch kernel's instantiation without pair passes serves scenes without cuboids)
+                                [&](uint32_t, const Entry& e, Closest& best) { blas_pass<BLOCK, MOT>(sc, r, e, t_min, t_min_f, stk, TRAVERSAL_STACK, best); });
 }
 
 // K2, batch form: a fixed grid walks the pool with a grid-stride loop; each lane traverses one ray
@@ -215,7 +217,8 @@ PT_DEV Closest closest_hit_flat(const SceneD& sc, bool alive, const RayD& r, dou
 // FLAT: SceneD::tlas_flat. PAIRS (FLAT only): SceneD::flat_pairs — the scene has cuboids, whose six faces behind one transform
 // are what the pair passes of flat_top_level pay for (scene 3: K2 -19 %, scene 7: -11 %); that instantiation runs three blocks
 // per CU (its extra state spills at 128 registers and costs more than the fourth block brings), the others four.
-template <bool FLAT, bool PAIRS>
+// MOT: motion is in effect (pt_amd.h): instances are posed at each ray's time. Forms of their own, so that the others stay what they were.
+template <bool FLAT, bool PAIRS, bool MOT = false>
 __global__ __launch_bounds__(BLOCK, PAIRS ? 3 : PT_EXTEND_BATCH_BLOCKS) void k_extend(SceneD sc, PoolD pool, CountersD* cnt) {
     __shared__ uint32_t stack[TRAVERSAL_STACK * BLOCK];
     __shared__ unsigned long long s_pair_t[PAIRS ? BLOCK : 1];
@@ -232,8 +235,8 @@ __global__ __launch_bounds__(BLOCK, PAIRS ? 3 : PT_EXTEND_BATCH_BLOCKS) void k_e
         RayD r{};
         if (alive) r = load_ray(pool, s);
         Closest c{D_INF, HIT_NONE};
-        if (FLAT) c = closest_hit_flat<PAIRS>(sc, alive, r, 1e-3, &stack[threadIdx.x], lane, pl);   // camera.rs:171,179
-        else if (alive) c = closest_hit(sc, r, 1e-3, &stack[threadIdx.x]);
+        if (FLAT) c = closest_hit_flat<PAIRS, MOT>(sc, alive, r, 1e-3, &stack[threadIdx.x], lane, pl);   // camera.rs:171,179
+        else if (alive) c = closest_hit<MOT>(sc, r, 1e-3, &stack[threadIdx.x]);
         stnt(&pool.hit_prim[s], hit_word(sc, alive ? c.id : dead_or_idle(state)));
         if (alive) ++nseg;
     }
@@ -300,7 +303,8 @@ static_assert(EXT_WINDOW % BLOCK == 0 && EXT_WINDOW <= 65536, "k_extend2: s_cand
 static_assert(EXT_WINDOW == SORT_WINDOW_SLOTS, "the pool is allocated in whole windows of this size (pt_render.cpp rounds n_alloc to 2048)");
 
 // KB: threads per block (256; [r3] other sizes for A/B — the window and the candidate list scale with it; MINB = waves per SIMD, which is what hipcc's launch bound means)
-template <int EXT_STACK, int MINB, int KB = BLOCK>
+// MOT: as in k_extend
+template <int EXT_STACK, int MINB, int KB = BLOCK, bool MOT = false>
 __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, CountersD* cnt) {
     constexpr int WIN = EXT_WINDOW / BLOCK * KB, CAND = (KB <= 128 ? EXT_CAND_SMALL : EXT_CAND) / BLOCK * KB;
     __shared__ uint32_t stack[EXT_STACK * KB];
@@ -379,11 +383,11 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
                         items = (items & ~(0xFFu << (8u * n_my))) | (ei << (8u * n_my));   // defer to phase B
                         ++n_my;
                     } else {
-                        blas_pass<KB>(sc, r, e, t_min, t_min_f, stk + (size_t)sp * KB, EXT_STACK - sp, best);   // a fifth mesh / a wide index: walk it now
+                        blas_pass<KB, MOT>(sc, r, e, t_min, t_min_f, stk + (size_t)sp * KB, EXT_STACK - sp, best);   // a fifth mesh / a wide index: walk it now
                         t_max_f = t_max_f32(best.t);
                     }
                 } else {
-                    const RayD lr = ray_to_local_chain<U>(sc, e.inst, r);
+                    const RayD lr = ray_to_local_chain<U, MOT>(sc, e.inst, r);
                     const uint32_t n = e.kind == ENTRY_CUBOID ? 6u : 1u;       // cuboid.rs: six quads, linear
                     for (uint32_t i = 0; i < n; ++i) test_world_prim<U>(sc, lr, t_min, e.first_prim + i, best);
                     t_max_f = t_max_f32(best.t);
@@ -392,7 +396,7 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
             if (sc.tlas_flat) {
                 // Small top level: the wave walks the ENTRY LIST together instead of each lane walking the tree
                 // (flat_top_level; the pair passes are left to the batch kernel: measured slower here, scene 6).
-                best = flat_top_level<false, true>(sc, alive, r, f, t_min, t_min_f, lane, PairLds{}, [&](uint32_t ei, const Entry& e, Closest& b) {
+                best = flat_top_level<false, true, MOT>(sc, alive, r, f, t_min, t_min_f, lane, PairLds{}, [&](uint32_t ei, const Entry& e, Closest& b) {
                     best = b;                                       // visit_entry works on this frame's `best`
                     visit_entry(std::true_type{}, ei, e, 0);
                     b = best;
@@ -432,7 +436,7 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
                         s_cand_items[pos] = items;
                         s_cand_sl[pos] = (uint16_t)sl;
                     } else {
-                        for (uint32_t k = 0; k < n_my; ++k) blas_pass<KB>(sc, r, sc.entries[(items >> (8u * k)) & 0xFFu], t_min, t_min_f, stk, EXT_STACK, best);
+                        for (uint32_t k = 0; k < n_my; ++k) blas_pass<KB, MOT>(sc, r, sc.entries[(items >> (8u * k)) & 0xFFu], t_min, t_min_f, stk, EXT_STACK, best);
                     }
                 }
             }
@@ -458,7 +462,7 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
                 const uint32_t ei = item_k < 4u ? (items >> (8u * item_k)) & 0xFFu : 0xFFu;
                 if (ei == 0xFFu) return false;
                 const Entry e = sc.entries[ei];
-                r = ray_to_local_chain(sc, e.inst, wr);
+                r = ray_to_local_chain<false, MOT>(sc, e.inst, wr);
                 first_prim = e.first_prim;
                 f = make_rayf(r.o, r.d, e.extent);
                 t_max_f = t_max_f32(best.t);

@@ -7,16 +7,18 @@ namespace pt {
 
 // Debug/parity probe: closest hit + reconstructed HitInfo for a batch of arbitrary rays.
 // out[15*i..] = {hit, t, prim_id, u, v, front, p.xyz, gn.xyz, sn.xyz}
+// MOT: the scene has moving instances (SceneD::inst_motion): every instance is posed at the ray's time, taken as given (no shutter)
+template <bool MOT>
 __global__ __launch_bounds__(BLOCK) void k_probe(SceneD sc, const double* rays /* o.xyz d.xyz time */, uint32_t n, double* out) {
     __shared__ uint32_t stack[TRAVERSAL_STACK * BLOCK];
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         const double* q = rays + 7 * (size_t)i;
         RayD r = make_ray(V3{q[0], q[1], q[2]}, V3{q[3], q[4], q[5]}, q[6]);
-        Closest c = closest_hit(sc, r, 1e-3, &stack[threadIdx.x]);
+        Closest c = closest_hit<MOT>(sc, r, 1e-3, &stack[threadIdx.x]);
         double* o = out + 15 * (size_t)i;
         for (int j = 0; j < 15; ++j) o[j] = 0.0;
         HitD h;
-        if (c.id != HIT_NONE && reconstruct_hit(sc, r, c.id, 1e-3, h)) {
+        if (c.id != HIT_NONE && reconstruct_hit<true, MOT>(sc, r, c.id, 1e-3, h)) {
             o[0] = 1.0; o[1] = c.t; o[2] = (double)c.id; o[3] = h.u; o[4] = h.v; o[5] = h.front ? 1.0 : 0.0;
             o[6] = h.point.x; o[7] = h.point.y; o[8] = h.point.z;
             o[9] = h.gn.x; o[10] = h.gn.y; o[11] = h.gn.z;
@@ -31,15 +33,15 @@ __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t see
 
 FormKernels forms_plain(const ShadeForm& f) { return unit_forms<UNIT_PLAIN>(f, k_aov); }
 static FormKernels form_kernels(const ShadeForm& f) {   // asks the unit that owns the form's k_shade, and the one that owns its k_init (pt_forms.h)
-    constexpr FormKernels (*unit[])(const ShadeForm&) = {forms_plain, forms_qmc, forms_med, forms_het, forms_int, forms_lse, forms_dsp};   // in FormUnit's order
-    const FormUnit k3 = form_unit(f.mode, f.qmc), k1 = form_unit(mode_has_media(f.mode) ? MODE_MED : MODE_PLAIN, f.qmc);   // K1 has a plain and a MED form only
+    constexpr FormKernels (*unit[])(const ShadeForm&) = {forms_plain, forms_qmc, forms_med, forms_het, forms_int, forms_lse, forms_dsp, forms_mot};   // in FormUnit's order
+    const FormUnit k3 = form_unit(f.mode, f.qmc, f.motion), k1 = form_unit(mode_has_media(f.mode) ? MODE_MED : MODE_PLAIN, f.qmc, f.motion);   // K1 has a plain, a MED and a MOT form only
     FormKernels k = unit[k3](f);
     if (k1 != k3) k.init = k.shade ? unit[k1](f).init : nullptr;
     return k;
 }
 
 ShadeForm shade_form(ShadeForm f) {
-    if (!shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.lights, f.list, f.qmc, f.mode)) f.variant = 42;
+    if (!shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.lights, f.list, f.qmc, f.mode, f.motion)) f.variant = 42;
     return f;
 }
 bool shade_form_sorts(const ShadeForm& f) { return SHADE_SHAPES[shade_row(f.variant)].sort; }
@@ -66,7 +68,8 @@ int shade_occupancy_blocks(const ShadeForm& f) {
     return k ? occupancy_blocks((const void*)k, SHADE_SHAPES[shade_row(f.variant)].kb) : 0;
 }
 void launch_probe(const SceneD& sc, const double* rays, uint32_t n, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_probe, grid_for(n, 2048), dim3(BLOCK), 0, st, sc, rays, n, out);
+    if (sc.inst_motion) hipLaunchKernelGGL(k_probe<true>, grid_for(n, 2048), dim3(BLOCK), 0, st, sc, rays, n, out);
+    else hipLaunchKernelGGL(k_probe<false>, grid_for(n, 2048), dim3(BLOCK), 0, st, sc, rays, n, out);
 }
 bool launch_aov(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, bool overwrite, int max_blocks,
                 hipStream_t st, const ShadeForm& form) {

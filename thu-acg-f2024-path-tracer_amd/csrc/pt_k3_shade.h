@@ -12,7 +12,8 @@ namespace pt {
 // QMC: the Sobol sampler (pt_scene_set_sampler; RngQ in pt_dev_math.h) — forms of their own, compiled in pt_k3_qmc.hip
 // MED: participating media are in effect — a camera ray's bounce word carries the camera medium (pt_types.h MEDIUM_SHIFT);
 // forms of their own, compiled in pt_k3_med.hip
-template <bool LIST = false, bool QMC = false, bool MED = false>
+// MOT: motion is in effect — generate_ray applies the shutter; forms of their own, compiled in pt_k3_mot.hip
+template <bool LIST = false, bool QMC = false, bool MED = false, bool MOT = false>
 __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t seed) {
     const uint32_t bounce0 = MED ? cam.medium << MEDIUM_SHIFT : 0u;   // the bounce word of a camera ray
     for (uint32_t s = blockIdx.x * BLOCK + threadIdx.x; s < pool.n_alloc; s += gridDim.x * BLOCK) {
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
             continue;
         }
         std::conditional_t<QMC, RngQ, Rng> rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, 0u};
-        RayD r = generate_ray(cam, row, col, rng);
+        RayD r = generate_ray<MOT>(cam, row, col, rng);
         store_ray(pool, pool.ray, s, r, sample, rng.draw, pixel, bounce0);
         pool.bounce[s] = 0;
     }
@@ -209,7 +210,9 @@ struct NoPrefetch {
 // case of mat_sample / mat_pdf_eval; a continued bounce of a path whose flag is clear multiplies the new throughput by the row and sets the flag.
 // Every other lane is the bounce above bit for bit.
 constexpr int LSE_KB = 512;                                            // threads per block of every shape that has LSE forms (pt_forms.h)
-template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true>
+// MOT: motion is in effect (the rule in pt_amd.h): the hit is rebuilt, and lights.sample / lights.pdf are evaluated, with every
+// instance posed at the path's time (inst_at); a regenerated camera ray takes its time through the shutter. Plain mode only.
+template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true, bool MOT = false>
 // UNI: the form may take the single-primitive path of phase A (k_shade: every two-wave shape).
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
@@ -323,7 +326,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         rng = RngT{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, in.draw};
         const uint32_t gid = in.hw & HIT_ID_MASK;
         const bool surface = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS &&
-                             (uni ? reconstruct_hit_prim<false, true>(sc, ray, pr0, 1e-3, hit) : reconstruct_hit<false>(sc, ray, gid, 1e-3, hit));
+                             (uni ? reconstruct_hit_prim<false, true, MOT>(sc, ray, pr0, 1e-3, hit) : reconstruct_hit<false, MOT>(sc, ray, gid, 1e-3, hit));
         PT_STAMP_SET(a1);
         if constexpr (MED) {
             if (med != 0u) {                                           // free flight: one draw, d = -log(1 - u) / density
@@ -427,7 +430,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 const double p_env = env->f, p_l = LIGHTS ? (1.0 - p_env) / 2.0 : 0.0;
                 rsel = rng_f64(rng);
                 if (LIGHTS && rsel < p_l) {
-                    dir = lights_sample(sc, hit.point, ray.time, rng);
+                    dir = lights_sample<MOT>(sc, hit.point, ray.time, rng);
                 } else if (rsel < p_l + p_env) {
                     uint64_t a, b;
                     rng_u64x2(rng, a, b);
@@ -446,7 +449,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 rsel = rng_f64(rng);
                 if (rsel < p_light) {
                     if constexpr (LSE) dir = lights_sample_exact(sc, hit.point, ray.time, rng);
-                    else dir = lights_sample(sc, hit.point, ray.time, rng);
+                    else dir = lights_sample<MOT>(sc, hit.point, ray.time, rng);
                 } else ok = mat_sample<RngT, DSP>(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir, ior_l);
             } else {
                 ++rng.draw;
@@ -469,7 +472,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 if constexpr (LIGHTS) from_light = rng_f64(rng) < p_light;
                 else ++rng.draw;                                       // the selector is drawn even without lights
                 if (from_light) {
-                    dir = lights_sample(sc, hit.point, ray.time, rng);
+                    dir = lights_sample<MOT>(sc, hit.point, ray.time, rng);
                 } else {
                     uint64_t a, b;
                     rng_u64x2(rng, a, b);
@@ -488,7 +491,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         mat_pdf_eval<DSP>(sc, *mp, hit, wo, dir, tv, lf, bsdf_pdf, brdf, ior_l);
         double light_pdf = 0.0;
         if constexpr (LSE) light_pdf = lights_pdf_exact<LSE_KB>(sc, hit.point, dir, ray.time, lstk);
-        else if constexpr (LIGHTS) light_pdf = lights_pdf(sc, hit.point, dir, ray.time);
+        else if constexpr (LIGHTS) light_pdf = lights_pdf<MOT>(sc, hit.point, dir, ray.time);
         double pdf = p_bsdf * bsdf_pdf + p_light * light_pdf;
         V3 attenuation = brdf / pdf;
         bool env_end = false;
@@ -535,7 +538,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         if (have_mdir) {
             const double ph = hg_phase(medium.g, dot(ray.d, dir));
             double light_pdf = 0.0;
-            if constexpr (LIGHTS) light_pdf = lights_pdf(sc, hit.point, dir, ray.time);
+            if constexpr (LIGHTS) light_pdf = lights_pdf<MOT>(sc, hit.point, dir, ray.time);
             const double pdf = p_bsdf * ph + p_light * light_pdf;
             if (!(pdf > 0.0) || !(pdf < D_INF)) {
                 finished = parked = true;                              // a zero or non-finite density ends the path
@@ -618,7 +621,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         } else if (more) {
             rng = RngT{(uint32_t)seed, (uint32_t)(seed >> 32), next_pixel, next_sample, 0u};
             if (!pool.dynamic) divmod_u31(next_pixel, cam.width, next_row, next_col);
-            ray = generate_ray(cam, next_row, next_col, rng);
+            ray = generate_ray<MOT>(cam, next_row, next_col, rng);
             thr = V3{1.0, 1.0, 1.0};
             rad = V3{0.0, 0.0, 0.0};
             bounce = 0;
@@ -691,9 +694,11 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // MED: participating media (shade_slot). A slot's class says nothing certain about a path inside a medium — it may scatter before the
 // hit, or instead of leaving — so these forms do not request work items a group ahead.
 // LSE: these forms hold the per-lane stack of the light meshes' all-hits walk, LIGHT_STACK levels x KB lanes in LDS
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, ShadeMode M = MODE_PLAIN, bool QMC = false>
+// MOT: motion (shade_slot)
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, ShadeMode M = MODE_PLAIN, bool QMC = false, bool MOT = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     constexpr bool ENV = M == MODE_ENV, MED = mode_has_media(M), LSE = M == MODE_LSE, DSP = M == MODE_DSP;   // (HET and INT change nothing here)
+    static_assert(!MOT || M == MODE_PLAIN, "k_shade: the MOT forms are plain-mode forms");
     static_assert((!LSE || LIGHTS) && (!(LSE || DSP) || (SORT && KB == LSE_KB)), "k_shade: the LSE forms need a lights list; the LSE and DSP forms are sorted 512-thread forms");
     __shared__ uint32_t s_lstack[LSE ? LIGHT_STACK * KB : 1];   // 48 KB: stack[level][thread] of lights_pdf_exact's mesh walk
     uint32_t* const lstk = LSE ? &s_lstack[threadIdx.x] : nullptr;
@@ -711,7 +716,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, M, QMC, MINW == 2>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
+            shade_slot<LIGHTS, LIST, NoPrefetch, M, QMC, MINW == 2, MOT>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -888,7 +893,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, M, QMC, MINW == 2>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, M, QMC, MINW == 2, MOT>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env, lstk);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

@@ -147,6 +147,7 @@ PT_DEV void test_world_prim(const SceneD& sc, const RayD& r, double t_min, uint3
     }
 }
 
+template <bool MOT = false>   // MOT: instances are posed at the ray's time (inst_at)
 PT_DEV Closest closest_hit(const SceneD& sc, const RayD& wray, double t_min, uint32_t* stk /* &stack[0][lane] */) {
     Closest best{D_INF, HIT_NONE};
     RayD r = wray;
@@ -173,7 +174,7 @@ PT_DEV Closest closest_hit(const SceneD& sc, const RayD& wray, double t_min, uin
             t_max_f = t_max_f32(best.t);
         } else if ((cur & REF_TYPE_MASK) == REF_ENTRY) {
             const Entry e = sc.entries[cur & 0x3FFFFFFFu];
-            const RayD lr = ray_to_local_chain(sc, e.inst, wray);
+            const RayD lr = ray_to_local_chain<false, MOT>(sc, e.inst, wray);
             if (e.kind == ENTRY_MESH) {
                 r = lr;
                 mesh_first_prim = e.first_prim;
@@ -195,9 +196,9 @@ PT_DEV Closest closest_hit(const SceneD& sc, const RayD& wray, double t_min, uin
     return best;
 }
 
-template <int STRIDE = BLOCK>   // STRIDE: threads per block = distance of a lane's consecutive stack entries in LDS
+template <int STRIDE = BLOCK, bool MOT = false>   // STRIDE: threads per block = distance of a lane's consecutive stack entries in LDS
 PT_DEV void blas_pass(const SceneD& sc, const RayD& wray, const Entry& e, double t_min, float t_min_f, uint32_t* stk, int cap, Closest& best) {
-    const RayD r = ray_to_local_chain(sc, e.inst, wray);
+    const RayD r = ray_to_local_chain<false, MOT>(sc, e.inst, wray);
     const RayF f = make_rayf(r.o, r.d, e.extent);
     float t_max_f = t_max_f32(best.t);
     int sp = 0;
@@ -243,7 +244,7 @@ PT_DEV V3 aov_albedo(const SceneD& sc, const MatD& m, const HitD& h) {
 // One thread per pixel walks samples [spp_begin, spp_end) in order; sample s's camera ray is k_init's for (pixel, s) — same Rng,
 // same generate_ray — and its closest hit is the one K2 finds (tree-independent). Adds (overwrite: stores) the
 // sums aov[8 * pixel + k]: albedo rgb, shading normal xyz, depth, hits. No atomics: every pixel has one writer.
-template <bool QMC>
+template <bool QMC, bool MOT = false>
 PT_DEV void aov_pixels(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_t spp_begin, uint32_t spp_end, double* aov, uint32_t overwrite) {
     __shared__ uint32_t stack[TRAVERSAL_STACK * BLOCK];
     const uint32_t n_pixels = cam.width * cam.height;
@@ -254,10 +255,10 @@ PT_DEV void aov_pixels(const SceneD& sc, const CamD& cam, uint64_t seed, uint32_
         double depth = 0.0, hits = 0.0;
         for (uint32_t s = spp_begin; s < spp_end; ++s) {
             std::conditional_t<QMC, RngQ, Rng> rng{(uint32_t)seed, (uint32_t)(seed >> 32), p, s, 0u};
-            const RayD r = generate_ray(cam, row, col, rng);
-            const Closest c = closest_hit(sc, r, 1e-3, &stack[threadIdx.x]);
+            const RayD r = generate_ray<MOT>(cam, row, col, rng);
+            const Closest c = closest_hit<MOT>(sc, r, 1e-3, &stack[threadIdx.x]);
             HitD h;
-            if (c.id != HIT_NONE && reconstruct_hit(sc, r, c.id, 1e-3, h)) {
+            if (c.id != HIT_NONE && reconstruct_hit<true, MOT>(sc, r, c.id, 1e-3, h)) {
                 alb = alb + aov_albedo(sc, sc.mats[h.mat], h);
                 nrm = nrm + h.sn;
                 depth = depth + h.dist;

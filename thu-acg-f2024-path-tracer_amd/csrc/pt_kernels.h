@@ -8,8 +8,8 @@
 namespace pt {
 // What a render asks of K1 / K3 / the AOV walk. variant: k_shade's shape code (pt_forms.h SHADE_SHAPES; PT_SHADE_VARIANT); lights: the scene
 // has a lights list; list: pixel-list render (PoolD::list); qmc: the Sobol sampler (pt_scene_set_sampler); mode: the
-// shading mode (pt_types.h ShadeMode). Which forms exist: pt_forms.h shade_form_exists.
-struct ShadeForm { int variant = 0; bool lights = false, list = false, qmc = false; ShadeMode mode = MODE_PLAIN; };
+// shading mode (pt_types.h ShadeMode); motion: motion is in effect (pt_scene_motion). Which forms exist: pt_forms.h shade_form_exists.
+struct ShadeForm { int variant = 0; bool lights = false, list = false, qmc = false; ShadeMode mode = MODE_PLAIN; bool motion = false; };
 // The form a render gets: pixel lists, qmc and every mode but the plain one exist for the default variant's shapes only — any other variant becomes 42.
 // The launchers and queries below take the form this returns.
 ShadeForm shade_form(ShadeForm asked);
@@ -19,13 +19,15 @@ bool shade_form_sorts(const ShadeForm& form);
 bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, const ShadeForm& form);
 // K2 variant code (`code` of launch_extend / extend_occupancy_blocks): -1 = batch kernel (-2 / -3 ask extend_occupancy_blocks for its
 // flat-top-level instantiation without / with pair passes), -(stack*10 + blocks) = two-phase kernel k_extend2<stack, blocks> for stack in {16, 20, 24}.
-void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st);
+// motion: the MOT forms (instances posed at each ray's time). They exist for the batch kernel and the default two-phase codes; another
+// two-phase code becomes the default one for its stack.
+void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st, bool motion = false);
 // wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
 // env: the table argument of a mode that has one (pt_types.h mode_has_table) — the ENV forms' tables; the DSP forms' weight table (device, DSP_BINS x 3) in `col` — else null
 bool launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, const ShadeForm& form, hipStream_t st,
                   uint32_t wide_window_min = 16, const EnvTabD* env = nullptr);
 // resident blocks per CU of the K2 / K3 kernel a render launches (shade: 0 when no kernel of that form exists)
-int extend_occupancy_blocks(int code);
+int extend_occupancy_blocks(int code, bool motion = false);
 int shade_occupancy_blocks(const ShadeForm& form);
 // pt_medium_probe: the medium functions k_shade's MED forms call (which 0: n x (u1, u2, dir.xyz) -> n x (new_dir.xyz, ph); 1: n x u ->
 // n free-flight distances); in / out: device
@@ -38,6 +40,7 @@ void launch_absorb_probe(const double absorption[3], const double* in, uint32_t 
 // pt_light_probe: lights.sample / lights.pdf as k_shade calls them (exact: the LSE forms' functions, else the reference's; which 0: n x
 // (origin.xyz, time) -> n x (dir.xyz, light index, face or -1, draws consumed), row i with the independent sampler's draws of (seed 0,
 // pixel i, sample 0) from draw 0; which 1: n x (origin.xyz, direction.xyz, time) -> n lights.pdf values); in / out: device
+// (a scene with moving instances — SceneD::inst_motion — is probed with every instance posed at the row's time)
 void launch_light_probe(const SceneD& sc, bool exact, int which, const double* in, uint32_t n, double* out, hipStream_t st);
 // pt_dispersion_probe: the device functions k_shade's DSP forms call (which 0: n x (pixel, sample) -> n x (u, lambda, bin, W_r, W_g, W_b, n(lambda)) under
 // sampler `kind`; 1: n wavelengths in nm -> n values n(lambda)); n_d, b, inv2_d: the glass's MatD::ior, p[1], p[2]; w: the weight table; in / out / w: device
@@ -76,6 +79,7 @@ bool launch_film_conv(const double* in, double* out, uint32_t rows, uint32_t col
 void launch_film_develop(const double* sums, uint32_t n_pixels, double scale, const uint32_t* counts, double k, double thr, double s, const double* glare,
                          uint32_t tonemap, double white, double* hdr, uint8_t* rgb8, hipStream_t st);
 // pt_camera_probe: generate_ray as k_init calls it under sampler `kind` (n x (pixel, sample) -> n x (origin.xyz, direction.xyz, time, draws consumed)); in / out: device
-void launch_camera_probe(const CamD& cam, int kind, uint64_t seed, const double* in, uint32_t n, double* out, hipStream_t st);
+// motion: the shutter is applied (motion is in effect)
+void launch_camera_probe(const CamD& cam, int kind, uint64_t seed, const double* in, uint32_t n, double* out, hipStream_t st, bool motion = false);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);
 }  // namespace pt

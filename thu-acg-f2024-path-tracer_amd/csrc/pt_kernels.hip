@@ -161,22 +161,25 @@ __global__ void k_math_probe(int which, const double* in, uint32_t n, double* ou
 }
 
 // pt_camera_probe: generate_ray as k_init calls it (the sample's stream from draw 0), under the camera's projection
-template <bool QMC>
+template <bool QMC, bool MOT = false>   // MOT: motion is in effect, the shutter is applied
 __global__ __launch_bounds__(BLOCK) void k_camera_probe(CamD cam, uint64_t seed, const double* in, uint32_t n, double* out) {
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         const uint32_t pixel = (uint32_t)in[2 * (size_t)i], sample = (uint32_t)in[2 * (size_t)i + 1];
         uint32_t row, col;
         divmod_u31(pixel, cam.width, row, col);
         std::conditional_t<QMC, RngQ, Rng> rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, 0u};
-        const RayD r = generate_ray(cam, row, col, rng);
+        const RayD r = generate_ray<MOT>(cam, row, col, rng);
         double* o = out + 8 * (size_t)i;
         o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z; o[6] = r.time; o[7] = (double)rng.draw;
     }
 }
 
 // ------------------------------------------------------------------------------- launchers
-void launch_camera_probe(const CamD& cam, int kind, uint64_t seed, const double* in, uint32_t n, double* out, hipStream_t st) {
-    if (kind == 1) hipLaunchKernelGGL(k_camera_probe<true>, grid_for(n, 2048), dim3(BLOCK), 0, st, cam, seed, in, n, out);
+void launch_camera_probe(const CamD& cam, int kind, uint64_t seed, const double* in, uint32_t n, double* out, hipStream_t st, bool motion) {
+    if (motion) {
+        if (kind == 1) hipLaunchKernelGGL((k_camera_probe<true, true>), grid_for(n, 2048), dim3(BLOCK), 0, st, cam, seed, in, n, out);
+        else hipLaunchKernelGGL((k_camera_probe<false, true>), grid_for(n, 2048), dim3(BLOCK), 0, st, cam, seed, in, n, out);
+    } else if (kind == 1) hipLaunchKernelGGL(k_camera_probe<true>, grid_for(n, 2048), dim3(BLOCK), 0, st, cam, seed, in, n, out);
     else hipLaunchKernelGGL(k_camera_probe<false>, grid_for(n, 2048), dim3(BLOCK), 0, st, cam, seed, in, n, out);
 }
 void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_t st) {

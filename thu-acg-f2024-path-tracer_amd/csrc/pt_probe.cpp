@@ -104,6 +104,8 @@ extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t
     if (which != 0 && which != 1) return set_error("pt_light_probe: which must be 0 or 1");
     if (s->dev.view.n_lights == 0u) return set_error("pt_light_probe: the world has no lights list");
     const bool exact = s->light_sampling == 1;
+    // (pt_render's refusal: the exact functions' chain walks read the stored poses, so they would answer for the scene at time 0)
+    if (exact && s->has_moving_instance) return set_error("pt_light_probe: motion together with exact light sampling is not supported (set light sampling to 0, or take the moving instances out)");
     if (exact && s->light_mesh_bad_area) return set_error("pt_light_probe: exact light sampling needs light meshes of finite, positive area");
     if (exact && s->light_blas_depth > (uint32_t)LIGHT_STACK) return set_error("pt_light_probe: exact light sampling: a light mesh's BVH is deeper than the 24 levels its pdf walk's stack holds");
     if (n == 0) return 0;
@@ -150,7 +152,7 @@ extern "C" int pt_camera_probe(pt_scene* s, const pt_camera* cam, uint64_t seed,
             return set_error("pt_camera_probe: takes (pixel, sample) pairs: pixel < width * height, sample a 32-bit unsigned integer");
     }
     return run_probe(s->ctx, {{in, (size_t)n * 2 * sizeof(double)}}, out, (size_t)n * 8 * sizeof(double), [&](void* const* d_in, void* d_out) {
-        launch_camera_probe(dc, s->sampler, seed, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
+        launch_camera_probe(dc, s->sampler, seed, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream, s->built && s->motion_on());
     });
 }
 

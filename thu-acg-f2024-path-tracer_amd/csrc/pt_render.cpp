@@ -199,6 +199,8 @@ int pt::make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
     dc.fw = (double)dc.width;
     dc.fh = (double)dc.height;
     st3(dc.forward, cd.forward); st3(dc.right, cd.right); st3(dc.up, cd.up);
+    dc.shutter_open = s->shutter_open;   // (pt_scene_set_shutter; read where motion is in effect)
+    dc.shutter_span = s->shutter_close - s->shutter_open;
     if ((dc.projection == PROJ_FISHEYE || dc.projection == PROJ_PANORAMA) && cam->defocus_angle != 0.0)
         return set_error("camera: the fisheye and panorama projections have no lens (defocus_angle must be 0)");
     if (dc.projection == PROJ_FISHEYE) {
@@ -275,6 +277,13 @@ static int render_mode(pt_scene* s, const CamD& dc, hipStream_t st, ShadeMode& m
     if (dsp && lse) return set_error("pt_render: spectral dispersion together with exact light sampling is not supported (set one of them off)");
     if (dsp && dc.max_depth > DSP_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^31 when spectral dispersion is in effect");
     if (dsp && !(env.col = dispersion_table(s, st))) return -1;   // the DSP forms read the weight table where the ENV forms read their tables (pt_types.h)
+    // motion is in effect (pt_amd.h): a placed instance was made by pt_instance_moving, or the shutter is not (0, 1) and something moves. Its
+    // kernels are plain-mode forms (pt_forms.h), so it excludes every other mode; otherwise no new code runs
+    const bool mot = s->motion_on();
+    if (mot && env_on) return set_error("pt_render: motion together with environment importance sampling is not supported (set the sampling off, or take the moving instances out and reset the shutter)");
+    if (mot && med) return set_error("pt_render: motion together with participating media or a glass interior is not supported (take the media out, or take the moving instances out and reset the shutter)");
+    if (mot && lse) return set_error("pt_render: motion together with exact light sampling is not supported (set light sampling to 0, or take the moving instances out and reset the shutter)");
+    if (mot && dsp) return set_error("pt_render: motion together with spectral dispersion is not supported (clear the dispersion, or take the moving instances out and reset the shutter)");
     mode = dsp ? MODE_DSP : lse ? MODE_LSE : !med ? (env_on ? MODE_ENV : MODE_PLAIN) : s->interior_on() ? MODE_INT : s->grid_media_on() ? MODE_HET : MODE_MED;
     return 0;
 }
@@ -425,7 +434,7 @@ int extend2_code(const pt_scene* s, const Switches& sw) {
 }
 Kernels choose_kernels(const Switches& sw, const pt_scene* s, const Job& job, const PoolPlan& p) {
     Kernels kn;
-    kn.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode});
+    kn.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode, s->motion_on()});
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
     // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
@@ -436,7 +445,7 @@ Kernels choose_kernels(const Switches& sw, const pt_scene* s, const Job& job, co
     kn.extend_code = (s->n_mesh_entries > 0 && two_phase != 0) ? -two_phase : -1;
     if (sw.k2 == Switches::K2_BATCH) kn.extend_code = -1;
     else if (sw.k2 == Switches::K2_TWOPHASE && two_phase != 0) kn.extend_code = -two_phase;
-    const int blocks_extend = extend_occupancy_blocks(kn.extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : kn.extend_code);
+    const int blocks_extend = extend_occupancy_blocks(kn.extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : kn.extend_code, kn.form.motion);
     kn.blocks_shade = shade_occupancy_blocks(kn.form);
     kn.grid_extend = s->ctx->n_cus * blocks_extend * sw.grid_mult;
     kn.grid_shade = s->ctx->n_cus * kn.blocks_shade * sw.grid_mult;
@@ -573,7 +582,7 @@ int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPla
     while (alive) {
         for (uint32_t i = 0; i < poll_every; ++i) {
             timer.begin(0, st);
-            launch_extend(s->dev.view, pool, s->d_counters, kn.grid_extend, kn.extend_code, st);
+            launch_extend(s->dev.view, pool, s->d_counters, kn.grid_extend, kn.extend_code, st, kn.form.motion);
             timer.end(st);
             timer.begin(1, st);
             if (!launch_shade(s->dev.view, dc, pool, s->d_counters, job.seed, kn.grid_shade, kn.form, st, sw.wide_window_min, mode_has_table(job.mode) ? &job.env : nullptr))
@@ -919,6 +928,7 @@ extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, 
     }
     ShadeForm aov_form;   // of a form, the AOV walk looks at the sampler only
     aov_form.qmc = s->sampler == 1;
+    aov_form.motion = s->motion_on();   // moving instances are posed at each sample's time, taken through the shutter
     if (!launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, aov_form))
         return set_error("pt_render_aovs: no k_aov form for this sampler");
     if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;

@@ -480,19 +480,26 @@ extern "C" int pt_mesh(pt_scene* s, double scale, uint32_t n_pos, const float* p
     }
     return push_obj(s, std::move(o));
 }
+static void make_pose(D3 axis, double angle, D3 tr, InstD& xf);
 extern "C" int pt_instance(pt_scene* s, int obj, const double axis[3], double angle, const double tr[3]) {   // instance.rs:20-30
     if (!OBJ_OK(s, obj)) return set_error("pt_instance: bad object handle");
     // the wrapped object may be wrapped again (shared geometry), may itself be an instance (nesting) and may also be placed directly
     HostObj o;
     o.kind = OBJ_INSTANCE;
     o.child = obj;
+    make_pose(d3(axis), angle, d3(tr), o.xf);
+    return push_obj(s, std::move(o));
+}
+// The forward transform and its analytic inverse of Instance::new(axis, angle, tr). THE operation sequence of an instance's pose: pt_instance,
+// the keys of pt_instance_moving, pt_motion_pose and — operation by operation — the device's pose_at (pt_dev_geom.h) all form it this way.
+static void make_pose(D3 axis, double angle, D3 tr, InstD& xf) {
     // DQuat::from_axis_angle, DMat4::from_rotation_translation (glam 0.29 quat_to_axes)
     // detmath, not libm: g++ turns a sin/cos pair into one sincos() call, clang keeps two calls, and glibc's sincos can
     // differ from its sin and cos in the last bit on some CPUs — found by fuzzing (one instance angle in 40 scenes gave
     // a rotation matrix one ulp off the oracle's). The shared implementation makes the transform machine-independent.
     double sn, cs;
     detmath::sincos(angle * 0.5, sn, cs);
-    D3 v = d3(axis) * sn;
+    D3 v = axis * sn;
     double qx = v.x, qy = v.y, qz = v.z, qw = cs;
     double x2 = qx + qx, y2 = qy + qy, z2 = qz + qz;
     double xx = qx * x2, xy = qx * y2, xz = qx * z2;
@@ -501,14 +508,129 @@ extern "C" int pt_instance(pt_scene* s, int obj, const double axis[3], double an
     D3 c0{1.0 - (yy + zz), xy + wz, xz - wy};
     D3 c1{xy - wz, 1.0 - (xx + zz), yz + wx};
     D3 c2{xz + wy, yz - wx, 1.0 - (xx + yy)};
-    D3 t = d3(tr);
+    D3 t = tr;
     // analytic rigid inverse: R^T and -(R^T t)  
     D3 i0{c0.x, c1.x, c2.x}, i1{c0.y, c1.y, c2.y}, i2{c0.z, c1.z, c2.z};
     D3 it = -xform_vector(i0, i1, i2, t);
-    st3(o.xf.c0, c0); st3(o.xf.c1, c1); st3(o.xf.c2, c2); st3(o.xf.t, t);
-    st3(o.xf.i0, i0); st3(o.xf.i1, i1); st3(o.xf.i2, i2); st3(o.xf.it, it);
-    o.xf.inner = o.xf.outer = -1;
+    st3(xf.c0, c0); st3(xf.c1, c1); st3(xf.c2, c2); st3(xf.t, t);
+    st3(xf.i0, i0); st3(xf.i1, i1); st3(xf.i2, i2); st3(xf.it, it);
+    xf.inner = xf.outer = -1;
+}
+// ---- motion (pt_instance_moving, pt_scene_set_shutter; the rule: pt_amd.h) ----
+static bool finite3(const double* v) { return v && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+static bool keys_ok(const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3]) {
+    return finite3(axis) && finite3(tr0) && finite3(tr1) && std::isfinite(angle0) && std::isfinite(angle1);
+}
+static InstMotionD make_keys(const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3]) {
+    InstMotionD k{};
+    for (int i = 0; i < 3; ++i) { k.axis[i] = axis[i]; k.tr0[i] = tr0[i]; k.dtr[i] = tr1[i] - tr0[i]; }
+    k.angle0 = angle0;
+    k.dangle = angle1 - angle0;
+    k.moves = 1u;
+    k.spins = angle0 != angle1 ? 1u : 0u;
+    return k;
+}
+// the pose of keys `k` at `time`: the rule's two lerps, then pt_instance's sequence (a key pair that does not spin builds the same columns
+// at every time — the ones the record stores)
+static void pose_of_keys(const InstMotionD& k, double time, InstD& xf) {
+    const double angle = k.angle0 + k.dangle * time;
+    const D3 tr = d3(k.tr0) + d3(k.dtr) * time;
+    make_pose(d3(k.axis), k.spins ? angle : k.angle0 + k.dangle * 0.0, tr, xf);
+}
+extern "C" int pt_instance_moving(pt_scene* s, int obj, const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3]) {
+    if (!s) return set_error("pt_instance_moving: null scene");
+    if (!OBJ_OK(s, obj)) return set_error("pt_instance_moving: bad object handle");
+    if (!keys_ok(axis, angle0, angle1, tr0, tr1)) return set_error("pt_instance_moving: axis, angles and translations must be finite");
+    HostObj o;
+    o.kind = OBJ_INSTANCE;
+    o.child = obj;
+    o.motion = make_keys(axis, angle0, angle1, tr0, tr1);
+    pose_of_keys(o.motion, 0.0, o.xf);   // InstD holds the pose at time 0
     return push_obj(s, std::move(o));
+}
+extern "C" int pt_scene_set_shutter(pt_scene* s, double open, double close) {
+    if (!s) return set_error("pt_scene_set_shutter: null scene");
+    if (!std::isfinite(open) || !std::isfinite(close) || !(0.0 <= open && open <= close && close <= 1.0))
+        return set_error("pt_scene_set_shutter: the shutter needs finite times with 0 <= open <= close <= 1");
+    s->shutter_open = open;
+    s->shutter_close = close;
+    return 0;
+}
+extern "C" int pt_scene_shutter(pt_scene* s, double out[2]) {
+    if (!s || !out) return set_error("pt_scene_shutter: null scene or buffer");
+    out[0] = s->shutter_open;
+    out[1] = s->shutter_close;
+    return 0;
+}
+extern "C" int pt_scene_motion(pt_scene* s) {
+    if (!s || !s->built) return set_error("pt_scene_motion: world not built");
+    return s->motion_on() ? 1 : 0;
+}
+extern "C" int pt_motion_pose(const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double time, double out24[24]) {
+    if (!out24) return set_error("pt_motion_pose: null buffer");
+    if (!keys_ok(axis, angle0, angle1, tr0, tr1) || !std::isfinite(time)) return set_error("pt_motion_pose: axis, angles, translations and time must be finite");
+    InstD xf;
+    pose_of_keys(make_keys(axis, angle0, angle1, tr0, tr1), time, xf);
+    memcpy(out24, xf.c0, 24 * sizeof(double));   // c0, c1, c2, t, i0, i1, i2, it: InstD's order
+    return 0;
+}
+static Box xform_box(const Box& b, const InstD& m) {   // box of the box (aabb.rs:50-76)
+    Box r;
+    for (int i = 0; i < 8; ++i) {
+        D3 p{(i & 1) ? b.hi.x : b.lo.x, (i & 2) ? b.hi.y : b.lo.y, (i & 4) ? b.hi.z : b.lo.z};
+        r.grow(xform_point(d3(m.c0), d3(m.c1), d3(m.c2), d3(m.t), p));
+    }
+    return r;
+}
+// One level of the box rule: the box of `b` under a moving instance over every time in [0, 1].
+// Translates only: the union of the transformed boxes at times 0 and 1 — exact, since every corner is R p + tr(t) with R fixed and tr(t)
+// monotone in t component by component (in floating point too: rounding is monotone). Spins: a corner p lands at R(t) p + tr(t) with
+// |R(t) p| = |p| <= rho, the largest corner norm, so the union of tr(0) +- rho and tr(1) +- rho holds it; rho is widened by 1e-14 relative and
+// the box by four ulps of its largest coordinate for the rounding of R(t) p and of the sum.
+static Box swept_box(const Box& b, const InstMotionD& k) {
+    InstD m0, m1;
+    pose_of_keys(k, 0.0, m0);
+    pose_of_keys(k, 1.0, m1);
+    Box r;
+    if (!k.spins) {
+        r = xform_box(b, m0);
+        r.grow(xform_box(b, m1));
+        return r;
+    }
+    double rho = 0.0;
+    for (int i = 0; i < 8; ++i) {
+        D3 p{(i & 1) ? b.hi.x : b.lo.x, (i & 2) ? b.hi.y : b.lo.y, (i & 4) ? b.hi.z : b.lo.z};
+        rho = std::fmax(rho, std::sqrt(dot(p, p)));
+    }
+    rho = rho * (1.0 + 1e-14);
+    const D3 e{rho, rho, rho};
+    r.grow(d3(m0.t) - e); r.grow(d3(m0.t) + e);
+    r.grow(d3(m1.t) - e); r.grow(d3(m1.t) + e);
+    double mx = 0.0;
+    for (double x : {r.lo.x, r.lo.y, r.lo.z, r.hi.x, r.hi.y, r.hi.z}) mx = std::fmax(mx, std::fabs(x));
+    const D3 pad{mx * (4.0 * DBL_EPSILON), mx * (4.0 * DBL_EPSILON), mx * (4.0 * DBL_EPSILON)};
+    r.lo = r.lo - pad;
+    r.hi = r.hi + pad;
+    return r;
+}
+extern "C" int pt_motion_swept_box(const double box[6], const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double out[6]) {
+    if (!box || !out) return set_error("pt_motion_swept_box: null buffer");
+    if (!finite3(box) || !finite3(box + 3) || !keys_ok(axis, angle0, angle1, tr0, tr1)) return set_error("pt_motion_swept_box: box, axis, angles and translations must be finite");
+    if (!(box[0] <= box[3] && box[1] <= box[4] && box[2] <= box[5])) return set_error("pt_motion_swept_box: the box needs lo <= hi on every axis");
+    Box b;
+    b.lo = d3(box);
+    b.hi = d3(box + 3);
+    const Box r = swept_box(b, make_keys(axis, angle0, angle1, tr0, tr1));
+    st3(out, r.lo);
+    st3(out + 3, r.hi);
+    return 0;
+}
+extern "C" int pt_world_entry_box(pt_scene* s, uint32_t entry, double out[6]) {
+    if (!s || !s->built) return set_error("pt_world_entry_box: world not built");
+    if (!out) return set_error("pt_world_entry_box: null buffer");
+    if ((size_t)entry * 6 >= s->entry_boxes.size()) return set_error("pt_world_entry_box: entry out of range");
+    memcpy(out, &s->entry_boxes[(size_t)entry * 6], 6 * sizeof(double));
+    return 0;
 }
 static int place(pt_scene* s, int obj, std::vector<int>& list, const char* who) {
     if (!OBJ_OK(s, obj)) return set_error(std::string(who) + ": bad object handle");
@@ -738,14 +860,6 @@ Box quad_box(const QuadD& q) {
     b.grow(o); b.grow(o + u); b.grow(o + v); b.grow(o + u + v);
     return b;
 }
-Box xform_box(const Box& b, const InstD& m) {
-    Box r;
-    for (int i = 0; i < 8; ++i) {
-        D3 p{(i & 1) ? b.hi.x : b.lo.x, (i & 2) ? b.hi.y : b.lo.y, (i & 4) ? b.hi.z : b.lo.z};
-        r.grow(xform_point(d3(m.c0), d3(m.c1), d3(m.c2), d3(m.t), p));
-    }
-    return r;
-}
 }  // namespace
 
 int pt::scene_build(pt_scene* s) {
@@ -763,6 +877,8 @@ int pt::scene_build(pt_scene* s) {
     std::vector<TriAttr> tri_attr;
     std::vector<uint32_t> tri_gid;
     std::vector<InstD> insts;
+    std::vector<InstMotionD> inst_motion;   // parallel to insts (SceneD::inst_motion); uploaded when an instance moves
+    bool any_moving = false;
     std::vector<uint32_t> lights;
     std::vector<double> light_cdf;   // the light meshes' running area sums (SceneD::light_cdf), one table per mesh object
     s->lights_have_mesh_or_sphere = s->light_mesh_bad_area = false;
@@ -795,6 +911,8 @@ int pt::scene_build(pt_scene* s) {
             if (guard > 64) return set_error("pt_world_build: instance chain too deep");
             chain.push_back((int)insts.size());
             insts.push_back(s->objs[oi].xf);
+            inst_motion.push_back(s->objs[oi].motion);
+            any_moving = any_moving || s->objs[oi].motion.moves != 0u;
             oi = s->objs[oi].child;
         }
         for (size_t k = 0; k < chain.size(); ++k) {
@@ -941,8 +1059,27 @@ int pt::scene_build(pt_scene* s) {
         }
         e.n_prims = (uint32_t)prims.size() - e.first_prim;
         Box world = local;
-        for (size_t k = chain.size(); k-- > 0;) world = xform_box(world, insts[chain[k]]);   // box of the box, per instance (aabb.rs:50-76)
-        if (!chain.empty() && o->kind == OBJ_MESH) {
+        bool chain_moves = false;
+        for (size_t k = chain.size(); k-- > 0;) {   // box of the box, per instance (aabb.rs:50-76); a moving level: the box rule over [0, 1] (swept_box)
+            const InstMotionD& mk = inst_motion[chain[k]];
+            chain_moves = chain_moves || mk.moves != 0u;
+            world = mk.moves ? swept_box(world, mk) : xform_box(world, insts[chain[k]]);
+        }
+        if (chain.size() == 1 && chain_moves && !inst_motion[chain[0]].spins && o->kind == OBJ_MESH) {
+            // a mesh under ONE instance that translates only: the bounds of its transformed vertices at times 0 and 1, as below — every
+            // vertex is R p + tr(t) with tr(t) monotone in t component by component, so the two ends hold every time in between
+            InstD m0, m1;
+            pose_of_keys(inst_motion[chain[0]], 0.0, m0);
+            pose_of_keys(inst_motion[chain[0]], 1.0, m1);
+            Box tight;
+            for (const TriD& t : o->tris)
+                for (const double* v : {t.v0, t.v1, t.v2}) {
+                    tight.grow(xform_point(d3(m0.c0), d3(m0.c1), d3(m0.c2), d3(m0.t), d3(v)));
+                    tight.grow(xform_point(d3(m1.c0), d3(m1.c1), d3(m1.c2), d3(m1.t), d3(v)));
+                }
+            world = tight;
+        }
+        if (!chain.empty() && o->kind == OBJ_MESH && !chain_moves) {
             // an instanced mesh gets the bounds of its TRANSFORMED VERTICES, not the box of its transformed box
             // (aabb.rs:50-76 does the latter): a mesh turned by ~50 degrees has a third less box to enter, and
             // every ray that enters costs a trip through the mesh pass. Any conservative box gives the same
@@ -986,6 +1123,9 @@ int pt::scene_build(pt_scene* s) {
     }
     std::vector<Box> entry_boxes(tlas_items.size());
     for (const BuildItem& it : tlas_items) entry_boxes[it.ref_payload] = it.box;
+    s->entry_boxes.clear();   // pt_world_entry_box: the f64 boxes, before the f32 rounding
+    for (const Box& b : entry_boxes)
+        for (double x : {b.lo.x, b.lo.y, b.lo.z, b.hi.x, b.hi.y, b.hi.z}) s->entry_boxes.push_back(x);
     // Build the TLAS over world entries (one entry per leaf).
     Builder tl{nodes, tlas_items, 1, MAX_TLAS_DEPTH, false, nullptr};
     Box wb;
@@ -1085,6 +1225,7 @@ int pt::scene_build(pt_scene* s) {
               upload(dev, mats, v.mats) && upload(dev, atlas, v.atlas) && upload(dev, atlas_f, v.atlas_f) && upload(dev, lights, v.lights) && upload(dev, entry_box, v.entry_box) && upload(dev, cuboid_box, v.cuboid_box) &&
               upload(dev, light_cdf, v.light_cdf);
     if (ok && any_attr) ok = upload(dev, tri_attr, v.tri_attr);
+    if (ok && any_moving) ok = upload(dev, inst_motion, v.inst_motion);
     if (ok && !grids.empty()) ok = upload(dev, grids, v.grids) && upload(dev, grid_vals, v.grid_vals);
     if (!ok) {
         dev.release();
@@ -1106,7 +1247,8 @@ int pt::scene_build(pt_scene* s) {
     dev.view = v;
     s->n_prims = v.n_prims;
     s->n_mesh_entries = 0;
-    s->motionless = true;
+    s->has_moving_instance = any_moving;
+    s->motionless = !any_moving;   // (a moving instance: a ray's time reaches its pose)
     for (const SphereD& sp : spheres)
         for (int i = 0; i < 3; ++i) s->motionless = s->motionless && sp.p1[i] == sp.p2[i];
     for (const Entry& e : entries) s->n_mesh_entries += e.kind == ENTRY_MESH ? 1u : 0u;

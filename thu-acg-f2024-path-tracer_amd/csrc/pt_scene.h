@@ -48,7 +48,8 @@ struct HostObj {
     std::vector<TriAttr> tri_attr;  // mesh with normals and/or uvs
     bool has_normals = false, has_uvs = false;
     int child = -1;                 // instance
-    InstD xf{};
+    InstD xf{};                     // (pt_instance_moving: the pose at time 0)
+    InstMotionD motion{};           // the keys of pt_instance_moving; moves = 0 for pt_instance
     // An object may be placed in the world directly any number of times and wrapped by any number of instances, and an instance
     // may wrap an instance (Instance::new / World::add_object take an Arc<dyn Hittable>, instance.rs:20-30, world.rs:18-24).
 };
@@ -77,7 +78,15 @@ struct pt_scene {
     bool float_hdr = false;        // scene scripts / host mirrors load Radiance files as f32 textures (pt_scene_set_float_hdr)
     uint32_t n_prims = 0;
     uint32_t n_mesh_entries = 0;   // world-level triangle meshes (picks the K2 variant)
-    bool motionless = false;       // no sphere moves (p1 == p2 everywhere): a ray's time never reaches an arithmetic result
+    bool motionless = false;       // no sphere moves (p1 == p2 everywhere) and no instance was made by pt_instance_moving: a ray's time never reaches an arithmetic result
+    // motion (pt_instance_moving, pt_scene_set_shutter). has_moving_instance (set by scene_build): some placed object's chain
+    // holds an instance made by pt_instance_moving. entry_boxes: the world boxes of the last build, six doubles per entry (pt_world_entry_box).
+    bool has_moving_instance = false;
+    double shutter_open = 0.0, shutter_close = 1.0;
+    std::vector<double> entry_boxes;
+    bool motion_on() const {       // "in effect": the kernels' MOT forms run
+        return has_moving_instance || ((shutter_open != 0.0 || shutter_close != 1.0) && !motionless);
+    }
     uint32_t stack_need = 0;       // worst-case traversal stack entries of this scene's BVHs
     uint32_t device_bvh_min_tris = 1u << 19;   // meshes with at least this many triangles get their BVH built on the GPU (0 = never)
     uint32_t n_device_blas = 0, device_blas_depth = 0;   // meshes of the last build that the GPU builder handled, deepest of them

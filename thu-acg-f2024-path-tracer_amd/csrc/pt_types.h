@@ -97,6 +97,14 @@ struct InstD {
     double c0[3], c1[3], c2[3], t[3], i0[3], i1[3], i2[3], it[3];
     int32_t inner, outer;
 };
+// The two keys of an instance made by pt_instance_moving (the rule: pt_amd.h), parallel to SceneD::insts; the differences
+// are formed once on the host. InstD holds the pose at time 0; the pose at a ray's time is rebuilt per lane by inst_at (pt_dev_geom.h)
+// with pt_instance's operation sequence. moves = 0: a pt_instance record, left as stored. spins = 0 (angle0 == angle1): the stored
+// rotation columns stay, only t and it are recomputed.
+struct InstMotionD {
+    double axis[3], angle0, dangle, tr0[3], dtr[3];
+    uint32_t moves, spins;
+};
 
 // ---- textures / materials ------------------------------------------------------------
 // TEX_IMAGE_F32: ImageTexture WITHOUT the `.to_rgb8()` squash of texture.rs:67 — the decoder's f32 samples (a Radiance .hdr decodes to
@@ -200,6 +208,8 @@ struct CamD {
     double focal_length;
     double fw, fh;           // width and height as doubles (converted on the host: see generate_ray)
     double forward[3], right[3], up[3];   // Camera::init's basis (pt_camera_init)
+    // the shutter (pt_scene_set_shutter): a camera ray's time is shutter_open + shutter_span * u. Read by the MOT forms of K1 / K3 only.
+    double shutter_open, shutter_span;
 };
 enum Projection : uint32_t { PROJ_PERSPECTIVE = 0, PROJ_ORTHOGRAPHIC = 1, PROJ_FISHEYE = 2, PROJ_PANORAMA = 3 };
 
@@ -240,6 +250,7 @@ struct SceneD {
     const float* grid_vals;      // their f32 samples, one array (GridD::ofs)
     const double* light_cdf;     // exact light sampling (pt_scene_set_light_sampling): per light mesh of n faces the n + 1 running
                                  // area sums C[0] = 0 .. C[n] = A in face order, at Entry::pad[0]; read by k_shade's LSE forms and the light probe only
+    const InstMotionD* inst_motion;   // parallel to insts, null when no instance moves; read by the MOT forms of K2 / K3 and the probes only
 };
 constexpr int LIGHT_STACK = 24;          // LDS entries per lane of the LSE forms' all-hits mesh walk (pt_dev_lights.h): the deepest light mesh tree they take
 constexpr uint32_t TLAS_FLAT_MAX = 24;   // round 1 (vector loads): 8-10 entries -26 % / -7 % K2 time, 17 entries (scene 5) +20 % -> limit 12;

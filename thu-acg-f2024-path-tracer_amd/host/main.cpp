@@ -103,6 +103,20 @@ static bool parse_number(const std::string& v, double& out) {
     out = strtod(v.c_str(), &end);
     return !v.empty() && end == v.c_str() + v.size();
 }
+// `n_min` to `n_max` comma-separated finite numbers, each parsed whole (--shutter, --motion)
+static bool parse_numbers(const std::string& v, size_t n_min, size_t n_max, std::vector<double>& x) {
+    x.clear();
+    for (size_t pos = 0; pos <= v.size();) {
+        const size_t comma = std::min(v.find(',', pos), v.size());
+        const std::string tok = v.substr(pos, comma - pos);
+        char* end = nullptr;
+        const double d = strtod(tok.c_str(), &end);
+        if (tok.empty() || !end || *end != 0 || !std::isfinite(d)) return false;
+        x.push_back(d);
+        pos = comma + 1;
+    }
+    return x.size() >= n_min && x.size() <= n_max;
+}
 // X,Y,Z,RADIUS[,R,G,B] of --mesh-light: four or seven numbers, each parsed whole; radius > 0, emission >= 0
 static bool parse_mesh_light(const std::string& v, double out[7]) {
     std::vector<double> x;
@@ -169,6 +183,10 @@ int main(int argc, char** argv) {
     double interior_v[8] = {0.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};   // density, albedo r g b, g, absorption r g b
     double dispersion = 0.0;   // the Abbe number of --dispersion, 0: not given
     int projection = 0;        // --projection: pt_scene_set_projection's kind
+    double shutter[2] = {0.0, 1.0};   // --shutter OPEN,CLOSE
+    bool motion = false;              // --motion DX,DY,DZ[,DEGREES]
+    bool stats = false;               // --stats: the render's statistics as one JSON line on stdout
+    double motion_v[4] = {0.0, 0.0, 0.0, 0.0};
     int light_sampling = -1;   // -1: not given (--mesh-light then implies exact)
     bool mesh_light = false;
     double mesh_light_v[7] = {0.0, 0.0, 0.0, 0.0, 10.0, 10.0, 10.0};   // centre x y z, radius, emission r g b
@@ -239,6 +257,21 @@ int main(int argc, char** argv) {
             else if (v == "panorama") projection = 3;
             else { std::cerr << "--projection must be perspective, orthographic, fisheye or panorama\n"; return 2; }
         }
+        else if (a == "--stats") stats = true;
+        else if (a == "--shutter") {
+            std::vector<double> x;
+            if (!parse_numbers(next(), 2, 2, x) || !(0.0 <= x[0] && x[0] <= x[1] && x[1] <= 1.0)) {
+                std::cerr << "--shutter must be OPEN,CLOSE with 0 <= OPEN <= CLOSE <= 1\n";
+                return 2;
+            }
+            shutter[0] = x[0]; shutter[1] = x[1];
+        }
+        else if (a == "--motion") {
+            std::vector<double> x;
+            if (!parse_numbers(next(), 3, 4, x)) { std::cerr << "--motion must be DX,DY,DZ[,DEGREES]: finite numbers\n"; return 2; }
+            for (size_t k = 0; k < x.size(); ++k) motion_v[k] = x[k];
+            motion = true;
+        }
         else if (a == "--mesh-light") {
             if (!parse_mesh_light(next(), mesh_light_v)) { std::cerr << "--mesh-light must be X,Y,Z,RADIUS[,R,G,B]: radius > 0, emission >= 0\n"; return 2; }
             mesh_light = true;
@@ -266,11 +299,16 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
                          "  --projection: orthographic frames the rectangle the scene's camera sees on its focal plane; fisheye is equidistant with the scene's vfov\n"
                          "           across the image height; panorama is an equirectangular image of everything around the camera position, in world axes: loaded as\n"
                          "           an environment map (--out-hdr, then --float-hdr) it lights another scene. fisheye and panorama have no lens: the scene's\n"
                          "           defocus_angle is set to 0 for them\n"
+                         "  --motion: every instance of the scene moves by (DX, DY, DZ) and turns by DEGREES about its own axis while the shutter is open, and blurs;\n"
+                         "           --shutter: the part of that unit interval the camera's shutter is open for (default 0,1; OPEN = CLOSE freezes the scene at that\n"
+                         "           instant; moving spheres follow it too). Not with --env-sampling, --fog, --smoke, --interior, --dispersion, --light-sampling exact\n"
+                         "           or --mesh-light\n"
+                         "  --stats: every kernel launch of a plain render is timed and its statistics are printed as one JSON line (tools/motion_eval.py reads it)\n"
                          "  --exposure, --tonemap, --white, --bloom: the film stage between the accumulator and the PNG: the image is scaled by 2^EV, light above the\n"
                          "           luminance THRESHOLD (default 1) spreads as glare of strength S (LEVELS Gaussians of SIGMA, 2 SIGMA, ... pixels; defaults 5 and 2),\n"
                          "           then the tone curve (reinhard maps the luminance W, default 4, to white). --out-hdr: the linear image after exposure and glare, f32\n"
@@ -304,6 +342,10 @@ int main(int argc, char** argv) {
         std::cerr << "--dispersion cannot be combined with --env-sampling, --fog, --smoke, --interior, --light-sampling exact or --mesh-light\n";
         return 2;
     }
+    if (motion && (env_sampling > 0.0 || fog || smoke || interior || dispersion > 0.0 || light_sampling == 1)) {
+        std::cerr << "--motion cannot be combined with --env-sampling, --fog, --smoke, --interior, --dispersion, --light-sampling exact or --mesh-light\n";
+        return 2;
+    }
     {   // the film options' ranges: the library's own test, before anything is rendered
         const pt_film_opts fo = film.to_c();
         if (pt_film_opts_check(&fo) != 0) {
@@ -324,6 +366,10 @@ int main(int argc, char** argv) {
         setup.world.sampler = sampler;
         setup.world.light_sampling = light_sampling;
         setup.world.projection = projection;
+        setup.world.shutter[0] = shutter[0]; setup.world.shutter[1] = shutter[1];
+        setup.world.instance_motion = motion;
+        for (int k = 0; k < 3; ++k) setup.world.motion[k] = motion_v[k];
+        setup.world.motion[3] = motion_v[3] * (3.14159265358979323846 / 180.0);
         if (projection >= 2) setup.camera.defocus_angle = 0.0;   // the library refuses a lens there (pt_scene_set_projection's rule)
         if (mesh_light) {   // an emissive level-4 icosphere (5120 triangles), in the world and in the lights list
             auto ball = TriangleMesh::from_obj(1.0, icosphere(4, Vec3{mesh_light_v[0], mesh_light_v[1], mesh_light_v[2]}, mesh_light_v[3]),
@@ -359,6 +405,7 @@ int main(int argc, char** argv) {
         setup.world.build_bvh(ctx, setup.camera.environment.is_map ? setup.camera.environment.map : nullptr);
         setup.camera.init();
         setup.camera.film = film;
+        setup.camera.print_stats = stats;
         std::cerr << "rendering production\n";   // camera.rs:101
         if (use_adaptive) {
             const uint32_t m = (uint32_t)std::max(2L, std::min(min_spp, (long)s));

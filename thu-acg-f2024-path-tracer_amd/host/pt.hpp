@@ -49,6 +49,8 @@ struct Emitter {
     int override_mat = -1;   // >= 0: the primitives emitted now carry this material instead of their own (HomogeneousVolume's boundary)
     const Volume* glass_interior = nullptr;   // the interior of every GlassBSDF without one of its own (World::glass_interior)
     double glass_dispersion = 0.0;            // the Abbe number of every GlassBSDF without one of its own (World::glass_dispersion), 0 = none
+    bool instance_motion = false;             // every Instance without keys of its own moves by motion[0..2] and turns by motion[3] radians (World::instance_motion)
+    double motion[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 // ---- textures (src/texture.rs) ---------------------------------------------------------
@@ -360,14 +362,32 @@ struct Instance : Hittable {   // instance.rs:20-30 — rotate, then translate
     HitPtr object;
     Vec3 axis, translation;
     double angle;
+    // this build's addition (pt_instance_moving): a second key — the pose goes from (angle, translation) at time 0 to (angle1, translation1) at time 1
+    bool moving = false;
+    Vec3 translation1;
+    double angle1 = 0.0;
     static std::shared_ptr<Instance> new_(HitPtr obj, Vec3 axis, double angle, Vec3 translation) {
         auto s = std::make_shared<Instance>();
         s->object = obj; s->axis = axis; s->angle = angle; s->translation = translation;
         return s;
     }
+    static std::shared_ptr<Instance> new_moving(HitPtr obj, Vec3 axis, double angle0, double angle1, Vec3 tr0, Vec3 tr1) {
+        auto s = new_(obj, axis, angle0, tr0);
+        s->moving = true; s->angle1 = angle1; s->translation1 = tr1;
+        return s;
+    }
     int emit(Emitter& e) const override {
         const double a[3] = {axis.x, axis.y, axis.z}, t[3] = {translation.x, translation.y, translation.z};
-        int h = pt_instance(e.scene, object->emit(e), a, angle, t);
+        int h;
+        if (moving) {
+            const double t1[3] = {translation1.x, translation1.y, translation1.z};
+            h = pt_instance_moving(e.scene, object->emit(e), a, angle, angle1, t, t1);
+        } else if (e.instance_motion) {   // World::instance_motion: tr1 = tr0 + D, angle1 = angle0 + the turn
+            const double t1[3] = {translation.x + e.motion[0], translation.y + e.motion[1], translation.z + e.motion[2]};
+            h = pt_instance_moving(e.scene, object->emit(e), a, angle, angle + e.motion[3], t, t1);
+        } else {
+            h = pt_instance(e.scene, object->emit(e), a, angle, t);
+        }
         if (h < 0) panic("Instance");
         return h;
     }
@@ -481,6 +501,8 @@ struct World {
         Emitter e{s, asset_dir, {}};
         e.glass_interior = glass_interior.get();
         e.glass_dispersion = glass_dispersion;
+        e.instance_motion = instance_motion;
+        for (int i = 0; i < 4; ++i) e.motion[i] = motion[i];
         for (auto& o : objects) if (pt_world_add_object(s, o->emit(e)) != 0) panic("World::add_object");
         for (auto& l : lights) if (pt_world_add_light(s, l->emit(e)) != 0) panic("World::add_light");
         if (env) env->emit(e);
@@ -501,6 +523,11 @@ struct World {
     double env_sampling = 0.0;   // this build's option: environment importance sampling weight (pt_scene_set_env_sampling; 0 = off)
     int light_sampling = 0;      // this build's option: 0 the reference's lights.sample / lights.pdf, 1 exact (pt_scene_set_light_sampling)
     int projection = 0;          // this build's option: 0 perspective (the reference's camera), 1 orthographic, 2 fisheye, 3 panorama (pt_scene_set_projection)
+    // this build's options (motion blur of instances): the camera shutter (pt_scene_set_shutter), and a second key applied to every Instance a
+    // scene script makes: tr1 = tr0 + motion[0..2], angle1 = angle0 + motion[3] radians (pt_render --motion)
+    double shutter[2] = {0.0, 1.0};
+    bool instance_motion = false;
+    double motion[4] = {0.0, 0.0, 0.0, 0.0};
     void build_bvh(pt_ctx* ctx, std::shared_ptr<ImageTexture> env = nullptr) {
         pt_scene* s = pt_scene_create(ctx);
         if (!s) panic("pt_scene_create");
@@ -510,6 +537,7 @@ struct World {
         if (sampler != 0 && pt_scene_set_sampler(s, sampler) != 0) panic("set_sampler");
         if (light_sampling != 0 && pt_scene_set_light_sampling(s, light_sampling) != 0) panic("set_light_sampling");
         if (projection != 0 && pt_scene_set_projection(s, projection) != 0) panic("set_projection");
+        if ((shutter[0] != 0.0 || shutter[1] != 1.0) && pt_scene_set_shutter(s, shutter[0], shutter[1]) != 0) panic("set_shutter");
         emit_into(s, env);
     }
     void release() {
@@ -608,17 +636,26 @@ struct Camera {
         }
     }
     // camera.rs:79-126: render, gamma, quantise, save PNG, print the wall-clock seconds
+    bool print_stats = false;   // this build's option (pt_render --stats): render() times every launch and prints the render's statistics as one JSON line
     void render(World& world, const std::string& filename, uint64_t seed = 1, pt_render_stats* stats_out = nullptr) const {
         auto start = std::chrono::steady_clock::now();
         pt_camera c = to_c(&world);
         const size_t n = image_width * image_height;
         std::vector<double> accum(n * 3, 0.0);
         pt_render_stats st;
-        if (pt_render(world.scene, &c, seed, 0, (uint32_t)samples_per_pixel, accum.data(), nullptr, &st) != 0) panic("Camera::render");
+        pt_render_opts ro;
+        std::memset(&ro, 0, sizeof ro);
+        ro.profile = 1u;   // (print_stats: every launch is timed, so K2's and K3's milliseconds are known)
+        if (pt_render(world.scene, &c, seed, 0, (uint32_t)samples_per_pixel, accum.data(), print_stats ? &ro : nullptr, &st) != 0) panic("Camera::render");
         develop(world, filename, accum, (uint32_t)samples_per_pixel, nullptr, "Camera::render");
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         std::fprintf(stderr, "[camera.rs:125] start.elapsed().as_secs_f64() = %.6f (render kernel time %.3f s, %.2f Msamples/s)\n", secs,
                      st.ms_total * 1e-3, (double)st.samples / (st.ms_total * 1e-3) * 1e-6);
+        if (print_stats)
+            std::printf("{\"samples\": %llu, \"segments\": %llu, \"ms_total\": %.4f, \"ms_extend\": %.4f, \"ms_shade\": %.4f, \"launches_extend\": %llu, \"launches_shade\": %llu, "
+                        "\"extend_variant\": %u, \"shade_variant\": %u, \"motion\": %d}\n",
+                        (unsigned long long)st.samples, (unsigned long long)st.segments, st.ms_total, st.ms_extend, st.ms_shade, (unsigned long long)st.launches_extend,
+                        (unsigned long long)st.launches_shade, st.extend_variant, st.shade_variant, pt_scene_motion(world.scene));
         if (stats_out) *stats_out = st;
     }
     // not in the reference: render to a noise target (pt_render_adaptive) with samples_per_pixel as the cap; each pixel is
