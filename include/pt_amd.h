@@ -59,6 +59,11 @@ typedef struct pt_render_stats {
     uint32_t blocks_extend, blocks_shade;
     uint32_t compactions;                  /* times the thinning pool was compacted at the frame's end (dynamic mode) */
     uint32_t n_alloc_end;                  /* slots the last launches still covered */
+    /* the sky pass (pt_sky_tiles below): 8x8 pixel tiles rendered outside the path pool, their samples — the tiles' pixels inside
+       the image x the samples per pixel, counted in `samples` and `segments` as well — and the HIP-event time of their kernel (profile=1).
+       All zero when the pass is off. */
+    uint64_t sky_tiles, sky_samples;
+    double ms_sky;
 } pt_render_stats;
 
 const char* pt_last_error(void);
@@ -417,6 +422,14 @@ int pt_scene_motion(pt_scene*);         /* 1: motion is in effect, 0: not, -1: t
 /* Host only, no context needed. pt_motion_pose: the InstD numbers of the pose at `time` (c0, c1, c2, t, i0, i1, i2, it: 24 doubles).
  * pt_motion_swept_box: one level of the box rule for box = (lo.xyz, hi.xyz). */
 int pt_motion_pose(const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double time, double out24[24]);
+/* Host only, no context needed. The sky pass's tile test: out_tiles[ty * tiles_x + tx] (tiles_x = ceil(width / 8), ceil(height / 8) rows) = 1 when NO
+   ray the perspective camera can generate for any pixel of the 8x8 tile (ty, tx), any sample — any lens point, any jitter within blur_strength —
+   can enter any of the n_boxes world-space boxes (six doubles each: lo.xyz, hi.xyz), else 0. Conservative: a 1 is a proof (the test and the proof are in
+   csrc/pt_sky_tiles.h), a 0 promises nothing. More than 64 boxes are tested as their union. n_boxes = 0 clears every tile; a camera inside or touching a
+   box clears none. A dynamic-mode pt_render of the whole frame in the plain shading mode (independent sampler, perspective projection, nothing
+   moving, no camera medium) applies the test to the boxes of the world's entries (pt_world_entry_box) and renders the cleared tiles — every sample of
+   theirs is the environment in the camera ray's direction — outside the path pool; the frame's sums and counts are what they are without. */
+int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, uint8_t* out_tiles);
 int pt_motion_swept_box(const double box[6], const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double out[6]);
 /* test probe: the f64 world box (lo.xyz, hi.xyz) of world entry `entry` (lights list first, then objects), before the f32 rounding */
 int pt_world_entry_box(pt_scene*, uint32_t entry, double out[6]);

@@ -79,6 +79,9 @@ class RenderStats(C.Structure):
         ("blocks_shade", C.c_uint32),
         ("compactions", C.c_uint32),
         ("n_alloc_end", C.c_uint32),
+        ("sky_tiles", C.c_uint64),
+        ("sky_samples", C.c_uint64),
+        ("ms_sky", C.c_double),
     ]
 
     def as_dict(self):
@@ -155,6 +158,7 @@ ABI_SYMBOLS = [
     "pt_mat_glass_set_dispersion", "pt_mat_glass_dispersion", "pt_dispersion_probe",
     "pt_scene_set_projection", "pt_scene_projection", "pt_camera_probe",
     "pt_instance_moving", "pt_scene_set_shutter", "pt_scene_shutter", "pt_scene_motion", "pt_motion_pose", "pt_motion_swept_box", "pt_world_entry_box",
+    "pt_sky_tiles",
 ]
 
 
@@ -223,6 +227,8 @@ def _load():
         lib.pt_motion_pose.argtypes = [d3, C.c_double, C.c_double, d3, d3, C.c_double, d3]
         lib.pt_motion_swept_box.argtypes = [d3, d3, C.c_double, C.c_double, d3, d3, d3]
         lib.pt_world_entry_box.argtypes = [C.c_void_p, C.c_uint32, d3]
+    if hasattr(lib, "pt_sky_tiles"):
+        lib.pt_sky_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -832,6 +838,16 @@ def motion_swept_box(box, axis, angle0, angle1, tr0, tr1) -> np.ndarray:
     out = (C.c_double * 6)()
     _check(lib.pt_motion_swept_box(b, _d3(axis), float(angle0), float(angle1), _d3(tr0), _d3(tr1), out), "pt_motion_swept_box")
     return np.array(out[:], dtype=np.float64)
+
+
+def sky_tiles(cam: Camera, boxes) -> np.ndarray:
+    """The sky pass's tile test (pt_sky_tiles; host only): boxes (n, 6) = (lo.xyz, hi.xyz) -> (tiles_y, tiles_x) uint8, 1 = no camera ray
+    of the 8x8 pixel tile can enter any box."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)
+    tiles_y, tiles_x = (image_height(cam) + 7) // 8, (cam.image_width + 7) // 8
+    out = np.zeros((tiles_y, tiles_x), dtype=np.uint8)
+    _check(lib.pt_sky_tiles(C.byref(cam), len(boxes), boxes.ctypes.data if len(boxes) else None, out.ctypes.data), "pt_sky_tiles")
+    return out
 
 
 def camera_init(cam: Camera):

@@ -45,6 +45,7 @@ ShadeForm shade_form(ShadeForm f) {
     return f;
 }
 bool shade_form_sorts(const ShadeForm& f) { return SHADE_SHAPES[shade_row(f.variant)].sort; }
+bool shade_form_maps_tiles(const ShadeForm& f) { return sky_pass_form(f.list, f.mode, f.qmc, f.motion, SHADE_SHAPES[shade_row(f.variant)].minw == 2); }
 
 bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, const ShadeForm& form) {
     const init_fn k = form_kernels(form).init;

@@ -26,7 +26,7 @@ __global__ __launch_bounds__(BLOCK) void k_init(CamD cam, PoolD pool, uint64_t s
             uint32_t item = s;
             if (pool.init_perm != 0u && s < (pool.n_slots & ~8191u)) item = (s & ~8191u) | ((s * pool.init_perm) & 8191u);
             has_work = s < pool.n_slots && (unsigned long long)item < pool.total_work;
-            idle = has_work && !work_item<LIST>(pool, item, pixel, sample, row, col);
+            idle = has_work && !work_item<LIST, sky_pass_form(LIST, MED ? MODE_MED : MODE_PLAIN, QMC, MOT)>(pool, item, pixel, sample, row, col);
             if (!has_work || idle) { pixel = 0; sample = 0; }
         } else {
             pixel = slot_pixel<LIST>(pool, s);
@@ -212,8 +212,9 @@ struct NoPrefetch {
 constexpr int LSE_KB = 512;                                            // threads per block of every shape that has LSE forms (pt_forms.h)
 // MOT: motion is in effect (the rule in pt_amd.h): the hit is rebuilt, and lights.sample / lights.pdf are evaluated, with every
 // instance posed at the path's time (inst_at); a regenerated camera ray takes its time through the shutter. Plain mode only.
-template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true, bool MOT = false>
+template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true, bool MOT = false, bool MAP = false>
 // UNI: the form may take the single-primitive path of phase A (k_shade: every two-wave shape).
+// MAP: the form reads the sky pass's tile map when it draws a work item (k_shade: sky_pass_form of its own arguments, pt_types.h).
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
 // [r3]): pre_mask = those lanes, pre_base = the returning atomic's value in the mask's first lane. 0 = not requested: ask here.
 // o_base (PoolD::reorder): the wave-uniform output position of lane 0 — the slot's records and state go to PoolD::ray_out / path_out /
@@ -589,7 +590,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 const unsigned long long w = shard_item(base + (unsigned long long)__popcll(need & ((1ull << lane) - 1ull)), from);
                 if (w < pool.total_work) {
                     more = true;
-                    next_idle = !work_item<LIST>(pool, w, next_pixel, next_sample, next_row, next_col);
+                    next_idle = !work_item<LIST, MAP>(pool, w, next_pixel, next_sample, next_row, next_col);
                 }
             }
             if (__ballot(asking && !more)) {
@@ -716,7 +717,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, M, QMC, MINW == 2, MOT>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
+            shade_slot<LIGHTS, LIST, NoPrefetch, M, QMC, MINW == 2, MOT, sky_pass_form(LIST, M, QMC, MOT, MINW == 2)>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -893,7 +894,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, M, QMC, MINW == 2, MOT>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, M, QMC, MINW == 2, MOT, sky_pass_form(LIST, M, QMC, MOT, MINW == 2)>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env, lstk);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

@@ -110,13 +110,33 @@ PT_DEV void divmod_u31(uint32_t a, uint32_t b, uint32_t& q, uint32_t& r) {   // 
     q = (uint32_t)((double)a / (double)b);
     r = a - q * b;
 }
+// the sky pass's tile map (PoolD::n_work_pixels != 0): active-tile index -> tile
+PT_DEV const uint32_t* pool_tile_map(const PoolD& pool) { return reinterpret_cast<const uint32_t*>(pool.accum + 3 * (size_t)pool.n_tile_pixels); }
 // dynamic mode: work item -> (pixel, sample) and the pixel's row / column; false when the item lies outside a ragged image edge
+// MAP: the form can run with the sky pass on (sky_pass_form, pt_types.h); every other form is compiled without the lookup, as it was
+template <bool MAP>
 PT_DEV bool work_to_pixel(const PoolD& pool, unsigned long long w, uint32_t& pixel, uint32_t& sample, uint32_t& row, uint32_t& col) {
     unsigned long long q;
     uint32_t in_frame;
-    divmod_u53(w, pool.n_tile_pixels, q, in_frame);
+    const bool mapped = MAP && pool.n_work_pixels != 0u;   // (a kernel argument: wave-uniform)
+    divmod_u53(w, mapped ? pool.n_work_pixels : pool.n_tile_pixels, q, in_frame);
     sample = pool.spp_begin + (uint32_t)q;
-    const uint32_t tile = in_frame >> 6, in_tile = in_frame & 63u;
+    uint32_t tile = in_frame >> 6;
+    const uint32_t in_tile = in_frame & 63u;
+    if (mapped) {
+        // the map entries of the calling lanes by SCALAR loads, one per distinct tile: the lanes hold consecutive items of at most two
+        // 64-item chunks (two tiles), or of a shuffled granule of k_init (PT_INIT_SHUFFLE) — a per-lane load's address pair cost a form scratch
+        const uint32_t* map = pool_tile_map(pool);
+        uint32_t mapped_tile = 0u;
+        unsigned long long todo = __ballot(true);
+        while (todo != 0ull) {
+            const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)tile, __ffsll((long long)todo) - 1);
+            const uint32_t m0 = ldu(&map[t0]);
+            if (tile == t0) mapped_tile = m0;
+            todo &= ~__ballot(tile == t0);
+        }
+        tile = mapped_tile;
+    }
     uint32_t ty, tx;
     divmod_u31(tile, pool.tiles_x, ty, tx);
     const uint32_t x = tx * 8u + (in_tile & 7u), y = ty * 8u + (in_tile >> 3);
@@ -135,10 +155,10 @@ PT_DEV bool work_to_pixel_list(const PoolD& pool, unsigned long long w, uint32_t
     divmod_u31(pixel, pool.width, row, col);
     return true;
 }
-template <bool LIST>
+template <bool LIST, bool MAP = false>
 PT_DEV bool work_item(const PoolD& pool, unsigned long long w, uint32_t& pixel, uint32_t& sample, uint32_t& row, uint32_t& col) {
     if constexpr (LIST) return work_to_pixel_list(pool, w, pixel, sample, row, col);
-    else return work_to_pixel(pool, w, pixel, sample, row, col);
+    else return work_to_pixel<MAP>(pool, w, pixel, sample, row, col);
 }
 // static mode: the pixel slot s owns
 template <bool LIST>

@@ -1,0 +1,115 @@
+// The sky pass: the tiles no camera ray of which can enter a box of the world (pt_sky_tiles.h) never enter the path pool.
+//   k_sky_classify  one thread per 8x8 pixel tile: the tile test
+//   k_sky_scan      one block: the flags -> the wavefront's tile map (active-tile index -> tile), the sure-sky tile list, the two counts
+//   k_sky           one wave per (sure-sky tile, chunk of samples): what K3 does for a camera ray that left the scene, and nothing else
+#include "pt_k_common.h"
+#include "pt_sky_tiles.h"
+
+namespace pt {
+
+__global__ __launch_bounds__(BLOCK) void k_sky_classify(SkyCam cam, uint32_t n_boxes, const double* boxes6, uint32_t tiles_x, uint32_t n_tiles, uint8_t* flags) {
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= n_tiles) return;
+    uint32_t ty, tx;
+    divmod_u31(t, tiles_x, ty, tx);
+    flags[t] = sky_tile_is_clear(cam, ty, tx, n_boxes, boxes6) ? 1u : 0u;
+}
+
+// Thread i ranks the tiles [i * per, (i + 1) * per): both lists come out in tile order. counts[0] = active tiles, counts[1] = sure-sky tiles,
+// counts[2] = the pixels of the sure-sky tiles that lie inside the image.
+__global__ __launch_bounds__(BLOCK) void k_sky_scan(const uint8_t* flags, uint32_t n_tiles, uint32_t width, uint32_t height, uint32_t* tile_map, uint32_t* sky_list,
+                                                     uint32_t* counts) {
+    __shared__ uint32_t s_sky[BLOCK], s_pixels;
+    const uint32_t tiles_x = (width + 7u) / 8u;
+    const uint32_t per = (n_tiles + BLOCK - 1) / BLOCK, t0 = threadIdx.x * per, t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
+    uint32_t mine = 0, pixels = 0;
+    if (threadIdx.x == 0) s_pixels = 0;
+    for (uint32_t t = t0; t < t1; ++t) {
+        if (!flags[t]) continue;
+        uint32_t ty, tx;
+        divmod_u31(t, tiles_x, ty, tx);
+        const uint32_t w = width - tx * 8u < 8u ? width - tx * 8u : 8u, h = height - ty * 8u < 8u ? height - ty * 8u : 8u;
+        ++mine;
+        pixels += w * h;
+    }
+    s_sky[threadIdx.x] = mine;
+    __syncthreads();
+    if (pixels) atomicAdd(&s_pixels, pixels);
+    for (uint32_t d = 1; d < BLOCK; d <<= 1) {   // inclusive scan of the threads' sky counts
+        const uint32_t v = threadIdx.x >= d ? s_sky[threadIdx.x - d] : 0u;
+        __syncthreads();
+        s_sky[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t sky_at = s_sky[threadIdx.x] - mine, act_at = (t0 < n_tiles ? t0 : n_tiles) - sky_at;
+    for (uint32_t t = t0; t < t1; ++t) {
+        if (flags[t]) sky_list[sky_at++] = t;
+        else tile_map[act_at++] = t;
+    }
+    if (threadIdx.x == BLOCK - 1) {
+        counts[0] = n_tiles - s_sky[BLOCK - 1];
+        counts[1] = s_sky[BLOCK - 1];
+        counts[2] = s_pixels;   // (every thread's addition lies before one of the scan's barriers)
+    }
+}
+
+// Lane = pixel of the tile (the tiled accumulator's order), so the 64 environment texels of an iteration are neighbours and the wave's
+// three atomics cover 64 consecutive words of a plane each. Per sample exactly K1 / K3's arithmetic for a camera ray that left the scene:
+// Rng{seed, pixel, sample, 0}, generate_ray, sample_environment, times the throughput (1, 1, 1), exact zeros skipped (add_radiance).
+// The samples of a chunk are summed in registers (the dynamic mode's order of additions is free: DESIGN.md §numerics).
+__global__ __launch_bounds__(BLOCK) void k_sky(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, const uint32_t* sky_list, uint32_t n_sky,
+                                                uint32_t chunk, uint32_t n_chunks) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)));
+    uint32_t ti, ci;
+    divmod_u31(wv, n_chunks, ti, ci);
+    if (ti >= n_sky) return;   // (wave-uniform)
+    const uint32_t tile = ldu(&sky_list[ti]);
+    uint32_t ty, tx;
+    divmod_u31(tile, pool.tiles_x, ty, tx);
+    const uint32_t col = tx * 8u + (lane & 7u), row = ty * 8u + (lane >> 3);
+    const bool in_image = col < pool.width && row < pool.height;
+    const uint32_t pixel = row * pool.width + col;
+    const uint32_t s0 = pool.spp_begin + ci * chunk, s1 = pool.spp_end - s0 < chunk ? pool.spp_end : s0 + chunk;
+    if (in_image) {
+        V3 sum{0.0, 0.0, 0.0};
+        bool any = false;
+        for (uint32_t sample = s0; sample < s1; ++sample) {
+            Rng rng{(uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, 0u};
+            const RayD r = generate_ray<false>(cam, row, col, rng);
+            const V3 c = V3{1.0, 1.0, 1.0} * sample_environment(sc, cam, r.d);
+            if (!(c.x == 0.0 && c.y == 0.0 && c.z == 0.0)) {
+                sum = sum + c;
+                any = true;
+            }
+        }
+        if (any) {
+            double* a = pool.accum + (size_t)tile * 64u + lane;
+            unsafeAtomicAdd(a, sum.x);
+            unsafeAtomicAdd(a + pool.n_tile_pixels, sum.y);
+            unsafeAtomicAdd(a + 2 * (size_t)pool.n_tile_pixels, sum.z);
+        }
+    }
+    // every one of these samples had exactly one segment
+    const unsigned long long n = (unsigned long long)__popcll(__ballot(in_image)) * (unsigned long long)(s1 - s0);
+    if (lane == 0u && n != 0ull) {
+        atomicAdd(&cnt->samples, n);
+        atomicAdd(&cnt->segments, n);
+    }
+}
+
+void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, uint32_t n_tiles, uint8_t* flags, uint32_t* tile_map, uint32_t* sky_list,
+                         uint32_t* counts, hipStream_t st) {
+    hipLaunchKernelGGL(k_sky_classify, dim3((n_tiles + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, cam, n_boxes, boxes6, (cam.width + 7u) / 8u, n_tiles, flags);
+    hipLaunchKernelGGL(k_sky_scan, dim3(1), dim3(BLOCK), 0, st, flags, n_tiles, cam.width, cam.height, tile_map, sky_list, counts);
+}
+void launch_sky(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, const uint32_t* sky_list, uint32_t n_sky, uint32_t chunk,
+                hipStream_t st) {
+    const uint32_t spp = pool.spp_end - pool.spp_begin;
+    if (n_sky == 0u || spp == 0u || chunk == 0u) return;
+    const uint32_t n_chunks = (spp + chunk - 1u) / chunk;
+    const uint64_t waves = (uint64_t)n_sky * n_chunks;   // (the caller keeps this below 2^31: sky_chunk)
+    hipLaunchKernelGGL(k_sky, dim3((uint32_t)((waves + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, st, sc, cam, pool, cnt, seed, sky_list, n_sky, chunk, n_chunks);
+}
+
+}  // namespace pt

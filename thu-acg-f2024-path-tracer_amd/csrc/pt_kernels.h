@@ -15,6 +15,8 @@ struct ShadeForm { int variant = 0; bool lights = false, list = false, qmc = fal
 ShadeForm shade_form(ShadeForm asked);
 // whether the form's k_shade sorts its windows by class (the shading-order output, PoolD::reorder, needs the sort's positions)
 bool shade_form_sorts(const ShadeForm& form);
+// whether the form's K1 / K3 read the sky pass's tile map (pt_types.h sky_pass_form): the pass is off for a render whose form does not
+bool shade_form_maps_tiles(const ShadeForm& form);
 // The launchers that take a form return false, having launched nothing, when no kernel of that form exists.
 bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, const ShadeForm& form);
 // K2 variant code (`code` of launch_extend / extend_occupancy_blocks): -1 = batch kernel (-2 / -3 ask extend_occupancy_blocks for its
@@ -56,6 +58,15 @@ void launch_resolve(const PoolD& pool, double* accum, int max_blocks, hipStream_
 // the frame's end (dynamic mode): live slots beyond new_end move into dead slots below it; holes / movers: scratch lists of `cap` entries, counts: 2 words
 void launch_compact(const PoolD& pool, uint32_t new_end, uint32_t* holes, uint32_t* movers, uint32_t* counts, uint32_t cap, int max_blocks, hipStream_t st);
 void launch_detile(const PoolD& pool, double* accum, int max_blocks, hipStream_t st);
+// pt_k_sky.hip: the sky pass. launch_sky_classify: the tile test of every tile against the boxes (device, six doubles each), then
+// tile_map (active-tile index -> tile), sky_list (the sure-sky tiles), both in tile order, and counts = {active tiles, sure-sky tiles, pixels of
+// the sure-sky tiles inside the image}; flags: n_tiles bytes of scratch. launch_sky: samples [spp_begin, spp_end) of every pixel of the listed
+// tiles, `chunk` samples per wave, added to the tiled accumulator and to the sample and segment counts.
+struct SkyCam;
+void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, uint32_t n_tiles, uint8_t* flags, uint32_t* tile_map, uint32_t* sky_list,
+                         uint32_t* counts, hipStream_t st);
+void launch_sky(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, const uint32_t* sky_list, uint32_t n_sky, uint32_t chunk,
+                hipStream_t st);
 // pt_adaptive.hip: the adaptive render's per-round kernels (see there)
 void launch_adapt_error(const double* E, const double* O, const uint32_t* stop, uint32_t n_pixels, double n_e, double n_o, double* err, hipStream_t st);
 void launch_adapt_select(const double* err, uint32_t* stop, uint32_t width, uint32_t height, double threshold, uint32_t stop_value, uint32_t* block_counts,

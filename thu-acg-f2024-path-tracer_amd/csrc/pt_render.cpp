@@ -16,6 +16,7 @@
 #include "../../include/pt_amd.h"
 #include "pt_kernels.h"
 #include "pt_scene.h"
+#include "pt_sky_tiles.h"
 
 using namespace pt;
 using namespace pt::host;
@@ -106,6 +107,52 @@ extern "C" int pt_camera_init(const pt_camera* c, double out[18], uint32_t* imag
     return 0;
 }
 
+// The sky pass's tile test (pt_sky_tiles.h) for a camera and a list of boxes: the camera as the render's kernels see it (make_camd's
+// center, pixel vectors and lens vectors), and the boxes the test walks — the caller's, or their union when there are more than SKY_MAX_BOXES.
+namespace {
+SkyCam sky_camera(const double center[3], const double forward[3], const double pixel00[3], const double pixel_du[3], const double pixel_dv[3],
+                  const double dof_right[3], const double dof_up[3], double blur_strength, uint32_t width, uint32_t height) {
+    SkyCam c;
+    memset(&c, 0, sizeof c);
+    for (int i = 0; i < 3; ++i) {
+        c.center[i] = center[i]; c.forward[i] = forward[i]; c.pixel00[i] = pixel00[i]; c.pixel_du[i] = pixel_du[i]; c.pixel_dv[i] = pixel_dv[i];
+        c.dof_right[i] = dof_right[i]; c.dof_up[i] = dof_up[i];
+    }
+    c.blur_strength = blur_strength;
+    c.width = width;
+    c.height = height;
+    return c;
+}
+std::vector<double> sky_boxes(uint32_t n_boxes, const double* boxes6) {
+    std::vector<double> b(boxes6, boxes6 + 6 * (size_t)n_boxes);
+    if (n_boxes <= SKY_MAX_BOXES) return b;
+    std::vector<double> u(b.begin(), b.begin() + 6);
+    for (uint32_t i = 1; i < n_boxes; ++i)
+        for (int a = 0; a < 3; ++a) {
+            if (!(b[6 * (size_t)i + a] >= u[a])) u[a] = b[6 * (size_t)i + a];           // (a NaN stays: the test then clears nothing)
+            if (!(b[6 * (size_t)i + 3 + a] <= u[3 + a])) u[3 + a] = b[6 * (size_t)i + 3 + a];
+        }
+    return u;
+}
+}  // namespace
+extern "C" int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, uint8_t* out_tiles) {
+    if (!cam || !out_tiles || (n_boxes && !boxes6)) return set_error("pt_sky_tiles: bad arguments");
+    CamDerived d;
+    if (derive_camera(cam, d) != 0) return -1;
+    const double lens_radius = std::tan((cam->defocus_angle / 2.0) * (PI / 180.0)) * cam->focal_length;   // (make_camd's)
+    double v[7][3];
+    const D3 vec[7] = {d.center, d.forward, d.pixel00, d.pixel_du, d.pixel_dv, d.right * lens_radius, d.up * lens_radius};
+    for (int i = 0; i < 7; ++i) st3(v[i], vec[i]);
+    SkyCam c = sky_camera(v[0], v[1], v[2], v[3], v[4], v[5], v[6], cam->blur_strength, cam->image_width, d.height);
+    const std::vector<double> boxes = sky_boxes(n_boxes, boxes6);
+    const uint32_t nb = (uint32_t)(boxes.size() / 6);
+    c.extent = sky_extent(c, nb, boxes.data());
+    const uint32_t tiles_x = (c.width + 7) / 8, tiles_y = (c.height + 7) / 8;
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) out_tiles[(size_t)ty * tiles_x + tx] = sky_tile_is_clear(c, ty, tx, nb, boxes.data()) ? 1 : 0;
+    return 0;
+}
+
 namespace {
 struct EventTimer {   // per-launch HIP-event timing, drained at the polling syncs
     struct Pending {
@@ -114,8 +161,8 @@ struct EventTimer {   // per-launch HIP-event timing, drained at the polling syn
     };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_list;
-    double ms[3] = {0, 0, 0};
-    uint64_t launches[3] = {0, 0, 0};
+    double ms[4] = {0, 0, 0, 0};   // K2, K3, the small kernels, k_sky
+    uint64_t launches[4] = {0, 0, 0, 0};
     bool enabled = false;
     hipEvent_t get() {
         if (!free_list.empty()) {
@@ -305,6 +352,13 @@ struct Job {
     CamD dc;
     ShadeMode mode;
     EnvTabD env;   // the table argument of a mode that has one
+    // the sky pass (classify_sky): on, and then the tiles of the frame the wavefront still renders, the sure-sky tiles k_sky
+    // renders, their list on the device, the pixels of theirs inside the image and the samples one k_sky wave takes
+    bool sky = false;
+    uint32_t n_active_tiles = 0, n_sky_tiles = 0, n_sky_pixels = 0, sky_chunk = 0;
+    const uint32_t* sky_list = nullptr;
+    const uint32_t* tile_map = nullptr;   // where classify_sky wrote the map: tiled_accum checks that the kernels will look there
+    ShadeForm form;   // the form of K1 / K3 this render launches (render_core; classify_sky and choose_kernels both read this one)
 };
 
 // Every experiment switch of a render (exp_env: read under PT_EXPERIMENT=1 only), read once. An explicit option wins over its switch.
@@ -317,7 +371,7 @@ struct Switches {
                               // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
                               // windows per block launched, else 22)
     bool pool_in_place = false, no_defer_regen = false, no_compact_records = false, init_shuffle = false, accum_linear = false, no_compact_pool = false,
-         prof = false;
+         prof = false, no_sky_pass = false;   // no_sky_pass: PT_SKY_PASS=0
     int grid_mult = 1;   // persistent grids: resident blocks per CU x CUs x this
     uint32_t wide_window_min = 16;
     int ext2 = 0;        // PT_EXT2 = stack*10 + blocks per CU picks the two-phase K2's instantiation (0: not set)
@@ -348,7 +402,72 @@ Switches read_switches(const pt_render_opts& opts) {
     if (const char* e = exp_env("PT_COMPACT_AT")) { sw.compact_num = (uint64_t)std::max(1, atoi(e)); sw.compact_den = 100; }   // per cent
     if (const char* e = exp_env("PT_POLL_CAP")) sw.poll_cap = (uint32_t)std::max(1, atoi(e));
     sw.prof = exp_env("PT_PROF") != nullptr;
+    if (const char* e = exp_env("PT_SKY_PASS")) sw.no_sky_pass = atoi(e) == 0;
     return sw;
+}
+
+// The bytes of the tiled frame accumulator (tiled_accum, below): three channel planes, and behind them the sky pass's tile map, one word per
+// tile (pt_k_common.h pool_tile_map).
+// tile_map_behind: where that map lies for an accumulator at `accum` — the one host statement of what pool_tile_map computes on the device.
+size_t tiled_accum_bytes(size_t n_tile_pixels) { return n_tile_pixels * 3 * sizeof(double) + n_tile_pixels / 64 * sizeof(uint32_t); }
+uint32_t* tile_map_behind(double* accum, size_t n_tile_pixels) { return reinterpret_cast<uint32_t*>(accum + 3 * n_tile_pixels); }
+
+// The sky pass, per render: the tiles whose camera rays provably enter no box of the world are classified on the device
+// (pt_sky_tiles.h; one thread per tile, then a one-block scan), the host reads the three counts back — the one small synchronisation — and
+// the wavefront's work items then cover the other tiles only (PoolD::n_work_pixels, the tile map behind the tiled accumulator) while k_sky
+// renders the sure-sky ones (run_wavefront). The pass is ON only for what k_sky's one form reproduces: the dynamic mode's whole-frame
+// render in the plain mode with the independent sampler under the perspective projection, nothing moving, no camera medium. Everywhere
+// else this step does nothing, and every kernel argument is what it was without it.
+int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
+    const CamD& dc = job.dc;
+    const uint64_t n_tiles64 = (uint64_t)((dc.width + 7) / 8) * ((dc.height + 7) / 8);
+    // A black constant environment: a sure-sky sample adds an exact zero, which nobody adds — there is no radiance for the pass to move,
+    // and the wavefront's miss is at its cheapest (no lookup, no atomic). Measured on scene 3 at 1920x1920 (8.2 % sure-sky tiles beside the
+    // open box): -1.3 % with the pass. Such a render keeps the wavefront alone and does not pay for the classification either.
+    const bool black = !dc.env_is_map && dc.env_color[0] == 0.0 && dc.env_color[1] == 0.0 && dc.env_color[2] == 0.0;
+    const bool on = !black && sw.slots_per_pixel == 0 && !job.list && job.mode == MODE_PLAIN && s->sampler == 0 && dc.projection == PROJ_PERSPECTIVE && !s->motion_on() &&
+                    shade_form_maps_tiles(job.form) && s->camera_medium < 0 && !sw.no_sky_pass && !sw.accum_linear /* k_sky adds into the tiled planes */ && job.spp != 0 && dc.max_depth != 0 &&
+                    n_tiles64 * 64 <= 0x7FFFFFFFull /* (plan_pool refuses the rest) */;
+    if (!on) return 0;
+    const uint32_t n_tiles = (uint32_t)n_tiles64;
+    const std::vector<double> boxes = sky_boxes((uint32_t)(s->entry_boxes.size() / 6), s->entry_boxes.data());
+    const uint32_t n_boxes = (uint32_t)(boxes.size() / 6);
+    SkyCam cam = sky_camera(dc.center, dc.forward, dc.pixel00, dc.pixel_du, dc.pixel_dv, dc.dof_right, dc.dof_up, dc.blur_strength, dc.width, dc.height);
+    cam.extent = sky_extent(cam, n_boxes, boxes.data());
+    // sky_mem: the counts (64 B), the boxes, the sure-sky tile list, the tiles' flags; the tile map lies behind the tiled accumulator's planes
+    const size_t box_bytes = (size_t)SKY_MAX_BOXES * 6 * sizeof(double);
+    if (!s->sky_mem.reserve(64 + box_bytes + (size_t)n_tiles * (sizeof(uint32_t) + 1), "hipMalloc(sky pass)")) return -1;
+    if (!s->tile_accum.reserve(tiled_accum_bytes((size_t)n_tiles * 64), "hipMalloc(tiled accumulator)")) return -1;
+    char* m = s->sky_mem.as<char>();
+    uint32_t* d_counts = (uint32_t*)m;
+    double* d_boxes = (double*)(m + 64);
+    uint32_t* d_sky_list = (uint32_t*)(m + 64 + box_bytes);
+    uint8_t* d_flags = (uint8_t*)(d_sky_list + n_tiles);
+    uint32_t* d_tile_map = tile_map_behind(s->tile_accum.as<double>(), (size_t)n_tiles * 64);
+    uint32_t counts[3] = {0, 0, 0};
+    // (`boxes` and `counts` are this function's: both copies are done at its synchronise, below)
+    if (n_boxes && !hip_ok(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice, job.st), "hipMemcpy(sky boxes)")) return -1;
+    timer.begin(2, job.st);
+    launch_sky_classify(cam, n_boxes, d_boxes, n_tiles, d_flags, d_tile_map, d_sky_list, d_counts, job.st);
+    timer.end(job.st);
+    if (!hip_ok(hipGetLastError(), "sky classification") ||
+        !hip_ok(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, job.st), "hipMemcpy(sky counts)") ||
+        !hip_ok(hipStreamSynchronize(job.st), "hipStreamSynchronize(sky classification)"))
+        return -1;
+    timer.drain();
+    if ((uint64_t)counts[0] + counts[1] != n_tiles) return set_error("pt_render: the sky pass's tile counts do not add up (internal error)");
+    if (counts[1] == 0) return 0;   // no sure-sky tile: the render is the wavefront's, its kernel arguments what they are without the pass
+    job.sky = true;
+    job.tile_map = d_tile_map;
+    job.n_active_tiles = counts[0];
+    job.n_sky_tiles = counts[1];
+    job.n_sky_pixels = counts[2];
+    job.sky_list = d_sky_list;
+    // one wave renders `chunk` samples of a tile: enough waves to fill the machine four times over, at least 32 samples each
+    const uint64_t target = (uint64_t)std::max(1, s->ctx->n_cus) * 4 * 8 * 4, per_tile = std::max<uint64_t>(1, target / std::max(1u, counts[1]));
+    job.sky_chunk = (uint32_t)std::max<uint64_t>(32, (job.spp + per_tile - 1) / per_tile);
+    while ((uint64_t)counts[1] * ((job.spp + job.sky_chunk - 1) / job.sky_chunk) > 0x7FFFFFFFull) job.sky_chunk *= 2;   // (k_sky's wave index)
+    return 0;
 }
 
 // Pool sizing (arithmetic only). slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
@@ -370,7 +489,8 @@ int plan_pool(const Switches& sw, const Job& job, int n_cus, PoolPlan& p) {
     const uint64_t n_tile_pixels64 = (uint64_t)p.tiles_x * tiles_y * 64;
     if (n_tile_pixels64 > 0x7FFFFFFFull) return set_error("pt_render: image too large");
     p.n_tile_pixels = (uint32_t)n_tile_pixels64;
-    p.total_work = p.dynamic ? (job.list ? (uint64_t)job.n_list : n_tile_pixels64) * job.spp : (uint64_t)job.n_items * job.spp;
+    // (the sky pass: the work items cover the active tiles only)
+    p.total_work = p.dynamic ? (job.list ? (uint64_t)job.n_list : job.sky ? (uint64_t)job.n_active_tiles * 64 : n_tile_pixels64) * job.spp : (uint64_t)job.n_items * job.spp;
     uint64_t n_slots64;
     if (p.dynamic) {
         // Resident paths: enough that per-launch fixed costs and kernel tails amortise (16.8M slots are 9% faster than
@@ -384,11 +504,15 @@ int plan_pool(const Switches& sw, const Job& job, int n_cus, PoolPlan& p) {
         // FHD @ 4000 spp: 33.6 M slots 2905, 67 M 2940, 134 M 2984, 268 M 2957 Msamples/s; @ 2000: 2886 / 2903 / 2923; @ 1000: 33.6 M 2822,
         // 67 M 2836, 134 M 2752; @ 500: 16.8 M 2688, 33.6 M 2750, 67 M 2694; @ 250: 8.4 M 2484, 16.8 M 2574; scene 3 1920x1920 @ 4000:
         // 1314 / 1328 / 1359; scene 5 4K @ 1000: 4355 / 4431 / 4499 (profiles/r03_pool_sweep.txt). 134 M slots are 14 GB of path records.
+        // The sky pass thins total_work, but the rule keeps reading the WHOLE frame's work: the slots hold the paths of the
+        // active tiles, which are as long as they were, and a pool sized from the thinner list came out a step smaller just where the
+        // steps lie — scene 6 at 1000 spp 33.5 M slots for 67 M (K2 +2 %, the frame's gain cut from 3 % to 1.3 %), at 500 spp -1.3 %.
+        const uint64_t rule_work = job.list ? p.total_work : n_tile_pixels64 * job.spp;
         uint64_t per_cu = 16384;   // a power of two (the tile-ordered work items and the 64 counter shards divide it evenly)
-        while (per_cu < 524288 && per_cu * 2 * (uint64_t)std::max(1, n_cus) * 30 <= p.total_work) per_cu *= 2;
+        while (per_cu < 524288 && per_cu * 2 * (uint64_t)std::max(1, n_cus) * 30 <= rule_work) per_cu *= 2;
         // one more doubling (268 M slots, 28 GB) only from 48 samples per slot: scene 3 1920x1920 @ 4000 spp (55 per slot) 1335 -> 1362,
         // while at 31 per slot scene 6 FHD @ 4000 loses 0.7 % and scene 5 4K @ 1000 0.5 % (initialising and compacting the pool costs 58 ms there)
-        if (per_cu == 524288 && per_cu * 2 * (uint64_t)std::max(1, n_cus) * 48 <= p.total_work) per_cu *= 2;
+        if (per_cu == 524288 && per_cu * 2 * (uint64_t)std::max(1, n_cus) * 48 <= rule_work) per_cu *= 2;
         uint64_t target = (uint64_t)n_cus * per_cu;
         if (sw.pool_slots_set) {
             target = sw.pool_slots;
@@ -434,7 +558,7 @@ int extend2_code(const pt_scene* s, const Switches& sw) {
 }
 Kernels choose_kernels(const Switches& sw, const pt_scene* s, const Job& job, const PoolPlan& p) {
     Kernels kn;
-    kn.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode, s->motion_on()});
+    kn.form = job.form;
     // Shading-order output (PoolD::reorder): the dynamic mode's sorted whole-frame k_shade writes every path to its position in the
     // window's sorted order in a second record area, and the two areas swap after each launch — K2's chunks are then K3's groups: a tile's
     // camera rays in pixel order, or 64 paths of one material class. Static mode, pixel lists and PT_POOL_IN_PLACE write in place.
@@ -502,6 +626,7 @@ int bind_pool(pt_scene* s, const Switches& sw, const Job& job, const PoolPlan& p
     pool.inv_width = 1.0 / (double)job.dc.width;
     pool.tiles_x = p.tiles_x;
     pool.n_tile_pixels = p.n_tile_pixels;
+    pool.n_work_pixels = job.sky ? job.n_active_tiles * 64u : 0u;
     pool.list = job.d_list;
     pool.n_list = job.list ? job.n_list : 0u;
     pool.list_store = job.list && job.opts.accum_on_device && job.opts.overwrite ? 1u : 0u;   // (a host accumulator is written by copy_back, pixel by pixel)
@@ -525,19 +650,22 @@ double* device_accum(const Job& job, double* accum, DevMem& own) {
     }
     return d_accum;
 }
-// dynamic mode: the kernels add into channel planes in work-item (tile) order (PoolD::accum_tiled); k_detile adds them to d_accum
+// dynamic mode: the kernels add into channel planes in work-item (tile) order (PoolD::accum_tiled); k_detile adds them to d_accum.
+// (tiled_accum_bytes, above: the tile map behind the planes is written by classify_sky and never cleared here)
 int tiled_accum(pt_scene* s, const Job& job, PoolD& pool) {
     const size_t tb = (size_t)pool.n_tile_pixels * 3 * sizeof(double);
-    if (!s->tile_accum.reserve(tb, "hipMalloc(tiled accumulator)")) return -1;
+    if (!s->tile_accum.reserve(tiled_accum_bytes(pool.n_tile_pixels), "hipMalloc(tiled accumulator)")) return -1;
     if (!hip_ok(hipMemsetAsync(s->tile_accum.as<double>(), 0, tb, job.st), "hipMemset(tiled accumulator)")) return -1;
     pool.accum = s->tile_accum.as<double>();
     pool.accum_tiled = 1u;
+    // the kernels find the map behind THIS accumulator's planes (pool_tile_map): the buffer classify_sky wrote into may not have moved
+    if (job.sky && tile_map_behind(pool.accum, pool.n_tile_pixels) != job.tile_map) return set_error("pt_render: the sky pass's tile map is not behind the tiled accumulator (internal error)");
     return 0;
 }
 // (init_cnt is the caller's: the copy is asynchronous, so it has to live until the render's next synchronise)
 int start_counters(pt_scene* s, const Job& job, uint32_t n_slots, CountersD& init_cnt) {
     memset(&init_cnt, 0, sizeof init_cnt);
-    init_cnt.alive = job.spp == 0 ? 0 : n_slots;   // every slot starts with one sample (k <= spp / n_slots <= total_work)
+    init_cnt.alive = job.spp == 0 || (job.sky && job.n_active_tiles == 0) ? 0 : n_slots;   // every slot starts with one sample (k <= spp / n_slots <= total_work)
     for (uint32_t sh = 0; sh < WORK_SHARDS; ++sh) {   // dynamic mode: items 0 .. n_slots-1 were handed out by k_init
         const uint64_t row = (uint64_t)WORK_SHARDS * 64, rows = n_slots / row, rem = n_slots % row;
         const uint64_t part = rem > (uint64_t)sh * 64 ? std::min<uint64_t>(rem - (uint64_t)sh * 64, 64) : 0;
@@ -570,15 +698,23 @@ int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPla
     (void)hipStreamSynchronize(st);
     const auto t0 = std::chrono::steady_clock::now();
 
-    timer.begin(2, st);
-    if (!launch_init(dc, pool, job.seed, kn.grid_shade, st, kn.form)) return set_error("pt_render: no k_init form for this render");
-    timer.end(st);
+    if (job.sky && job.n_sky_tiles != 0 && job.spp != 0) {   // the sure-sky tiles' samples, ahead of the wavefront
+        timer.begin(3, st);
+        launch_sky(s->dev.view, dc, pool, s->d_counters, job.seed, job.sky_list, job.n_sky_tiles, job.sky_chunk, st);
+        timer.end(st);
+    }
+    const bool wavefront = !(job.sky && job.n_active_tiles == 0);   // a frame that is all sky has none
+    if (wavefront) {
+        timer.begin(2, st);
+        if (!launch_init(dc, pool, job.seed, kn.grid_shade, st, kn.form)) return set_error("pt_render: no k_init form for this render");
+        timer.end(st);
+    }
     const uint64_t per_slot = p.dynamic ? (p.total_work + p.n_slots - 1) / std::max<uint64_t>(p.n_slots, 1) + 1 : (job.spp + p.k - 1) / p.k;
     const uint64_t max_iterations = per_slot * ((uint64_t)std::max(1u, dc.max_depth) + 1) + 4;   // + 1: a parked slot idles one iteration
     uint32_t poll_every = 8;
     const bool compact_ok = p.dynamic && !sw.no_compact_pool;
     // max_depth = 0: trace() returns zero radiance for every sample (camera.rs:177); nothing to launch
-    bool alive = job.spp != 0 && dc.max_depth != 0;
+    bool alive = job.spp != 0 && dc.max_depth != 0 && wavefront;
     while (alive) {
         for (uint32_t i = 0; i < poll_every; ++i) {
             timer.begin(0, st);
@@ -664,7 +800,7 @@ void print_prof(const CountersD* cnt) {
     }
 }
 
-void fill_stats(const pt_scene* s, const PoolPlan& p, const Kernels& kn, const PoolD& pool, const EventTimer& timer, const RunResult& r, pt_render_stats* stats) {
+void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kernels& kn, const PoolD& pool, const EventTimer& timer, const RunResult& r, pt_render_stats* stats) {
     memset(stats, 0, sizeof *stats);
     stats->samples = s->h_counters->samples;
     stats->segments = s->h_counters->segments;
@@ -683,6 +819,9 @@ void fill_stats(const pt_scene* s, const PoolPlan& p, const Kernels& kn, const P
     stats->blocks_shade = (uint32_t)kn.grid_shade;
     stats->compactions = r.compactions;
     stats->n_alloc_end = pool.n_alloc;
+    stats->sky_tiles = job.sky ? job.n_sky_tiles : 0u;
+    stats->sky_samples = job.sky ? (uint64_t)job.n_sky_pixels * job.spp : 0u;
+    stats->ms_sky = timer.ms[3];
 }
 // the statistics of an adaptive render: its passes' counts and times added up, the pool and the kernels of the last pass
 void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
@@ -702,6 +841,9 @@ void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
     sum.blocks_shade = ps.blocks_shade;
     sum.compactions += ps.compactions;
     sum.n_alloc_end = ps.n_alloc_end;
+    sum.sky_tiles = std::max(sum.sky_tiles, ps.sky_tiles);
+    sum.sky_samples += ps.sky_samples;
+    sum.ms_sky += ps.ms_sky;
 }
 
 // The render core behind pt_render, pt_render_pixels and the passes of pt_render_adaptive. d_list (device) / h_list (host, the same
@@ -730,6 +872,10 @@ int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_b
     if (render_mode(s, job.dc, job.st, job.mode, job.env) != 0) return -1;
 
     const Switches sw = read_switches(job.opts);
+    job.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode, s->motion_on()});
+    EventTimer timer;
+    timer.enabled = job.opts.profile != 0;
+    if (classify_sky(s, sw, job, timer) != 0) return -1;
     PoolPlan plan;
     if (plan_pool(sw, job, s->ctx->n_cus, plan) != 0) return -1;
     const Kernels kn = choose_kernels(sw, s, job, plan);
@@ -745,13 +891,11 @@ int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_b
     CountersD init_cnt;
     if (start_counters(s, job, plan.n_slots, init_cnt) != 0) return -1;
 
-    EventTimer timer;
-    timer.enabled = job.opts.profile != 0;
     RunResult run;
     if (run_wavefront(s, sw, job, plan, kn, pool, d_accum, timer, run) != 0) return -1;
     if (copy_back(job, d_accum, accum) != 0) return -1;
     if (sw.prof) print_prof(s->h_counters);
-    if (stats) fill_stats(s, plan, kn, pool, timer, run, stats);
+    if (stats) fill_stats(s, job, plan, kn, pool, timer, run, stats);
     return 0;
 }
 }  // namespace

@@ -98,6 +98,7 @@ struct pt_scene {
     pt::GrowBuf tile_accum;        // dynamic mode: the frame accumulator in tile order (PoolD::accum_tiled)
     pt::GrowBuf compact_scratch;   // the end-of-frame compaction's hole / mover lists + counters (pt_render.cpp)
     pt::GrowBuf pixel_list;        // pt_render_pixels: the device pixel list (tiled order)
+    pt::GrowBuf sky_mem;           // the sky pass: counts, boxes, tile flags, the sure-sky tile list (pt_render.cpp classify_sky; the tile map is in tile_accum)
     // environment importance sampling (pt_scene_set_env_sampling): the mixture weight, and the f64 tables of ONE
     // environment texture, built at the first render or probe that needs them (pt_render.cpp env_tables) and kept until destroy
     double env_f = 0.0;

@@ -2,6 +2,7 @@
 // Everything the kernels read lives in HBM as plain arrays of these PODs (records for the per-path
 // state and for the small read-only scene tables that sit in L2).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace pt {
@@ -161,6 +162,10 @@ enum ShadeMode { MODE_PLAIN, MODE_ENV, MODE_MED, MODE_HET, MODE_INT, MODE_LSE, M
 constexpr bool mode_has_media(ShadeMode m) { return m == MODE_MED || m == MODE_HET || m == MODE_INT; }
 constexpr bool mode_has_grid(ShadeMode m) { return m == MODE_HET || m == MODE_INT; }
 constexpr bool mode_has_table(ShadeMode m) { return m == MODE_ENV || m == MODE_DSP; }
+// The forms of K1 / K3 the sky pass can run with (pt_render.cpp classify_sky switches the pass off for every other): the whole
+// frame in the plain mode, independent sampler, nothing moving, a two-wave shape of k_shade (every shape but the three-wave experiments).
+// Only these read the tile map (pt_k_common.h work_to_pixel); every other form's code is what it was before the pass existed.
+constexpr bool sky_pass_form(bool list, ShadeMode m, bool qmc, bool motion, bool two_waves = true) { return !list && m == MODE_PLAIN && !qmc && !motion && two_waves; }
 constexpr uint32_t CLASS_MISS = 0u, CLASS_IDLE = 1u + MAT_KINDS, CLASS_DEAD = 2u + MAT_KINDS, N_CLASSES = 3u + MAT_KINDS;
 // MAT_SHEEN: p[0..2] = base colour, p[3] = sheen_tint (sheen.rs). MAT_CLEARCOAT: alpha_g (clearcoat.rs).
 // MAT_MIX: p[0] = t, color_tex / rough_tex hold the two child MATERIAL indices (mix.rs; children are leaves).
@@ -326,6 +331,11 @@ struct PoolD {
     uint32_t defer_regen, compact;                   // dynamic mode: a path that ends ON A SURFACE (roulette, sampler, depth) parks its slot
                                                   // as SLOT_IDLE; it is refilled next iteration among the idle slots (k_shade)
     uint32_t width, height, tiles_x, n_tile_pixels;   // dynamic mode: 8x8 tiling, n_tile_pixels = tiles_x*tiles_y*64
+    // The sky pass (pt_k_sky.hip) is on: the work items cover the ACTIVE tiles only, n_work_pixels = 64 x their number, and
+    // work_to_pixel maps an item's active-tile index through the tile map — u32 tile indices that lie BEHIND the three planes of the tiled
+    // accumulator (pool_tile_map). 0: the pass is off, an item's tile is its index. The word fills what was padding and the map has no
+    // pointer of its own, so that PoolD keeps its size and every field its offset: K2's code does not change by a byte.
+    uint32_t n_work_pixels;
     // pixel-list renders (pt_render_pixels, pt_render_adaptive; the kernels' LIST = true forms only): n_list row-major pixel ids
     // in TILED-index order, so that consecutive work items / slots are neighbouring pixels as in a whole-frame render. Dynamic mode:
     // work item w = (pixel list[w mod n_list], sample spp_begin + w / n_list); static mode: slot s owns pixel list[s mod n_list].
@@ -344,6 +354,8 @@ struct PoolD {
     uint32_t reorder;
     uint32_t init_perm;                           // experiment (PT_INIT_SHUFFLE): k_init gives slot s the item pi(s) inside each 8192-slot granule, 0 = identity
 };
+
+static_assert(sizeof(PoolD) == 216 && offsetof(PoolD, list) == 168 && offsetof(PoolD, n_work_pixels) == 164, "PoolD's layout is part of K2's code");
 
 // The work counter of the dynamic mode is SHARDED: one word saturates at ~88 dequeues/us on this
 // chip (MI355X_MICROARCH.md, row "dequeue") and a frame needs one dequeue per wave per iteration
