@@ -433,6 +433,57 @@ int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, u
 int pt_motion_swept_box(const double box[6], const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double out[6]);
 /* test probe: the f64 world box (lo.xyz, hi.xyz) of world entry `entry` (lights list first, then objects), before the f32 rounding */
 int pt_world_entry_box(pt_scene*, uint32_t entry, double out[6]);
+/* ---- punctual lights: point, spot and directional "sun" lights (the reference's unfinished hittable/light.rs PointLight { position, power },
+ *      finished, with two siblings; opt-in) ----
+ * Arithmetic: f64, one IEEE rounding per written operation. A scene keeps a list of n <= 2048 punctual lights, each a record formed on the host:
+ *   kind 0, pt_light_point(position, power), mirrors PointLight::new: I_c = power_c / (4 * PI), in W/sr.
+ *   kind 1, pt_light_spot(position, target, inner_deg, outer_deg, intensity): axis = normalize(target - position), 0 <= inner_deg <= outer_deg < 180
+ *     (angles from the axis), cos_i = cos(inner_deg * (PI / 180)) and cos_o likewise, by the deterministic cosine of pt_instance's angles
+ *     (pt_math_probe which 4); I = the on-axis intensity.
+ *   kind 2, pt_light_directional(direction, irradiance): axis = normalize(direction), the way the light travels; I = the irradiance on a plane
+ *     facing the light.
+ *   Each call returns the light's index k >= 0, or -1 and adds nothing: a non-finite or negative colour, a non-finite position, a zero-length
+ *   axis, angles out of range, the list full. pt_scene_clear_punctual_lights empties the list, pt_scene_punctual_count is its length,
+ *   pt_scene_punctual_light(k, out16) the record as stored: kind, pos.xyz, axis.xyz, I.rgb, cos_i, cos_o, four zeros. The list takes effect at the
+ *   next pt_world_build. pt_scene_set_punctual_fraction(f), 0 < f < 1 and finite (else -1, the setting stays), default 0.5, takes effect at once.
+ * In effect: n > 0 at the last build. Otherwise every entry point launches the kernels it launches without this feature and produces the same
+ *   bits, whatever f is. In effect for pt_render, pt_render_pixels, pt_render_adaptive and pt_render_multi, static and dynamic pools, with and
+ *   without a lights list, both samplers. pt_render_aovs and pt_intersect do not change. A render returns -1 when environment importance
+ *   sampling, any participating or interior medium, exact light sampling, dispersion or motion is in effect too, or max_depth >= 2^20. The sky
+ *   pass stays off.
+ * At a surface bounce, after emission and roulette, the selector draw r is made as without: p_punct = f, p_light = lights ? (1 - f) / 2 : 0,
+ *   p_bsdf = 1 - p_light - p_punct. r < p_light: lights.sample; r < p_light + p_punct: the punctual branch; otherwise mat.sample — the order of
+ *   the environment-sampling mixture. The light and BSDF branches are the bounce without this feature with pdf = p_bsdf * bsdf_pdf + p_light *
+ *   light_pdf under these weights (a punctual direction has measure zero there and adds no term).
+ * The punctual branch. One index draw k = gen_range(0..n), the conversion of the lights list's index draw (under the Sobol sampler a single
+ *   draw, not pair-aligned). With x the hit point — kinds 0, 1: L = pos - x, d2 = dot(L, L), D = sqrt(d2), w = L / D, E_c = I_c / d2; kind 1 in
+ *   addition c = -dot(w, axis), s = cos_i > cos_o ? clamp((c - cos_o) / (cos_i - cos_o), 0, 1) : (c >= cos_o ? 1 : 0), fall = (s * s) * (3 - 2 * s),
+ *   E_c = (I_c * fall) / d2; kind 2: w = -axis, E = I. Then e = mat.eval(wo, w), the material's own eval with its cosine factor (the call the
+ *   lights branch makes), pm = f / (double)n, thr' = ((thr * e) * E) / pm componentwise. The path ends when d2 is 0 or not finite, or thr' is
+ *   exactly (0, 0, 0). Otherwise it continues as a SHADOW segment: the ray Ray::new(point + (1e-3 * signum(dot(w, gn))) * gn, w, time) — the
+ *   offset of every continued ray —, ++bounce, and the depth bound as at any bounce: a shadow segment that would be the max_depth-th ray is never
+ *   resolved, so max_depth = 2 is the first depth at which these lights show, as for area lights.
+ * Resolving a SHADOW segment, when K3 next visits the path, before anything else (no emission, no roulette, no draw). With o the stored ray
+ *   origin: D' = length(pos_k - o) for kinds 0 and 1, +inf for kind 2. The light is visible iff the ray missed or hit.dist >= D' (a surface
+ *   behind the light does not shadow it). If visible, radiance += thr; the environment is not added on a miss. The path ends either way.
+ * Consequences. The lights are invisible to camera and BSDF rays. Any surface occludes, glass included: no caustics from them and no light
+ *   through windows. Selection is uniform, not by power. The sample's expectation is direct lighting by the list plus the estimator of
+ *   everything else as it is without: each branch is divided by its own probability. */
+int pt_light_point(pt_scene*, const double position[3], const double power[3]);
+int pt_light_spot(pt_scene*, const double position[3], const double target[3], double inner_deg, double outer_deg, const double intensity[3]);
+int pt_light_directional(pt_scene*, const double direction[3], const double irradiance[3]);
+int pt_scene_clear_punctual_lights(pt_scene*);
+int pt_scene_punctual_count(pt_scene*);
+int pt_scene_punctual_light(pt_scene*, int k, double out[16]);
+int pt_scene_set_punctual_fraction(pt_scene*, double f);
+double pt_scene_punctual_fraction(pt_scene*);
+/* test probe: the punctual branch's device functions as k_shade calls them. which 0: in = n x point.xyz; row i uses the independent sampler's
+ * draws of (seed 0, pixel i, sample 0) from draw 0; out = n x (k, w.xyz, D, E.rgb, draws consumed). which 1: in = n x (k, point.xyz), out = n x
+ * (w.xyz, D, E.rgb). -1 when the world was built without punctual lights. */
+int pt_punctual_probe(pt_scene*, int which, const double* in, uint32_t n, double* out);
+/* Host only, no context needed: the device's light evaluation compiled for the host. rec16: a record as pt_scene_punctual_light returns it;
+ * out7 = (w.xyz, D, E.rgb). */
+int pt_punctual_eval(const double rec16[16], const double point[3], double out7[7]);
 /* ---- world: src/hittable/world.rs:10-29 -------------------------------------------------- */
 int pt_world_add_object(pt_scene*, int obj);
 int pt_world_add_light(pt_scene*, int obj);

@@ -159,6 +159,8 @@ ABI_SYMBOLS = [
     "pt_scene_set_projection", "pt_scene_projection", "pt_camera_probe",
     "pt_instance_moving", "pt_scene_set_shutter", "pt_scene_shutter", "pt_scene_motion", "pt_motion_pose", "pt_motion_swept_box", "pt_world_entry_box",
     "pt_sky_tiles",
+    "pt_light_point", "pt_light_spot", "pt_light_directional", "pt_scene_clear_punctual_lights", "pt_scene_punctual_count", "pt_scene_punctual_light",
+    "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval",
 ]
 
 
@@ -227,6 +229,18 @@ def _load():
         lib.pt_motion_pose.argtypes = [d3, C.c_double, C.c_double, d3, d3, C.c_double, d3]
         lib.pt_motion_swept_box.argtypes = [d3, d3, C.c_double, C.c_double, d3, d3, d3]
         lib.pt_world_entry_box.argtypes = [C.c_void_p, C.c_uint32, d3]
+    if hasattr(lib, "pt_light_point"):   # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_light_point.argtypes = [C.c_void_p, d3, d3]
+        lib.pt_light_spot.argtypes = [C.c_void_p, d3, d3, C.c_double, C.c_double, d3]
+        lib.pt_light_directional.argtypes = [C.c_void_p, d3, d3]
+        lib.pt_scene_clear_punctual_lights.argtypes = [C.c_void_p]
+        lib.pt_scene_punctual_count.argtypes = [C.c_void_p]
+        lib.pt_scene_punctual_light.argtypes = [C.c_void_p, C.c_int, d3]
+        lib.pt_scene_set_punctual_fraction.argtypes = [C.c_void_p, C.c_double]
+        lib.pt_scene_punctual_fraction.argtypes = [C.c_void_p]
+        lib.pt_scene_punctual_fraction.restype = C.c_double
+        lib.pt_punctual_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.pt_punctual_eval.argtypes = [d3, d3, d3]
     if hasattr(lib, "pt_sky_tiles"):
         lib.pt_sky_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -547,6 +561,45 @@ class Scene:
         _check(lib.pt_light_probe(self.handle, which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_light_probe")
         return out
 
+    # ---- punctual lights (the rule is in include/pt_amd.h). The list takes effect at the next world_build. ----
+    def light_point(self, position, power):
+        """A point light of the given power in W per channel (pt_light_point: PointLight::new of the reference); returns its index."""
+        return _check(lib.pt_light_point(self.handle, _d3(position), _d3(power)), "light_point")
+
+    def light_spot(self, position, target, inner_deg, outer_deg, intensity):
+        """A spot light aimed at `target`: full intensity (W/sr) inside the inner cone, a smoothstep to zero at the outer one; angles from the axis."""
+        return _check(lib.pt_light_spot(self.handle, _d3(position), _d3(target), float(inner_deg), float(outer_deg), _d3(intensity)), "light_spot")
+
+    def light_directional(self, direction, irradiance):
+        """A sun: light travelling along `direction`, `irradiance` on a plane facing it (pt_light_directional)."""
+        return _check(lib.pt_light_directional(self.handle, _d3(direction), _d3(irradiance)), "light_directional")
+
+    def clear_punctual_lights(self): return _check(lib.pt_scene_clear_punctual_lights(self.handle), "clear_punctual_lights")
+    def punctual_count(self) -> int: return _check(lib.pt_scene_punctual_count(self.handle), "pt_scene_punctual_count")
+
+    def punctual_light(self, k) -> np.ndarray:
+        """Light k's record exactly as stored, 16 doubles: kind, pos.xyz, axis.xyz, I.rgb, cos_i, cos_o, four zeros."""
+        out = (C.c_double * 16)()
+        _check(lib.pt_scene_punctual_light(self.handle, int(k), out), "pt_scene_punctual_light")
+        return np.array(out[:], dtype=np.float64)
+
+    def set_punctual_fraction(self, f):
+        """The selector's share of the punctual branch at a bounce, 0 < f < 1 (default 0.5)."""
+        return _check(lib.pt_scene_set_punctual_fraction(self.handle, float(f)), "set_punctual_fraction")
+
+    def punctual_fraction(self) -> float: return lib.pt_scene_punctual_fraction(self.handle)
+
+    def punctual_probe(self, which: int, arr: np.ndarray) -> np.ndarray:
+        """The punctual branch's device functions as the kernels call them. which 0: arr = (n, 3) points -> (n, 9) {k, w.xyz, D, E.rgb, draws
+        consumed}, row i with the independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0; which 1: arr = (n, 4) (k, point.xyz)
+        -> (n, 7) {w.xyz, D, E.rgb}."""
+        if which not in (0, 1):
+            raise PtError("punctual_probe: which must be 0 or 1")
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, 3 if which == 0 else 4))
+        out = np.empty((len(arr), 9 if which == 0 else 7), dtype=np.float64)
+        _check(lib.pt_punctual_probe(self.handle, which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_punctual_probe")
+        return out
+
     def set_projection(self, kind):
         """How a pixel becomes a camera ray: "perspective" (0, the default: the reference's pinhole / thin-lens camera), "orthographic"
         (1: parallel rays framing the perspective camera's focal plane), "fisheye" (2: equidistant, vfov across the image height) or
@@ -837,6 +890,15 @@ def motion_swept_box(box, axis, angle0, angle1, tr0, tr1) -> np.ndarray:
     b = (C.c_double * 6)(*[float(x) for x in box])
     out = (C.c_double * 6)()
     _check(lib.pt_motion_swept_box(b, _d3(axis), float(angle0), float(angle1), _d3(tr0), _d3(tr1), out), "pt_motion_swept_box")
+    return np.array(out[:], dtype=np.float64)
+
+
+def punctual_eval(rec16, point) -> np.ndarray:
+    """What a punctual light sends to a point (pt_punctual_eval; host only — the device's function compiled for the host): rec16 = a record as
+    Scene.punctual_light returns it -> (w.xyz, D, E.rgb)."""
+    rec = (C.c_double * 16)(*[float(x) for x in rec16])
+    out = (C.c_double * 7)()
+    _check(lib.pt_punctual_eval(rec, _d3(point), out), "pt_punctual_eval")
     return np.array(out[:], dtype=np.float64)
 
 

@@ -33,19 +33,19 @@ __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t see
 
 FormKernels forms_plain(const ShadeForm& f) { return unit_forms<UNIT_PLAIN>(f, k_aov); }
 static FormKernels form_kernels(const ShadeForm& f) {   // asks the unit that owns the form's k_shade, and the one that owns its k_init (pt_forms.h)
-    constexpr FormKernels (*unit[])(const ShadeForm&) = {forms_plain, forms_qmc, forms_med, forms_het, forms_int, forms_lse, forms_dsp, forms_mot};   // in FormUnit's order
-    const FormUnit k3 = form_unit(f.mode, f.qmc, f.motion), k1 = form_unit(mode_has_media(f.mode) ? MODE_MED : MODE_PLAIN, f.qmc, f.motion);   // K1 has a plain, a MED and a MOT form only
+    constexpr FormKernels (*unit[])(const ShadeForm&) = {forms_plain, forms_qmc, forms_med, forms_het, forms_int, forms_lse, forms_dsp, forms_mot, forms_plt};   // in FormUnit's order
+    const FormUnit k3 = form_unit(f.mode, f.qmc, f.motion, f.punctual), k1 = form_unit(mode_has_media(f.mode) ? MODE_MED : MODE_PLAIN, f.qmc, f.motion);   // K1 has a plain, a MED and a MOT form only
     FormKernels k = unit[k3](f);
     if (k1 != k3) k.init = k.shade ? unit[k1](f).init : nullptr;
     return k;
 }
 
 ShadeForm shade_form(ShadeForm f) {
-    if (!shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.lights, f.list, f.qmc, f.mode, f.motion)) f.variant = 42;
+    if (!shade_form_exists(SHADE_SHAPES[shade_row(f.variant)], f.lights, f.list, f.qmc, f.mode, f.motion, f.punctual)) f.variant = 42;
     return f;
 }
 bool shade_form_sorts(const ShadeForm& f) { return SHADE_SHAPES[shade_row(f.variant)].sort; }
-bool shade_form_maps_tiles(const ShadeForm& f) { return sky_pass_form(f.list, f.mode, f.qmc, f.motion, SHADE_SHAPES[shade_row(f.variant)].minw == 2); }
+bool shade_form_maps_tiles(const ShadeForm& f) { return sky_pass_form(f.list, f.mode, f.qmc, f.motion || f.punctual, SHADE_SHAPES[shade_row(f.variant)].minw == 2); }
 
 bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_blocks, hipStream_t st, const ShadeForm& form) {
     const init_fn k = form_kernels(form).init;

@@ -4,6 +4,7 @@
 #include "pt_k_common.h"
 #include "pt_dev_lights.h"
 #include "pt_dev_dispersion.h"
+#include "pt_dev_punctual.h"
 
 namespace pt {
 
@@ -212,7 +213,12 @@ struct NoPrefetch {
 constexpr int LSE_KB = 512;                                            // threads per block of every shape that has LSE forms (pt_forms.h)
 // MOT: motion is in effect (the rule in pt_amd.h): the hit is rebuilt, and lights.sample / lights.pdf are evaluated, with every
 // instance posed at the path's time (inst_at); a regenerated camera ray takes its time through the shutter. Plain mode only.
-template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true, bool MOT = false, bool MAP = false>
+// PLT: punctual lights are in effect (the rule in pt_amd.h): the scene's list of point, spot and directional lights is not empty. The
+// selector gives the punctual branch the share SceneD::punctual_f: it draws one light, weights the throughput by the material's eval and what the
+// light sends, and continues the path as a SHADOW segment — flag and light index ride in the upper bits of the bounce word (pt_types.h). The next visit
+// resolves the segment right after the hit is rebuilt: the throughput is added when nothing lies in front of the light, and the path ends either
+// way. Every other lane is the plain bounce under the reduced weights. Plain mode only.
+template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true, bool MOT = false, bool MAP = false, bool PLT = false>
 // UNI: the form may take the single-primitive path of phase A (k_shade: every two-wave shape).
 // MAP: the form reads the sky pass's tile map when it draws a work item (k_shade: sky_pass_form of its own arguments, pt_types.h).
 // pre_mask / pre_base: the work items of this group's certain-to-end lanes were requested one group AHEAD (k_shade's prefetch point,
@@ -237,6 +243,15 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         if (bounce < SLOT_IDLE) {
             mono = (bounce & DSP_MONO_BIT) != 0u;
             bounce &= DSP_BOUNCE_MASK;
+        }
+    }
+    bool shadow = false;                                               // PLT: the path is on its SHADOW segment towards light plk
+    uint32_t plk = 0u;
+    if constexpr (PLT) {
+        if (bounce < SLOT_IDLE) {
+            shadow = (bounce & PLT_SHADOW_BIT) != 0u;
+            plk = (bounce >> PLT_INDEX_SHIFT) & PLT_INDEX_MASK;
+            bounce &= PLT_BOUNCE_MASK;
         }
     }
     const bool alive = bounce != SLOT_DEAD;
@@ -359,7 +374,18 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 }
             }
         }
-        if (MED && scatter) {
+        if (PLT && shadow) {
+            // a SHADOW segment is resolved before anything else — no emission, no roulette, no draw: the light is visible when the ray missed
+            // or its hit lies at or beyond the light; the environment is not added. The path ends either way: a lane that missed is in the
+            // `early` ballot already, one that hit ends like a roulette death.
+            if constexpr (PLT) {
+                const double o[3] = {ray.o.x, ray.o.y, ray.o.z};
+                const double dl = punctual_shadow_distance(sc.punctual[plk], o);
+                if (!surface || hit.dist >= dl) add_radiance(pool, pixel, rad, thr);
+                finished = true;
+                parked = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS;
+            }
+        } else if (MED && scatter) {
             // a medium vertex: no emission, no surface
         } else if (!surface) {
             add_radiance(pool, pixel, rad, thr * sample_environment(sc, cam, ray.d));   // camera.rs:180-183
@@ -406,13 +432,18 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     PT_STAMP(a2);
     const bool any_hit = __ballot(is_hit || (MED && (scatter || boundary))) != 0ull;
     bool fetched = false;                                              // wave-uniform
-    if (any_hit && !LIGHTS && !ENV) { prefetch(); fetched = true; }    // P1
+    if (any_hit && !LIGHTS && !ENV && !PLT) { prefetch(); fetched = true; }    // P1 (PLT: B1 reads the light's record)
     // ---- phase B1: roulette and the next direction ------------------------------------------------------------------------
-    const double p_light = LIGHTS ? 0.5 : 0.0;                         // :199-200 (the host picks the instantiation by World::lights)
-    const double p_bsdf = 1.0 - p_light;
+    double p_punct = 0.0;                                              // PLT: the punctual branch's share f of the selector
+    if constexpr (PLT) p_punct = sc.punctual_f;
+    const double p_light = PLT ? (LIGHTS ? (1.0 - p_punct) / 2.0 : 0.0) : LIGHTS ? 0.5 : 0.0;   // :199-200 (the host picks the instantiation by World::lights)
+    const double p_bsdf = PLT ? 1.0 - p_light - p_punct : 1.0 - p_light;
     const V3 wo = -ray.d;
     V3 dir{};
     bool have_dir = false;
+    bool punct_dir = false;                                            // PLT: the bounce took the punctual branch (dir = w, towards light plk)
+    V3 punct_e{};                                                      // ... E, what the light sends to the hit point
+    bool punct_ok = false;                                             // ... d2 is finite and not 0
     bool env_lane = false, env_dir = false;                            // ENV: the bounce takes the mixture / its direction is an env sample
     double q_env = 0.0;                                                // ENV: q_env(dir) (pt_amd.h)
     if (is_hit) {
@@ -445,6 +476,22 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                     const bool above = to_local(lf.f, dir).z > 0.0;
                     if (!env_dir) q_env = above ? env_pdf(sc, ldu(&sc.tex[cam.env_tex]), *env, dir) : 0.0;
                     else if (!above) ok = false;
+                }
+            } else if constexpr (PLT) {
+                // one selector draw: lights below p_light, the punctual list below p_light + f, the BSDF above — the order of the ENV mixture
+                rsel = rng_f64(rng);
+                if (LIGHTS && rsel < p_light) {
+                    dir = lights_sample<MOT>(sc, hit.point, ray.time, rng);
+                } else if (rsel < p_light + p_punct) {
+                    plk = rng_index(rng, sc.n_punctual) & PLT_INDEX_MASK;   // one index draw, as the lights list's
+                    const double x[3] = {hit.point.x, hit.point.y, hit.point.z};
+                    const PunctualEval pe = punctual_eval(sc.punctual[plk], x);
+                    dir = V3{pe.w[0], pe.w[1], pe.w[2]};
+                    punct_e = V3{pe.E[0], pe.E[1], pe.E[2]};
+                    punct_ok = pe.d2 != 0.0 && pe.d2 - pe.d2 == 0.0;     // (neither 0 nor inf nor NaN)
+                    punct_dir = true;
+                } else {
+                    ok = mat_sample<RngT, DSP>(sc, *mp, hit, wo, rng, cam.two_pi_scale, tv, lf, dir, ior_l);
                 }
             } else if constexpr (LIGHTS) {
                 rsel = rng_f64(rng);
@@ -496,6 +543,21 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         double pdf = p_bsdf * bsdf_pdf + p_light * light_pdf;
         V3 attenuation = brdf / pdf;
         bool env_end = false;
+        if constexpr (PLT) {
+            if (punct_dir) {
+                // thr' = ((thr * e) * E) / pm with pm = f / n: the branch's own probability, no density (the direction has measure zero under the others)
+                const double pm = p_punct / (double)sc.n_punctual;
+                const V3 t = ((thr * brdf) * punct_e) / pm;
+                env_end = !punct_ok || (t.x == 0.0 && t.y == 0.0 && t.z == 0.0);
+                if (!env_end) {
+                    ray = make_ray(hit.point + (1e-3 * signum(dot(dir, hit.gn))) * hit.gn, dir, ray.time);
+                    thr = t;
+                    shadow = true;
+                    ++bounce;
+                    if (bounce >= cam.max_depth) finished = parked = true;   // a shadow segment that would be the max_depth-th ray is never resolved
+                }
+            }
+        }
         if constexpr (ENV) {
             if (env_lane) {
                 // the mixture's density: p_bsdf * s_b + p_light * light_pdf + p_env * q_env, with s_b the BSDF sampler's density. Diffuse:
@@ -515,7 +577,9 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             }
         }
         if (env_end) {
-            finished = parked = true;                                  // (ENV: a zero-density or zero-throughput bounce ends the path)
+            finished = parked = true;                                  // (ENV: a zero-density or zero-throughput bounce ends the path; PLT: the punctual branch's endings)
+        } else if (PLT && punct_dir) {
+            // (continued above, as a SHADOW segment)
         } else {
             double e = 1e-3 * signum(dot(dir, hit.gn));                // :217-222
             if constexpr (INT) {
@@ -627,6 +691,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             rad = V3{0.0, 0.0, 0.0};
             bounce = 0;
             if constexpr (DSP) mono = false;
+            if constexpr (PLT) shadow = false;
             if constexpr (MED) med = cam.medium;
             sample = next_sample;
             pixel = next_pixel;
@@ -642,7 +707,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         const uint32_t state_new = bounce < SLOT_IDLE ? 0u : bounce, state_old = was_idle ? SLOT_IDLE : 0u;
         if (reorder || state_new != state_old) pool.bounce_out[o] = state_new;
         if (bounce < SLOT_IDLE) {
-            const uint32_t bounce_word = MED ? bounce | (med << MEDIUM_SHIFT) : DSP && mono ? bounce | DSP_MONO_BIT : bounce;
+            const uint32_t bounce_word = MED ? bounce | (med << MEDIUM_SHIFT) : DSP && mono ? bounce | DSP_MONO_BIT : PLT && shadow ? bounce | PLT_SHADOW_BIT | (plk << PLT_INDEX_SHIFT) : bounce;
             store_ray(pool, pool.ray_out, o, ray, sample, rng.draw, pixel, bounce_word);
             if (!pool.compact || bounce != 0u) store_path(pool.path_out, o, thr, pixel, bounce_word);
             if (!pool.dynamic) { pool.rx[s] = rad.x; pool.ry[s] = rad.y; pool.rz[s] = rad.z; }
@@ -696,10 +761,12 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // hit, or instead of leaving — so these forms do not request work items a group ahead.
 // LSE: these forms hold the per-lane stack of the light meshes' all-hits walk, LIGHT_STACK levels x KB lanes in LDS
 // MOT: motion (shade_slot)
-template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, ShadeMode M = MODE_PLAIN, bool QMC = false, bool MOT = false>
+// PLT: punctual lights (shade_slot)
+template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, ShadeMode M = MODE_PLAIN, bool QMC = false, bool MOT = false, bool PLT = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     constexpr bool ENV = M == MODE_ENV, MED = mode_has_media(M), LSE = M == MODE_LSE, DSP = M == MODE_DSP;   // (HET and INT change nothing here)
     static_assert(!MOT || M == MODE_PLAIN, "k_shade: the MOT forms are plain-mode forms");
+    static_assert(!PLT || (M == MODE_PLAIN && !MOT), "k_shade: the PLT forms are plain-mode forms without motion");
     static_assert((!LSE || LIGHTS) && (!(LSE || DSP) || (SORT && KB == LSE_KB)), "k_shade: the LSE forms need a lights list; the LSE and DSP forms are sorted 512-thread forms");
     __shared__ uint32_t s_lstack[LSE ? LIGHT_STACK * KB : 1];   // 48 KB: stack[level][thread] of lights_pdf_exact's mesh walk
     uint32_t* const lstk = LSE ? &s_lstack[threadIdx.x] : nullptr;
@@ -717,7 +784,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
         for (uint32_t base = blockIdx.x * KB; base < pool.n_alloc; base += gridDim.x * KB) {
             const uint32_t s = base + threadIdx.x;
             const SlotIn in = load_slot_global(pool, s, true);
-            shade_slot<LIGHTS, LIST, NoPrefetch, M, QMC, MINW == 2, MOT, sky_pass_form(LIST, M, QMC, MOT, MINW == 2)>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
+            shade_slot<LIGHTS, LIST, NoPrefetch, M, QMC, MINW == 2, MOT, sky_pass_form(LIST, M, QMC, MOT || PLT, MINW == 2), PLT>(sc, cam, pool, cnt, seed, s, s - (uint32_t)lane, lane, in, shard, n_done, n_died, NoPrefetch{}, 0ull, 0ull, 0u, &env, lstk);
         }
     } else {
         constexpr int WIN = KB * PER;                           // slots per window: eight (or sixteen) per thread
@@ -884,7 +951,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
                         // the next group's lanes that are certain to end there (ray left the scene / idle slot): their work items now.
                         // Scenes without a lights list only: K3 -1.2 % (scene 6), -0.7 % (scene 5); the lights instantiation, three
                         // registers from the limit, got 0.9 % SLOWER with it (closed scenes have next to no leaving rays anyway).
-                        if constexpr (!LIGHTS && !ENV && !MED) {
+                        if constexpr (!LIGHTS && !ENV && !MED && !PLT) {
                         const uint32_t cn = s_hw[sn - wbase] >> HIT_CLASS_SHIFT;
                         pre_mask_next = __ballot(en && (cn == CLASS_MISS || cn == CLASS_IDLE));
                         pre_shard_next = shard;
@@ -894,7 +961,7 @@ __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc,
 #endif
                     }
                 };
-                shade_slot<LIGHTS, LIST, decltype(prefetch)&, M, QMC, MINW == 2, MOT, sky_pass_form(LIST, M, QMC, MOT, MINW == 2)>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
+                shade_slot<LIGHTS, LIST, decltype(prefetch)&, M, QMC, MINW == 2, MOT, sky_pass_form(LIST, M, QMC, MOT || PLT, MINW == 2), PLT>(sc, cam, pool, cnt, seed, s, wbase + (n_groups - 1u - g) * 64u, lane, in, shard, n_done,
                                                              n_died, prefetch, pre_mask, pre_base, pre_shard, &env, lstk);
                 pre_mask = pre_mask_next;
                 pre_base = pre_base_next;

@@ -8,8 +8,9 @@
 namespace pt {
 // What a render asks of K1 / K3 / the AOV walk. variant: k_shade's shape code (pt_forms.h SHADE_SHAPES; PT_SHADE_VARIANT); lights: the scene
 // has a lights list; list: pixel-list render (PoolD::list); qmc: the Sobol sampler (pt_scene_set_sampler); mode: the
-// shading mode (pt_types.h ShadeMode); motion: motion is in effect (pt_scene_motion). Which forms exist: pt_forms.h shade_form_exists.
-struct ShadeForm { int variant = 0; bool lights = false, list = false, qmc = false; ShadeMode mode = MODE_PLAIN; bool motion = false; };
+// shading mode (pt_types.h ShadeMode); motion: motion is in effect (pt_scene_motion); punctual: punctual lights are in effect
+// (pt_light_point ...). Which forms exist: pt_forms.h shade_form_exists.
+struct ShadeForm { int variant = 0; bool lights = false, list = false, qmc = false; ShadeMode mode = MODE_PLAIN; bool motion = false, punctual = false; };
 // The form a render gets: pixel lists, qmc and every mode but the plain one exist for the default variant's shapes only — any other variant becomes 42.
 // The launchers and queries below take the form this returns.
 ShadeForm shade_form(ShadeForm asked);
@@ -91,6 +92,9 @@ void launch_film_develop(const double* sums, uint32_t n_pixels, double scale, co
                          uint32_t tonemap, double white, double* hdr, uint8_t* rgb8, hipStream_t st);
 // pt_camera_probe: generate_ray as k_init calls it under sampler `kind` (n x (pixel, sample) -> n x (origin.xyz, direction.xyz, time, draws consumed)); in / out: device
 // motion: the shutter is applied (motion is in effect)
+// pt_punctual_probe: the punctual lights' device functions as k_shade's PLT forms call them (which 0: n x point.xyz -> n x (k, w.xyz, D, E.rgb, draws
+// consumed), row i with the independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0; 1: n x (k, point.xyz) -> n x (w.xyz, D, E.rgb)); in / out: device
+void launch_punctual_probe(const SceneD& sc, int which, const double* in, uint32_t n, double* out, hipStream_t st);
 void launch_camera_probe(const CamD& cam, int kind, uint64_t seed, const double* in, uint32_t n, double* out, hipStream_t st, bool motion = false);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);
 }  // namespace pt

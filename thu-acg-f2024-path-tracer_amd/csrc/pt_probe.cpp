@@ -116,6 +116,24 @@ extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t
     });
 }
 
+extern "C" int pt_punctual_probe(pt_scene* s, int which, const double* in, uint32_t n, double* out) {
+    if (!s || !s->built) return set_error("pt_punctual_probe: world not built");
+    if (which != 0 && which != 1) return set_error("pt_punctual_probe: which must be 0 or 1");
+    const uint32_t n_lights = s->dev.view.n_punctual;
+    if (n_lights == 0u) return set_error("pt_punctual_probe: the world was built without punctual lights");
+    if (n == 0) return 0;
+    if (!in || !out) return set_error("pt_punctual_probe: null buffer");
+    if (which == 1)
+        for (uint32_t i = 0; i < n; ++i) {
+            const double k = in[4 * (size_t)i];
+            if (!(k >= 0.0 && k < (double)n_lights) || k != std::floor(k)) return set_error("pt_punctual_probe: which 1 takes (k, point.xyz) rows with k a light of the built list");
+        }
+    const size_t n_in = (size_t)n * (which == 0 ? 3 : 4), n_out = (size_t)n * (which == 0 ? 9 : 7);
+    return run_probe(s->ctx, {{in, n_in * sizeof(double)}}, out, n_out * sizeof(double), [&](void* const* d_in, void* d_out) {
+        launch_punctual_probe(s->dev.view, which, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
+    });
+}
+
 extern "C" int pt_dispersion_probe(pt_scene* s, int glass_mat, int which, uint64_t seed, const double* in, uint32_t n, double* out) {
     if (!s || !s->ctx) return set_error("pt_dispersion_probe: null scene");
     if (glass_mat < 0 || (size_t)glass_mat >= s->mats.size() || s->mats[glass_mat].kind != MAT_GLASS || s->mats[glass_mat].p[3] == 0.0)

@@ -331,6 +331,15 @@ static int render_mode(pt_scene* s, const CamD& dc, hipStream_t st, ShadeMode& m
     if (mot && med) return set_error("pt_render: motion together with participating media or a glass interior is not supported (take the media out, or take the moving instances out and reset the shutter)");
     if (mot && lse) return set_error("pt_render: motion together with exact light sampling is not supported (set light sampling to 0, or take the moving instances out and reset the shutter)");
     if (mot && dsp) return set_error("pt_render: motion together with spectral dispersion is not supported (clear the dispersion, or take the moving instances out and reset the shutter)");
+    // punctual lights are in effect (pt_amd.h): the list held a light at the last build. Their kernels are plain-mode forms without motion
+    // (pt_forms.h), and a path's SHADOW flag and light index ride in bits 20..31 of its bounce word; otherwise no new code runs
+    const bool plt = s->punctual_on();
+    if (plt && env_on) return set_error("pt_render: punctual lights together with environment importance sampling are not supported (set the sampling off, or clear the punctual lights and rebuild)");
+    if (plt && med) return set_error("pt_render: punctual lights together with participating media or a glass interior are not supported (take the media out, or clear the punctual lights and rebuild)");
+    if (plt && lse) return set_error("pt_render: punctual lights together with exact light sampling are not supported (set light sampling to 0, or clear the punctual lights and rebuild)");
+    if (plt && dsp) return set_error("pt_render: punctual lights together with spectral dispersion are not supported (clear the dispersion, or clear the punctual lights and rebuild)");
+    if (plt && mot) return set_error("pt_render: punctual lights together with motion are not supported (take the moving instances out and reset the shutter, or clear the punctual lights and rebuild)");
+    if (plt && dc.max_depth > PLT_BOUNCE_MASK) return set_error("pt_render: max_depth must be below 2^20 when punctual lights are in effect");
     mode = dsp ? MODE_DSP : lse ? MODE_LSE : !med ? (env_on ? MODE_ENV : MODE_PLAIN) : s->interior_on() ? MODE_INT : s->grid_media_on() ? MODE_HET : MODE_MED;
     return 0;
 }
@@ -425,7 +434,7 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     // and the wavefront's miss is at its cheapest (no lookup, no atomic). Measured on scene 3 at 1920x1920 (8.2 % sure-sky tiles beside the
     // open box): -1.3 % with the pass. Such a render keeps the wavefront alone and does not pay for the classification either.
     const bool black = !dc.env_is_map && dc.env_color[0] == 0.0 && dc.env_color[1] == 0.0 && dc.env_color[2] == 0.0;
-    const bool on = !black && sw.slots_per_pixel == 0 && !job.list && job.mode == MODE_PLAIN && s->sampler == 0 && dc.projection == PROJ_PERSPECTIVE && !s->motion_on() &&
+    const bool on = !black && sw.slots_per_pixel == 0 && !job.list && job.mode == MODE_PLAIN && s->sampler == 0 && dc.projection == PROJ_PERSPECTIVE && !s->motion_on() && !s->punctual_on() &&
                     shade_form_maps_tiles(job.form) && s->camera_medium < 0 && !sw.no_sky_pass && !sw.accum_linear /* k_sky adds into the tiled planes */ && job.spp != 0 && dc.max_depth != 0 &&
                     n_tiles64 * 64 <= 0x7FFFFFFFull /* (plan_pool refuses the rest) */;
     if (!on) return 0;
@@ -872,7 +881,7 @@ int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_b
     if (render_mode(s, job.dc, job.st, job.mode, job.env) != 0) return -1;
 
     const Switches sw = read_switches(job.opts);
-    job.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode, s->motion_on()});
+    job.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode, s->motion_on(), s->punctual_on()});
     EventTimer timer;
     timer.enabled = job.opts.profile != 0;
     if (classify_sky(s, sw, job, timer) != 0) return -1;

@@ -2,6 +2,7 @@
 #include "pt_scene.h"
 #include "pt_bvh_device.h"
 #include "pt_detmath.h"
+#include "pt_dev_punctual.h"
 
 #include <hip/hip_runtime.h>
 
@@ -572,6 +573,99 @@ extern "C" int pt_motion_pose(const double axis[3], double angle0, double angle1
     InstD xf;
     pose_of_keys(make_keys(axis, angle0, angle1, tr0, tr1), time, xf);
     memcpy(out24, xf.c0, 24 * sizeof(double));   // c0, c1, c2, t, i0, i1, i2, it: InstD's order
+    return 0;
+}
+// ---- punctual lights (pt_light_point, pt_light_spot, pt_light_directional; the rule: pt_amd.h) ----
+static bool colour_ok(const double* c) { return finite3(c) && c[0] >= 0.0 && c[1] >= 0.0 && c[2] >= 0.0; }
+static int push_punctual(pt_scene* s, const PunctualD& L, const char* who) {
+    if (s->punctual.size() >= PLT_MAX_LIGHTS) return set_error(std::string(who) + ": the list of punctual lights is full (2048)");
+    s->punctual.push_back(L);
+    return (int)s->punctual.size() - 1;
+}
+// axis = normalize(v), or false for a zero-length or non-finite one
+static bool unit_axis(D3 v, double out[3]) {
+    const double len = length(v);
+    if (!(len > 0.0) || !std::isfinite(len)) return false;
+    const D3 a = normalize(v);
+    if (!std::isfinite(a.x) || !std::isfinite(a.y) || !std::isfinite(a.z)) return false;
+    st3(out, a);
+    return true;
+}
+extern "C" int pt_light_point(pt_scene* s, const double position[3], const double power[3]) {
+    if (!s) return set_error("pt_light_point: null scene");
+    if (!finite3(position)) return set_error("pt_light_point: the position must be finite");
+    if (!colour_ok(power)) return set_error("pt_light_point: the power must be finite and not negative");
+    PunctualD L{};
+    L.kind = 0u;
+    for (int i = 0; i < 3; ++i) { L.pos[i] = position[i]; L.I[i] = power[i] / (4.0 * PI); }
+    return push_punctual(s, L, "pt_light_point");
+}
+extern "C" int pt_light_spot(pt_scene* s, const double position[3], const double target[3], double inner_deg, double outer_deg, const double intensity[3]) {
+    if (!s) return set_error("pt_light_spot: null scene");
+    if (!finite3(position) || !finite3(target)) return set_error("pt_light_spot: position and target must be finite");
+    if (!colour_ok(intensity)) return set_error("pt_light_spot: the intensity must be finite and not negative");
+    if (!std::isfinite(inner_deg) || !std::isfinite(outer_deg) || !(0.0 <= inner_deg && inner_deg <= outer_deg && outer_deg < 180.0))
+        return set_error("pt_light_spot: the cone angles need 0 <= inner_deg <= outer_deg < 180");
+    PunctualD L{};
+    L.kind = 1u;
+    if (!unit_axis(d3(target) - d3(position), L.axis)) return set_error("pt_light_spot: target and position must differ (zero-length axis)");
+    double sn;
+    detmath::sincos(inner_deg * (PI / 180.0), sn, L.cos_i);   // the deterministic cosine of pt_instance's angles
+    detmath::sincos(outer_deg * (PI / 180.0), sn, L.cos_o);
+    for (int i = 0; i < 3; ++i) { L.pos[i] = position[i]; L.I[i] = intensity[i]; }
+    return push_punctual(s, L, "pt_light_spot");
+}
+extern "C" int pt_light_directional(pt_scene* s, const double direction[3], const double irradiance[3]) {
+    if (!s) return set_error("pt_light_directional: null scene");
+    if (!finite3(direction)) return set_error("pt_light_directional: the direction must be finite");
+    if (!colour_ok(irradiance)) return set_error("pt_light_directional: the irradiance must be finite and not negative");
+    PunctualD L{};
+    L.kind = 2u;
+    if (!unit_axis(d3(direction), L.axis)) return set_error("pt_light_directional: the direction must not be zero");
+    for (int i = 0; i < 3; ++i) L.I[i] = irradiance[i];
+    return push_punctual(s, L, "pt_light_directional");
+}
+extern "C" int pt_scene_clear_punctual_lights(pt_scene* s) {
+    if (!s) return set_error("pt_scene_clear_punctual_lights: null scene");
+    s->punctual.clear();
+    return 0;
+}
+extern "C" int pt_scene_punctual_count(pt_scene* s) {
+    if (!s) return set_error("pt_scene_punctual_count: null scene");
+    return (int)s->punctual.size();
+}
+static void punctual_to16(const PunctualD& L, double out[16]) {   // kind, pos, axis, I, cos_i, cos_o, then zeros
+    out[0] = (double)L.kind;
+    for (int i = 0; i < 3; ++i) { out[1 + i] = L.pos[i]; out[4 + i] = L.axis[i]; out[7 + i] = L.I[i]; }
+    out[10] = L.cos_i; out[11] = L.cos_o;
+    for (int i = 12; i < 16; ++i) out[i] = 0.0;
+}
+extern "C" int pt_scene_punctual_light(pt_scene* s, int k, double out[16]) {
+    if (!s || !out) return set_error("pt_scene_punctual_light: null scene or buffer");
+    if (k < 0 || (size_t)k >= s->punctual.size()) return set_error("pt_scene_punctual_light: no such light");
+    punctual_to16(s->punctual[k], out);
+    return 0;
+}
+extern "C" int pt_scene_set_punctual_fraction(pt_scene* s, double f) {
+    if (!s) return set_error("pt_scene_set_punctual_fraction: null scene");
+    if (!std::isfinite(f) || !(0.0 < f && f < 1.0)) return set_error("pt_scene_set_punctual_fraction: the fraction must be finite with 0 < f < 1");
+    s->punctual_f = f;
+    s->dev.view.punctual_f = f;   // (read by the PLT forms only: a scene without punctual lights renders the same bits whatever f is)
+    return 0;
+}
+extern "C" double pt_scene_punctual_fraction(pt_scene* s) {
+    if (!s) { set_error("pt_scene_punctual_fraction: null scene"); return -1.0; }
+    return s->punctual_f;
+}
+extern "C" int pt_punctual_eval(const double rec16[16], const double point[3], double out7[7]) {
+    if (!rec16 || !point || !out7) return set_error("pt_punctual_eval: null buffer");
+    if (!(rec16[0] == 0.0 || rec16[0] == 1.0 || rec16[0] == 2.0)) return set_error("pt_punctual_eval: the record's kind must be 0, 1 or 2");
+    PunctualD L{};
+    L.kind = (uint32_t)rec16[0];
+    for (int i = 0; i < 3; ++i) { L.pos[i] = rec16[1 + i]; L.axis[i] = rec16[4 + i]; L.I[i] = rec16[7 + i]; }
+    L.cos_i = rec16[10]; L.cos_o = rec16[11];
+    const PunctualEval e = punctual_eval(L, point);   // the device's function, compiled for the host
+    out7[0] = e.w[0]; out7[1] = e.w[1]; out7[2] = e.w[2]; out7[3] = e.D; out7[4] = e.E[0]; out7[5] = e.E[1]; out7[6] = e.E[2];
     return 0;
 }
 static Box xform_box(const Box& b, const InstD& m) {   // box of the box (aabb.rs:50-76)
@@ -1227,6 +1321,7 @@ int pt::scene_build(pt_scene* s) {
     if (ok && any_attr) ok = upload(dev, tri_attr, v.tri_attr);
     if (ok && any_moving) ok = upload(dev, inst_motion, v.inst_motion);
     if (ok && !grids.empty()) ok = upload(dev, grids, v.grids) && upload(dev, grid_vals, v.grid_vals);
+    if (ok && !s->punctual.empty()) ok = upload(dev, s->punctual, v.punctual);
     if (!ok) {
         dev.release();
         return -1;
@@ -1236,6 +1331,8 @@ int pt::scene_build(pt_scene* s) {
     v.n_entries = (uint32_t)entries.size();
     v.n_prims = (uint32_t)prims.size();
     v.n_lights = (uint32_t)lights.size();
+    v.n_punctual = (uint32_t)s->punctual.size();
+    v.punctual_f = s->punctual_f;
     uint32_t flat_max = TLAS_FLAT_MAX;
     if (const char* ev = exp_env("PT_FLAT_MAX")) flat_max = (uint32_t)atoi(ev);
     bool pair_ids_fit = true;   // the flat walk packs (primitive id, lane) into one word: ids of spheres / quads / cuboid faces below 2^26
@@ -1247,6 +1344,7 @@ int pt::scene_build(pt_scene* s) {
     dev.view = v;
     s->n_prims = v.n_prims;
     s->n_mesh_entries = 0;
+    s->n_punctual_built = v.n_punctual;
     s->has_moving_instance = any_moving;
     s->motionless = !any_moving;   // (a moving instance: a ray's time reaches its pose)
     for (const SphereD& sp : spheres)

@@ -137,6 +137,12 @@ struct pt_scene {
     bool world_has_dispersion = false;
     bool dispersion_on() const { return world_has_dispersion; }   // "in effect": the kernels' DSP forms run
     double* disp_w = nullptr;
+    // punctual lights (pt_light_point / pt_light_spot / pt_light_directional): the list as the calls formed it, the selector's
+    // share of the punctual branch, and the number of lights of the last build (the device list: DeviceBuffers::view.punctual)
+    std::vector<pt::PunctualD> punctual;
+    double punctual_f = 0.5;
+    uint32_t n_punctual_built = 0;
+    bool punctual_on() const { return n_punctual_built != 0u; }   // "in effect": the kernels' PLT forms run
     int projection = 0;            // pt_scene_set_projection: 0 perspective, 1 orthographic, 2 fisheye, 3 panorama (CamD::projection)
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;

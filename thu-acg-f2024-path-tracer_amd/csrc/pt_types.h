@@ -147,6 +147,18 @@ constexpr uint32_t MEDIUM_SHIFT = 20, MEDIUM_BOUNCE_MASK = (1u << MEDIUM_SHIFT) 
 // their EnvTabD argument, which only the ENV forms read otherwise.
 constexpr uint32_t DSP_MONO_BIT = 1u << 31, DSP_BOUNCE_MASK = DSP_MONO_BIT - 1u;
 constexpr int DSP_BINS = 64;
+// Punctual lights (pt_light_point / pt_light_spot / pt_light_directional; the rule: pt_amd.h). One record per light, formed
+// on the host: kind 0 point (I = power / 4 pi), 1 spot (axis = normalize(target - position), the two cosines from the host's deterministic
+// cosine), 2 directional (axis = the way the light travels, I = the irradiance). A path on its SHADOW segment — the ray from a surface
+// towards light k that the next visit of K3 resolves — carries the flag in bit 31 of its bounce word and k in bits 20..30, which the plain
+// mode leaves free as it does DSP's MONO bit. Only the PLT forms of k_shade pack and unpack them; a camera ray's word is 0, so K1 has no PLT
+// form. The host refuses a max_depth that reaches the field (pt_render).
+struct PunctualD {
+    uint32_t kind, pad;
+    double pos[3], axis[3], I[3], cos_i, cos_o;
+};
+constexpr uint32_t PLT_MAX_LIGHTS = 2048, PLT_SHADOW_BIT = 1u << 31, PLT_INDEX_SHIFT = 20, PLT_INDEX_MASK = PLT_MAX_LIGHTS - 1u,
+                   PLT_BOUNCE_MASK = (1u << PLT_INDEX_SHIFT) - 1u;
 // THE shading mode of a render: which of the mutually exclusive features is in effect (the rules: pt_amd.h; which one a scene gets, or why
 // it gets none: pt_render.cpp render_mode). k_shade and shade_slot are compiled once per mode; "the X forms" are the kernels whose mode has X:
 //   PLAIN  none of them
@@ -165,6 +177,7 @@ constexpr bool mode_has_table(ShadeMode m) { return m == MODE_ENV || m == MODE_D
 // The forms of K1 / K3 the sky pass can run with (pt_render.cpp classify_sky switches the pass off for every other): the whole
 // frame in the plain mode, independent sampler, nothing moving, a two-wave shape of k_shade (every shape but the three-wave experiments).
 // Only these read the tile map (pt_k_common.h work_to_pixel); every other form's code is what it was before the pass existed.
+// (`motion`: the form has a trailing bool — MOT, or PLT of the punctual lights — that keeps the pass off.)
 constexpr bool sky_pass_form(bool list, ShadeMode m, bool qmc, bool motion, bool two_waves = true) { return !list && m == MODE_PLAIN && !qmc && !motion && two_waves; }
 constexpr uint32_t CLASS_MISS = 0u, CLASS_IDLE = 1u + MAT_KINDS, CLASS_DEAD = 2u + MAT_KINDS, N_CLASSES = 3u + MAT_KINDS;
 // MAT_SHEEN: p[0..2] = base colour, p[3] = sheen_tint (sheen.rs). MAT_CLEARCOAT: alpha_g (clearcoat.rs).
@@ -256,6 +269,9 @@ struct SceneD {
     const double* light_cdf;     // exact light sampling (pt_scene_set_light_sampling): per light mesh of n faces the n + 1 running
                                  // area sums C[0] = 0 .. C[n] = A in face order, at Entry::pad[0]; read by k_shade's LSE forms and the light probe only
     const InstMotionD* inst_motion;   // parallel to insts, null when no instance moves; read by the MOT forms of K2 / K3 and the probes only
+    const PunctualD* punctual;   // the punctual lights of the last build, null when there are none; read by the PLT forms of K3 and the probe only
+    uint32_t n_punctual;
+    double punctual_f;           // pt_scene_set_punctual_fraction: the selector's share of the punctual branch
 };
 constexpr int LIGHT_STACK = 24;          // LDS entries per lane of the LSE forms' all-hits mesh walk (pt_dev_lights.h): the deepest light mesh tree they take
 constexpr uint32_t TLAS_FLAT_MAX = 24;   // round 1 (vector loads): 8-10 entries -26 % / -7 % K2 time, 17 entries (scene 5) +20 % -> limit 12;

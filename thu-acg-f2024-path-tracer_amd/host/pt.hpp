@@ -486,9 +486,56 @@ struct HeterogeneousVolume : Volume {
     const char* name() const override { return "HeterogeneousVolume"; }
 };
 
+// ---- punctual lights (the reference's unfinished hittable/light.rs PointLight, finished, and two siblings; pt_light_point / pt_light_spot /
+// pt_light_directional). They have no geometry: World::add_punctual keeps them in a list of their own.
+struct PunctualLight {
+    virtual ~PunctualLight() = default;
+    virtual int emit(pt_scene* s) const = 0;   // the light's index, or -1
+};
+struct PointLight : PunctualLight {   // light.rs: PointLight { position, power }
+    Vec3 position, power;
+    static std::shared_ptr<PointLight> new_(Vec3 position, Vec3 power) {
+        auto l = std::make_shared<PointLight>();
+        l->position = position; l->power = power;
+        return l;
+    }
+    int emit(pt_scene* s) const override {
+        const double p[3] = {position.x, position.y, position.z}, w[3] = {power.x, power.y, power.z};
+        return pt_light_point(s, p, w);
+    }
+};
+struct SpotLight : PunctualLight {
+    Vec3 position, target, intensity;
+    double inner_deg = 0.0, outer_deg = 0.0;
+    static std::shared_ptr<SpotLight> new_(Vec3 position, Vec3 target, double inner_deg, double outer_deg, Vec3 intensity) {
+        auto l = std::make_shared<SpotLight>();
+        l->position = position; l->target = target; l->inner_deg = inner_deg; l->outer_deg = outer_deg; l->intensity = intensity;
+        return l;
+    }
+    int emit(pt_scene* s) const override {
+        const double p[3] = {position.x, position.y, position.z}, t[3] = {target.x, target.y, target.z}, i[3] = {intensity.x, intensity.y, intensity.z};
+        return pt_light_spot(s, p, t, inner_deg, outer_deg, i);
+    }
+};
+struct DirectionalLight : PunctualLight {
+    Vec3 direction, irradiance;
+    static std::shared_ptr<DirectionalLight> new_(Vec3 direction, Vec3 irradiance) {
+        auto l = std::make_shared<DirectionalLight>();
+        l->direction = direction; l->irradiance = irradiance;
+        return l;
+    }
+    int emit(pt_scene* s) const override {
+        const double d[3] = {direction.x, direction.y, direction.z}, e[3] = {irradiance.x, irradiance.y, irradiance.z};
+        return pt_light_directional(s, d, e);
+    }
+};
+
 // ---- World (src/hittable/world.rs:10-29) -------------------------------------------------
 struct World {
     std::vector<HitPtr> objects, lights;
+    std::vector<std::shared_ptr<PunctualLight>> punctual;   // this build's addition: the punctual lights (add_punctual)
+    double punctual_fraction = 0.5;                         // ... and the selector's share of their branch (pt_scene_set_punctual_fraction)
+    template <class T> void add_punctual(std::shared_ptr<T> l) { punctual.push_back(l); }
     pt_scene* scene = nullptr;   // set by build_bvh / emit_into
     bool owns_scene = false;
     std::map<const void*, int> handles;   // description -> C-ABI handle (for Camera's env map)
@@ -506,6 +553,8 @@ struct World {
         for (auto& o : objects) if (pt_world_add_object(s, o->emit(e)) != 0) panic("World::add_object");
         for (auto& l : lights) if (pt_world_add_light(s, l->emit(e)) != 0) panic("World::add_light");
         if (env) env->emit(e);
+        for (auto& l : punctual) if (l->emit(s) < 0) panic("World::add_punctual");
+        if (punctual_fraction != 0.5 && pt_scene_set_punctual_fraction(s, punctual_fraction) != 0) panic("set_punctual_fraction");
         if (camera_medium && pt_scene_set_camera_medium(s, camera_medium->medium(e)) != 0) panic("World::camera_medium");
         if (pt_world_build(s) != 0) panic("World::build_bvh");
         scene = s;
