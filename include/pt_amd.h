@@ -484,6 +484,46 @@ int pt_punctual_probe(pt_scene*, int which, const double* in, uint32_t n, double
 /* Host only, no context needed: the device's light evaluation compiled for the host. rec16: a record as pt_scene_punctual_light returns it;
  * out7 = (w.xyz, D, E.rgb). */
 int pt_punctual_eval(const double rec16[16], const double point[3], double out7[7]);
+/* ---- light shafts: punctual lights that light participating media (a spot light's cone in haze, a lamp in fog, sun beams through smoke; opt-in;
+ *      DESIGN.md section 22) ----
+ * pt_scene_set_punctual_media(on): 0 (default) or 1; any other value returns -1 and leaves the setting. It takes effect at once, without a rebuild.
+ *   pt_scene_punctual_media reads it.
+ * In effect for a render: the setting is 1, punctual lights are in effect (n > 0 at the last build) and media are in effect with homogeneous
+ *   (pt_mat_medium) or grid (pt_mat_medium_grid) media only, as the material of a boundary object or as the camera medium. With the setting 0
+ *   everything is as without it, the refusal of the pair included. With the setting 1 and only one of the two features in effect, that feature's
+ *   kernels run and produce its bits. With a glass interior or a tinted medium in effect the render is still refused (-1); so it is with
+ *   environment importance sampling, exact light sampling, dispersion or motion, as for either feature. max_depth must be at most 255 then: a path
+ *   keeps its medium (12 bits), the SHADOW flag, the light's index (11 bits) and its bounce number (8 bits) in one word. In effect for pt_render,
+ *   pt_render_pixels, pt_render_adaptive and pt_render_multi, static and dynamic pools, with and without a lights list, both samplers.
+ *   pt_render_aovs, pt_intersect and the sky pass do not change.
+ * The rule is pt_mat_medium's steps 1-4 (pt_mat_medium_grid's step 1 for a grid medium) and the punctual rule above, with these additions and
+ *   nothing else. f64, one rounding per written operation; draws are converted as those rules convert them.
+ * Medium vertex (step 2), at x with the segment's direction dir. Roulette as there. The selector draw r is READ (without this feature a medium
+ *   vertex without a lights list only advances the counter). The shares are the surface bounce's under punctual lights: p_punct = f, p_light =
+ *   lights ? (1 - f) / 2 : 0, p_bsdf = 1 - p_light - p_punct. r < p_light: lights.sample; r < p_light + p_punct: the punctual branch; otherwise
+ *   the phase sample. The lights and phase branches are step 2's with pdf = p_bsdf * ph + p_light * light_pdf under these weights.
+ *   The punctual branch: one index draw k, the surface rule's (a single draw under the Sobol sampler); (w, D, d2, E) of light k at x as there;
+ *   ph = hg_phase(g, dot(dir, w)) — the phase function stands where the surface has its eval, and there is no cosine —; pm = f / (double)n;
+ *   thr' = ((thr * (albedo * ph)) * E) / pm componentwise. The path ends when d2 is 0 or not finite, or thr' is exactly (0, 0, 0). Otherwise it
+ *   continues as a SHADOW segment Ray::new(x, w, time) — no offset, as for a scattered ray —, ++bounce, the depth bound as at any bounce; m is kept.
+ * Surface bounce (step 4): the punctual rule as it is. The SHADOW segment keeps the path's m.
+ * Resolving a SHADOW segment, when K3 next visits the path, before anything else. With o the stored origin: D' = length(pos_k - o) (+inf for a
+ *   directional light), t = the hit distance or +inf on a miss, t_end = t < D' ? t : D'. In this order:
+ *   1 Lost crossing: m is a medium that some world object bounds and the ray missed: m becomes none, no draw (step 1's exception, unchanged).
+ *   2 Free flight, if m is set: step 1's over [0, t_end) with its draws — a homogeneous medium one draw, d = -log(1 - u) / density; a grid
+ *     medium grid_track with t_end in place of t. A collision at a distance below t_end: the light is BLOCKED, the path ends, nothing is added.
+ *   3 Boundary crossing: otherwise, if the ray hit a medium's boundary at t < D', the segment goes on: m toggles exactly as in step 3, the
+ *     origin moves to the offset hit point, ++bounce and the depth bound (a segment the bound cuts contributes nothing, like any ray beyond
+ *     max_depth). The path stays a SHADOW segment towards light k; the throughput is unchanged. D' is formed again from the new origin.
+ *   4 Resolution: otherwise the light is visible iff the ray missed or t >= D'. If visible, radiance += thr. The path ends either way; the
+ *     environment is never added.
+ * Consequences. In expectation a shadow segment carries the transmittance exp(-integral of sigma) of everything between its origin and the
+ *   light: the analog free flight collides before t_end with probability 1 - exp(-integral), so the estimate is unbiased — for grids too, by
+ *   delta tracking. A sun in an UNBOUNDED homogeneous medium is always blocked (D' = t = +inf): use a bounded fog box. A shadow segment spends
+ *   one bounce of depth per boundary it crosses. Everything the punctual rule states stays true: the lights are invisible to camera, phase and
+ *   BSDF rays, every surface blocks them, selection is uniform. */
+int pt_scene_set_punctual_media(pt_scene*, int on);
+int pt_scene_punctual_media(pt_scene*);
 /* ---- world: src/hittable/world.rs:10-29 -------------------------------------------------- */
 int pt_world_add_object(pt_scene*, int obj);
 int pt_world_add_light(pt_scene*, int obj);

@@ -160,7 +160,7 @@ ABI_SYMBOLS = [
     "pt_instance_moving", "pt_scene_set_shutter", "pt_scene_shutter", "pt_scene_motion", "pt_motion_pose", "pt_motion_swept_box", "pt_world_entry_box",
     "pt_sky_tiles",
     "pt_light_point", "pt_light_spot", "pt_light_directional", "pt_scene_clear_punctual_lights", "pt_scene_punctual_count", "pt_scene_punctual_light",
-    "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval",
+    "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval", "pt_scene_set_punctual_media", "pt_scene_punctual_media",
 ]
 
 
@@ -241,6 +241,9 @@ def _load():
         lib.pt_scene_punctual_fraction.restype = C.c_double
         lib.pt_punctual_probe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_punctual_eval.argtypes = [d3, d3, d3]
+    if hasattr(lib, "pt_scene_set_punctual_media"):
+        lib.pt_scene_set_punctual_media.argtypes = [C.c_void_p, C.c_int]
+        lib.pt_scene_punctual_media.argtypes = [C.c_void_p]
     if hasattr(lib, "pt_sky_tiles"):
         lib.pt_sky_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -588,6 +591,12 @@ class Scene:
         return _check(lib.pt_scene_set_punctual_fraction(self.handle, float(f)), "set_punctual_fraction")
 
     def punctual_fraction(self) -> float: return lib.pt_scene_punctual_fraction(self.handle)
+
+    def set_punctual_media(self, on):
+        """Light shafts: 1 lets the punctual lights light participating media (homogeneous and grid media), 0 (default) refuses the pair."""
+        return _check(lib.pt_scene_set_punctual_media(self.handle, int(on)), "set_punctual_media")
+
+    def punctual_media(self) -> int: return lib.pt_scene_punctual_media(self.handle)
 
     def punctual_probe(self, which: int, arr: np.ndarray) -> np.ndarray:
         """The punctual branch's device functions as the kernels call them. which 0: arr = (n, 3) points -> (n, 9) {k, w.xyz, D, E.rgb, draws

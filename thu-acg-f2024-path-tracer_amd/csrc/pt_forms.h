@@ -34,18 +34,21 @@ constexpr bool shade_form_exists(const ShadeShape& s, bool lights, bool list, bo
            (!motion || mode == MODE_PLAIN);
 }
 // ... and with the fifth bool: the PLT forms (punctual lights in effect) are plain-mode forms of the default variant's shapes
-// too, without motion; every other form is what it is above.
+// too, without motion — and, for light shafts, MED and HET forms of the same shapes; every other form is what it is above.
 constexpr bool shade_form_exists(const ShadeShape& s, bool lights, bool list, bool qmc, ShadeMode mode, bool motion, bool punctual) {
-    return punctual ? (s.variant == 22 || s.variant == 32 || s.variant == 42) && mode == MODE_PLAIN && !motion : shade_form_exists(s, lights, list, qmc, mode, motion);
+    return punctual ? (s.variant == 22 || s.variant == 32 || s.variant == 42) && (mode == MODE_PLAIN || mode == MODE_MED || mode == MODE_HET) && !motion
+                    : shade_form_exists(s, lights, list, qmc, mode, motion);
 }
 // the unit that compiles a form: pt_k3.hip, pt_k3_qmc.hip, or the mode's own — pt_k3_med.hip (§12), pt_k3_het.hip (§13),
 // pt_k3_int.hip (§14), pt_k3_lse.hip (§15), pt_k3_dsp.hip (§16), each with and without QMC. K1 has a plain and a MED form only — a camera
 // ray's bounce word is the MED forms', or 0 — so a render's k_init comes from the unit of (its mode has media ? MED : PLAIN, qmc).
 // The MOT forms of K1 / K3 (plain mode, with and without QMC) are pt_k3_mot.hip's (§19). The PLT forms of K3 (plain mode, with and without
 // QMC) are pt_k3_plt.hip's (§21); K1 has none — a camera ray's bounce word is 0 — so such a render's k_init is the plain or QMC unit's.
-enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED, UNIT_HET, UNIT_INT, UNIT_LSE, UNIT_DSP, UNIT_MOT, UNIT_PLT };
+// The light-shaft forms of K3 (PLT in the modes MED and HET, with and without QMC) are pt_k3_shf.hip's (§22); a camera ray's bounce word is
+// the MED forms', so such a render's k_init is pt_k3_med.hip's.
+enum FormUnit { UNIT_PLAIN, UNIT_QMC, UNIT_MED, UNIT_HET, UNIT_INT, UNIT_LSE, UNIT_DSP, UNIT_MOT, UNIT_PLT, UNIT_SHF };
 constexpr FormUnit form_unit(ShadeMode mode, bool qmc, bool motion = false, bool punctual = false) {
-    if (punctual) return UNIT_PLT;
+    if (punctual) return mode == MODE_MED || mode == MODE_HET ? UNIT_SHF : UNIT_PLT;
     if (motion) return UNIT_MOT;
     switch (mode) {
     case MODE_MED: return UNIT_MED; case MODE_HET: return UNIT_HET; case MODE_INT: return UNIT_INT; case MODE_LSE: return UNIT_LSE; case MODE_DSP: return UNIT_DSP;
@@ -79,8 +82,8 @@ template <FormUnit U> FormKernels unit_forms(const ShadeForm& f, aov_fn aov) {
                                         if constexpr (!(med && mot) && form_unit(med ? MODE_MED : MODE_PLAIN, qmc, mot) == U) return k_init<list, qmc, med, mot>; else return nullptr; },
                                     f.list, f.qmc, mode_has_media(f.mode), f.motion), aov};
 }
-// the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip, pt_k3_het.hip, pt_k3_int.hip, pt_k3_lse.hip, pt_k3_dsp.hip, pt_k3_mot.hip, pt_k3_plt.hip) — the only calls from one kernel unit into another
+// the units' accessors (pt_k3.hip, pt_k3_qmc.hip, pt_k3_med.hip, pt_k3_het.hip, pt_k3_int.hip, pt_k3_lse.hip, pt_k3_dsp.hip, pt_k3_mot.hip, pt_k3_plt.hip, pt_k3_shf.hip) — the only calls from one kernel unit into another
 FormKernels forms_plain(const ShadeForm& f), forms_qmc(const ShadeForm& f), forms_med(const ShadeForm& f), forms_het(const ShadeForm& f), forms_int(const ShadeForm& f),
-    forms_lse(const ShadeForm& f), forms_dsp(const ShadeForm& f), forms_mot(const ShadeForm& f), forms_plt(const ShadeForm& f);
+    forms_lse(const ShadeForm& f), forms_dsp(const ShadeForm& f), forms_mot(const ShadeForm& f), forms_plt(const ShadeForm& f), forms_shf(const ShadeForm& f);
 
 }  // namespace pt

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(BLOCK) void k_aov(SceneD sc, CamD cam, uint64_t see
 
 FormKernels forms_plain(const ShadeForm& f) { return unit_forms<UNIT_PLAIN>(f, k_aov); }
 static FormKernels form_kernels(const ShadeForm& f) {   // asks the unit that owns the form's k_shade, and the one that owns its k_init (pt_forms.h)
-    constexpr FormKernels (*unit[])(const ShadeForm&) = {forms_plain, forms_qmc, forms_med, forms_het, forms_int, forms_lse, forms_dsp, forms_mot, forms_plt};   // in FormUnit's order
+    constexpr FormKernels (*unit[])(const ShadeForm&) = {forms_plain, forms_qmc, forms_med, forms_het, forms_int, forms_lse, forms_dsp, forms_mot, forms_plt, forms_shf};   // in FormUnit's order
     const FormUnit k3 = form_unit(f.mode, f.qmc, f.motion, f.punctual), k1 = form_unit(mode_has_media(f.mode) ? MODE_MED : MODE_PLAIN, f.qmc, f.motion);   // K1 has a plain, a MED and a MOT form only
     FormKernels k = unit[k3](f);
     if (k1 != k3) k.init = k.shade ? unit[k1](f).init : nullptr;

@@ -217,7 +217,12 @@ constexpr int LSE_KB = 512;                                            // thread
 // selector gives the punctual branch the share SceneD::punctual_f: it draws one light, weights the throughput by the material's eval and what the
 // light sends, and continues the path as a SHADOW segment — flag and light index ride in the upper bits of the bounce word (pt_types.h). The next visit
 // resolves the segment right after the hit is rebuilt: the throughput is added when nothing lies in front of the light, and the path ends either
-// way. Every other lane is the plain bounce under the reduced weights. Plain mode only.
+// way. Every other lane is the plain bounce under the reduced weights. Plain mode, or:
+// SHF = PLT in a media mode (MED or HET): light shafts (the rule in pt_amd.h; pt_scene_set_punctual_media). Medium and shadow segment share
+// the bounce word (pt_types.h SHF_*). A medium vertex reads its selector and may take the punctual branch, weighted by the phase function. Phase A's
+// free flight of a SHADOW segment runs to min(hit, light): a collision blocks the light; a segment that reaches a medium's boundary in front of
+// the light crosses it (B2's boundary code) and stays a SHADOW segment; otherwise it is resolved as in the plain mode. Every other lane is the
+// MED / HET form's bounce under PLT's weights.
 template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true, bool MOT = false, bool MAP = false, bool PLT = false>
 // UNI: the form may take the single-primitive path of phase A (k_shade: every two-wave shape).
 // MAP: the form reads the sky pass's tile map when it draws a work item (k_shade: sky_pass_form of its own arguments, pt_types.h).
@@ -229,6 +234,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                        uint32_t& shard, uint32_t& n_done, uint32_t& n_died, Prefetch&& prefetch, unsigned long long pre_mask = 0ull,
                        unsigned long long pre_base = 0ull, uint32_t pre_shard = 0u, const EnvTabD* env = nullptr, uint32_t* lstk = nullptr) {
     constexpr bool ENV = M == MODE_ENV, MED = mode_has_media(M), HET = mode_has_grid(M), INT = M == MODE_INT, LSE = M == MODE_LSE, DSP = M == MODE_DSP;
+    constexpr bool SHF = PLT && MED;
     PT_STAMP(1);
     uint32_t bounce = in.bounce;
     uint32_t med = 0u;                                                 // MED: the path's medium (material index + 1), 0 = none
@@ -249,9 +255,15 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     uint32_t plk = 0u;
     if constexpr (PLT) {
         if (bounce < SLOT_IDLE) {
+            if constexpr (SHF) {                                       // (the medium is out of the word already)
+                shadow = (bounce & SHF_SHADOW_BIT) != 0u;
+                plk = (bounce >> SHF_INDEX_SHIFT) & PLT_INDEX_MASK;
+                bounce &= SHF_BOUNCE_MASK;
+            } else {
             shadow = (bounce & PLT_SHADOW_BIT) != 0u;
             plk = (bounce >> PLT_INDEX_SHIFT) & PLT_INDEX_MASK;
             bounce &= PLT_BOUNCE_MASK;
+            }
         }
     }
     const bool alive = bounce != SLOT_DEAD;
@@ -297,6 +309,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     // ---- phase A: all global-memory reads of the bounce -------------------------------------------------------------
     bool is_hit = false;
     bool scatter = false, boundary = false;                            // MED: the lane is at a medium vertex (hit.point) / at a medium's boundary
+    bool blocked = false;                                              // SHF: the SHADOW segment collided in front of its end
+    double shadow_dl = D_INF;                                          // SHF: D' of the lane's SHADOW segment
     MediumD medium{};
     uint32_t interior = 0u;                                            // INT: the hit is on a glass with an interior: that medium (material index + 1)
     HitD hit{};
@@ -344,6 +358,12 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         const bool surface = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS &&
                              (uni ? reconstruct_hit_prim<false, true, MOT>(sc, ray, pr0, 1e-3, hit) : reconstruct_hit<false, MOT>(sc, ray, gid, 1e-3, hit));
         PT_STAMP_SET(a1);
+        if constexpr (SHF) {
+            if (shadow) {
+                const double o[3] = {ray.o.x, ray.o.y, ray.o.z};
+                shadow_dl = punctual_shadow_distance(sc.punctual[plk], o);
+            }
+        }
         if constexpr (MED) {
             if (med != 0u) {                                           // free flight: one draw, d = -log(1 - u) / density
                 medium = load_medium(sc, med);
@@ -357,7 +377,9 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                     if constexpr (HET) {
                         const uint32_t grid = (uint32_t)sc.mats[med - 1u].p[6];   // the medium's row of SceneD::grids + 1, 0 = homogeneous
                         if (grid != 0u) {                              // delta tracking through the grid, clipped to its box
-                            const GridTrack tr = grid_track(sc.grids + (grid - 1u), sc.grid_vals, ray.o, ray.d, surface ? hit.dist : D_INF, rng);
+                            double t_trk = surface ? hit.dist : D_INF;
+                            if constexpr (SHF) { if (shadow && !(t_trk < shadow_dl)) t_trk = shadow_dl; }   // a SHADOW segment ends at min(t, D')
+                            const GridTrack tr = grid_track(sc.grids + (grid - 1u), sc.grid_vals, ray.o, ray.d, t_trk, rng);
                             rng.draw = tr.draw;
                             if (tr.collided) d = tr.s;
                             tracked = true;
@@ -365,6 +387,9 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                     }
                     if (!tracked && (!INT || medium.density > 0.0)) d = medium_free_flight(rng_f64(rng), medium.density);   // (INT: density 0 makes no draw)
                     const double t_seg = surface ? hit.dist : D_INF;
+                    if (SHF && shadow) {
+                        blocked = d < (t_seg < shadow_dl ? t_seg : shadow_dl);   // a collision in front of min(t, D'): the light is blocked
+                    } else
                     if (d < t_seg) {
                         scatter = true;
                         hit.point = ray.o + ray.d * d;
@@ -378,7 +403,18 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             // a SHADOW segment is resolved before anything else — no emission, no roulette, no draw: the light is visible when the ray missed
             // or its hit lies at or beyond the light; the environment is not added. The path ends either way: a lane that missed is in the
             // `early` ballot already, one that hit ends like a roulette death.
-            if constexpr (PLT) {
+            if constexpr (SHF) {
+                // the free flight above ran over [0, min(t, D')). Not blocked: a medium's boundary in front of the light is crossed (B2's boundary
+                // code: toggle, offset, ++bounce, the depth bound) and the path stays a SHADOW segment; anything else resolves the segment. A lane
+                // that missed with no medium is in the `early` ballot and ends here; one that ends otherwise asks for work in phase C.
+                if (!blocked && surface && hit.dist < shadow_dl && sc.mats[hit.mat].kind == MAT_MEDIUM) {
+                    boundary = true;
+                } else {
+                    if (!blocked && (!surface || hit.dist >= shadow_dl)) add_radiance(pool, pixel, rad, thr);
+                    finished = true;
+                    parked = (in.hw >> HIT_CLASS_SHIFT) != CLASS_MISS;
+                }
+            } else if constexpr (PLT) {
                 const double o[3] = {ray.o.x, ray.o.y, ray.o.z};
                 const double dl = punctual_shadow_distance(sc.punctual[plk], o);
                 if (!surface || hit.dist >= dl) add_radiance(pool, pixel, rad, thr);
@@ -517,10 +553,22 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             }
             if (!finished) {
                 bool from_light = false;
-                if constexpr (LIGHTS) from_light = rng_f64(rng) < p_light;
+                double rsel = 1.0;                                     // SHF: the selector is read — lights below p_light, the punctual list below p_light + f
+                if constexpr (SHF) { rsel = rng_f64(rng); from_light = LIGHTS && rsel < p_light; }
+                else if constexpr (LIGHTS) from_light = rng_f64(rng) < p_light;
                 else ++rng.draw;                                       // the selector is drawn even without lights
                 if (from_light) {
                     dir = lights_sample<MOT>(sc, hit.point, ray.time, rng);
+                } else if (SHF && rsel < p_light + p_punct) {
+                    if constexpr (SHF) {                               // the surface bounce's punctual branch at the vertex x = hit.point
+                        plk = rng_index(rng, sc.n_punctual) & PLT_INDEX_MASK;
+                        const double x[3] = {hit.point.x, hit.point.y, hit.point.z};
+                        const PunctualEval pe = punctual_eval(sc.punctual[plk], x);
+                        dir = V3{pe.w[0], pe.w[1], pe.w[2]};
+                        punct_e = V3{pe.E[0], pe.E[1], pe.E[2]};
+                        punct_ok = pe.d2 != 0.0 && pe.d2 - pe.d2 == 0.0;
+                        punct_dir = true;
+                    }
                 } else {
                     uint64_t a, b;
                     rng_u64x2(rng, a, b);
@@ -602,6 +650,20 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     if constexpr (MED) {
         if (have_mdir) {
             const double ph = hg_phase(medium.g, dot(ray.d, dir));
+            if (SHF && punct_dir) {
+                // thr' = ((thr * (albedo * ph)) * E) / pm, pm = f / n: the phase function where the surface has its eval, no cosine
+                const double pm = p_punct / (double)sc.n_punctual;
+                const V3 t = ((thr * (medium.albedo * ph)) * punct_e) / pm;
+                if (!punct_ok || (t.x == 0.0 && t.y == 0.0 && t.z == 0.0)) {
+                    finished = parked = true;
+                } else {
+                    ray = make_ray(hit.point, dir, ray.time);          // no offset, as for a scattered ray
+                    thr = t;
+                    shadow = true;
+                    ++bounce;
+                    if (bounce >= cam.max_depth) finished = parked = true;
+                }
+            } else {
             double light_pdf = 0.0;
             if constexpr (LIGHTS) light_pdf = lights_pdf<MOT>(sc, hit.point, dir, ray.time);
             const double pdf = p_bsdf * ph + p_light * light_pdf;
@@ -612,6 +674,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 ray = make_ray(hit.point, dir, ray.time);              // no offset: nothing to leave
                 ++bounce;
                 if (bounce >= cam.max_depth) finished = parked = true;
+            }
             }
         } else if (boundary) {
             // no draw, no roulette, no emission: the path changes medium and goes straight on, offset like every continued ray
@@ -707,7 +770,8 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         const uint32_t state_new = bounce < SLOT_IDLE ? 0u : bounce, state_old = was_idle ? SLOT_IDLE : 0u;
         if (reorder || state_new != state_old) pool.bounce_out[o] = state_new;
         if (bounce < SLOT_IDLE) {
-            const uint32_t bounce_word = MED ? bounce | (med << MEDIUM_SHIFT) : DSP && mono ? bounce | DSP_MONO_BIT : PLT && shadow ? bounce | PLT_SHADOW_BIT | (plk << PLT_INDEX_SHIFT) : bounce;
+            const uint32_t bounce_word = SHF ? bounce | (med << MEDIUM_SHIFT) | (shadow ? SHF_SHADOW_BIT | (plk << SHF_INDEX_SHIFT) : 0u) :
+                                         MED ? bounce | (med << MEDIUM_SHIFT) : DSP && mono ? bounce | DSP_MONO_BIT : PLT && shadow ? bounce | PLT_SHADOW_BIT | (plk << PLT_INDEX_SHIFT) : bounce;
             store_ray(pool, pool.ray_out, o, ray, sample, rng.draw, pixel, bounce_word);
             if (!pool.compact || bounce != 0u) store_path(pool.path_out, o, thr, pixel, bounce_word);
             if (!pool.dynamic) { pool.rx[s] = rad.x; pool.ry[s] = rad.y; pool.rz[s] = rad.z; }
@@ -761,12 +825,12 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 // hit, or instead of leaving — so these forms do not request work items a group ahead.
 // LSE: these forms hold the per-lane stack of the light meshes' all-hits walk, LIGHT_STACK levels x KB lanes in LDS
 // MOT: motion (shade_slot)
-// PLT: punctual lights (shade_slot)
+// PLT: punctual lights (shade_slot); in the modes MED and HET: light shafts
 template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, ShadeMode M = MODE_PLAIN, bool QMC = false, bool MOT = false, bool PLT = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     constexpr bool ENV = M == MODE_ENV, MED = mode_has_media(M), LSE = M == MODE_LSE, DSP = M == MODE_DSP;   // (HET and INT change nothing here)
     static_assert(!MOT || M == MODE_PLAIN, "k_shade: the MOT forms are plain-mode forms");
-    static_assert(!PLT || (M == MODE_PLAIN && !MOT), "k_shade: the PLT forms are plain-mode forms without motion");
+    static_assert(!PLT || ((M == MODE_PLAIN || M == MODE_MED || M == MODE_HET) && !MOT), "k_shade: the PLT forms are plain-mode forms, or MED / HET forms (light shafts), without motion");
     static_assert((!LSE || LIGHTS) && (!(LSE || DSP) || (SORT && KB == LSE_KB)), "k_shade: the LSE forms need a lights list; the LSE and DSP forms are sorted 512-thread forms");
     __shared__ uint32_t s_lstack[LSE ? LIGHT_STACK * KB : 1];   // 48 KB: stack[level][thread] of lights_pdf_exact's mesh walk
     uint32_t* const lstk = LSE ? &s_lstack[threadIdx.x] : nullptr;

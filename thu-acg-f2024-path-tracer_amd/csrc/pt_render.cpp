@@ -332,10 +332,15 @@ static int render_mode(pt_scene* s, const CamD& dc, hipStream_t st, ShadeMode& m
     if (mot && lse) return set_error("pt_render: motion together with exact light sampling is not supported (set light sampling to 0, or take the moving instances out and reset the shutter)");
     if (mot && dsp) return set_error("pt_render: motion together with spectral dispersion is not supported (clear the dispersion, or take the moving instances out and reset the shutter)");
     // punctual lights are in effect (pt_amd.h): the list held a light at the last build. Their kernels are plain-mode forms without motion
-    // (pt_forms.h), and a path's SHADOW flag and light index ride in bits 20..31 of its bounce word; otherwise no new code runs
+    // (pt_forms.h), and a path's SHADOW flag and light index ride in bits 20..31 of its bounce word; otherwise no new code runs.
+    // Light shafts (pt_scene_set_punctual_media): with the option set, punctual lights and media in the modes MED and HET are
+    // in effect together — forms of their own, whose bounce word holds the medium, the flag, the index and an 8-bit bounce number (pt_types.h SHF_*).
     const bool plt = s->punctual_on();
+    const bool shf = plt && med && s->punctual_media != 0;
+    if (shf && s->interior_on()) return set_error("pt_render: punctual lights together with a glass interior or a tinted medium are not supported, also with pt_scene_set_punctual_media (take the interiors / tinted media out, or clear the punctual lights and rebuild)");
+    if (shf && dc.max_depth > SHF_BOUNCE_MASK) return set_error("pt_render: max_depth must be at most 255 when punctual lights light participating media (pt_scene_set_punctual_media)");
     if (plt && env_on) return set_error("pt_render: punctual lights together with environment importance sampling are not supported (set the sampling off, or clear the punctual lights and rebuild)");
-    if (plt && med) return set_error("pt_render: punctual lights together with participating media or a glass interior are not supported (take the media out, or clear the punctual lights and rebuild)");
+    if (plt && med && !shf) return set_error("pt_render: punctual lights together with participating media or a glass interior are not supported (take the media out, or clear the punctual lights and rebuild)");
     if (plt && lse) return set_error("pt_render: punctual lights together with exact light sampling are not supported (set light sampling to 0, or clear the punctual lights and rebuild)");
     if (plt && dsp) return set_error("pt_render: punctual lights together with spectral dispersion are not supported (clear the dispersion, or clear the punctual lights and rebuild)");
     if (plt && mot) return set_error("pt_render: punctual lights together with motion are not supported (take the moving instances out and reset the shutter, or clear the punctual lights and rebuild)");

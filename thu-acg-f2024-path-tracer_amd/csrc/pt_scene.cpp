@@ -653,6 +653,16 @@ extern "C" int pt_scene_set_punctual_fraction(pt_scene* s, double f) {
     s->dev.view.punctual_f = f;   // (read by the PLT forms only: a scene without punctual lights renders the same bits whatever f is)
     return 0;
 }
+extern "C" int pt_scene_set_punctual_media(pt_scene* s, int on) {
+    if (!s) return set_error("pt_scene_set_punctual_media: null scene");
+    if (on != 0 && on != 1) return set_error("pt_scene_set_punctual_media: the setting is 0 or 1");
+    s->punctual_media = on;   // (read by pt_render's choice of the kernels only: nothing to rebuild)
+    return 0;
+}
+extern "C" int pt_scene_punctual_media(pt_scene* s) {
+    if (!s) return set_error("pt_scene_punctual_media: null scene");
+    return s->punctual_media;
+}
 extern "C" double pt_scene_punctual_fraction(pt_scene* s) {
     if (!s) { set_error("pt_scene_punctual_fraction: null scene"); return -1.0; }
     return s->punctual_f;

@@ -143,6 +143,8 @@ struct pt_scene {
     double punctual_f = 0.5;
     uint32_t n_punctual_built = 0;
     bool punctual_on() const { return n_punctual_built != 0u; }   // "in effect": the kernels' PLT forms run
+    // light shafts (pt_scene_set_punctual_media): the option that lets punctual lights and participating media be in effect together
+    int punctual_media = 0;
     int projection = 0;            // pt_scene_set_projection: 0 perspective, 1 orthographic, 2 fisheye, 3 panorama (CamD::projection)
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;

@@ -159,6 +159,12 @@ struct PunctualD {
 };
 constexpr uint32_t PLT_MAX_LIGHTS = 2048, PLT_SHADOW_BIT = 1u << 31, PLT_INDEX_SHIFT = 20, PLT_INDEX_MASK = PLT_MAX_LIGHTS - 1u,
                    PLT_BOUNCE_MASK = (1u << PLT_INDEX_SHIFT) - 1u;
+// Light shafts (pt_scene_set_punctual_media): punctual lights and participating media in effect together. Medium AND shadow
+// segment travel in the one bounce word: the medium stays in bits 20..31 (MEDIUM_SHIFT — a camera ray's word is the MED forms', so K1 has no
+// form of its own), the SHADOW flag is bit 19, the light index bits 8..18, the bounce number bits 0..7. Only the forms of k_shade that have
+// both PLT and a media mode pack and unpack this layout; the host refuses a max_depth above SHF_BOUNCE_MASK (pt_render).
+constexpr uint32_t SHF_SHADOW_BIT = 1u << 19, SHF_INDEX_SHIFT = 8, SHF_BOUNCE_MASK = (1u << SHF_INDEX_SHIFT) - 1u;
+static_assert((PLT_INDEX_MASK << SHF_INDEX_SHIFT) < SHF_SHADOW_BIT && SHF_SHADOW_BIT < (1u << MEDIUM_SHIFT), "the fields of a light-shaft bounce word do not overlap");
 // THE shading mode of a render: which of the mutually exclusive features is in effect (the rules: pt_amd.h; which one a scene gets, or why
 // it gets none: pt_render.cpp render_mode). k_shade and shade_slot are compiled once per mode; "the X forms" are the kernels whose mode has X:
 //   PLAIN  none of them

@@ -191,6 +191,7 @@ int main(int argc, char** argv) {
     bool mesh_light = false;
     std::vector<std::vector<double>> point_lights, spot_lights, suns;   // --point-light, --spot-light, --sun: repeatable
     double punctual_fraction = 0.5;                                      // --punctual-fraction F
+    bool light_shafts = false;                                           // --light-shafts: the punctual lights light --fog / --smoke
     double mesh_light_v[7] = {0.0, 0.0, 0.0, 0.0, 10.0, 10.0, 10.0};   // centre x y z, radius, emission r g b
     long aov_spp = 16;
     Film film;   // --exposure, --tonemap, --white, --bloom, --out-hdr
@@ -292,6 +293,7 @@ int main(int argc, char** argv) {
         else if (a == "--punctual-fraction") {
             if (!parse_number(next(), punctual_fraction) || !(punctual_fraction > 0.0 && punctual_fraction < 1.0)) { std::cerr << "--punctual-fraction must be a number F with 0 < F < 1\n"; return 2; }
         }
+        else if (a == "--light-shafts") light_shafts = true;
         else if (a == "--mesh-light") {
             if (!parse_mesh_light(next(), mesh_light_v)) { std::cerr << "--mesh-light must be X,Y,Z,RADIUS[,R,G,B]: radius > 0, emission >= 0\n"; return 2; }
             mesh_light = true;
@@ -319,7 +321,7 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
                          "  --projection: orthographic frames the rectangle the scene's camera sees on its focal plane; fisheye is equidistant with the scene's vfov\n"
                          "           across the image height; panorama is an equirectangular image of everything around the camera position, in world axes: loaded as\n"
                          "           an environment map (--out-hdr, then --float-hdr) it lights another scene. fisheye and panorama have no lens: the scene's\n"
@@ -332,7 +334,8 @@ int main(int argc, char** argv) {
                          "           X,Y,Z aimed at TX,TY,TZ with on-axis intensity R,G,B (W/sr), full inside INNER degrees from the axis and fading to zero at OUTER; a sun\n"
                          "           whose light travels along DX,DY,DZ with irradiance R,G,B. --punctual-fraction: the share F of a bounce's one sample they get (default\n"
                          "           0.5). They are invisible to the camera and every surface shadows them, glass included. Not with --env-sampling, --fog, --smoke,\n"
-                         "           --interior, --dispersion, --light-sampling exact, --mesh-light or --motion\n"
+                         "           --interior, --dispersion, --light-sampling exact, --mesh-light or --motion. --light-shafts: the lights also light --fog and\n"
+                         "           --smoke (a spot light's cone in haze, sun beams through a plume), which they are refused with otherwise; max_depth is at most 255 then\n"
                          "  --stats: every kernel launch of a plain render is timed and its statistics are printed as one JSON line (tools/motion_eval.py reads it)\n"
                          "  --exposure, --tonemap, --white, --bloom: the film stage between the accumulator and the PNG: the image is scaled by 2^EV, light above the\n"
                          "           luminance THRESHOLD (default 1) spreads as glare of strength S (LEVELS Gaussians of SIGMA, 2 SIGMA, ... pixels; defaults 5 and 2),\n"
@@ -371,8 +374,8 @@ int main(int argc, char** argv) {
         std::cerr << "--motion cannot be combined with --env-sampling, --fog, --smoke, --interior, --dispersion, --light-sampling exact or --mesh-light\n";
         return 2;
     }
-    if ((!point_lights.empty() || !spot_lights.empty() || !suns.empty()) && (env_sampling > 0.0 || fog || smoke || interior || dispersion > 0.0 || light_sampling == 1 || mesh_light || motion)) {
-        std::cerr << "--point-light, --spot-light and --sun cannot be combined with --env-sampling, --fog, --smoke, --interior, --dispersion, --light-sampling exact, --mesh-light or --motion\n";
+    if ((!point_lights.empty() || !spot_lights.empty() || !suns.empty()) && (env_sampling > 0.0 || ((fog || smoke) && !light_shafts) || interior || dispersion > 0.0 || light_sampling == 1 || mesh_light || motion)) {
+        std::cerr << "--point-light, --spot-light and --sun cannot be combined with --env-sampling, --fog, --smoke (unless --light-shafts is given), --interior, --dispersion, --light-sampling exact, --mesh-light or --motion\n";
         return 2;
     }
     {   // the film options' ranges: the library's own test, before anything is rendered
@@ -403,6 +406,7 @@ int main(int argc, char** argv) {
         for (const auto& x : spot_lights) setup.world.add_punctual(SpotLight::new_(Vec3{x[0], x[1], x[2]}, Vec3{x[3], x[4], x[5]}, x[6], x[7], Vec3{x[8], x[9], x[10]}));
         for (const auto& x : suns) setup.world.add_punctual(DirectionalLight::new_(Vec3{x[0], x[1], x[2]}, Vec3{x[3], x[4], x[5]}));
         setup.world.punctual_fraction = punctual_fraction;
+        setup.world.punctual_media = light_shafts;
         if (projection >= 2) setup.camera.defocus_angle = 0.0;   // the library refuses a lens there (pt_scene_set_projection's rule)
         if (mesh_light) {   // an emissive level-4 icosphere (5120 triangles), in the world and in the lights list
             auto ball = TriangleMesh::from_obj(1.0, icosphere(4, Vec3{mesh_light_v[0], mesh_light_v[1], mesh_light_v[2]}, mesh_light_v[3]),

@@ -535,6 +535,7 @@ struct World {
     std::vector<HitPtr> objects, lights;
     std::vector<std::shared_ptr<PunctualLight>> punctual;   // this build's addition: the punctual lights (add_punctual)
     double punctual_fraction = 0.5;                         // ... and the selector's share of their branch (pt_scene_set_punctual_fraction)
+    bool punctual_media = false;                            // ... and whether they light participating media (pt_scene_set_punctual_media: light shafts)
     template <class T> void add_punctual(std::shared_ptr<T> l) { punctual.push_back(l); }
     pt_scene* scene = nullptr;   // set by build_bvh / emit_into
     bool owns_scene = false;
@@ -555,6 +556,7 @@ struct World {
         if (env) env->emit(e);
         for (auto& l : punctual) if (l->emit(s) < 0) panic("World::add_punctual");
         if (punctual_fraction != 0.5 && pt_scene_set_punctual_fraction(s, punctual_fraction) != 0) panic("set_punctual_fraction");
+        if (punctual_media && pt_scene_set_punctual_media(s, 1) != 0) panic("set_punctual_media");
         if (camera_medium && pt_scene_set_camera_medium(s, camera_medium->medium(e)) != 0) panic("World::camera_medium");
         if (pt_world_build(s) != 0) panic("World::build_bvh");
         scene = s;
