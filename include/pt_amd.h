@@ -62,6 +62,16 @@ typedef struct pt_render_stats {
     /* the sky pass (pt_sky_tiles below): 8x8 pixel tiles rendered outside the path pool, their samples — the tiles' pixels inside
        the image x the samples per pixel, counted in `samples` and `segments` as well — and the HIP-event time of their kernel (profile=1).
        All zero when the pass is off. */
+    /* the short-path pass (pt_short_tiles below): tiles whose camera rays can enter only boxes of shadeable entries, rendered
+       ahead of the path pool as far as a sample's path is camera -> miss or camera -> one diffuse hit -> miss — short_samples, counted in
+       `samples` and `segments` as well; the other samples of those tiles (hard_samples) are the path pool's; the HIP-event time of the pass's
+       kernel (profile=1). All zero when the pass is off. (In front of the sky pass's fields, which stay the structure's last: a caller built
+       against the header before these four must be rebuilt, the sky fields' offsets having moved by 32 bytes.)
+       Device memory: the pass keeps a list sized for EVERY sample of the tiles it takes (4 bytes each, 8 where tile, pixel and sample do not
+       fit in 32 bits), capped at the bytes of the path pool's records — scene 6 at 1920x1080 @ 4000 spp: 7.9 GB beside a 27 GB pool; where the
+       cap binds the pass takes fewer tiles. PT_EXPERIMENT=1 PT_SHORT_CAP_BYTES=n lowers the cap for a host with less memory. */
+    uint64_t short_tiles, short_samples, hard_samples;
+    double ms_short;
     uint64_t sky_tiles, sky_samples;
     double ms_sky;
 } pt_render_stats;
@@ -430,6 +440,13 @@ int pt_motion_pose(const double axis[3], double angle0, double angle1, const dou
    moving, no camera medium) applies the test to the boxes of the world's entries (pt_world_entry_box) and renders the cleared tiles — every sample of
    theirs is the environment in the camera ray's direction — outside the path pool; the frame's sums and counts are what they are without. */
 int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, uint8_t* out_tiles);
+/* Host only, no context needed. The same test read per box (csrc/pt_sky_tiles.h sky_tile_class): out_tiles = 1 for a sure-sky tile as above, 2 for a
+   SHORT tile — every box the test could NOT clear has shadeable[b] != 0, so a camera ray of the tile enters boxes of shadeable entries or none — and 0
+   for every other tile (the path pool's). shadeable: n_boxes bytes, or null for none. More than 64 boxes, a NaN or an infinity, a camera inside or touching a
+   box that is not shadeable: no tile is 2. A render as described above, on a scene without a lights list whose top level is walked flat, renders the
+   short tiles' samples ahead of the path pool where their path is camera -> miss or camera -> one hit of a shadeable entry (a still world-level
+   sphere or quad, diffuse, no normal map, no instance) -> miss; sums and counts are what they are without (PT_SHORT_PASS=0 under PT_EXPERIMENT=1). */
+int pt_short_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, uint8_t* out_tiles);
 int pt_motion_swept_box(const double box[6], const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double out[6]);
 /* test probe: the f64 world box (lo.xyz, hi.xyz) of world entry `entry` (lights list first, then objects), before the f32 rounding */
 int pt_world_entry_box(pt_scene*, uint32_t entry, double out[6]);

@@ -79,6 +79,10 @@ class RenderStats(C.Structure):
         ("blocks_shade", C.c_uint32),
         ("compactions", C.c_uint32),
         ("n_alloc_end", C.c_uint32),
+        ("short_tiles", C.c_uint64),
+        ("short_samples", C.c_uint64),
+        ("hard_samples", C.c_uint64),
+        ("ms_short", C.c_double),
         ("sky_tiles", C.c_uint64),
         ("sky_samples", C.c_uint64),
         ("ms_sky", C.c_double),
@@ -158,7 +162,7 @@ ABI_SYMBOLS = [
     "pt_mat_glass_set_dispersion", "pt_mat_glass_dispersion", "pt_dispersion_probe",
     "pt_scene_set_projection", "pt_scene_projection", "pt_camera_probe",
     "pt_instance_moving", "pt_scene_set_shutter", "pt_scene_shutter", "pt_scene_motion", "pt_motion_pose", "pt_motion_swept_box", "pt_world_entry_box",
-    "pt_sky_tiles",
+    "pt_sky_tiles", "pt_short_tiles",
     "pt_light_point", "pt_light_spot", "pt_light_directional", "pt_scene_clear_punctual_lights", "pt_scene_punctual_count", "pt_scene_punctual_light",
     "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval", "pt_scene_set_punctual_media", "pt_scene_punctual_media",
 ]
@@ -246,6 +250,8 @@ def _load():
         lib.pt_scene_punctual_media.argtypes = [C.c_void_p]
     if hasattr(lib, "pt_sky_tiles"):
         lib.pt_sky_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pt_short_tiles"):             # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_short_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -918,6 +924,19 @@ def sky_tiles(cam: Camera, boxes) -> np.ndarray:
     tiles_y, tiles_x = (image_height(cam) + 7) // 8, (cam.image_width + 7) // 8
     out = np.zeros((tiles_y, tiles_x), dtype=np.uint8)
     _check(lib.pt_sky_tiles(C.byref(cam), len(boxes), boxes.ctypes.data if len(boxes) else None, out.ctypes.data), "pt_sky_tiles")
+    return out
+
+
+def short_tiles(cam: Camera, boxes, shadeable) -> np.ndarray:
+    """The tile test read per box (pt_short_tiles; host only): boxes (n, 6), shadeable (n,) flags -> (tiles_y, tiles_x) uint8, 1 = sure sky,
+    2 = short (every box the test cannot clear is shadeable), 0 = the path pool's."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)
+    flags = np.ascontiguousarray(shadeable, dtype=np.uint8).reshape(-1)
+    assert len(flags) == len(boxes)
+    tiles_y, tiles_x = (image_height(cam) + 7) // 8, (cam.image_width + 7) // 8
+    out = np.zeros((tiles_y, tiles_x), dtype=np.uint8)
+    _check(lib.pt_short_tiles(C.byref(cam), len(boxes), boxes.ctypes.data if len(boxes) else None, flags.ctypes.data if len(boxes) else None, out.ctypes.data),
+           "pt_short_tiles")
     return out
 
 

@@ -112,6 +112,10 @@ PT_DEV void divmod_u31(uint32_t a, uint32_t b, uint32_t& q, uint32_t& r) {   // 
 }
 // the sky pass's tile map (PoolD::n_work_pixels != 0): active-tile index -> tile
 PT_DEV const uint32_t* pool_tile_map(const PoolD& pool) { return reinterpret_cast<const uint32_t*>(pool.accum + 3 * (size_t)pool.n_tile_pixels); }
+// ... and behind the map, at the next 8-byte boundary, the short-path pass's record of its hard list (pt_types.h ShortHdrD; the host: short_hdr_behind)
+PT_DEV const ShortHdrD* pool_short_hdr(const PoolD& pool) {
+    return reinterpret_cast<const ShortHdrD*>(pool_tile_map(pool) + (((size_t)pool.n_tile_pixels / 64u + 1u) & ~(size_t)1u));
+}
 // dynamic mode: work item -> (pixel, sample) and the pixel's row / column; false when the item lies outside a ragged image edge
 // MAP: the form can run with the sky pass on (sky_pass_form, pt_types.h); every other form is compiled without the lookup, as it was
 template <bool MAP>
@@ -119,21 +123,38 @@ PT_DEV bool work_to_pixel(const PoolD& pool, unsigned long long w, uint32_t& pix
     unsigned long long q;
     uint32_t in_frame;
     const bool mapped = MAP && pool.n_work_pixels != 0u;   // (a kernel argument: wave-uniform)
-    divmod_u53(w, mapped ? pool.n_work_pixels : pool.n_tile_pixels, q, in_frame);
-    sample = pool.spp_begin + (uint32_t)q;
-    uint32_t tile = in_frame >> 6;
-    const uint32_t in_tile = in_frame & 63u;
+    // the short-path pass's hard samples are the items behind the tile items: (tile, pixel in tile, sample) from the list
+    const unsigned long long tile_items = (unsigned long long)pool.n_work_pixels * (unsigned long long)(pool.spp_end - pool.spp_begin);
+    const bool hard = mapped && w >= tile_items;
+    uint32_t tile, in_tile;
+    if (hard) {
+        const ShortHdrD* h = pool_short_hdr(pool);
+        const unsigned long long i = w - tile_items;   // (< n_hard: the caller has checked w < total_work)
+        const uint32_t sbits = ldu(&h->sample_bits);
+        const void* list = (const void*)ldu((const unsigned long long*)&h->hard);
+        const unsigned long long e = ldu(&h->wide) ? ((const unsigned long long*)list)[i] : (unsigned long long)((const uint32_t*)list)[i];
+        sample = pool.spp_begin + (uint32_t)(e & ((1ull << sbits) - 1ull));
+        in_tile = (uint32_t)(e >> sbits) & 63u;
+        tile = ((const uint32_t*)ldu((const unsigned long long*)&h->short_list))[(uint32_t)(e >> (sbits + 6u))];
+    } else {
+        divmod_u53(w, mapped ? pool.n_work_pixels : pool.n_tile_pixels, q, in_frame);
+        sample = pool.spp_begin + (uint32_t)q;
+        tile = in_frame >> 6;
+        in_tile = in_frame & 63u;
+    }
     if (mapped) {
         // the map entries of the calling lanes by SCALAR loads, one per distinct tile: the lanes hold consecutive items of at most two
         // 64-item chunks (two tiles), or of a shuffled granule of k_init (PT_INIT_SHUFFLE) — a per-lane load's address pair cost a form scratch
+        // (a hard sample's tile comes from its entry and is left alone)
         const uint32_t* map = pool_tile_map(pool);
-        uint32_t mapped_tile = 0u;
-        unsigned long long todo = __ballot(true);
+        uint32_t mapped_tile = tile;
+        unsigned long long todo = __ballot(!hard);
         while (todo != 0ull) {
             const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)tile, __ffsll((long long)todo) - 1);
             const uint32_t m0 = ldu(&map[t0]);
-            if (tile == t0) mapped_tile = m0;
-            todo &= ~__ballot(tile == t0);
+            const bool mine = !hard && tile == t0;
+            if (mine) mapped_tile = m0;
+            todo &= ~__ballot(mine);
         }
         tile = mapped_tile;
     }

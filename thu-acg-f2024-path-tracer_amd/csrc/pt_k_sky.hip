@@ -1,55 +1,81 @@
 // The sky pass: the tiles no camera ray of which can enter a box of the world (pt_sky_tiles.h) never enter the path pool.
 //   k_sky_classify  one thread per 8x8 pixel tile: the tile test
-//   k_sky_scan      one block: the flags -> the wavefront's tile map (active-tile index -> tile), the sure-sky tile list, the two counts
+//   k_sky_scan      one block: the flags -> the wavefront's tile map (active-tile index -> tile), the sure-sky tile list, the short-path
+//                   pass's tile list (k_short is in pt_k_short.hip), the counts
 //   k_sky           one wave per (sure-sky tile, chunk of samples): what K3 does for a camera ray that left the scene, and nothing else
 #include "pt_k_common.h"
 #include "pt_sky_tiles.h"
 
 namespace pt {
 
-__global__ __launch_bounds__(BLOCK) void k_sky_classify(SkyCam cam, uint32_t n_boxes, const double* boxes6, uint32_t tiles_x, uint32_t n_tiles, uint8_t* flags) {
+__global__ __launch_bounds__(BLOCK) void k_sky_classify(SkyCam cam, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, uint32_t tiles_x,
+                                                         uint32_t n_tiles, uint8_t* flags) {
     const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
     if (t >= n_tiles) return;
     uint32_t ty, tx;
     divmod_u31(t, tiles_x, ty, tx);
-    flags[t] = sky_tile_is_clear(cam, ty, tx, n_boxes, boxes6) ? 1u : 0u;
+    flags[t] = sky_tile_class(cam, ty, tx, n_boxes, boxes6, shadeable);   // (shadeable = 0: sure sky or wavefront, the sky pass's two kinds)
 }
 
-// Thread i ranks the tiles [i * per, (i + 1) * per): both lists come out in tile order. counts[0] = active tiles, counts[1] = sure-sky tiles,
-// counts[2] = the pixels of the sure-sky tiles that lie inside the image.
-__global__ __launch_bounds__(BLOCK) void k_sky_scan(const uint8_t* flags, uint32_t n_tiles, uint32_t width, uint32_t height, uint32_t* tile_map, uint32_t* sky_list,
-                                                     uint32_t* counts) {
-    __shared__ uint32_t s_sky[BLOCK], s_pixels;
+// Thread i ranks the tiles [i * per, (i + 1) * per): the three lists come out in tile order. Of the SHORT tiles the first max_short (in
+// tile order) go to short_list; the others stay the wavefront's (the hard list's cap). counts[0] = active tiles, [1] =
+// sure-sky tiles, [2] = the pixels of the sure-sky tiles that lie inside the image, [3] = short tiles taken, [4] = their pixels inside the
+// image, [5] = short tiles found.
+__global__ __launch_bounds__(BLOCK) void k_sky_scan(const uint8_t* flags, uint32_t n_tiles, uint32_t width, uint32_t height, uint32_t max_short, uint32_t* tile_map,
+                                                     uint32_t* sky_list, uint32_t* short_list, uint32_t* counts) {
+    __shared__ uint32_t s_sky[BLOCK], s_short[BLOCK], s_pixels, s_short_pixels;
     const uint32_t tiles_x = (width + 7u) / 8u;
     const uint32_t per = (n_tiles + BLOCK - 1) / BLOCK, t0 = threadIdx.x * per, t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
-    uint32_t mine = 0, pixels = 0;
-    if (threadIdx.x == 0) s_pixels = 0;
-    for (uint32_t t = t0; t < t1; ++t) {
-        if (!flags[t]) continue;
+    uint32_t mine = 0, mine_short = 0, pixels = 0;
+    if (threadIdx.x == 0) s_pixels = s_short_pixels = 0;
+    auto tile_pixels = [&](uint32_t t) {
         uint32_t ty, tx;
         divmod_u31(t, tiles_x, ty, tx);
         const uint32_t w = width - tx * 8u < 8u ? width - tx * 8u : 8u, h = height - ty * 8u < 8u ? height - ty * 8u : 8u;
-        ++mine;
-        pixels += w * h;
+        return w * h;
+    };
+    for (uint32_t t = t0; t < t1; ++t) {
+        if (flags[t] == SKY_TILE_SKY) {
+            ++mine;
+            pixels += tile_pixels(t);
+        } else if (flags[t] == SKY_TILE_SHORT) {
+            ++mine_short;
+        }
     }
     s_sky[threadIdx.x] = mine;
+    s_short[threadIdx.x] = mine_short;
     __syncthreads();
     if (pixels) atomicAdd(&s_pixels, pixels);
-    for (uint32_t d = 1; d < BLOCK; d <<= 1) {   // inclusive scan of the threads' sky counts
-        const uint32_t v = threadIdx.x >= d ? s_sky[threadIdx.x - d] : 0u;
+    for (uint32_t d = 1; d < BLOCK; d <<= 1) {   // inclusive scans of the threads' sky and short counts
+        const uint32_t v = threadIdx.x >= d ? s_sky[threadIdx.x - d] : 0u, u = threadIdx.x >= d ? s_short[threadIdx.x - d] : 0u;
         __syncthreads();
         s_sky[threadIdx.x] += v;
+        s_short[threadIdx.x] += u;
         __syncthreads();
     }
-    uint32_t sky_at = s_sky[threadIdx.x] - mine, act_at = (t0 < n_tiles ? t0 : n_tiles) - sky_at;
+    uint32_t sky_at = s_sky[threadIdx.x] - mine, short_at = s_short[threadIdx.x] - mine_short;
+    uint32_t act_at = (t0 < n_tiles ? t0 : n_tiles) - sky_at - (short_at < max_short ? short_at : max_short);
+    uint32_t short_pixels = 0;
     for (uint32_t t = t0; t < t1; ++t) {
-        if (flags[t]) sky_list[sky_at++] = t;
-        else tile_map[act_at++] = t;
+        if (flags[t] == SKY_TILE_SKY) {
+            sky_list[sky_at++] = t;
+        } else if (flags[t] == SKY_TILE_SHORT && short_at++ < max_short) {
+            short_list[short_at - 1u] = t;
+            short_pixels += tile_pixels(t);
+        } else {
+            tile_map[act_at++] = t;
+        }
     }
+    if (short_pixels) atomicAdd(&s_short_pixels, short_pixels);
+    __syncthreads();
     if (threadIdx.x == BLOCK - 1) {
-        counts[0] = n_tiles - s_sky[BLOCK - 1];
+        const uint32_t n_short = s_short[BLOCK - 1], taken = n_short < max_short ? n_short : max_short;
+        counts[0] = n_tiles - s_sky[BLOCK - 1] - taken;
         counts[1] = s_sky[BLOCK - 1];
-        counts[2] = s_pixels;   // (every thread's addition lies before one of the scan's barriers)
+        counts[2] = s_pixels;
+        counts[3] = taken;
+        counts[4] = s_short_pixels;
+        counts[5] = n_short;
     }
 }
 
@@ -98,10 +124,10 @@ __global__ __launch_bounds__(BLOCK) void k_sky(SceneD sc, CamD cam, PoolD pool, 
     }
 }
 
-void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, uint32_t n_tiles, uint8_t* flags, uint32_t* tile_map, uint32_t* sky_list,
-                         uint32_t* counts, hipStream_t st) {
-    hipLaunchKernelGGL(k_sky_classify, dim3((n_tiles + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, cam, n_boxes, boxes6, (cam.width + 7u) / 8u, n_tiles, flags);
-    hipLaunchKernelGGL(k_sky_scan, dim3(1), dim3(BLOCK), 0, st, flags, n_tiles, cam.width, cam.height, tile_map, sky_list, counts);
+void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, uint32_t max_short, uint32_t n_tiles, uint8_t* flags,
+                         uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, hipStream_t st) {
+    hipLaunchKernelGGL(k_sky_classify, dim3((n_tiles + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, cam, n_boxes, boxes6, shadeable, (cam.width + 7u) / 8u, n_tiles, flags);
+    hipLaunchKernelGGL(k_sky_scan, dim3(1), dim3(BLOCK), 0, st, flags, n_tiles, cam.width, cam.height, max_short, tile_map, sky_list, short_list, counts);
 }
 void launch_sky(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, const uint32_t* sky_list, uint32_t n_sky, uint32_t chunk,
                 hipStream_t st) {

@@ -63,9 +63,15 @@ void launch_detile(const PoolD& pool, double* accum, int max_blocks, hipStream_t
 // tile_map (active-tile index -> tile), sky_list (the sure-sky tiles), both in tile order, and counts = {active tiles, sure-sky tiles, pixels of
 // the sure-sky tiles inside the image}; flags: n_tiles bytes of scratch. launch_sky: samples [spp_begin, spp_end) of every pixel of the listed
 // tiles, `chunk` samples per wave, added to the tiled accumulator and to the sample and segment counts.
+// The short-path pass: `shadeable` = the boxes (bit b = box b) of the entries k_short can shade, 0 = none: only sure-sky and
+// wavefront tiles come out. Of the SHORT tiles — every box not cleared is shadeable — the first max_short in tile order go to short_list, the
+// rest stay in tile_map; counts[3..5] = short tiles taken, their pixels inside the image, short tiles found. launch_short (pt_k_short.hip):
+// samples [spp_begin, spp_end) of every pixel of the short tiles, finished where the path is camera -> (miss | shadeable hit -> miss), else
+// appended to the hard list (pt_types.h ShortArgsD).
 struct SkyCam;
-void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, uint32_t n_tiles, uint8_t* flags, uint32_t* tile_map, uint32_t* sky_list,
-                         uint32_t* counts, hipStream_t st);
+void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, uint32_t max_short, uint32_t n_tiles, uint8_t* flags,
+                         uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, hipStream_t st);
+void launch_short(const SceneD& sc, const CamD& cam, const PoolD& pool, uint64_t seed, const ShortArgsD& a, hipStream_t st);
 void launch_sky(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, const uint32_t* sky_list, uint32_t n_sky, uint32_t chunk,
                 hipStream_t st);
 // pt_adaptive.hip: the adaptive render's per-round kernels (see there)

@@ -135,8 +135,16 @@ std::vector<double> sky_boxes(uint32_t n_boxes, const double* boxes6) {
     return u;
 }
 }  // namespace
+static int tiles_of(const char* who, const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, bool classes, uint8_t* out_tiles);
 extern "C" int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, uint8_t* out_tiles) {
-    if (!cam || !out_tiles || (n_boxes && !boxes6)) return set_error("pt_sky_tiles: bad arguments");
+    return tiles_of("pt_sky_tiles", cam, n_boxes, boxes6, nullptr, false, out_tiles);
+}
+extern "C" int pt_short_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, uint8_t* out_tiles) {
+    return tiles_of("pt_short_tiles", cam, n_boxes, boxes6, shadeable, true, out_tiles);
+}
+// classes: the three kinds of tile (sky_tile_class), with the shadeable boxes flagged; else 1 = sure sky, 0 = not (sky_tile_is_clear)
+static int tiles_of(const char* who, const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, bool classes, uint8_t* out_tiles) {
+    if (!cam || !out_tiles || (n_boxes && !boxes6)) return set_error(std::string(who) + ": bad arguments");
     CamDerived d;
     if (derive_camera(cam, d) != 0) return -1;
     const double lens_radius = std::tan((cam->defocus_angle / 2.0) * (PI / 180.0)) * cam->focal_length;   // (make_camd's)
@@ -147,9 +155,13 @@ extern "C" int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double
     const std::vector<double> boxes = sky_boxes(n_boxes, boxes6);
     const uint32_t nb = (uint32_t)(boxes.size() / 6);
     c.extent = sky_extent(c, nb, boxes.data());
+    unsigned long long mask = 0ull;   // (more boxes than the cap are their union: nothing is shadeable)
+    for (uint32_t b = 0; shadeable && nb == n_boxes && b < nb; ++b)
+        if (shadeable[b]) mask |= 1ull << b;
     const uint32_t tiles_x = (c.width + 7) / 8, tiles_y = (c.height + 7) / 8;
     for (uint32_t ty = 0; ty < tiles_y; ++ty)
-        for (uint32_t tx = 0; tx < tiles_x; ++tx) out_tiles[(size_t)ty * tiles_x + tx] = sky_tile_is_clear(c, ty, tx, nb, boxes.data()) ? 1 : 0;
+        for (uint32_t tx = 0; tx < tiles_x; ++tx)
+            out_tiles[(size_t)ty * tiles_x + tx] = classes ? sky_tile_class(c, ty, tx, nb, boxes.data(), mask) : sky_tile_is_clear(c, ty, tx, nb, boxes.data()) ? 1 : 0;
     return 0;
 }
 
@@ -161,8 +173,8 @@ struct EventTimer {   // per-launch HIP-event timing, drained at the polling syn
     };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_list;
-    double ms[4] = {0, 0, 0, 0};   // K2, K3, the small kernels, k_sky
-    uint64_t launches[4] = {0, 0, 0, 0};
+    double ms[5] = {0, 0, 0, 0, 0};   // K2, K3, the small kernels, k_sky, k_short
+    uint64_t launches[5] = {0, 0, 0, 0, 0};
     bool enabled = false;
     hipEvent_t get() {
         if (!free_list.empty()) {
@@ -372,6 +384,16 @@ struct Job {
     uint32_t n_active_tiles = 0, n_sky_tiles = 0, n_sky_pixels = 0, sky_chunk = 0;
     const uint32_t* sky_list = nullptr;
     const uint32_t* tile_map = nullptr;   // where classify_sky wrote the map: tiled_accum checks that the kernels will look there
+    // the short-path pass (classify_sky, run_short): the short tiles taken, their pixels inside the image, their list on the
+    // device, the hard samples the pass left to the wavefront, the samples it finished and their segments
+    uint32_t n_short_tiles = 0, n_short_pixels = 0;
+    const uint32_t* short_list = nullptr;
+    uint64_t n_hard = 0, short_samples = 0, short_segments = 0;
+    uint32_t short_chunk = 0, short_sample_bits = 0;
+    bool short_wide = false;
+    const uint32_t* shade_prims = nullptr;
+    unsigned long long* short_words = nullptr;   // k_short's three device words (ShortArgsD::n_hard)
+    ShortHdrD short_hdr;   // the record behind the tile map (run_short)
     ShadeForm form;   // the form of K1 / K3 this render launches (render_core; classify_sky and choose_kernels both read this one)
 };
 
@@ -385,7 +407,8 @@ struct Switches {
                               // -1.6 % on scene 6's 33.6 M-slot pool, +2.5 % on scene 5's 16.8 M; 42 = per launch, 32 while the pool holds >= 16 such
                               // windows per block launched, else 22)
     bool pool_in_place = false, no_defer_regen = false, no_compact_records = false, init_shuffle = false, accum_linear = false, no_compact_pool = false,
-         prof = false, no_sky_pass = false;   // no_sky_pass: PT_SKY_PASS=0
+         prof = false, no_sky_pass = false, no_short_pass = false;   // no_sky_pass: PT_SKY_PASS=0; no_short_pass: PT_SHORT_PASS=0
+    uint64_t short_cap_bytes = 0;   // PT_SHORT_CAP_BYTES: the hard list's byte cap in place of the pool's bytes (0: not set)
     int grid_mult = 1;   // persistent grids: resident blocks per CU x CUs x this
     uint32_t wide_window_min = 16;
     int ext2 = 0;        // PT_EXT2 = stack*10 + blocks per CU picks the two-phase K2's instantiation (0: not set)
@@ -417,14 +440,18 @@ Switches read_switches(const pt_render_opts& opts) {
     if (const char* e = exp_env("PT_POLL_CAP")) sw.poll_cap = (uint32_t)std::max(1, atoi(e));
     sw.prof = exp_env("PT_PROF") != nullptr;
     if (const char* e = exp_env("PT_SKY_PASS")) sw.no_sky_pass = atoi(e) == 0;
+    if (const char* e = exp_env("PT_SHORT_PASS")) sw.no_short_pass = atoi(e) == 0;
+    if (const char* e = exp_env("PT_SHORT_CAP_BYTES")) sw.short_cap_bytes = strtoull(e, nullptr, 10);
     return sw;
 }
 
 // The bytes of the tiled frame accumulator (tiled_accum, below): three channel planes, and behind them the sky pass's tile map, one word per
 // tile (pt_k_common.h pool_tile_map).
 // tile_map_behind: where that map lies for an accumulator at `accum` — the one host statement of what pool_tile_map computes on the device.
-size_t tiled_accum_bytes(size_t n_tile_pixels) { return n_tile_pixels * 3 * sizeof(double) + n_tile_pixels / 64 * sizeof(uint32_t); }
+// ... and behind the map, at the next 8-byte boundary, the short-path pass's record of its hard list (ShortHdrD; pt_k_common.h pool_short_hdr)
+size_t tiled_accum_bytes(size_t n_tile_pixels) { return n_tile_pixels * 3 * sizeof(double) + ((n_tile_pixels / 64 + 1) & ~(size_t)1) * sizeof(uint32_t) + sizeof(ShortHdrD); }
 uint32_t* tile_map_behind(double* accum, size_t n_tile_pixels) { return reinterpret_cast<uint32_t*>(accum + 3 * n_tile_pixels); }
+ShortHdrD* short_hdr_behind(double* accum, size_t n_tile_pixels) { return reinterpret_cast<ShortHdrD*>(tile_map_behind(accum, n_tile_pixels) + ((n_tile_pixels / 64 + 1) & ~(size_t)1)); }
 
 // The sky pass, per render: the tiles whose camera rays provably enter no box of the world are classified on the device
 // (pt_sky_tiles.h; one thread per tile, then a one-block scan), the host reads the three counts back — the one small synchronisation — and
@@ -432,6 +459,7 @@ uint32_t* tile_map_behind(double* accum, size_t n_tile_pixels) { return reinterp
 // renders the sure-sky ones (run_wavefront). The pass is ON only for what k_sky's one form reproduces: the dynamic mode's whole-frame
 // render in the plain mode with the independent sampler under the perspective projection, nothing moving, no camera medium. Everywhere
 // else this step does nothing, and every kernel argument is what it was without it.
+uint64_t pool_bytes_for_cap(const Switches& sw, const Job& job, int n_cus);   // (below, after plan_pool)
 int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     const CamD& dc = job.dc;
     const uint64_t n_tiles64 = (uint64_t)((dc.width + 7) / 8) * ((dc.height + 7) / 8);
@@ -448,40 +476,141 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     const uint32_t n_boxes = (uint32_t)(boxes.size() / 6);
     SkyCam cam = sky_camera(dc.center, dc.forward, dc.pixel00, dc.pixel_du, dc.pixel_dv, dc.dof_right, dc.dof_up, dc.blur_strength, dc.width, dc.height);
     cam.extent = sky_extent(cam, n_boxes, boxes.data());
-    // sky_mem: the counts (64 B), the boxes, the sure-sky tile list, the tiles' flags; the tile map lies behind the tiled accumulator's planes
-    const size_t box_bytes = (size_t)SKY_MAX_BOXES * 6 * sizeof(double);
-    if (!s->sky_mem.reserve(64 + box_bytes + (size_t)n_tiles * (sizeof(uint32_t) + 1), "hipMalloc(sky pass)")) return -1;
+    // The short-path pass is on where the sky pass is, and only when K2 walks the top level flat (k_short calls that walk), the
+    // scene has no lights list (the selector draw then only moves the counter), some entry is shadeable (pt_scene.cpp; every entry has its own
+    // box here: more than SKY_MAX_BOXES would be walked as their union) and a path may have two segments.
+    unsigned long long shadeable = 0ull;
+    const bool short_on = !sw.no_short_pass && s->dev.view.tlas_flat != 0u && s->dev.view.n_lights == 0u && !s->shade_prims.empty() && dc.max_depth >= 2u &&
+                          s->entry_shadeable.size() == (size_t)n_boxes && s->entry_boxes.size() / 6 == (size_t)n_boxes;
+    if (short_on)
+        for (uint32_t i = 0; i < n_boxes; ++i)
+            if (s->entry_shadeable[i]) shadeable |= 1ull << i;
+    // sky_mem: the counts and k_short's three words (64 B), the boxes, the sure-sky tile list, the short tile list, the shadeable primitives'
+    // ids, the tiles' flags; the tile map lies behind the tiled accumulator's planes
+    const size_t box_bytes = (size_t)SKY_MAX_BOXES * 6 * sizeof(double), prim_bytes = (size_t)SKY_MAX_BOXES * sizeof(uint32_t);
+    if (!s->sky_mem.reserve(64 + box_bytes + prim_bytes + (size_t)n_tiles * (2 * sizeof(uint32_t) + 1), "hipMalloc(sky pass)")) return -1;
     if (!s->tile_accum.reserve(tiled_accum_bytes((size_t)n_tiles * 64), "hipMalloc(tiled accumulator)")) return -1;
     char* m = s->sky_mem.as<char>();
     uint32_t* d_counts = (uint32_t*)m;
     double* d_boxes = (double*)(m + 64);
-    uint32_t* d_sky_list = (uint32_t*)(m + 64 + box_bytes);
-    uint8_t* d_flags = (uint8_t*)(d_sky_list + n_tiles);
+    uint32_t* d_prims = (uint32_t*)(m + 64 + box_bytes);
+    uint32_t* d_sky_list = (uint32_t*)(m + 64 + box_bytes + prim_bytes);
+    uint32_t* d_short_list = d_sky_list + n_tiles;
+    uint8_t* d_flags = (uint8_t*)(d_short_list + n_tiles);
     uint32_t* d_tile_map = tile_map_behind(s->tile_accum.as<double>(), (size_t)n_tiles * 64);
-    uint32_t counts[3] = {0, 0, 0};
+    uint32_t counts[6] = {0, 0, 0, 0, 0, 0};
     // (`boxes` and `counts` are this function's: both copies are done at its synchronise, below)
     if (n_boxes && !hip_ok(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice, job.st), "hipMemcpy(sky boxes)")) return -1;
-    timer.begin(2, job.st);
-    launch_sky_classify(cam, n_boxes, d_boxes, n_tiles, d_flags, d_tile_map, d_sky_list, d_counts, job.st);
-    timer.end(job.st);
-    if (!hip_ok(hipGetLastError(), "sky classification") ||
-        !hip_ok(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, job.st), "hipMemcpy(sky counts)") ||
-        !hip_ok(hipStreamSynchronize(job.st), "hipStreamSynchronize(sky classification)"))
-        return -1;
-    timer.drain();
-    if ((uint64_t)counts[0] + counts[1] != n_tiles) return set_error("pt_render: the sky pass's tile counts do not add up (internal error)");
-    if (counts[1] == 0) return 0;   // no sure-sky tile: the render is the wavefront's, its kernel arguments what they are without the pass
+    if (short_on && !hip_ok(hipMemcpyAsync(d_prims, s->shade_prims.data(), s->shade_prims.size() * sizeof(uint32_t), hipMemcpyHostToDevice, job.st), "hipMemcpy(shadeable ids)")) return -1;
+    auto classify = [&](uint32_t max_short) -> int {
+        timer.begin(2, job.st);
+        launch_sky_classify(cam, n_boxes, d_boxes, shadeable, max_short, n_tiles, d_flags, d_tile_map, d_sky_list, d_short_list, d_counts, job.st);
+        timer.end(job.st);
+        if (!hip_ok(hipGetLastError(), "sky classification") ||
+            !hip_ok(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, job.st), "hipMemcpy(sky counts)") ||
+            !hip_ok(hipStreamSynchronize(job.st), "hipStreamSynchronize(sky classification)"))
+            return -1;
+        timer.drain();
+        if ((uint64_t)counts[0] + counts[1] + counts[3] != n_tiles) return set_error("pt_render: the sky pass's tile counts do not add up (internal error)");
+        return 0;
+    };
+    if (classify(0xFFFFFFFFu) != 0) return -1;
+    if (counts[3] != 0) {
+        // The hard list holds, at worst, every sample of the tiles taken; its bytes are capped at the pool's (or PT_SHORT_CAP_BYTES). Where the cap
+        // binds the pass takes the first max_short short tiles in tile order and the rest stay the wavefront's: the classification runs once more
+        // with that bound. One tile at least stays the wavefront's, whose forms read the hard list only when PoolD::n_work_pixels is not 0.
+        job.short_sample_bits = 1u;
+        while ((1ull << job.short_sample_bits) < (uint64_t)job.spp) ++job.short_sample_bits;
+        uint32_t ord_bits = 1u;
+        while ((1ull << ord_bits) < (uint64_t)counts[5]) ++ord_bits;
+        job.short_wide = ord_bits + 6u + job.short_sample_bits > 32u;
+        const uint64_t entry_bytes = job.short_wide ? 8 : 4, cap_bytes = sw.short_cap_bytes ? sw.short_cap_bytes : pool_bytes_for_cap(sw, job, s->ctx->n_cus);
+        uint64_t max_short = cap_bytes / entry_bytes / ((uint64_t)64 * job.spp);
+        if (counts[0] == 0 && max_short >= counts[5]) max_short = counts[5] - 1u;
+        if (max_short < counts[3] && classify((uint32_t)max_short) != 0) return -1;
+    }
+    if (counts[1] == 0 && counts[3] == 0) return 0;   // neither a sure-sky nor a short tile: the render is the wavefront's, its kernel arguments what they are without the passes
     job.sky = true;
     job.tile_map = d_tile_map;
     job.n_active_tiles = counts[0];
     job.n_sky_tiles = counts[1];
     job.n_sky_pixels = counts[2];
     job.sky_list = d_sky_list;
+    job.n_short_tiles = counts[3];
+    job.n_short_pixels = counts[4];
+    job.short_list = d_short_list;
+    job.shade_prims = d_prims;
+    job.short_words = (unsigned long long*)(m + 32);
     // one wave renders `chunk` samples of a tile: enough waves to fill the machine four times over, at least 32 samples each
-    const uint64_t target = (uint64_t)std::max(1, s->ctx->n_cus) * 4 * 8 * 4, per_tile = std::max<uint64_t>(1, target / std::max(1u, counts[1]));
-    job.sky_chunk = (uint32_t)std::max<uint64_t>(32, (job.spp + per_tile - 1) / per_tile);
-    while ((uint64_t)counts[1] * ((job.spp + job.sky_chunk - 1) / job.sky_chunk) > 0x7FFFFFFFull) job.sky_chunk *= 2;   // (k_sky's wave index)
+    const uint64_t target = (uint64_t)std::max(1, s->ctx->n_cus) * 4 * 8 * 4;
+    auto chunk_for = [&](uint32_t n_tiles_of) {
+        const uint64_t per_tile = std::max<uint64_t>(1, target / std::max(1u, n_tiles_of));
+        uint32_t chunk = (uint32_t)std::max<uint64_t>(32, (job.spp + per_tile - 1) / per_tile);
+        while ((uint64_t)n_tiles_of * ((job.spp + chunk - 1) / chunk) > 0x7FFFFFFFull) chunk *= 2;   // (the kernels' wave index)
+        return chunk;
+    };
+    job.sky_chunk = chunk_for(counts[1]);
+    job.short_chunk = chunk_for(counts[3]);
     return 0;
+}
+
+// The short-path pass itself, between the classification and the pool's plan: k_short renders the short tiles' samples into
+// the tiled accumulator — cleared here, not by tiled_accum — and appends the hard ones to the scene's list; the host reads back their number
+// and the pass's sample and segment counts (one more small synchronisation ahead of k_init) and writes the record K1 / K3 find the list by.
+int run_short(pt_scene* s, Job& job, EventTimer& timer) {
+    if (!job.sky) return 0;
+    const size_t n_tile_pixels = (size_t)((job.dc.width + 7) / 8) * ((job.dc.height + 7) / 8) * 64;
+    double* planes = s->tile_accum.as<double>();
+    ShortHdrD& hdr = job.short_hdr;   // (the job's: the copy below is asynchronous)
+    memset(&hdr, 0, sizeof hdr);
+    if (job.n_short_tiles != 0) {
+        const uint64_t cap = (uint64_t)job.n_short_pixels * job.spp;   // every sample of the tiles taken (their pixels inside the image)
+        if (!s->short_mem.reserve((size_t)cap * (job.short_wide ? 8 : 4), "hipMalloc(hard list)")) return -1;
+        if (!hip_ok(hipMemsetAsync(planes, 0, n_tile_pixels * 3 * sizeof(double), job.st), "hipMemset(tiled accumulator)")) return -1;
+        if (!hip_ok(hipMemsetAsync(job.short_words, 0, 3 * sizeof(unsigned long long), job.st), "hipMemset(short pass counts)")) return -1;
+        PoolD pool;   // what k_short reads of it: the frame, its tiling, the sample range, the tiled planes
+        memset(&pool, 0, sizeof pool);
+        pool.accum = planes;
+        pool.accum_tiled = 1u;
+        pool.width = job.dc.width;
+        pool.height = job.dc.height;
+        pool.tiles_x = (job.dc.width + 7) / 8;
+        pool.n_tile_pixels = (uint32_t)n_tile_pixels;
+        pool.spp_begin = job.spp_begin;
+        pool.spp_end = job.spp_end;
+        ShortArgsD a;
+        memset(&a, 0, sizeof a);
+        a.short_list = job.short_list;
+        a.n_short = job.n_short_tiles;
+        a.chunk = job.short_chunk;
+        a.n_chunks = (job.spp + job.short_chunk - 1) / job.short_chunk;
+        a.shade_prims = job.shade_prims;
+        a.n_shade = (uint32_t)s->shade_prims.size();
+        a.hard = s->short_mem.as<void>();
+        a.n_hard = job.short_words;
+        a.cap = cap;
+        a.wide = job.short_wide ? 1u : 0u;
+        a.sample_bits = job.short_sample_bits;
+        unsigned long long words[3] = {0, 0, 0};
+        timer.begin(4, job.st);
+        launch_short(s->dev.view, job.dc, pool, job.seed, a, job.st);
+        timer.end(job.st);
+        if (!hip_ok(hipGetLastError(), "short-path pass") ||
+            !hip_ok(hipMemcpyAsync(words, job.short_words, sizeof words, hipMemcpyDeviceToHost, job.st), "hipMemcpy(short pass counts)") ||
+            !hip_ok(hipStreamSynchronize(job.st), "hipStreamSynchronize(short-path pass)"))
+            return -1;
+        timer.drain();
+        if (words[0] > cap || words[0] + words[1] != cap) return set_error("pt_render: the short-path pass's sample counts do not add up (internal error)");
+        job.n_hard = words[0];
+        job.short_samples = words[1];
+        job.short_segments = words[2];
+        hdr.hard = s->short_mem.as<void>();
+        hdr.short_list = job.short_list;
+        hdr.wide = a.wide;
+        hdr.sample_bits = a.sample_bits;
+        hdr.n_hard = job.n_hard;
+    }
+    return hip_ok(hipMemcpyAsync(short_hdr_behind(planes, n_tile_pixels), &hdr, sizeof hdr, hipMemcpyHostToDevice, job.st), "hipMemcpy(hard list record)") ? 0 : -1;
 }
 
 // Pool sizing (arithmetic only). slots_per_pixel = 0 (default): DYNAMIC work assignment — a fixed pool that fills
@@ -505,6 +634,7 @@ int plan_pool(const Switches& sw, const Job& job, int n_cus, PoolPlan& p) {
     p.n_tile_pixels = (uint32_t)n_tile_pixels64;
     // (the sky pass: the work items cover the active tiles only)
     p.total_work = p.dynamic ? (job.list ? (uint64_t)job.n_list : job.sky ? (uint64_t)job.n_active_tiles * 64 : n_tile_pixels64) * job.spp : (uint64_t)job.n_items * job.spp;
+    if (p.dynamic && job.sky) p.total_work += job.n_hard;   // (the short-path pass's hard samples, behind the tile items)
     uint64_t n_slots64;
     if (p.dynamic) {
         // Resident paths: enough that per-launch fixed costs and kernel tails amortise (16.8M slots are 9% faster than
@@ -543,6 +673,16 @@ int plan_pool(const Switches& sw, const Job& job, int n_cus, PoolPlan& p) {
     p.k = k;
     p.n_slots = (uint32_t)n_slots64;
     return 0;
+}
+
+// The bytes the hard list of the short-path pass is capped at: the pool's records and state words for the whole frame's plan
+uint64_t pool_bytes_for_cap(const Switches& sw, const Job& job, int n_cus) {
+    PoolPlan p;
+    Job whole = job;
+    whole.sky = false;
+    if (plan_pool(sw, whole, n_cus, p) != 0) return 0;
+    const uint64_t n_al = ((uint64_t)p.n_slots + 8191) & ~(uint64_t)8191;
+    return n_al * (sizeof(RayRec) + sizeof(PathRec) + 2 * sizeof(uint32_t));
 }
 
 // The kernels of a render: the form of k_init / k_shade that exists for it, K2's variant, the persistent grids.
@@ -669,7 +809,8 @@ double* device_accum(const Job& job, double* accum, DevMem& own) {
 int tiled_accum(pt_scene* s, const Job& job, PoolD& pool) {
     const size_t tb = (size_t)pool.n_tile_pixels * 3 * sizeof(double);
     if (!s->tile_accum.reserve(tiled_accum_bytes(pool.n_tile_pixels), "hipMalloc(tiled accumulator)")) return -1;
-    if (!hip_ok(hipMemsetAsync(s->tile_accum.as<double>(), 0, tb, job.st), "hipMemset(tiled accumulator)")) return -1;
+    // (the short-path pass has cleared the planes ahead of its kernel, whose sums they hold by now: run_short)
+    if (job.n_short_tiles == 0 && !hip_ok(hipMemsetAsync(s->tile_accum.as<double>(), 0, tb, job.st), "hipMemset(tiled accumulator)")) return -1;
     pool.accum = s->tile_accum.as<double>();
     pool.accum_tiled = 1u;
     // the kernels find the map behind THIS accumulator's planes (pool_tile_map): the buffer classify_sky wrote into may not have moved
@@ -816,8 +957,8 @@ void print_prof(const CountersD* cnt) {
 
 void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kernels& kn, const PoolD& pool, const EventTimer& timer, const RunResult& r, pt_render_stats* stats) {
     memset(stats, 0, sizeof *stats);
-    stats->samples = s->h_counters->samples;
-    stats->segments = s->h_counters->segments;
+    stats->samples = s->h_counters->samples + job.short_samples;   // (k_short counts into words of its own: the counters start after it)
+    stats->segments = s->h_counters->segments + job.short_segments;
     stats->iterations = r.iterations;
     stats->n_slots = p.n_slots;
     stats->slots_per_pixel = p.dynamic ? 0u : p.k;
@@ -833,6 +974,10 @@ void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kern
     stats->blocks_shade = (uint32_t)kn.grid_shade;
     stats->compactions = r.compactions;
     stats->n_alloc_end = pool.n_alloc;
+    stats->short_tiles = job.n_short_tiles;
+    stats->short_samples = job.short_samples;
+    stats->hard_samples = job.n_hard;
+    stats->ms_short = timer.ms[4];
     stats->sky_tiles = job.sky ? job.n_sky_tiles : 0u;
     stats->sky_samples = job.sky ? (uint64_t)job.n_sky_pixels * job.spp : 0u;
     stats->ms_sky = timer.ms[3];
@@ -855,6 +1000,10 @@ void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
     sum.blocks_shade = ps.blocks_shade;
     sum.compactions += ps.compactions;
     sum.n_alloc_end = ps.n_alloc_end;
+    sum.short_tiles = std::max(sum.short_tiles, ps.short_tiles);
+    sum.short_samples += ps.short_samples;
+    sum.hard_samples += ps.hard_samples;
+    sum.ms_short += ps.ms_short;
     sum.sky_tiles = std::max(sum.sky_tiles, ps.sky_tiles);
     sum.sky_samples += ps.sky_samples;
     sum.ms_sky += ps.ms_sky;
@@ -890,6 +1039,7 @@ int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_b
     EventTimer timer;
     timer.enabled = job.opts.profile != 0;
     if (classify_sky(s, sw, job, timer) != 0) return -1;
+    if (run_short(s, job, timer) != 0) return -1;
     PoolPlan plan;
     if (plan_pool(sw, job, s->ctx->n_cus, plan) != 0) return -1;
     const Kernels kn = choose_kernels(sw, s, job, plan);

@@ -1225,6 +1225,23 @@ int pt::scene_build(pt_scene* s) {
         s->world_has_dispersion = s->world_has_dispersion || (kind == MAT_GLASS && s->mats[pr.mat].p[3] != 0.0);   // a dispersive glass
         pr.kind |= (kind == MAT_MEDIUM ? MEDIUM_SORT_KIND : kind) << PRIM_MAT_KIND_SHIFT;
     }
+    // the short-path pass's shadeable entries (pt_k_short.hip shades them itself): a world-level sphere or quad, no instance
+    // chain, still, a diffuse material without a normal map (fetch_tex looks up whatever colour texture it has)
+    s->entry_shadeable.assign(entries.size(), 0);
+    s->shade_prims.clear();
+    for (size_t i = 0; i < entries.size(); ++i) {
+        const Entry& e = entries[i];
+        if ((e.kind != ENTRY_SPHERE && e.kind != ENTRY_QUAD) || e.inst >= 0 || e.n_prims != 1u) continue;
+        const PrimRef& pr = prims[e.first_prim];
+        const MatD& m = s->mats[pr.mat];
+        if (pr.inst >= 0 || m.kind != MAT_DIFFUSE || m.nmap_tex >= 0) continue;
+        if ((pr.kind & 0xFFu) == PRIM_SPHERE) {
+            const SphereD& sp = spheres[pr.index];
+            if (!(sp.p1[0] == sp.p2[0] && sp.p1[1] == sp.p2[1] && sp.p1[2] == sp.p2[2])) continue;
+        } else if ((pr.kind & 0xFFu) != PRIM_QUAD) continue;
+        s->entry_shadeable[i] = 1;
+        s->shade_prims.push_back(e.first_prim);
+    }
     std::vector<Box> entry_boxes(tlas_items.size());
     for (const BuildItem& it : tlas_items) entry_boxes[it.ref_payload] = it.box;
     s->entry_boxes.clear();   // pt_world_entry_box: the f64 boxes, before the f32 rounding

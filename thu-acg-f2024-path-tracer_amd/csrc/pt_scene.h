@@ -84,6 +84,10 @@ struct pt_scene {
     bool has_moving_instance = false;
     double shutter_open = 0.0, shutter_close = 1.0;
     std::vector<double> entry_boxes;
+    // the short-path pass: one flag per entry of the last build — the entry is SHADEABLE: a world-level sphere or quad without
+    // an instance chain that does not move, its material diffuse without a normal map — and the global primitive ids of the flagged entries
+    std::vector<uint8_t> entry_shadeable;
+    std::vector<uint32_t> shade_prims;
     bool motion_on() const {       // "in effect": the kernels' MOT forms run
         return has_moving_instance || ((shutter_open != 0.0 || shutter_close != 1.0) && !motionless);
     }
@@ -99,6 +103,7 @@ struct pt_scene {
     pt::GrowBuf compact_scratch;   // the end-of-frame compaction's hole / mover lists + counters (pt_render.cpp)
     pt::GrowBuf pixel_list;        // pt_render_pixels: the device pixel list (tiled order)
     pt::GrowBuf sky_mem;           // the sky pass: counts, boxes, tile flags, the sure-sky tile list (pt_render.cpp classify_sky; the tile map is in tile_accum)
+    pt::GrowBuf short_mem;         // the short-path pass's hard list (pt_render.cpp run_short; its tile list and the shadeable ids are in sky_mem)
     // environment importance sampling (pt_scene_set_env_sampling): the mixture weight, and the f64 tables of ONE
     // environment texture, built at the first render or probe that needs them (pt_render.cpp env_tables) and kept until destroy
     double env_f = 0.0;

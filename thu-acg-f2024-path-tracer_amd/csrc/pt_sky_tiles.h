@@ -1,6 +1,8 @@
 // The sure-sky tile test: can ANY camera ray of an 8x8 pixel tile enter one of the world's boxes? A tile for which the
 // answer is a proven "no" is rendered by k_sky (pt_k_sky.hip) without ever entering the path pool; every other tile takes the wavefront.
 // One function, compiled for the host (pt_sky_tiles, the CPU tests) and for the device (k_sky_classify), plain f64 + - * and comparisons.
+// The same plane tests, read per box, also find the SHORT tiles of the short-path pass (sky_tile_class below): tiles whose
+// camera rays can enter only boxes of entries that pass shades itself.
 //
 // The ray set of a tile (generate_ray, pt_dev_geom.h, perspective projection). With R = dof_right, U = dof_up (the basis times the lens radius):
 //   origins   o = center + R px + U py,  px^2 + py^2 <= 1                                     (the lens disk; `center` itself when R = U = 0)
@@ -73,12 +75,13 @@ PT_SKY_HD double sky_extent(const SkyCam& c, uint32_t n_boxes, const double* box
     return e;
 }
 
-// true: no ray generate_ray can produce for any pixel of tile (ty, tx), any sample, enters any of the boxes. See the proof above.
-PT_SKY_HD bool sky_tile_is_clear(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6) {
-    if (n_boxes == 0u) return true;
-    if (n_boxes > SKY_MAX_BOXES) return false;
+// The boxes the tile test could NOT clear for tile (ty, tx), bit b = box b: some ray generate_ray can produce for a pixel of the tile, some
+// sample, may enter box b; every box whose bit is 0 is entered by none (the proof above). All ones where nothing can be said.
+PT_SKY_HD unsigned long long sky_tile_uncleared(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6) {
+    if (n_boxes == 0u) return 0ull;
+    if (n_boxes > SKY_MAX_BOXES) return ~0ull;
     const uint32_t r0 = ty * 8u, c0 = tx * 8u;
-    if (r0 >= c.height || c0 >= c.width) return false;
+    if (r0 >= c.height || c0 >= c.width) return ~0ull;
     const uint32_t r1 = r0 + 7u < c.height ? r0 + 7u : c.height - 1u, c1 = c0 + 7u < c.width ? c0 + 7u : c.width - 1u;
     const double g = sky_abs(c.blur_strength) + 0.5;
     const double fy[2] = {(double)r0 - g, (double)r1 + g}, fx[2] = {(double)c0 - g, (double)c1 + g};
@@ -133,7 +136,26 @@ PT_SKY_HD bool sky_tile_is_clear(const SkyCam& c, uint32_t ty, uint32_t tx, uint
             if (outside) todo &= ~(1ull << b);
         }
     }
-    return todo == 0ull;
+    return todo;
+}
+// true: no ray generate_ray can produce for any pixel of tile (ty, tx), any sample, enters any of the boxes.
+PT_SKY_HD bool sky_tile_is_clear(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6) {
+    return sky_tile_uncleared(c, ty, tx, n_boxes, boxes6) == 0ull;
+}
+// The three kinds of tile. SURE SKY: every box is cleared. SHORT: every box that is NOT cleared is flagged in `shadeable`
+// (bit b = box b: the box of an entry the short-path pass can shade, pt_scene.cpp) — a camera ray of the tile hits such an entry or nothing.
+// WAVEFRONT: everything else, and every tile about which nothing can be said (a tile outside the image, more boxes than the cap, a NaN or an
+// infinity among the boxes or in the camera: sky_extent is then not finite). Only where the pass pays depends on this; no result does.
+enum SkyTileClass : uint8_t { SKY_TILE_WAVEFRONT = 0, SKY_TILE_SKY = 1, SKY_TILE_SHORT = 2 };
+PT_SKY_HD uint8_t sky_tile_class(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable) {
+    if (n_boxes > SKY_MAX_BOXES || ty * 8u >= c.height || tx * 8u >= c.width) return SKY_TILE_WAVEFRONT;
+    const unsigned long long todo = sky_tile_uncleared(c, ty, tx, n_boxes, boxes6);
+    if (todo == 0ull) return SKY_TILE_SKY;
+    if (!(c.extent < 1.7976931348623157e308) || (todo & ~shadeable) != 0ull) return SKY_TILE_WAVEFRONT;
+    for (uint32_t b = 0; b < n_boxes; ++b)   // (a box with a NaN or an infinity is never cleared: flagged or not, it makes no tile short)
+        for (int i = 0; i < 6 && ((todo >> b) & 1ull); ++i)
+            if (!(boxes6[6 * (size_t)b + i] - boxes6[6 * (size_t)b + i] == 0.0)) return SKY_TILE_WAVEFRONT;
+    return SKY_TILE_SHORT;
 }
 
 }  // namespace pt

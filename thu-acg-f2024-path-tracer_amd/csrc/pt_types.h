@@ -379,6 +379,31 @@ struct PoolD {
 
 static_assert(sizeof(PoolD) == 216 && offsetof(PoolD, list) == 168 && offsetof(PoolD, n_work_pixels) == 164, "PoolD's layout is part of K2's code");
 
+// The short-path pass (pt_k_short.hip): the samples of its tiles it could not finish — the HARD samples — are work items of
+// the wavefront behind the tile items: item n_work_pixels x spp + i is entry i of the hard list. This record says where the list is; it lies
+// behind the sky pass's tile map (pt_k_common.h pool_short_hdr), so PoolD stays what it is. An entry packs (ordinal of the tile in the
+// short-tile list) << (6 + sample_bits) | (pixel in tile) << sample_bits | (sample - spp_begin), in 4 bytes where that fits (wide = 0) and
+// in 8 where it does not; the host decides per render. The host writes the record whenever the sky pass is on (n_hard = 0: no such items).
+struct ShortHdrD {
+    const void* hard;
+    const uint32_t* short_list;
+    uint32_t wide, sample_bits;
+    unsigned long long n_hard;
+};
+// k_short's own arguments: the short tiles (in tile order) and how their samples are cut into waves; the global ids of the shadeable
+// primitives; the hard list, its format (ShortHdrD), its capacity in entries and three device words: [0] counts what was appended, [1] the
+// samples the pass finished, [2] their segments (the render's counters are started after the pass: the host adds these to them).
+struct ShortArgsD {
+    const uint32_t* short_list;
+    uint32_t n_short, chunk, n_chunks;
+    const uint32_t* shade_prims;
+    uint32_t n_shade;
+    void* hard;
+    unsigned long long* n_hard;
+    unsigned long long cap;
+    uint32_t wide, sample_bits;
+};
+
 // The work counter of the dynamic mode is SHARDED: one word saturates at ~88 dequeues/us on this
 // chip (MI355X_MICROARCH.md, row "dequeue") and a frame needs one dequeue per wave per iteration
 // (65k per launch at 4M resident paths), which alone would cost ~0.75 ms per launch. Shard s hands
