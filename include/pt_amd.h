@@ -711,6 +711,67 @@ int pt_film_develop(pt_ctx*, uint32_t width, uint32_t height, const double* sums
 int pt_save_hdr(const char* path, uint32_t w, uint32_t h, const float* rgb);
 int pt_save_pfm(const char* path, uint32_t w, uint32_t h, const float* rgb);
 
+/* ---- the physical sky: Preetham daylight, a ground and a sun disc, baked into a float lat-long map (no counterpart in the reference) ----
+ * A stage of its own: it produces a W x H x 3 f32 map in the layout of an environment texture; the render kernels never see anything else.
+ * pt_tex_sky bakes and hands the map to pt_tex_image_rgbf32, so the handle it returns is usable as pt_camera.env_tex (env_is_map = 1), with
+ * pt_scene_set_env_sampling, the panorama projection and the film stage unchanged.
+ * The rule. f64, one IEEE rounding per written operation, no contraction; exp, sincos, acos, pow are pt_detmath.h's on host and device.
+ *  s = v' / |v'| with v' = sun_dir / (its largest |component|), |v'| = sqrt((x^2 + y^2) + z^2); T = turbidity; c_s = clamp(s.y, 0, 1),
+ *  theta_s = acos(c_s): a sun below the horizon is held at the horizon for the sky's formulas. dot(d, s) = (d.x s.x + d.y s.y) + d.z s.z.
+ *  Texel (i, j) (column, row; sample_environment's, PROJ_PANORAMA's and the environment sampler's geometry): centre theta = ((j + 0.5) pi) / H,
+ *  phi = -pi + ((2 pi) (i + 0.5)) / W, d = (sin theta cos phi, cos theta, sin theta sin phi);
+ *  solid angle w_ij = (cos((j pi) / H) - cos(((j + 1) pi) / H)) * ((2 pi) / W).
+ *  Sky, d.y > 0 (Preetham, Shirley, Smits 1999; directions are used as given, unit length is the caller's business):
+ *   c_g = clamp(dot(d, s), -1, 1), gamma = acos(c_g);
+ *   F(c_t, gamma, c_g; A..E) = (1 + A exp(B / c_t)) * ((1 + C exp(D gamma)) + E (c_g c_g));
+ *   A..E = a T + b with (a, b):
+ *     Y: (0.1787, -1.4630) (-0.3554, 0.4275) (-0.0227, 5.3251) (0.1206, -2.5771) (-0.0670, 0.3703)
+ *     x: (-0.0193, -0.2592) (-0.0665, 0.0008) (-0.0004, 0.2125) (-0.0641, -0.8989) (-0.0033, 0.0452)
+ *     y: (-0.0167, -0.2608) (-0.0950, 0.0092) (-0.0079, 0.2102) (-0.0441, -1.6537) (-0.0109, 0.0529)
+ *   zenith: chi = (4/9 - T/120) (pi - 2 theta_s); Yz = ((4.0453 T - 4.9710) (sin chi / cos chi) - 0.2155 T) + 2.4192;
+ *     xz = ((T T) p_0 + T p_1) + p_2 with p_r = ((M_r0 theta_s^3 + M_r1 theta_s^2) + M_r2 theta_s) + M_r3, theta_s^2 = theta_s theta_s,
+ *     theta_s^3 = theta_s^2 theta_s, Mx = (0.00166, -0.00375, 0.00209, 0; -0.02903, 0.06377, -0.03202, 0.00394; 0.11693, -0.21196, 0.06052, 0.25886);
+ *     yz likewise with My = (0.00275, -0.00610, 0.00317, 0; -0.04214, 0.08970, -0.04153, 0.00516; 0.15346, -0.26756, 0.06670, 0.26688);
+ *   q = (qz F(d.y, gamma, c_g)) / F(1, theta_s, c_s) for q in Y, x, y (the zenith values and the denominators are formed once, on the host);
+ *   X = (x / y) Y, Z = (((1 - x) - y) / y) Y; linear sRGB (D65): r = (3.2404542 X - 1.5371385 Y) - 0.4985314 Z,
+ *   g = (-0.9692660 X + 1.8760108 Y) + 0.0415560 Z, b = (0.0556434 X - 0.2040259 Y) + 1.0572252 Z; each max(0, .), then times `scale`.
+ *   Model units are kcd/m^2 (klx for irradiance); `scale` brings them to the renderer's.
+ *  Sun irradiance E_sun (an approximation: Preetham's Rayleigh and Angstrom terms only; ozone, gas and water vapour are left out). s.y > 0:
+ *   m = 1 / (s.y + 0.15 pow(93.885 - (theta_s 180) / pi, -1.253)); beta = 0.04608 T - 0.04586; lambda = (0.610, 0.550, 0.465) um for r, g, b;
+ *   tau_c = 0.008735 pow(lambda_c, -4.08) + beta pow(lambda_c, -1.3); E_sun,c = 127.5 exp(-(tau_c m)). s.y <= 0: E_sun = 0.
+ *   pt_sky_sun_irradiance = (scale sun_scale) E_sun,c.
+ *  Ground, d.y <= 0 (a Lambertian plane lit by this sky): G_c = ((scale albedo_c) (E_sky,c + (sun_scale E_sun,c) max(0, s.y))) / pi, where
+ *   E_sky,c = sum_a sum_b sky_c(d_ab) wgt_a of the unscaled sky (scale = 1) over 16 x 64 midpoints theta_a = ((a + 0.5) (pi/2)) / 16,
+ *   phi_b = -pi + ((2 pi) (b + 0.5)) / 64, wgt_a = (cos theta_a (cos((a (pi/2)) / 16) - cos(((a + 1) (pi/2)) / 16))) * ((2 pi) / 64), b inner, a outer,
+ *   in order: it does not depend on W and H.
+ *  The disc, pt_sky_bake only (sun_scale > 0 and E_sun > 0, else nothing is added): each texel has 8 x 8 sub-directions
+ *   theta = ((j + (a + 0.5) / 8) pi) / H, phi = -pi + ((2 pi) (i + (b + 0.5) / 8)) / W; n_ij = how many have dot(d_sub, s) >= cos(alpha),
+ *   alpha = (sun_radius_deg pi) / 180 (sub-directions below the horizon count too). If every n_ij is 0, the texel sample_environment reads
+ *   for direction s gets n = 64. Omega = sum_j (((sum_i n_ij) / 64) (cos((j pi) / H) - cos(((j + 1) pi) / H))) * ((2 pi) / W), rows in order
+ *   (the row sums are integers: no order to fix); L_sun,c = ((scale sun_scale) E_sun,c) / Omega; texel = (float)(sky-or-ground at the centre +
+ *   L_sun,c (n_ij / 64)). So sum_ij disc_ij w_ij = pt_sky_sun_irradiance at every map size, and two bakes of the same options are the same bytes.
+ * Every entry point returns -1 for options outside the ranges below (NaN included; pt_sky_opts_check is that test alone and names the field),
+ * a null buffer with n > 0, W or H = 0 or W * H > 2^26. NULL options mean the defaults. Device memory of a bake, for the call's duration:
+ * the disc's window (1 B per texel of it) and 4 B per row; a host `rgb` adds its device copy (12 B per texel). */
+typedef struct pt_sky_opts {
+    double sun_dir[3];        /* from the scene towards the sun, world axes (y up), any finite length > 0; normalised once on the host */
+    double turbidity;         /* T, finite, 1.7 <= T <= 10. Default 3 */
+    double ground_albedo[3];  /* each finite, in [0, 1]. Default 0.3 */
+    double sun_radius_deg;    /* angular radius alpha of the disc, 0 < alpha <= 10. Default 0.2665 */
+    double sun_scale;         /* >= 0, finite; multiplies the sun's irradiance; 0 = no disc in the map. Default 1 */
+    double scale;             /* > 0, finite; multiplies everything (model units are kcd/m^2). Default 0.04 */
+} pt_sky_opts;
+int pt_sky_opts_default(pt_sky_opts*);              /* sun_dir = (0, 1, 0) */
+int pt_sky_opts_check(const pt_sky_opts* /* NULL = defaults */);
+/* host only, no context: n directions xyz -> n x rgb: the sky above, the ground below, NO disc */
+int pt_sky_eval(const pt_sky_opts*, const double* dirs, uint32_t n, double* out_rgb);
+int pt_sky_sun_irradiance(const pt_sky_opts*, double out[3]);   /* zeros when the sun is not above the horizon */
+/* device: pt_sky_eval by the bake kernel's device function (the same bits); the bake (w*h*3 floats, row-major, disc included; `rgb` a host
+ * buffer, or with rgb_on_device a device pointer); and the bake followed by exactly pt_tex_image_rgbf32 of its result, whose handle it returns */
+int pt_sky_probe(pt_ctx*, const pt_sky_opts*, const double* dirs, uint32_t n, double* out_rgb);
+int pt_sky_bake(pt_ctx*, const pt_sky_opts*, uint32_t w, uint32_t h, float* rgb, int rgb_on_device);
+int pt_tex_sky(pt_scene*, const pt_sky_opts*, uint32_t w, uint32_t h);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

@@ -137,6 +137,25 @@ class FilmOpts(C.Structure):
                          on_device, stream)
 
 
+class SkyOpts(C.Structure):
+    """pt_sky_opts: the physical sky's sun direction, turbidity, ground, disc and scales (include/pt_amd.h has the rule). A fresh instance
+    holds the defaults: the sun at the zenith, turbidity 3."""
+
+    _fields_ = [
+        ("sun_dir", C.c_double * 3),
+        ("turbidity", C.c_double),
+        ("ground_albedo", C.c_double * 3),
+        ("sun_radius_deg", C.c_double),
+        ("sun_scale", C.c_double),
+        ("scale", C.c_double),
+    ]
+
+    def __init__(self, sun_dir=(0.0, 1.0, 0.0), turbidity=3.0, ground_albedo=(0.3, 0.3, 0.3), sun_radius_deg=0.2665, sun_scale=1.0, scale=0.04):
+        if np.ndim(ground_albedo) == 0:
+            ground_albedo = (ground_albedo,) * 3
+        super().__init__(_d3(sun_dir), turbidity, _d3(ground_albedo), sun_radius_deg, sun_scale, scale)
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -165,6 +184,7 @@ ABI_SYMBOLS = [
     "pt_sky_tiles", "pt_short_tiles",
     "pt_light_point", "pt_light_spot", "pt_light_directional", "pt_scene_clear_punctual_lights", "pt_scene_punctual_count", "pt_scene_punctual_light",
     "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval", "pt_scene_set_punctual_media", "pt_scene_punctual_media",
+    "pt_sky_opts_default", "pt_sky_opts_check", "pt_sky_eval", "pt_sky_sun_irradiance", "pt_sky_probe", "pt_sky_bake", "pt_tex_sky",
 ]
 
 
@@ -313,6 +333,14 @@ def _load():
         lib.pt_film_opts_check.argtypes = [C.POINTER(FilmOpts)]
         lib.pt_save_hdr.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.pt_save_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    if hasattr(lib, "pt_sky_bake"):                # (absent from an older build in an A/B run: PT_AMD_LIB)
+        lib.pt_sky_opts_default.argtypes = [C.POINTER(SkyOpts)]
+        lib.pt_sky_opts_check.argtypes = [C.POINTER(SkyOpts)]
+        lib.pt_sky_eval.argtypes = [C.POINTER(SkyOpts), C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.pt_sky_sun_irradiance.argtypes = [C.POINTER(SkyOpts), d3]
+        lib.pt_sky_probe.argtypes = [C.c_void_p, C.POINTER(SkyOpts), C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.pt_sky_bake.argtypes = [C.c_void_p, C.POINTER(SkyOpts), C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]
+        lib.pt_tex_sky.argtypes = [C.c_void_p, C.POINTER(SkyOpts), C.c_uint32, C.c_uint32]
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -445,6 +473,43 @@ class Context:
                                    hdr.ctypes.data, rgb8.ctypes.data), "pt_film_develop")
         return hdr, rgb8
 
+    def sky_bake(self, w: int, h: int, *, device_ptr=None, **opts):
+        """pt_sky_bake: the physical sky as an (h, w, 3) float32 lat-long map, disc included. `opts`: the fields of SkyOpts.
+        device_ptr: the address of w*h*3 floats of device memory to fill instead (e.g. tensor.data_ptr()); None is returned then."""
+        o = SkyOpts(**opts)
+        if device_ptr is not None:
+            _check(lib.pt_sky_bake(self.handle, C.byref(o), w, h, device_ptr, 1), "pt_sky_bake")
+            return None
+        out = np.empty((h, w, 3), dtype=np.float32)
+        _check(lib.pt_sky_bake(self.handle, C.byref(o), w, h, out.ctypes.data, 0), "pt_sky_bake")
+        return out
+
+    def sky_probe(self, dirs: np.ndarray, **opts) -> np.ndarray:
+        """pt_sky_probe: sky_eval by the bake kernel's device function: (n, 3) unit directions -> (n, 3) radiance, no disc."""
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        out = np.empty((len(dirs), 3), dtype=np.float64)
+        o = SkyOpts(**opts)
+        _check(lib.pt_sky_probe(self.handle, C.byref(o), dirs.ctypes.data, len(dirs), out.ctypes.data), "pt_sky_probe")
+        return out
+
+
+def sky_eval(dirs: np.ndarray, **opts) -> np.ndarray:
+    """pt_sky_eval (host only): (n, 3) unit directions -> (n, 3) radiance of the physical sky: the sky above, the ground below, no disc."""
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    out = np.empty((len(dirs), 3), dtype=np.float64)
+    o = SkyOpts(**opts)
+    _check(lib.pt_sky_eval(C.byref(o), dirs.ctypes.data, len(dirs), out.ctypes.data), "pt_sky_eval")
+    return out
+
+
+def sky_sun_irradiance(**opts) -> np.ndarray:
+    """pt_sky_sun_irradiance (host only): the irradiance (rgb) the sun of these options brings to a surface facing it: what the baked disc
+    carries, and what Scene.light_directional needs to stand in for it. Zeros when the sun is not above the horizon."""
+    out = (C.c_double * 3)()
+    o = SkyOpts(**opts)
+    _check(lib.pt_sky_sun_irradiance(C.byref(o), out), "pt_sky_sun_irradiance")
+    return np.array(out[:], dtype=np.float64)
+
 
 def adaptive_schedule(min_spp: int, max_spp: int):
     """Round boundaries [0, b_1, ..., max_spp] of Scene.render_adaptive (pt_adaptive_schedule)."""
@@ -524,6 +589,12 @@ class Scene:
         img = np.ascontiguousarray(img, dtype=np.float32)
         h, w = img.shape[:2]
         return _check(lib.pt_tex_image_rgbf32(self.handle, w, h, img.ctypes.data), "tex_image_rgbf32")
+
+    def tex_sky(self, w: int, h: int, **opts):
+        """pt_tex_sky: the physical sky (the fields of SkyOpts) baked on the GPU into a w x h float image texture: use the handle as
+        Camera.env_tex with env_is_map = 1."""
+        o = SkyOpts(**opts)
+        return _check(lib.pt_tex_sky(self.handle, C.byref(o), w, h), "pt_tex_sky")
 
     def set_float_hdr(self, on: bool = True):
         """Scene scripts (build_scene) load Radiance .hdr files as f32 textures from now on."""

@@ -195,6 +195,8 @@ int main(int argc, char** argv) {
     double mesh_light_v[7] = {0.0, 0.0, 0.0, 0.0, 10.0, 10.0, 10.0};   // centre x y z, radius, emission r g b
     long aov_spp = 16;
     Film film;   // --exposure, --tonemap, --white, --bloom, --out-hdr
+    bool sky = false, sky_no_disc = false;   // --sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]], --sky-no-disc
+    std::vector<double> sky_v;
     uint64_t seed = 1;
     std::string out, assets = "assets";
     for (int i = 1; i < argc; ++i) {
@@ -316,12 +318,25 @@ int main(int argc, char** argv) {
             if (!parse_bloom(next(), film)) { std::cerr << "--bloom must be S[,THRESHOLD[,SIGMA[,LEVELS]]]: numbers, LEVELS a whole one\n"; return 2; }
         }
         else if (a == "--out-hdr") film.hdr_filename = next();
+        else if (a == "--sky") {
+            if (!parse_numbers(next(), 2, 4, sky_v)) {
+                pt_set_error_message("--sky must be ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]]: finite numbers");
+                std::cerr << pt_last_error() << "\n";
+                return 2;
+            }
+            sky = true;
+        }
+        else if (a == "--sky-no-disc") sky_no_disc = true;
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]]\n"
+                         "  --sky: the scene's environment becomes a physical sky (Preetham daylight, a ground below the horizon and the sun's disc) baked on the GPU\n"
+                         "           into a WIDTH x WIDTH/2 float map (default 2048): the sun stands ELEVATION_DEG above the horizon at AZIMUTH_DEG from +x towards +z,\n"
+                         "           TURBIDITY 1.7 (clear) .. 10 (hazy), default 3. Works with --env-sampling (which finds the disc), --exposure, --tonemap, --out-hdr.\n"
+                         "           --sky-no-disc leaves the disc out of the map and prints the --sun argument that brings the same sun back as a punctual light\n"
                          "  --projection: orthographic frames the rectangle the scene's camera sees on its focal plane; fisheye is equidistant with the scene's vfov\n"
                          "           across the image height; panorama is an equirectangular image of everything around the camera position, in world axes: loaded as\n"
                          "           an environment map (--out-hdr, then --float-hdr) it lights another scene. fisheye and panorama have no lens: the scene's\n"
@@ -385,6 +400,34 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    pt_sky_opts sky_opts;
+    uint32_t sky_width = 2048;
+    pt_sky_opts_default(&sky_opts);
+    if (sky_no_disc && !sky) { std::cerr << "--sky-no-disc needs --sky\n"; return 2; }
+    if (sky) {   // the sky options' ranges: the library's own test, before anything is rendered
+        const double rad = 3.14159265358979323846 / 180.0;
+        const double el = sky_v[0] * rad, az = sky_v[1] * rad;
+        sky_opts.sun_dir[0] = std::cos(el) * std::cos(az);
+        sky_opts.sun_dir[1] = std::sin(el);
+        sky_opts.sun_dir[2] = std::cos(el) * std::sin(az);
+        if (sky_v.size() > 2) sky_opts.turbidity = sky_v[2];
+        int bad = pt_sky_opts_check(&sky_opts);
+        if (bad == 0 && sky_v.size() > 3) {
+            if (!(sky_v[3] >= 2.0 && sky_v[3] <= 8192.0) || sky_v[3] != std::floor(sky_v[3])) bad = pt_set_error_message("WIDTH must be a whole number in 2..8192");
+            else sky_width = (uint32_t)sky_v[3];
+        }
+        if (bad != 0) {
+            std::cerr << "--sky: " << pt_last_error() << "\n";
+            return 2;
+        }
+        if (sky_no_disc) {
+            double e[3];
+            if (pt_sky_sun_irradiance(&sky_opts, e) != 0) { std::cerr << "--sky: " << pt_last_error() << "\n"; return 2; }
+            std::printf("--sun %.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", -sky_opts.sun_dir[0], -sky_opts.sun_dir[1], -sky_opts.sun_dir[2], e[0], e[1], e[2]);
+            std::fflush(stdout);
+            sky_opts.sun_scale = 0.0;
+        }
+    }
     if (scene < 1 || scene > 7) return 0;   // `_ => ()` main.rs:643
     pt_ctx* ctx = nullptr;
     if (pt_ctx_create(device, &ctx) != 0) {
@@ -394,6 +437,7 @@ int main(int argc, char** argv) {
     try {
         SceneSetup setup = make_scene(scene, w, s, assets, 1);
         setup.world.float_hdr = float_hdr;
+        if (sky) setup.camera.environment = EnvironmentType::Map(Sky::new_(sky_opts, sky_width, sky_width / 2));
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;
         setup.world.light_sampling = light_sampling;

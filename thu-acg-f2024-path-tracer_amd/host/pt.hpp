@@ -114,6 +114,26 @@ struct ImageTexture : Texture<Vec3> {
     static std::shared_ptr<ImageTexture> new_(const std::string& f) { auto t = std::make_shared<ImageTexture>(); t->filename = f; return t; }
     int emit(Emitter& e) const override;
 };
+// not in the reference: the physical sky (pt_tex_sky; include/pt_amd.h has the rule) as an image texture that is baked on the GPU when the
+// world is emitted instead of read from a file: Camera::environment = EnvironmentType::Map(Sky::new_(opts)).
+struct Sky : ImageTexture {
+    pt_sky_opts opts;
+    uint32_t width = 2048, height = 1024;
+    static pt_sky_opts defaults() { pt_sky_opts o; pt_sky_opts_default(&o); return o; }
+    static std::shared_ptr<Sky> new_(const pt_sky_opts& o, uint32_t w = 2048, uint32_t h = 1024) {
+        auto t = std::make_shared<Sky>();
+        t->opts = o; t->width = w; t->height = h;
+        t->filename = "<sky>";
+        return t;
+    }
+    int emit(Emitter& e) const override {
+        auto it = e.done.find(this);
+        if (it != e.done.end()) return it->second;
+        int h = pt_tex_sky(e.scene, &opts, width, height);
+        if (h < 0) panic("Sky");
+        return e.done[this] = h;
+    }
+};
 
 // ---- materials (src/bsdf/*.rs, src/material.rs:150-191) ---------------------------------
 struct BxDFMaterial {
