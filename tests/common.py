@@ -413,3 +413,125 @@ def forms_scene(mode="PLAIN", lights=True):
     s.add("world_build")
     s.camera = default_camera(width=FORMS_W, aspect=FORMS_W / FORMS_H, spp=4, env_is_map=1, env_tex=env)
     return s
+
+
+# ---- one reused scene through every shading mode (tests/test_mode_walk_gpu.py, tests/test_mode_walk_cpu.py) -----------------------------
+# The bounce word of a path record has five layouts (csrc/pt_types.h); the states of one family share one.
+WALK_FAMILIES = (("PLAIN", "ENV", "LSE", "MOT"), ("MED", "HET", "INT", "INT2"), ("DSP",), ("PLT",), ("SHF",))
+WALK_POINT = ((0.5, 3.0, 0.5), (200.0, 180.0, 160.0))                                        # light_point(position, power)
+WALK_SPOT = ((-2.0, 3.5, -1.0), (0.0, 0.0, 0.0), 20.0, 40.0, (30.0, 30.0, 40.0))             # light_spot(position, target, inner, outer, intensity)
+# States whose forms do not exist for the Sobol sampler, with the reason: none. csrc/pt_forms.h shade_form_exists gives the default
+# variant's shapes (22, 32, 42) every mode, MOT and PLT with and without QMC, and K1 / k_aov have a QMC form each.
+WALK_NO_QMC = {}
+
+
+def walk_family(state):
+    return next(i for i, f in enumerate(WALK_FAMILIES) if state in f)
+
+
+def mode_walk_scene(lights, extra=()):
+    """forms_scene("PLAIN", lights) with, ahead of its build, what the states of WALK_STATES need, so that most transitions are setters:
+    a fog, a 4x4x4 grid medium and a tinted medium on no object, a sphere with p1 != p2 (a shutter other than (0, 1) then puts MOT in
+    effect), a second float environment map of 16x8 and an all-zero one of the first's size; without a lights list, an emissive quad among
+    the objects. `extra`: functions f(add, H) that add more
+    through add(method, *args) ahead of the build. Returns (spec, H), H the handles by name as Refs into the spec's results."""
+    s = forms_scene("PLAIN", lights)
+    assert s.calls[-1][0] == "world_build"
+    s.calls.pop()
+    first = lambda method: SceneSpec.Ref(next(i for i, c in enumerate(s.calls) if c[0] == method))
+    rng = np.random.default_rng(77)
+    H = dict(env=first("tex_image_rgbf32"), glass=first("mat_glass"), metal=first("mat_metal"))
+    H["fog"] = s.add("mat_medium", 0.04, (0.9, 0.9, 0.9), 0.3)
+    H["grid"] = s.add("mat_medium_grid", 0.5, (0.9, 0.8, 0.7), 0.3, rng.uniform(0.0, 1.0, size=(4, 4, 4)).astype(np.float32), (-3.4, -0.5, -2.9), (3.4, 3.3, 3.0))
+    # (thin enough that, as the unbounded camera medium of a scene without lights, it still lets the environment's light through)
+    H["tinted"] = s.add("mat_medium_tinted", 0.1, (0.9, 0.8, 0.7), 0.2, (0.06, 0.02, 0.12))
+    s.add("world_add_object", s.add("sphere", 0.35, (-0.7, 2.3, 0.8), (-0.1, 2.9, 0.8), H["metal"]))
+    if not lights:      # an emitter as an ordinary object, no lights list: an unbounded homogeneous camera medium lets no path out to the environment
+        s.add("world_add_object", s.add("quad", (-1.5, 4.0, -1.5), (3.0, 0.0, 0.0), (0.0, 0.0, 3.0), s.add("mat_light", s.add("tex_solid_rgb", 8.0, 8.0, 7.0))))
+    H["env2"] = s.add("tex_image_rgbf32", rng.uniform(0.05, 1.6 if not lights else 0.5, size=(8, 16, 3)).astype(np.float32))
+    H["env0"] = s.add("tex_image_rgbf32", np.zeros((4, 8, 3), dtype=np.float32))
+    for f in extra:
+        f(s.add, H)
+    s.add("world_build")
+    return s, H
+
+
+def _walk_punctual(g):
+    g.light_point(*WALK_POINT)
+    g.light_spot(*WALK_SPOT)
+    g.world_build()
+
+
+def _walk_no_punctual(g):
+    g.clear_punctual_lights()
+    g.world_build()
+
+
+def _walk_shf_enter(g, H):
+    _walk_punctual(g)
+    g.set_camera_medium(H["fog"])
+    g.set_punctual_media(1)
+
+
+def _walk_shf_leave(g, H):
+    _walk_no_punctual(g)
+    g.set_camera_medium(-1)
+    g.set_punctual_media(0)
+
+
+def _walk_rebuilt(call):
+    return lambda g, H: (call(g, H), g.world_build())
+
+
+# name -> (enter(scene, H), leave(scene, H)): enter puts the state in effect on a scene in the PLAIN state, leave returns it to PLAIN, both
+# through the public API, with world_build() exactly where the API asks for it. H: the handles of mode_walk_scene on that scene.
+WALK_STATES = {
+    "PLAIN": (lambda g, H: None, lambda g, H: None),
+    "ENV": (lambda g, H: g.set_env_sampling(0.5), lambda g, H: g.set_env_sampling(0.0)),
+    "MED": (lambda g, H: g.set_camera_medium(H["fog"]), lambda g, H: g.set_camera_medium(-1)),
+    "HET": (lambda g, H: g.set_camera_medium(H["grid"]), lambda g, H: g.set_camera_medium(-1)),
+    "INT": (lambda g, H: g.set_camera_medium(H["tinted"]), lambda g, H: g.set_camera_medium(-1)),
+    "INT2": (_walk_rebuilt(lambda g, H: g.mat_glass_set_interior(H["glass"], H["tinted"])), _walk_rebuilt(lambda g, H: g.mat_glass_set_interior(H["glass"], -1))),
+    "LSE": (lambda g, H: g.set_light_sampling("exact"), lambda g, H: g.set_light_sampling("reference")),          # needs a lights list
+    "DSP": (_walk_rebuilt(lambda g, H: g.mat_glass_set_dispersion(H["glass"], 30.0)), _walk_rebuilt(lambda g, H: g.mat_glass_set_dispersion(H["glass"], 0.0))),
+    "MOT": (lambda g, H: g.set_shutter(0.25, 0.75), lambda g, H: g.set_shutter(0.0, 1.0)),
+    "PLT": (lambda g, H: _walk_punctual(g), lambda g, H: _walk_no_punctual(g)),
+    "SHF": (_walk_shf_enter, _walk_shf_leave),
+}
+# which state a ShadeMode (csrc/pt_types.h) and a FormUnit (csrc/pt_forms.h) is put in effect by; UNIT_QMC is the sampler axis of PLAIN and ENV
+WALK_MODE_STATE = {"MODE_PLAIN": "PLAIN", "MODE_ENV": "ENV", "MODE_MED": "MED", "MODE_HET": "HET", "MODE_INT": "INT", "MODE_LSE": "LSE", "MODE_DSP": "DSP"}
+WALK_UNIT_STATE = {"UNIT_PLAIN": "PLAIN", "UNIT_QMC": "PLAIN", "UNIT_MED": "MED", "UNIT_HET": "HET", "UNIT_INT": "INT", "UNIT_LSE": "LSE", "UNIT_DSP": "DSP",
+                   "UNIT_MOT": "MOT", "UNIT_PLT": "PLT", "UNIT_SHF": "SHF"}
+
+
+def walk_states(lights):
+    """The states of a scene with (`lights`) or without a lights list, in the table's order: LSE needs the list."""
+    return [n for n in WALK_STATES if lights or n != "LSE"]
+
+
+def walk_pair_circuit(states):
+    """A closed walk over `states` that takes every ordered pair (a, b), a != b, as (previous, next) exactly once: an Eulerian circuit of
+    the complete digraph, by Hierholzer's algorithm with the neighbours in the list's order. len(states) * (len(states) - 1) + 1 visits,
+    from states[0] back to states[0]."""
+    n = len(states)
+    unused = [[j for j in range(n) if j != i] for i in range(n)]
+    stack, circuit = [0], []
+    while stack:
+        v = stack[-1]
+        if unused[v]:
+            stack.append(unused[v].pop(0))
+        else:
+            circuit.append(stack.pop())
+    return [states[i] for i in reversed(circuit)]
+
+
+def walk_family_sequence(states):
+    """A closed walk that visits every state once (the first one twice, to close it) with neighbours of another bounce-word family on both
+    sides: always the first unvisited state of the family with the most of them left, the previous visit's family excepted."""
+    left = [[s for s in f if s in states] for f in WALK_FAMILIES]
+    seq, last = [], -1
+    while any(left):
+        k = max((i for i in range(len(left)) if i != last and left[i]), key=lambda i: (len(left[i]), -i))
+        seq.append(left[k].pop(0))
+        last = k
+    return seq + seq[:1]
