@@ -541,6 +541,56 @@ int pt_punctual_eval(const double rec16[16], const double point[3], double out7[
  *   BSDF rays, every surface blocks them, selection is uniform. */
 int pt_scene_set_punctual_media(pt_scene*, int on);
 int pt_scene_punctual_media(pt_scene*);
+/* ---- the light grid: punctual lights picked by importance per scene cell (a street of lamps, a string of spots, a chandelier; opt-in;
+ *      DESIGN.md section 26) ----
+ * The two sections above stay what they are: with the selection kind 0, the default, every bit and every draw is theirs. Kind 1 replaces one
+ * thing, the choice of the light k and its probability, at the surface bounce's punctual branch and at the light-shaft medium vertex's.
+ * Arithmetic: f64, one IEEE rounding per written operation, no contraction.
+ * Settings. pt_scene_set_punctual_selection(kind): 0 uniform (default), 1 the light grid; any other value returns -1 and leaves the setting;
+ *   pt_scene_punctual_selection reads it. pt_scene_set_punctual_grid(nx, ny, nz, box6_or_NULL): the dims are 0, 0, 0 (automatic, the default) or
+ *   each in 1..64; a box (lo.xyz, hi.xyz), when given, must be finite with hi >= lo per axis; NULL (default) means the world's bounds at the
+ *   build. A refused call returns -1 and changes nothing. Like the light list, both settings take effect at the next pt_world_build; they do
+ *   not clear `built`. pt_scene_punctual_grid(dims3, box6) reports what the LAST BUILD used (either pointer may be NULL); -1 when the grid is
+ *   not in effect.
+ * In effect: the kind was 1 at the last build and n > 0. Otherwise nothing new runs and no table exists. pt_render's refusals are the two
+ *   sections' own, unchanged.
+ * Build (pt_world_build). Box: the one given, or the union of pt_world_entry_box over all entries; if that union is not finite the build fails
+ *   (-1) and asks for a box. Automatic dims: R = 16; an axis of extent ext gets clamp(ceil(R * ext / ext_max), 1, R) cells — the longest R —,
+ *   an axis of extent 0 one cell; R is halved until cells * n <= 2^25. Explicit dims with cells * n > 2^25 fail the build (2^25 entries are
+ *   256 MiB of doubles).
+ *   Cell (ix, iy, iz) has index (iz * ny + iy) * nx + ix. Per axis s = (hi - lo) / (double)n_axis, a = lo + i * s, b = lo + (i + 1) * s (i and
+ *   i + 1 as doubles), m = (a + b) * 0.5, h = (b - a) * 0.5; rc2 = (hx * hx + hy * hy) + hz * hz.
+ *   Weight of light k for the cell: Y = (I_r + I_g) + I_b. Kind 2: w = Y. Kinds 0 and 1: per axis t = p < a ? a - p : (p > b ? p - b : 0) with p
+ *   the light's position, dmin2 = (tx * tx + ty * ty) + tz * tz, w = Y / (dmin2 + rc2). Kind 1 adds a cone cull: v = m - pos, d2 = (vx * vx +
+ *   vy * vy) + vz * vz, and only when d2 > rc2: d = sqrt(d2), sa = sqrt(rc2) / d, ca = sqrt(1 - sa * sa), c_m = ((vx * ax + vy * ay) + vz * az) / d
+ *   with a the light's axis, so = sqrt(max(0, 1 - cos_o * cos_o)), c_far = cos_o * ca - so * sa; if cos_o > -ca && c_m < c_far - 1e-9 then
+ *   w = 0. c_far is cos(theta_o + alpha): the cull fires when the cell's bounding sphere lies wholly outside the outer cone.
+ *   Row of the cell: W = the sum of the w_k in ascending k. If W is not finite or not > 0, every p_k = 1 / (double)n; otherwise p_k = 0.875 *
+ *   (w_k / W) + 0.125 / (double)n. C[k] = C[k-1] + p_k in ascending k with C[-1] = 0, and C[n-1] is stored as exactly 1.0. The one-eighth
+ *   uniform floor gives every light a probability of at least 1 / (8n) in every cell: the importance may be wrong — it ignores occlusion and
+ *   the material, and its cone test is a bound on a sphere — and the estimator stays unbiased.
+ * Selection at a vertex x. Cell: per axis inv = (hi > lo) ? n_axis / (hi - lo) : 0, q = (x - lo) * inv, i = q >= 0 ? (q < (double)n_axis ?
+ *   (uint32)q : n_axis - 1) : 0 — a NaN and every point outside the box take a border cell (the vertices of an unbounded medium are such
+ *   points). Draw: u = one draw by the rand Standard f64 conversion ((v >> 11) * 2^-53); under the Sobol sampler a single draw, not
+ *   pair-aligned, like the index draw it replaces. k = the smallest index with u < C[k] (it exists: C[n-1] = 1), p = C[k] - (k > 0 ? C[k-1] :
+ *   0). Weight: pm = f * p, thr' = ((thr * e) * E) / pm; at a medium vertex albedo * ph stands where e stands. Everything after that —
+ *   endings, the SHADOW segment, the bounce word, resolution — is the two sections' own; k is an index below n.
+ *   The probability that u lands in [C[k-1], C[k]) is that difference up to u's 2^-53 lattice: against p >= 1 / 16384 (n <= 2048) the relative
+ *   error is below 2e-12.
+ * Exactly one draw is made (gen_range rejects half of its draws when n is a power of two). */
+int pt_scene_set_punctual_selection(pt_scene*, int kind);
+int pt_scene_punctual_selection(pt_scene*);
+int pt_scene_set_punctual_grid(pt_scene*, uint32_t nx, uint32_t ny, uint32_t nz, const double* box6_or_null);
+int pt_scene_punctual_grid(pt_scene*, uint32_t dims3[3], double box6[6]);
+/* pt_punctual_probe with the light grid in effect (-1 otherwise). which 2: in = n x point.xyz; row i uses the independent sampler's draws of
+ * (seed 0, pixel i, sample 0) from draw 0; out = n x (cell, k, p, draws consumed, w.xyz, D, E.rgb). which 3: in = n x (cell, k), out = n x
+ * C[cell][k]. */
+/* Host only, no context needed: the device's functions compiled for the host. pt_punctual_grid_row: recs16 = n records as
+ * pt_scene_punctual_light returns them (1 <= n <= 2048), box6 finite with hi >= lo, dims3 each in 1..64, cell < nx * ny * nz; out_cdf = the
+ * cell's n values C[0..n-1]. pt_punctual_grid_select: table = the WHOLE table, row after row in cell order, nx * ny * nz rows of n doubles;
+ * for each of the m (point.xyz, u) pairs out3 = (cell, k, p). */
+int pt_punctual_grid_row(const double* recs16, uint32_t n, const double box6[6], const uint32_t dims3[3], uint32_t cell, double* out_cdf);
+int pt_punctual_grid_select(const double box6[6], const uint32_t dims3[3], const double* table, uint32_t n, const double* points, const double* u, uint32_t m, double* out3);
 /* ---- world: src/hittable/world.rs:10-29 -------------------------------------------------- */
 int pt_world_add_object(pt_scene*, int obj);
 int pt_world_add_light(pt_scene*, int obj);

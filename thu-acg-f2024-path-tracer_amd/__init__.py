@@ -184,6 +184,7 @@ ABI_SYMBOLS = [
     "pt_sky_tiles", "pt_short_tiles",
     "pt_light_point", "pt_light_spot", "pt_light_directional", "pt_scene_clear_punctual_lights", "pt_scene_punctual_count", "pt_scene_punctual_light",
     "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval", "pt_scene_set_punctual_media", "pt_scene_punctual_media",
+    "pt_scene_set_punctual_selection", "pt_scene_punctual_selection", "pt_scene_set_punctual_grid", "pt_scene_punctual_grid", "pt_punctual_grid_row", "pt_punctual_grid_select",
     "pt_sky_opts_default", "pt_sky_opts_check", "pt_sky_eval", "pt_sky_sun_irradiance", "pt_sky_probe", "pt_sky_bake", "pt_tex_sky",
 ]
 
@@ -268,6 +269,13 @@ def _load():
     if hasattr(lib, "pt_scene_set_punctual_media"):
         lib.pt_scene_set_punctual_media.argtypes = [C.c_void_p, C.c_int]
         lib.pt_scene_punctual_media.argtypes = [C.c_void_p]
+    if hasattr(lib, "pt_scene_set_punctual_selection"):
+        lib.pt_scene_set_punctual_selection.argtypes = [C.c_void_p, C.c_int]
+        lib.pt_scene_punctual_selection.argtypes = [C.c_void_p]
+        lib.pt_scene_set_punctual_grid.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.pt_scene_punctual_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pt_punctual_grid_row.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.pt_punctual_grid_select.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     if hasattr(lib, "pt_sky_tiles"):
         lib.pt_sky_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p]
     if hasattr(lib, "pt_short_tiles"):             # (absent from an older build in an A/B run: PT_AMD_LIB)
@@ -675,14 +683,41 @@ class Scene:
 
     def punctual_media(self) -> int: return lib.pt_scene_punctual_media(self.handle)
 
+    def set_punctual_selection(self, kind):
+        """How the punctual branch picks its light: "uniform" (0, the default) or "grid" (1: by importance per scene cell, the light grid of
+        DESIGN.md §26). Takes effect at the next world_build."""
+        kind = {"uniform": 0, "grid": 1}.get(kind, kind)
+        if not isinstance(kind, (int, np.integer)) or isinstance(kind, bool):
+            raise PtError('set_punctual_selection: the kind is "uniform" or "grid"')
+        return _check(lib.pt_scene_set_punctual_selection(self.handle, int(kind)), "set_punctual_selection")
+
+    def punctual_selection(self) -> str: return ("uniform", "grid")[_check(lib.pt_scene_punctual_selection(self.handle), "pt_scene_punctual_selection")]
+
+    def set_punctual_grid(self, nx=0, ny=0, nz=0, box=None):
+        """The light grid's dims (0, 0, 0: automatic; else each in 1..64) and box (lo.xyz, hi.xyz; None: the world's bounds at the build).
+        Takes effect at the next world_build."""
+        if min(int(nx), int(ny), int(nz)) < 0:
+            raise PtError("set_punctual_grid: the dims are 0, 0, 0 (automatic) or each in 1..64")
+        b = None if box is None else np.ascontiguousarray(box, dtype=np.float64).reshape(6)
+        return _check(lib.pt_scene_set_punctual_grid(self.handle, int(nx), int(ny), int(nz), None if b is None else b.ctypes.data), "set_punctual_grid")
+
+    def punctual_grid(self):
+        """((nx, ny, nz), box6) of the light grid the last world_build used; raises when the grid is not in effect."""
+        dims, box = np.zeros(3, dtype=np.uint32), np.zeros(6, dtype=np.float64)
+        _check(lib.pt_scene_punctual_grid(self.handle, dims.ctypes.data, box.ctypes.data), "pt_scene_punctual_grid")
+        return tuple(int(d) for d in dims), box
+
     def punctual_probe(self, which: int, arr: np.ndarray) -> np.ndarray:
         """The punctual branch's device functions as the kernels call them. which 0: arr = (n, 3) points -> (n, 9) {k, w.xyz, D, E.rgb, draws
         consumed}, row i with the independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0; which 1: arr = (n, 4) (k, point.xyz)
-        -> (n, 7) {w.xyz, D, E.rgb}."""
-        if which not in (0, 1):
-            raise PtError("punctual_probe: which must be 0 or 1")
-        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, 3 if which == 0 else 4))
-        out = np.empty((len(arr), 9 if which == 0 else 7), dtype=np.float64)
+        -> (n, 7) {w.xyz, D, E.rgb}. With the light grid in effect: which 2: arr = (n, 3) points -> (n, 11) {cell, k, p, draws consumed, w.xyz,
+        D, E.rgb}; which 3: arr = (n, 2) (cell, k) -> (n,) C[cell][k]."""
+        if which not in (0, 1, 2, 3):
+            raise PtError("punctual_probe: which must be 0, 1, 2 or 3")
+        arr = np.ascontiguousarray(arr, dtype=np.float64).reshape((-1, (3, 4, 3, 2)[which]))
+        out = np.empty((len(arr), (9, 7, 11, 1)[which]), dtype=np.float64)
+        if which == 3:
+            out = out.reshape(-1)
         _check(lib.pt_punctual_probe(self.handle, which, arr.ctypes.data, len(arr), out.ctypes.data), "pt_punctual_probe")
         return out
 
@@ -986,6 +1021,35 @@ def punctual_eval(rec16, point) -> np.ndarray:
     out = (C.c_double * 7)()
     _check(lib.pt_punctual_eval(rec, _d3(point), out), "pt_punctual_eval")
     return np.array(out[:], dtype=np.float64)
+
+
+def _grid_args(box, dims):
+    return np.ascontiguousarray(box, dtype=np.float64).reshape(6), np.ascontiguousarray(dims, dtype=np.uint32).reshape(3)
+
+
+def punctual_grid_row(recs16, box, dims, cell) -> np.ndarray:
+    """One row of the light grid's table (pt_punctual_grid_row; host only — the build kernel's functions compiled for the host): recs16 = (n, 16)
+    records as Scene.punctual_light returns them, box = (lo.xyz, hi.xyz), dims = (nx, ny, nz) -> the cell's CDF C[0..n-1]."""
+    recs = np.ascontiguousarray(recs16, dtype=np.float64).reshape(-1, 16)
+    b, d = _grid_args(box, dims)
+    out = np.empty(len(recs), dtype=np.float64)
+    _check(lib.pt_punctual_grid_row(recs.ctypes.data, len(recs), b.ctypes.data, d.ctypes.data, int(cell), out.ctypes.data), "pt_punctual_grid_row")
+    return out
+
+
+def punctual_grid_select(box, dims, table, points, u) -> np.ndarray:
+    """The light grid's selection (pt_punctual_grid_select; host only): table = (cells, n) the whole table, points (m, 3), u (m,) -> (m, 3)
+    {cell, k, p}."""
+    b, d = _grid_args(box, dims)
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    if table.ndim != 2 or table.shape[0] != int(d[0]) * int(d[1]) * int(d[2]) or len(u) != len(points):
+        raise PtError("punctual_grid_select: table is (nx * ny * nz, n), and there is one u per point")
+    out = np.empty((len(points), 3), dtype=np.float64)
+    _check(lib.pt_punctual_grid_select(b.ctypes.data, d.ctypes.data, table.ctypes.data, table.shape[1], points.ctypes.data, u.ctypes.data, len(points), out.ctypes.data),
+           "pt_punctual_grid_select")
+    return out
 
 
 def sky_tiles(cam: Camera, boxes) -> np.ndarray:

@@ -223,6 +223,30 @@ constexpr int LSE_KB = 512;                                            // thread
 // free flight of a SHADOW segment runs to min(hit, light): a collision blocks the light; a segment that reaches a medium's boundary in front of
 // the light crosses it (B2's boundary code) and stays a SHADOW segment; otherwise it is resolved as in the plain mode. Every other lane is the
 // MED / HET form's bounce under PLT's weights.
+// The light grid (pt_scene_set_punctual_selection): SceneD::punctual_cdf is set — a RUN-TIME branch of the PLT and SHF forms, no form
+// of its own. B1 picks the light by one draw and a binary search in the row of the vertex's cell instead of the index draw and hands its
+// probability p to B2, where pm = f * p. The search is a real function (PT_GRID_CALL, as grid_track is): inlined at both sites of a
+// light-shaft form its loop's registers came on top of B1's (the register table: DESIGN.md §26).
+struct GridPick {
+    uint32_t k;
+    double p;
+};
+#ifndef PT_GRID_PICK_INLINE
+#define PT_GRID_CALL static __device__ __noinline__   // (static: a unit without PLT forms holds no copy)
+#else
+#define PT_GRID_CALL static __device__ __forceinline__
+#endif
+PT_GRID_CALL GridPick punctual_grid_search(const double* row, uint32_t n, double u) {
+    GridPick r;
+    r.k = punctual_select(row, n, u, r.p);
+    return r;
+}
+PT_DEV uint32_t punctual_grid_pick(const SceneD& sc, const double x[3], double u, double& p) {
+    const uint32_t cell = punctual_grid_cell(sc.punctual_grid, x);
+    const GridPick r = punctual_grid_search(sc.punctual_cdf + (size_t)cell * sc.punctual_grid.stride, sc.n_punctual, u);
+    p = r.p;
+    return r.k;
+}
 template <bool LIGHTS, bool LIST, class Prefetch, ShadeMode M = MODE_PLAIN, bool QMC = false, bool UNI = true, bool MOT = false, bool MAP = false, bool PLT = false>
 // UNI: the form may take the single-primitive path of phase A (k_shade: every two-wave shape).
 // MAP: the form reads the sky pass's tile map when it draws a work item (k_shade: sky_pass_form of its own arguments, pt_types.h).
@@ -480,6 +504,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
     bool punct_dir = false;                                            // PLT: the bounce took the punctual branch (dir = w, towards light plk)
     V3 punct_e{};                                                      // ... E, what the light sends to the hit point
     bool punct_ok = false;                                             // ... d2 is finite and not 0
+    double punct_p = 0.0;                                              // ... the light grid's probability of plk in the vertex's cell (read when sc.punctual_cdf is set)
     bool env_lane = false, env_dir = false;                            // ENV: the bounce takes the mixture / its direction is an env sample
     double q_env = 0.0;                                                // ENV: q_env(dir) (pt_amd.h)
     if (is_hit) {
@@ -519,8 +544,9 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                 if (LIGHTS && rsel < p_light) {
                     dir = lights_sample<MOT>(sc, hit.point, ray.time, rng);
                 } else if (rsel < p_light + p_punct) {
-                    plk = rng_index(rng, sc.n_punctual) & PLT_INDEX_MASK;   // one index draw, as the lights list's
                     const double x[3] = {hit.point.x, hit.point.y, hit.point.z};
+                    if (sc.punctual_cdf) plk = punctual_grid_pick(sc, x, rng_f64(rng), punct_p) & PLT_INDEX_MASK;   // the light grid: one draw (§26)
+                    else plk = rng_index(rng, sc.n_punctual) & PLT_INDEX_MASK;   // one index draw, as the lights list's
                     const PunctualEval pe = punctual_eval(sc.punctual[plk], x);
                     dir = V3{pe.w[0], pe.w[1], pe.w[2]};
                     punct_e = V3{pe.E[0], pe.E[1], pe.E[2]};
@@ -561,8 +587,9 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
                     dir = lights_sample<MOT>(sc, hit.point, ray.time, rng);
                 } else if (SHF && rsel < p_light + p_punct) {
                     if constexpr (SHF) {                               // the surface bounce's punctual branch at the vertex x = hit.point
-                        plk = rng_index(rng, sc.n_punctual) & PLT_INDEX_MASK;
                         const double x[3] = {hit.point.x, hit.point.y, hit.point.z};
+                        if (sc.punctual_cdf) plk = punctual_grid_pick(sc, x, rng_f64(rng), punct_p) & PLT_INDEX_MASK;
+                        else plk = rng_index(rng, sc.n_punctual) & PLT_INDEX_MASK;
                         const PunctualEval pe = punctual_eval(sc.punctual[plk], x);
                         dir = V3{pe.w[0], pe.w[1], pe.w[2]};
                         punct_e = V3{pe.E[0], pe.E[1], pe.E[2]};
@@ -594,7 +621,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
         if constexpr (PLT) {
             if (punct_dir) {
                 // thr' = ((thr * e) * E) / pm with pm = f / n: the branch's own probability, no density (the direction has measure zero under the others)
-                const double pm = p_punct / (double)sc.n_punctual;
+                const double pm = sc.punctual_cdf ? p_punct * punct_p : p_punct / (double)sc.n_punctual;   // (the light grid: pm = f * p)
                 const V3 t = ((thr * brdf) * punct_e) / pm;
                 env_end = !punct_ok || (t.x == 0.0 && t.y == 0.0 && t.z == 0.0);
                 if (!env_end) {
@@ -652,7 +679,7 @@ PT_DEV void shade_slot(const SceneD& sc, const CamD& cam, const PoolD& pool, Cou
             const double ph = hg_phase(medium.g, dot(ray.d, dir));
             if (SHF && punct_dir) {
                 // thr' = ((thr * (albedo * ph)) * E) / pm, pm = f / n: the phase function where the surface has its eval, no cosine
-                const double pm = p_punct / (double)sc.n_punctual;
+                const double pm = sc.punctual_cdf ? p_punct * punct_p : p_punct / (double)sc.n_punctual;
                 const V3 t = ((thr * (medium.albedo * ph)) * punct_e) / pm;
                 if (!punct_ok || (t.x == 0.0 && t.y == 0.0 && t.z == 0.0)) {
                     finished = parked = true;
@@ -829,6 +856,7 @@ static_assert(SORT_WINDOW <= 65536, "k_shade: s_perm holds 16-bit slot offsets")
 template <bool SORT, int MINW, bool LIGHTS, int KB = BLOCK, int PER = SORT_WINDOW / BLOCK, bool LIST = false, ShadeMode M = MODE_PLAIN, bool QMC = false, bool MOT = false, bool PLT = false>
 __global__ __launch_bounds__(KB, KB == BLOCK ? MINW : 1) void k_shade(SceneD sc, CamD cam, PoolD pool, CountersD* cnt, uint64_t seed, EnvTabD env) {
     constexpr bool ENV = M == MODE_ENV, MED = mode_has_media(M), LSE = M == MODE_LSE, DSP = M == MODE_DSP;   // (HET and INT change nothing here)
+    static_assert(sizeof(SceneD) + sizeof(CamD) + sizeof(PoolD) + sizeof(CountersD*) + sizeof(uint64_t) + sizeof(EnvTabD) + 64 <= 4096, "k_shade: the arguments fit the 4 KiB of kernel arguments");
     static_assert(!MOT || M == MODE_PLAIN, "k_shade: the MOT forms are plain-mode forms");
     static_assert(!PLT || ((M == MODE_PLAIN || M == MODE_MED || M == MODE_HET) && !MOT), "k_shade: the PLT forms are plain-mode forms, or MED / HET forms (light shafts), without motion");
     static_assert((!LSE || LIGHTS) && (!(LSE || DSP) || (SORT && KB == LSE_KB)), "k_shade: the LSE forms need a lights list; the LSE and DSP forms are sorted 512-thread forms");

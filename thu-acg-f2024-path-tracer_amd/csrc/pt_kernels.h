@@ -98,8 +98,11 @@ void launch_film_develop(const double* sums, uint32_t n_pixels, double scale, co
                          uint32_t tonemap, double white, double* hdr, uint8_t* rgb8, hipStream_t st);
 // pt_camera_probe: generate_ray as k_init calls it under sampler `kind` (n x (pixel, sample) -> n x (origin.xyz, direction.xyz, time, draws consumed)); in / out: device
 // motion: the shutter is applied (motion is in effect)
+// the light grid's table: g.cells rows of n doubles into `table`; stage: through LDS (the default) or lane-per-cell stores
+void launch_punctual_grid(const PunctualD* lights, uint32_t n, const PunctualGridBuild& g, double* table, bool stage, hipStream_t st);
 // pt_punctual_probe: the punctual lights' device functions as k_shade's PLT forms call them (which 0: n x point.xyz -> n x (k, w.xyz, D, E.rgb, draws
 // consumed), row i with the independent sampler's draws of (seed 0, pixel i, sample 0) from draw 0; 1: n x (k, point.xyz) -> n x (w.xyz, D, E.rgb)); in / out: device
+// (the light grid in effect: 2: n x point.xyz -> n x (cell, k, p, draws consumed, w.xyz, D, E.rgb); 3: n x (cell, k) -> n x C[cell][k])
 void launch_punctual_probe(const SceneD& sc, int which, const double* in, uint32_t n, double* out, hipStream_t st);
 void launch_camera_probe(const CamD& cam, int kind, uint64_t seed, const double* in, uint32_t n, double* out, hipStream_t st, bool motion = false);
 void launch_math_probe(int which, const double* in, uint32_t n, double* out, hipStream_t st);

@@ -118,9 +118,10 @@ extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t
 
 extern "C" int pt_punctual_probe(pt_scene* s, int which, const double* in, uint32_t n, double* out) {
     if (!s || !s->built) return set_error("pt_punctual_probe: world not built");
-    if (which != 0 && which != 1) return set_error("pt_punctual_probe: which must be 0 or 1");
+    if (which < 0 || which > 3) return set_error("pt_punctual_probe: which must be 0, 1, 2 or 3");
     const uint32_t n_lights = s->dev.view.n_punctual;
     if (n_lights == 0u) return set_error("pt_punctual_probe: the world was built without punctual lights");
+    if (which >= 2 && !s->dev.view.punctual_cdf) return set_error("pt_punctual_probe: which 2 and 3 need the light grid in effect (pt_scene_set_punctual_selection, then pt_world_build)");
     if (n == 0) return 0;
     if (!in || !out) return set_error("pt_punctual_probe: null buffer");
     if (which == 1)
@@ -128,7 +129,14 @@ extern "C" int pt_punctual_probe(pt_scene* s, int which, const double* in, uint3
             const double k = in[4 * (size_t)i];
             if (!(k >= 0.0 && k < (double)n_lights) || k != std::floor(k)) return set_error("pt_punctual_probe: which 1 takes (k, point.xyz) rows with k a light of the built list");
         }
-    const size_t n_in = (size_t)n * (which == 0 ? 3 : 4), n_out = (size_t)n * (which == 0 ? 9 : 7);
+    if (which == 3)
+        for (uint32_t i = 0; i < n; ++i) {
+            const double c = in[2 * (size_t)i], k = in[2 * (size_t)i + 1];
+            if (!(c >= 0.0 && c < (double)s->grid_built.cells) || c != std::floor(c) || !(k >= 0.0 && k < (double)n_lights) || k != std::floor(k))
+                return set_error("pt_punctual_probe: which 3 takes (cell, k) rows with a cell of the built grid and k a light of the built list");
+        }
+    static const size_t IN_COLS[4] = {3, 4, 3, 2}, OUT_COLS[4] = {9, 7, 11, 1};
+    const size_t n_in = (size_t)n * IN_COLS[which], n_out = (size_t)n * OUT_COLS[which];
     return run_probe(s->ctx, {{in, n_in * sizeof(double)}}, out, n_out * sizeof(double), [&](void* const* d_in, void* d_out) {
         launch_punctual_probe(s->dev.view, which, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
     });

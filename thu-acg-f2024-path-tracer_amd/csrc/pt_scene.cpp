@@ -3,6 +3,7 @@
 #include "pt_bvh_device.h"
 #include "pt_detmath.h"
 #include "pt_dev_punctual.h"
+#include "pt_kernels.h"
 
 #include <hip/hip_runtime.h>
 
@@ -678,6 +679,88 @@ extern "C" int pt_punctual_eval(const double rec16[16], const double point[3], d
     out7[0] = e.w[0]; out7[1] = e.w[1]; out7[2] = e.w[2]; out7[3] = e.D; out7[4] = e.E[0]; out7[5] = e.E[1]; out7[6] = e.E[2];
     return 0;
 }
+// ---- the light grid (pt_scene_set_punctual_selection, pt_scene_set_punctual_grid; the rule: pt_amd.h) ----
+static PunctualD punctual_from16(const double* r) {
+    PunctualD L{};
+    L.kind = (uint32_t)r[0];
+    for (int i = 0; i < 3; ++i) { L.pos[i] = r[1 + i]; L.axis[i] = r[4 + i]; L.I[i] = r[7 + i]; }
+    L.cos_i = r[10]; L.cos_o = r[11];
+    return L;
+}
+static bool grid_dims_ok(const uint32_t d[3]) { return d[0] >= 1u && d[0] <= PLT_GRID_MAX_DIM && d[1] >= 1u && d[1] <= PLT_GRID_MAX_DIM && d[2] >= 1u && d[2] <= PLT_GRID_MAX_DIM; }
+static bool grid_box_ok(const double b[6]) {
+    for (int i = 0; i < 6; ++i) if (!std::isfinite(b[i])) return false;
+    return b[3] >= b[0] && b[4] >= b[1] && b[5] >= b[2];
+}
+static PunctualGridD grid_descriptor(const double box[6], const uint32_t dims[3], uint32_t n) {
+    PunctualGridD g{};
+    for (int ax = 0; ax < 3; ++ax) {
+        g.lo[ax] = box[ax];
+        g.inv[ax] = box[3 + ax] > box[ax] ? (double)dims[ax] / (box[3 + ax] - box[ax]) : 0.0;
+        g.n[ax] = dims[ax];
+    }
+    g.stride = n;
+    return g;
+}
+extern "C" int pt_scene_set_punctual_selection(pt_scene* s, int kind) {
+    if (!s) return set_error("pt_scene_set_punctual_selection: null scene");
+    if (kind != 0 && kind != 1) return set_error("pt_scene_set_punctual_selection: the kind is 0 (uniform) or 1 (the light grid)");
+    s->punctual_selection = kind;   // (takes effect at the next pt_world_build, like the list)
+    return 0;
+}
+extern "C" int pt_scene_punctual_selection(pt_scene* s) {
+    if (!s) return set_error("pt_scene_punctual_selection: null scene");
+    return s->punctual_selection;
+}
+extern "C" int pt_scene_set_punctual_grid(pt_scene* s, uint32_t nx, uint32_t ny, uint32_t nz, const double* box6) {
+    if (!s) return set_error("pt_scene_set_punctual_grid: null scene");
+    const uint32_t d[3] = {nx, ny, nz};
+    if (!((nx == 0u && ny == 0u && nz == 0u) || grid_dims_ok(d))) return set_error("pt_scene_set_punctual_grid: the dims are 0, 0, 0 (automatic) or each in 1..64");
+    if (box6 && !grid_box_ok(box6)) return set_error("pt_scene_set_punctual_grid: the box must be finite with hi >= lo on every axis");
+    for (int i = 0; i < 3; ++i) s->grid_dims_set[i] = d[i];
+    s->grid_box_given = box6 != nullptr;
+    if (box6) memcpy(s->grid_box_set, box6, sizeof s->grid_box_set);
+    return 0;
+}
+extern "C" int pt_scene_punctual_grid(pt_scene* s, uint32_t dims3[3], double box6[6]) {
+    if (!s) return set_error("pt_scene_punctual_grid: null scene");
+    if (!s->built || s->grid_built.cells == 0u) return set_error("pt_scene_punctual_grid: the light grid is not in effect");
+    if (dims3) memcpy(dims3, s->grid_built.dims, 3 * sizeof(uint32_t));
+    if (box6) memcpy(box6, s->grid_built.box, 6 * sizeof(double));
+    return 0;
+}
+static int grid_twin_args(const char* who, uint32_t n, const double* box6, const uint32_t* dims3) {
+    if (!box6 || !dims3) return set_error(std::string(who) + ": null buffer");
+    if (n == 0u || n > PLT_MAX_LIGHTS) return set_error(std::string(who) + ": the list holds 1..2048 lights");
+    if (!grid_dims_ok(dims3)) return set_error(std::string(who) + ": each dim is in 1..64");
+    if (!grid_box_ok(box6)) return set_error(std::string(who) + ": the box must be finite with hi >= lo on every axis");
+    return 0;
+}
+extern "C" int pt_punctual_grid_row(const double* recs16, uint32_t n, const double box6[6], const uint32_t dims3[3], uint32_t cell, double* out_cdf) {
+    if (grid_twin_args("pt_punctual_grid_row", n, box6, dims3) != 0) return -1;
+    if (!recs16 || !out_cdf) return set_error("pt_punctual_grid_row: null buffer");
+    if (cell >= dims3[0] * dims3[1] * dims3[2]) return set_error("pt_punctual_grid_row: no such cell");
+    for (uint32_t k = 0; k < n; ++k) {
+        const double kind = recs16[16 * (size_t)k];
+        if (!(kind == 0.0 || kind == 1.0 || kind == 2.0)) return set_error("pt_punctual_grid_row: a record's kind must be 0, 1 or 2");
+    }
+    const PunctualCell c = punctual_grid_geometry(box6, dims3, cell);   // the device's functions, compiled for the host
+    punctual_grid_row([&](uint32_t k) { return punctual_from16(recs16 + 16 * (size_t)k); }, n, c, [&](uint32_t k, double C) { out_cdf[k] = C; });
+    return 0;
+}
+extern "C" int pt_punctual_grid_select(const double box6[6], const uint32_t dims3[3], const double* table, uint32_t n, const double* points, const double* u, uint32_t m, double* out3) {
+    if (grid_twin_args("pt_punctual_grid_select", n, box6, dims3) != 0) return -1;
+    if (m == 0u) return 0;
+    if (!table || !points || !u || !out3) return set_error("pt_punctual_grid_select: null buffer");
+    const PunctualGridD g = grid_descriptor(box6, dims3, n);
+    for (uint32_t i = 0; i < m; ++i) {
+        const uint32_t cell = punctual_grid_cell(g, points + 3 * (size_t)i);
+        double p;
+        const uint32_t k = punctual_select(table + (size_t)cell * n, n, u[i], p);
+        out3[3 * (size_t)i] = (double)cell; out3[3 * (size_t)i + 1] = (double)k; out3[3 * (size_t)i + 2] = p;
+    }
+    return 0;
+}
 static Box xform_box(const Box& b, const InstD& m) {   // box of the box (aabb.rs:50-76)
     Box r;
     for (int i = 0; i < 8; ++i) {
@@ -1247,6 +1330,36 @@ int pt::scene_build(pt_scene* s) {
     s->entry_boxes.clear();   // pt_world_entry_box: the f64 boxes, before the f32 rounding
     for (const Box& b : entry_boxes)
         for (double x : {b.lo.x, b.lo.y, b.lo.z, b.hi.x, b.hi.y, b.hi.z}) s->entry_boxes.push_back(x);
+    // the light grid: its box and dims are settled, and their refusals made, before the top level is built and anything is uploaded
+    PunctualGridBuild gb{};
+    s->grid_built = gb;
+    if (s->punctual_selection == 1 && !s->punctual.empty()) {
+        const uint64_t n = s->punctual.size();
+        if (s->grid_box_given) memcpy(gb.box, s->grid_box_set, sizeof gb.box);
+        else {
+            Box u;
+            for (const Box& b : entry_boxes) { u.grow(b.lo); u.grow(b.hi); }
+            const double ub[6] = {u.lo.x, u.lo.y, u.lo.z, u.hi.x, u.hi.y, u.hi.z};
+            if (entry_boxes.empty() || !grid_box_ok(ub)) return set_error("pt_world_build: the light grid needs a finite box and the world's bounds are not finite: give one (pt_scene_set_punctual_grid)");
+            memcpy(gb.box, ub, sizeof gb.box);
+        }
+        if (s->grid_dims_set[0] != 0u) {
+            memcpy(gb.dims, s->grid_dims_set, sizeof gb.dims);
+            if ((uint64_t)gb.dims[0] * gb.dims[1] * gb.dims[2] * n > PLT_GRID_MAX_ENTRIES)
+                return set_error("pt_world_build: the light grid's table would hold more than 2^25 entries (cells x lights): take fewer cells (pt_scene_set_punctual_grid)");
+        } else {
+            const double ext[3] = {gb.box[3] - gb.box[0], gb.box[4] - gb.box[1], gb.box[5] - gb.box[2]};
+            const double ext_max = std::max(ext[0], std::max(ext[1], ext[2]));
+            for (uint32_t R = PLT_GRID_AUTO_RES;; R /= 2u) {
+                for (int ax = 0; ax < 3; ++ax) {
+                    const double c = ext[ax] > 0.0 ? std::ceil((double)R * ext[ax] / ext_max) : 1.0;   // (the longest axis: exactly R)
+                    gb.dims[ax] = (uint32_t)(c < 1.0 ? 1.0 : (c > (double)R ? (double)R : c));
+                }
+                if ((uint64_t)gb.dims[0] * gb.dims[1] * gb.dims[2] * n <= PLT_GRID_MAX_ENTRIES || R == 1u) break;
+            }
+        }
+        gb.cells = gb.dims[0] * gb.dims[1] * gb.dims[2];
+    }
     // Build the TLAS over world entries (one entry per leaf).
     Builder tl{nodes, tlas_items, 1, MAX_TLAS_DEPTH, false, nullptr};
     Box wb;
@@ -1349,10 +1462,35 @@ int pt::scene_build(pt_scene* s) {
     if (ok && any_moving) ok = upload(dev, inst_motion, v.inst_motion);
     if (ok && !grids.empty()) ok = upload(dev, grids, v.grids) && upload(dev, grid_vals, v.grid_vals);
     if (ok && !s->punctual.empty()) ok = upload(dev, s->punctual, v.punctual);
+    if (ok && gb.cells != 0u) {   // the table: one row of n doubles per cell, formed on the GPU from the list just uploaded
+        void* table = nullptr;
+        const uint32_t n = (uint32_t)s->punctual.size();
+        ok = hip_ok(hipMalloc(&table, (size_t)gb.cells * n * sizeof(double)), "hipMalloc(light grid)");
+        if (ok) {
+            dev.allocs.push_back(table);
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            const bool timed = exp_env("PT_VERBOSE") && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+            if (timed) (void)hipEventRecord(e0, s->ctx->stream);
+            launch_punctual_grid(v.punctual, n, gb, (double*)table, !exp_env("PT_GRID_DIRECT"), s->ctx->stream);
+            if (timed) (void)hipEventRecord(e1, s->ctx->stream);
+            ok = hip_ok(hipGetLastError(), "kernel launch") && hip_ok(hipStreamSynchronize(s->ctx->stream), "hipStreamSynchronize");
+            float ms = 0.0f;
+            if (ok && timed && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) {
+                s->grid_build_ms = ms;
+                fprintf(stderr, "[pt] light grid: %u x %u x %u cells x %u lights, %zu bytes, built in %.3f ms (%s)\n", gb.dims[0], gb.dims[1], gb.dims[2], n,
+                        (size_t)gb.cells * n * sizeof(double), ms, exp_env("PT_GRID_DIRECT") ? "direct stores" : "staged through LDS");
+            }
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+            v.punctual_cdf = (const double*)table;
+            v.punctual_grid = grid_descriptor(gb.box, gb.dims, n);
+        }
+    }
     if (!ok) {
         dev.release();
         return -1;
     }
+    s->grid_built = gb;
     v.tlas_root = tlas_root;
     v.tlas_extent = box_extent(wb);
     v.n_entries = (uint32_t)entries.size();

@@ -150,6 +150,14 @@ struct pt_scene {
     bool punctual_on() const { return n_punctual_built != 0u; }   // "in effect": the kernels' PLT forms run
     // light shafts (pt_scene_set_punctual_media): the option that lets punctual lights and participating media be in effect together
     int punctual_media = 0;
+    // the light grid (pt_scene_set_punctual_selection / pt_scene_set_punctual_grid): the settings wait for the next build like
+    // the list; grid_built: what the last build used (cells = 0: the grid is not in effect; the table: DeviceBuffers::view.punctual_cdf)
+    int punctual_selection = 0;    // 0 uniform, 1 the light grid
+    uint32_t grid_dims_set[3] = {0u, 0u, 0u};   // all 0: automatic
+    bool grid_box_given = false;
+    double grid_box_set[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    pt::PunctualGridBuild grid_built{};
+    double grid_build_ms = 0.0;    // the table kernel's time at the last build (PT_VERBOSE prints it)
     int projection = 0;            // pt_scene_set_projection: 0 perspective, 1 orthographic, 2 fisheye, 3 panorama (CamD::projection)
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
     pt::CountersD* d_counters = nullptr;

@@ -159,6 +159,19 @@ struct PunctualD {
 };
 constexpr uint32_t PLT_MAX_LIGHTS = 2048, PLT_SHADOW_BIT = 1u << 31, PLT_INDEX_SHIFT = 20, PLT_INDEX_MASK = PLT_MAX_LIGHTS - 1u,
                    PLT_BOUNCE_MASK = (1u << PLT_INDEX_SHIFT) - 1u;
+// The light grid (pt_scene_set_punctual_selection kind 1; the rule: pt_amd.h): a uniform world-space grid of n[0] x n[1] x n[2]
+// cells over the box that starts at lo; inv = n / (hi - lo) per axis (0 on an axis of extent 0). Cell (ix, iy, iz) has index (iz * n[1] + iy)
+// * n[0] + ix, and row `cell` of the table (SceneD::punctual_cdf) is the cell's CDF over the whole list: `stride` doubles, the list's length.
+struct PunctualGridD {
+    double lo[3], inv[3];
+    uint32_t n[3], stride;
+};
+struct PunctualGridBuild {   // what the build kernel and pt_punctual_grid_row form a row from: the box (lo.xyz, hi.xyz), the dims, their product
+    double box[6];
+    uint32_t dims[3], cells;
+};
+constexpr uint64_t PLT_GRID_MAX_ENTRIES = 1ull << 25;   // cells x lights: 256 MiB of doubles
+constexpr uint32_t PLT_GRID_MAX_DIM = 64, PLT_GRID_AUTO_RES = 16;
 // Light shafts (pt_scene_set_punctual_media): punctual lights and participating media in effect together. Medium AND shadow
 // segment travel in the one bounce word: the medium stays in bits 20..31 (MEDIUM_SHIFT — a camera ray's word is the MED forms', so K1 has no
 // form of its own), the SHADOW flag is bit 19, the light index bits 8..18, the bounce number bits 0..7. Only the forms of k_shade that have
@@ -278,7 +291,10 @@ struct SceneD {
     const PunctualD* punctual;   // the punctual lights of the last build, null when there are none; read by the PLT forms of K3 and the probe only
     uint32_t n_punctual;
     double punctual_f;           // pt_scene_set_punctual_fraction: the selector's share of the punctual branch
+    const double* punctual_cdf;  // the light grid's table of the last build, null when the grid is not in effect: the PLT and light-shaft
+    PunctualGridD punctual_grid; // forms of K3 branch on it at run time; nothing else reads either
 };
+static_assert(sizeof(SceneD) <= 512, "SceneD travels by value: with CamD, PoolD and the rest of k_shade's arguments it stays far below the 4 KiB of kernel arguments");
 constexpr int LIGHT_STACK = 24;          // LDS entries per lane of the LSE forms' all-hits mesh walk (pt_dev_lights.h): the deepest light mesh tree they take
 constexpr uint32_t TLAS_FLAT_MAX = 24;   // round 1 (vector loads): 8-10 entries -26 % / -7 % K2 time, 17 entries (scene 5) +20 % -> limit 12;
                                           // round 2 (scalar loads, ldu): 17 entries -20 % -> limit raised

@@ -191,6 +191,8 @@ int main(int argc, char** argv) {
     bool mesh_light = false;
     std::vector<std::vector<double>> point_lights, spot_lights, suns;   // --point-light, --spot-light, --sun: repeatable
     double punctual_fraction = 0.5;                                      // --punctual-fraction F
+    int punctual_selection = 0;                                          // --punctual-selection uniform|grid[,NX,NY,NZ]: the light grid
+    uint32_t punctual_grid[3] = {0u, 0u, 0u};
     bool light_shafts = false;                                           // --light-shafts: the punctual lights light --fog / --smoke
     double mesh_light_v[7] = {0.0, 0.0, 0.0, 0.0, 10.0, 10.0, 10.0};   // centre x y z, radius, emission r g b
     long aov_spp = 16;
@@ -295,6 +297,20 @@ int main(int argc, char** argv) {
         else if (a == "--punctual-fraction") {
             if (!parse_number(next(), punctual_fraction) || !(punctual_fraction > 0.0 && punctual_fraction < 1.0)) { std::cerr << "--punctual-fraction must be a number F with 0 < F < 1\n"; return 2; }
         }
+        else if (a == "--punctual-selection") {
+            const std::string v = next();
+            bool ok = v == "uniform" || v == "grid";
+            punctual_selection = v == "uniform" ? 0 : 1;
+            if (!ok && v.rfind("grid,", 0) == 0) {
+                std::vector<double> x;
+                ok = parse_numbers(v.substr(5), 3, 3, x);
+                for (size_t k = 0; ok && k < 3; ++k) {
+                    ok = x[k] >= 1.0 && x[k] <= 64.0 && x[k] == std::floor(x[k]);
+                    if (ok) punctual_grid[k] = (uint32_t)x[k];
+                }
+            }
+            if (!ok) { std::cerr << "--punctual-selection must be uniform, grid or grid,NX,NY,NZ with whole numbers 1..64\n"; return 2; }
+        }
         else if (a == "--light-shafts") light_shafts = true;
         else if (a == "--mesh-light") {
             if (!parse_mesh_light(next(), mesh_light_v)) { std::cerr << "--mesh-light must be X,Y,Z,RADIUS[,R,G,B]: radius > 0, emission >= 0\n"; return 2; }
@@ -332,7 +348,7 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]]\n"
                          "  --sky: the scene's environment becomes a physical sky (Preetham daylight, a ground below the horizon and the sun's disc) baked on the GPU\n"
                          "           into a WIDTH x WIDTH/2 float map (default 2048): the sun stands ELEVATION_DEG above the horizon at AZIMUTH_DEG from +x towards +z,\n"
                          "           TURBIDITY 1.7 (clear) .. 10 (hazy), default 3. Works with --env-sampling (which finds the disc), --exposure, --tonemap, --out-hdr.\n"
@@ -351,6 +367,8 @@ int main(int argc, char** argv) {
                          "           0.5). They are invisible to the camera and every surface shadows them, glass included. Not with --env-sampling, --fog, --smoke,\n"
                          "           --interior, --dispersion, --light-sampling exact, --mesh-light or --motion. --light-shafts: the lights also light --fog and\n"
                          "           --smoke (a spot light's cone in haze, sun beams through a plume), which they are refused with otherwise; max_depth is at most 255 then\n"
+                         "           --punctual-selection grid: the branch picks its light by importance per cell of a grid over the scene (NX,NY,NZ cells, each 1..64;\n"
+                         "           automatic without them) instead of uniformly: for scenes with many lamps\n"
                          "  --stats: every kernel launch of a plain render is timed and its statistics are printed as one JSON line (tools/motion_eval.py reads it)\n"
                          "  --exposure, --tonemap, --white, --bloom: the film stage between the accumulator and the PNG: the image is scaled by 2^EV, light above the\n"
                          "           luminance THRESHOLD (default 1) spreads as glare of strength S (LEVELS Gaussians of SIGMA, 2 SIGMA, ... pixels; defaults 5 and 2),\n"
@@ -451,6 +469,8 @@ int main(int argc, char** argv) {
         for (const auto& x : suns) setup.world.add_punctual(DirectionalLight::new_(Vec3{x[0], x[1], x[2]}, Vec3{x[3], x[4], x[5]}));
         setup.world.punctual_fraction = punctual_fraction;
         setup.world.punctual_media = light_shafts;
+        setup.world.punctual_selection = punctual_selection;
+        for (int k = 0; k < 3; ++k) setup.world.punctual_grid[k] = punctual_grid[k];
         if (projection >= 2) setup.camera.defocus_angle = 0.0;   // the library refuses a lens there (pt_scene_set_projection's rule)
         if (mesh_light) {   // an emissive level-4 icosphere (5120 triangles), in the world and in the lights list
             auto ball = TriangleMesh::from_obj(1.0, icosphere(4, Vec3{mesh_light_v[0], mesh_light_v[1], mesh_light_v[2]}, mesh_light_v[3]),

@@ -556,6 +556,8 @@ struct World {
     std::vector<std::shared_ptr<PunctualLight>> punctual;   // this build's addition: the punctual lights (add_punctual)
     double punctual_fraction = 0.5;                         // ... and the selector's share of their branch (pt_scene_set_punctual_fraction)
     bool punctual_media = false;                            // ... and whether they light participating media (pt_scene_set_punctual_media: light shafts)
+    int punctual_selection = 0;                             // ... how their branch picks its light: 0 uniformly, 1 the light grid (pt_scene_set_punctual_selection)
+    uint32_t punctual_grid[3] = {0u, 0u, 0u};               // ... and the grid's dims, 0 0 0 = automatic, over the world's bounds (pt_scene_set_punctual_grid)
     template <class T> void add_punctual(std::shared_ptr<T> l) { punctual.push_back(l); }
     pt_scene* scene = nullptr;   // set by build_bvh / emit_into
     bool owns_scene = false;
@@ -577,6 +579,8 @@ struct World {
         for (auto& l : punctual) if (l->emit(s) < 0) panic("World::add_punctual");
         if (punctual_fraction != 0.5 && pt_scene_set_punctual_fraction(s, punctual_fraction) != 0) panic("set_punctual_fraction");
         if (punctual_media && pt_scene_set_punctual_media(s, 1) != 0) panic("set_punctual_media");
+        if (punctual_selection != 0 && pt_scene_set_punctual_selection(s, punctual_selection) != 0) panic("set_punctual_selection");
+        if (punctual_grid[0] != 0u && pt_scene_set_punctual_grid(s, punctual_grid[0], punctual_grid[1], punctual_grid[2], nullptr) != 0) panic("set_punctual_grid");
         if (camera_medium && pt_scene_set_camera_medium(s, camera_medium->medium(e)) != 0) panic("World::camera_medium");
         if (pt_world_build(s) != 0) panic("World::build_bvh");
         scene = s;
