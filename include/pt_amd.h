@@ -822,6 +822,64 @@ int pt_sky_probe(pt_ctx*, const pt_sky_opts*, const double* dirs, uint32_t n, do
 int pt_sky_bake(pt_ctx*, const pt_sky_opts*, uint32_t w, uint32_t h, float* rgb, int rgb_on_device);
 int pt_tex_sky(pt_scene*, const pt_sky_opts*, uint32_t w, uint32_t h);
 
+/* ---- mesh tessellation and displacement mapping (not in the reference, opt-in) ----
+ * A stage of its own in front of pt_mesh: a coarse mesh and a height image in, an ordinary fine mesh out. No render kernel knows of it.
+ * pt_mesh_tessellate runs on the GPU (csrc/pt_tess.hip), pt_mesh_tessellate_host is its host twin; the two return the same bytes.
+ * Input: pt_mesh's: f32 positions, u32 index triples, optional f32 normals and texcoords indexed by the position index. The attribute
+ *  arrays are brought to n = n_pos entries first (entries past n_pos dropped, missing ones zero: no index refers to them).
+ * Arithmetic: f64 on the f32 values widened, in the order written here, no fused operation; each written vertex attribute is rounded
+ *  to f32 once (so level l + 1 reads the f32 values level l wrote). sqrt and floor are the IEEE operations.
+ * One level, n vertices and F faces -> n + E vertices and 4F faces:
+ *  face f = (a, b, c) has the edges e0 = (a, b), e1 = (b, c), e2 = (c, a); an edge's key is (min << 32) | max (a == b is an edge like any
+ *  other). The E distinct keys in ascending order: the midpoint of the key of rank r is vertex n + r. Old vertices keep their indices,
+ *  unreferenced ones stay. Midpoint position and texcoord: (A + B) * 0.5 per component. Midpoint normal: s = A + B per component,
+ *  L = sqrt((s.x s.x + s.y s.y) + s.z s.z); L finite and > 0: s / L per component, else the normal of the endpoint with the smaller index.
+ *  Children, winding kept: 4f = (a, ab, ca), 4f + 1 = (ab, b, bc), 4f + 2 = (ca, bc, c), 4f + 3 = (ab, bc, ca).
+ * Smooth normals of a mesh: per vertex, the corners 3f + k that refer to it in ascending order; sum = 0, then sum += c_f componentwise
+ *  with c_f = (p1 - p0) x (p2 - p0) of face f (e1 = p1 - p0, e2 = p2 - p0, c = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z,
+ *  e1.x e2.y - e1.y e2.x)): area weighting. L as above; L finite and > 0: sum / L, else the normal the vertex had, else (0, 1, 0).
+ * Displacement (height != NULL), after the last level, per vertex with texcoord (u, v) and normal N: N is the carried (interpolated)
+ *  normal as stored, not renormalised; an input without normals gets the smooth normals of the subdivided, undisplaced mesh (rounded
+ *  to f32 like any attribute), and those are then its carried normals. The image is height_w x height_h f32, row 0 at v = 1.
+ *  wrap 0 (clamp): u, v clamped to [0, 1], texel indices clamped to the image; wrap 1 (repeat): u - floor(u), indices modulo W / H
+ *  (a true modulo). x = u W - 0.5, y = (1 - v) H - 0.5, i0 = floor(x), tx = x - i0, j0 = floor(y), ty = y - j0, i1 = i0 + 1, j1 = j0 + 1;
+ *  h = (h00 (1 - tx) + h10 tx) (1 - ty) + (h01 (1 - tx) + h11 tx) ty with hab = texel (ia, jb); d = scale (h - midlevel);
+ *  p' = p + N d per component. d = 0 where u, v or h is not finite.
+ * Normals written (`normals`): 0 auto = smooth when displacing, else the input's if it had any, else none; 1 keep = the carried
+ *  normals (none when there are none); 2 smooth = recomputed from the final positions (a vertex without a usable sum keeps its carried
+ *  normal); 3 none (pt_mesh then shades flat).
+ * Refused with -1 before any device work: a NULL output pointer or a NULL array with a count above 0; n_idx % 3 != 0; an index out of
+ *  range for any given array; a height without texcoords or with height_w or height_h = 0; levels > 12; 4^levels F > 0x07FFFFFF
+ *  (pt_mesh's cap); n + (4^levels - 1) F > 2^32 - 1 (that bounds n + E at every level); an unknown wrap or normals value. NULL options
+ *  mean the defaults. NaN and infinite positions, normals, texcoords and texels are data. Outputs are malloc'd: free them with pt_free;
+ *  *out_nrm / *out_uv are NULL where there is none; *out_n_idx counts indices. A failed device allocation returns -1 with nothing held.
+ * Device memory, per level of F faces and n vertices: the two meshes (32 B a vertex with both attributes, 12 B a face, old and new)
+ *  plus 108 B a face of edge keys, slots, flags, ranks and midpoint indices, and the radix sort's own buffer. A mesh whose vertices are duplicated along texcoord seams
+ *  (pt_load_obj_single_index) cracks there under displacement: the duplicates move along different normals. Welding is not done here. */
+typedef struct pt_tess_opts {
+    uint32_t levels;               /* 0..12. Default 1 */
+    uint32_t height_w, height_h;
+    const float* height;           /* NULL: no displacement */
+    double scale, midlevel;        /* Defaults 1 and 0.5 */
+    int wrap;                      /* 0 clamp (default), 1 repeat */
+    int normals;                   /* 0 auto (default), 1 keep, 2 smooth, 3 none */
+} pt_tess_opts;
+int pt_tess_opts_default(pt_tess_opts*);
+int pt_mesh_tessellate(pt_ctx*, const pt_tess_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                       uint32_t n_nrm, const float* nrm, uint32_t n_uv, const float* uv,
+                       float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx, float** out_nrm, float** out_uv);
+int pt_mesh_tessellate_host(const pt_tess_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                            uint32_t n_nrm, const float* nrm, uint32_t n_uv, const float* uv,
+                            float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx, float** out_nrm, float** out_uv);
+/* host only: the drop-in mesh for pt_quad(q, u, v). Vertex (i, j), 0 <= i <= nu, 0 <= j <= nv, has index j (nu + 1) + i, position
+ * (q + u (i / nu)) + v (j / nv) and texcoord (i / nu, j / nv), all f64 rounded to f32 once; every vertex has the normal c / L,
+ * c = cross(u, v), L as above. Cell (i, j) has the faces (v00, v10, v11) and (v00, v11, v01), cells in row order. -1 for nu or nv = 0,
+ * more than 0x07FFFFFF faces, or u x v without a finite length above 0. */
+int pt_mesh_grid(const double q[3], const double u[3], const double v[3], uint32_t nu, uint32_t nv,
+                 float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx, float** out_nrm, float** out_uv);
+/* host only: w x h RGB8 -> w x h heights ((0.2126 r + 0.7152 g) + 0.0722 b) / 255, f64 rounded to f32 */
+int pt_height_from_rgb8(uint32_t w, uint32_t h, const uint8_t* rgb, float* out);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

@@ -156,6 +156,38 @@ class SkyOpts(C.Structure):
         super().__init__(_d3(sun_dir), turbidity, _d3(ground_albedo), sun_radius_deg, sun_scale, scale)
 
 
+TESS_WRAPS = {"clamp": 0, "repeat": 1}                          # pt_tess_opts.wrap
+TESS_NORMALS = {"auto": 0, "keep": 1, "smooth": 2, "none": 3}   # pt_tess_opts.normals
+
+
+class TessOpts(C.Structure):
+    """pt_tess_opts: subdivision levels, the height image and how it displaces, which normals are written (include/pt_amd.h has the
+    rule). A fresh instance holds the defaults: one level, no displacement. `height` is an (H, W) float32 image, row 0 at v = 1; the
+    instance keeps it alive."""
+
+    _fields_ = [
+        ("levels", C.c_uint32),
+        ("height_w", C.c_uint32),
+        ("height_h", C.c_uint32),
+        ("height", C.c_void_p),
+        ("scale", C.c_double),
+        ("midlevel", C.c_double),
+        ("wrap", C.c_int),
+        ("normals", C.c_int),
+    ]
+
+    def __init__(self, levels=1, height=None, scale=1.0, midlevel=0.5, wrap="clamp", normals="auto"):
+        wrap = TESS_WRAPS.get(wrap, wrap)
+        normals = TESS_NORMALS.get(normals, normals)
+        if height is None:
+            super().__init__(levels, 0, 0, None, scale, midlevel, wrap, normals)
+        else:
+            self._height = np.ascontiguousarray(height, dtype=np.float32)
+            if self._height.ndim != 2:
+                raise ValueError("height must be an (H, W) image")
+            super().__init__(levels, self._height.shape[1], self._height.shape[0], self._height.ctypes.data, scale, midlevel, wrap, normals)
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -186,6 +218,7 @@ ABI_SYMBOLS = [
     "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval", "pt_scene_set_punctual_media", "pt_scene_punctual_media",
     "pt_scene_set_punctual_selection", "pt_scene_punctual_selection", "pt_scene_set_punctual_grid", "pt_scene_punctual_grid", "pt_punctual_grid_row", "pt_punctual_grid_select",
     "pt_sky_opts_default", "pt_sky_opts_check", "pt_sky_eval", "pt_sky_sun_irradiance", "pt_sky_probe", "pt_sky_bake", "pt_tex_sky",
+    "pt_tess_opts_default", "pt_mesh_tessellate", "pt_mesh_tessellate_host", "pt_mesh_grid", "pt_height_from_rgb8",
 ]
 
 
@@ -349,6 +382,15 @@ def _load():
         lib.pt_sky_probe.argtypes = [C.c_void_p, C.POINTER(SkyOpts), C.c_void_p, C.c_uint32, C.c_void_p]
         lib.pt_sky_bake.argtypes = [C.c_void_p, C.POINTER(SkyOpts), C.c_uint32, C.c_uint32, C.c_void_p, C.c_int]
         lib.pt_tex_sky.argtypes = [C.c_void_p, C.POINTER(SkyOpts), C.c_uint32, C.c_uint32]
+    if hasattr(lib, "pt_mesh_tessellate"):         # (absent from an older build in an A/B run: PT_AMD_LIB)
+        fpp, upp, up = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)
+        mesh_in = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        mesh_out = [fpp, up, upp, up, fpp, fpp]
+        lib.pt_tess_opts_default.argtypes = [C.POINTER(TessOpts)]
+        lib.pt_mesh_tessellate.argtypes = [C.c_void_p, C.POINTER(TessOpts)] + mesh_in + mesh_out
+        lib.pt_mesh_tessellate_host.argtypes = [C.POINTER(TessOpts)] + mesh_in + mesh_out
+        lib.pt_mesh_grid.argtypes = [d3, d3, d3, C.c_uint32, C.c_uint32] + mesh_out
+        lib.pt_height_from_rgb8.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -492,6 +534,12 @@ class Context:
         _check(lib.pt_sky_bake(self.handle, C.byref(o), w, h, out.ctypes.data, 0), "pt_sky_bake")
         return out
 
+    def tessellate(self, pos, idx, nrm=None, uv=None, levels=1, height=None, scale=1.0, midlevel=0.5, wrap="clamp", normals="auto"):
+        """pt_mesh_tessellate: `levels` 1-to-4 subdivisions of a triangle mesh on the GPU, then displacement along the normals by the
+        (H, W) float32 image `height` (scale * (h - midlevel)) -> (pos, idx, nrm | None, uv | None), ready for Scene.mesh.
+        wrap: "clamp" / "repeat"; normals: "auto" / "keep" / "smooth" / "none" (include/pt_amd.h has the rule)."""
+        return _tessellate(self.handle, pos, idx, nrm, uv, TessOpts(levels, height, scale, midlevel, wrap, normals))
+
     def sky_probe(self, dirs: np.ndarray, **opts) -> np.ndarray:
         """pt_sky_probe: sky_eval by the bake kernel's device function: (n, 3) unit directions -> (n, 3) radiance, no disc."""
         dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
@@ -499,6 +547,77 @@ class Context:
         o = SkyOpts(**opts)
         _check(lib.pt_sky_probe(self.handle, C.byref(o), dirs.ctypes.data, len(dirs), out.ctypes.data), "pt_sky_probe")
         return out
+
+
+class _MeshOut:
+    """The six outputs of pt_mesh_tessellate / pt_mesh_grid: handed to the call by reference, copied into arrays, freed with pt_free."""
+
+    def __init__(self):
+        self.pos, self.idx, self.nrm, self.uv = C.POINTER(C.c_float)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)()
+        self.n_pos, self.n_idx = C.c_uint32(), C.c_uint32()
+
+    def refs(self):
+        return (C.byref(self.pos), C.byref(self.n_pos), C.byref(self.idx), C.byref(self.n_idx), C.byref(self.nrm), C.byref(self.uv))
+
+    def take(self):
+        n, m = self.n_pos.value, self.n_idx.value
+        arr = lambda p, k, dt: np.ctypeslib.as_array(p, (n * k,)).copy().reshape(-1, k) if n else np.zeros((0, k), dt)
+        out = (arr(self.pos, 3, np.float32), np.ctypeslib.as_array(self.idx, (m,)).copy() if m else np.zeros(0, np.uint32),
+               arr(self.nrm, 3, np.float32) if self.nrm else None, arr(self.uv, 2, np.float32) if self.uv else None)
+        self.free()
+        return out
+
+    def free(self):
+        for p in (self.pos, self.idx, self.nrm, self.uv):
+            if p:
+                lib.pt_free(p)
+
+
+def _mesh_in(pos, idx, nrm, uv):
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    nrm = None if nrm is None else np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3)
+    uv = None if uv is None else np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    args = (len(pos), pos.ctypes.data, len(idx), idx.ctypes.data, 0 if nrm is None else len(nrm), None if nrm is None else nrm.ctypes.data,
+            0 if uv is None else len(uv), None if uv is None else uv.ctypes.data)
+    return args, (pos, idx, nrm, uv)   # (the arrays: kept alive by the caller for the length of the call)
+
+
+def _tessellate(ctx, pos, idx, nrm, uv, opts):
+    args, keep = _mesh_in(pos, idx, nrm, uv)
+    out = _MeshOut()
+    if ctx is None:
+        rc = lib.pt_mesh_tessellate_host(C.byref(opts), *args, *out.refs())
+    else:
+        rc = lib.pt_mesh_tessellate(ctx, C.byref(opts), *args, *out.refs())
+    if rc < 0:
+        out.free()
+    _check(rc, "pt_mesh_tessellate_host" if ctx is None else "pt_mesh_tessellate")
+    return out.take()
+
+
+def tessellate_host(pos, idx, nrm=None, uv=None, levels=1, height=None, scale=1.0, midlevel=0.5, wrap="clamp", normals="auto"):
+    """pt_mesh_tessellate_host: Context.tessellate on the host, the same bytes (no context needed)."""
+    return _tessellate(None, pos, idx, nrm, uv, TessOpts(levels, height, scale, midlevel, wrap, normals))
+
+
+def mesh_grid(q, u, v, nu: int, nv: int):
+    """pt_mesh_grid: the (nu x nv)-cell triangle mesh that stands in for pt_quad(q, u, v) -> (pos, idx, nrm, uv)."""
+    out = _MeshOut()
+    rc = lib.pt_mesh_grid(_d3(q), _d3(u), _d3(v), nu, nv, *out.refs())
+    if rc < 0:
+        out.free()
+    _check(rc, "pt_mesh_grid")
+    return out.take()
+
+
+def height_from_rgb8(rgb8: np.ndarray) -> np.ndarray:
+    """pt_height_from_rgb8: (H, W, 3) uint8 -> (H, W) float32 Rec. 709 luminance in [0, 1]: a height image for tessellate."""
+    rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
+    h, w = rgb8.shape[:2]
+    out = np.empty((h, w), np.float32)
+    _check(lib.pt_height_from_rgb8(w, h, rgb8.ctypes.data, out.ctypes.data), "pt_height_from_rgb8")
+    return out
 
 
 def sky_eval(dirs: np.ndarray, **opts) -> np.ndarray:

@@ -168,6 +168,39 @@ static Mesh icosphere(int level, Vec3 centre, double radius) {
     return m;
 }
 
+// --displace: the Quad of the scene whose material carries a normal map gives way to a tessellated, displaced grid mesh of the same q, u, v
+// with the same base colour and no normal map. v = SCALE[, LEVELS[, MIDLEVEL]].
+static void displace_brick_wall(World& world, pt_ctx* ctx, const std::string& file, const std::string& asset_dir, const std::vector<double>& v) {
+    std::string path = file;
+    if (!std::ifstream(path)) {   // "assets/bricks/color.png" the way the scene scripts name their images: relative to --assets
+        const std::string prefix = "assets/";
+        path = asset_dir + "/" + (file.compare(0, prefix.size(), prefix) == 0 ? file.substr(prefix.size()) : file);
+    }
+    uint8_t* rgb = nullptr;
+    uint32_t w = 0, h = 0;
+    const bool jpeg = (path.size() > 4 && path.substr(path.size() - 4) == ".jpg") || (path.size() > 5 && path.substr(path.size() - 5) == ".jpeg");
+    if ((jpeg ? pt_load_jpeg_rgb8(path.c_str(), &rgb, &w, &h) : pt_load_png_rgb8(path.c_str(), &rgb, &w, &h)) != 0) panic("--displace " + file);
+    std::vector<float> height((size_t)w * h);
+    pt_height_from_rgb8(w, h, rgb, height.data());
+    pt_free(rgb);
+    pt_tess_opts o;
+    pt_tess_opts_default(&o);
+    o.levels = v.size() > 1 ? (uint32_t)v[1] : 2u;
+    o.height_w = w;
+    o.height_h = h;
+    o.height = height.data();
+    o.scale = v[0];
+    if (v.size() > 2) o.midlevel = v[2];
+    for (auto& obj : world.objects) {
+        auto quad = std::dynamic_pointer_cast<Quad>(obj);
+        auto mat = quad ? std::dynamic_pointer_cast<DiffuseBRDF>(quad->material) : nullptr;
+        if (!mat || !mat->normal_map) continue;
+        obj = TriangleMesh::from_obj(1.0, Mesh::grid(quad->q, quad->u, quad->v, 64, 64).tessellated(ctx, o), DiffuseBRDF::from_textures(mat->base_color, nullptr));
+        return;
+    }
+    throw std::runtime_error("--displace: the scene has no wall with a normal-mapped material");
+}
+
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
@@ -199,6 +232,9 @@ int main(int argc, char** argv) {
     Film film;   // --exposure, --tonemap, --white, --bloom, --out-hdr
     bool sky = false, sky_no_disc = false;   // --sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]], --sky-no-disc
     std::vector<double> sky_v;
+    bool displace = false;                   // --displace FILE,SCALE[,LEVELS[,MIDLEVEL]]
+    std::string displace_file;
+    std::vector<double> displace_v;
     uint64_t seed = 1;
     std::string out, assets = "assets";
     for (int i = 1; i < argc; ++i) {
@@ -343,12 +379,26 @@ int main(int argc, char** argv) {
             sky = true;
         }
         else if (a == "--sky-no-disc") sky_no_disc = true;
+        else if (a == "--displace") {
+            const std::string v = next();
+            const size_t comma = v.find(',');
+            displace_file = v.substr(0, comma);
+            if (comma == std::string::npos || displace_file.empty() || !parse_numbers(v.substr(comma + 1), 1, 3, displace_v) ||
+                (displace_v.size() > 1 && (displace_v[1] < 0.0 || displace_v[1] > 12.0 || displace_v[1] != std::floor(displace_v[1])))) {
+                std::cerr << "--displace must be FILE,SCALE[,LEVELS[,MIDLEVEL]]: finite numbers, LEVELS a whole one in 0..12\n";
+                return 2;
+            }
+            displace = true;
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]]\n"
+                         "  --displace: scene 7 only: the wall that carries the normal-mapped bricks becomes a 64 x 64 grid mesh, subdivided LEVELS times (default 2) on\n"
+                         "           the GPU and pushed along its normal by SCALE * (luminance of the PNG or JPEG image FILE - MIDLEVEL) (MIDLEVEL default 0.5): real relief\n"
+                         "           with a silhouette and shadows; the wall keeps the brick colours and drops the normal map\n"
                          "  --sky: the scene's environment becomes a physical sky (Preetham daylight, a ground below the horizon and the sun's disc) baked on the GPU\n"
                          "           into a WIDTH x WIDTH/2 float map (default 2048): the sun stands ELEVATION_DEG above the horizon at AZIMUTH_DEG from +x towards +z,\n"
                          "           TURBIDITY 1.7 (clear) .. 10 (hazy), default 3. Works with --env-sampling (which finds the disc), --exposure, --tonemap, --out-hdr.\n"
@@ -418,6 +468,7 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (displace && scene != 7) { std::cerr << "--displace works on scene 7 only (the wall with the normal-mapped bricks)\n"; return 2; }
     pt_sky_opts sky_opts;
     uint32_t sky_width = 2048;
     pt_sky_opts_default(&sky_opts);
@@ -455,6 +506,12 @@ int main(int argc, char** argv) {
     try {
         SceneSetup setup = make_scene(scene, w, s, assets, 1);
         setup.world.float_hdr = float_hdr;
+        if (displace) {
+            displace_brick_wall(setup.world, ctx, displace_file, assets, displace_v);
+            // the wall goes to the host's SAH builder at every size: from 2^19 triangles on it would get the device's LBVH, whose depth under the
+            // scene's other entries can pass the traversal stack
+            setup.world.device_bvh_threshold = 0;
+        }
         if (sky) setup.camera.environment = EnvironmentType::Map(Sky::new_(sky_opts, sky_width, sky_width / 2));
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;

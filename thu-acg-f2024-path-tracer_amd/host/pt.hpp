@@ -341,6 +341,35 @@ struct Cuboid : Hittable {   // cuboid.rs:11-58
 struct Mesh {
     std::vector<float> positions, normals, texcoords;
     std::vector<uint32_t> indices;
+    // not in the reference: mesh tessellation and displacement (include/pt_amd.h has the rule).
+    // grid: the (nu x nv)-cell mesh that stands in for Quad::new_(q, u, v, ..) (pt_mesh_grid); tessellated: `opts.levels` subdivisions and
+    // the displacement by opts.height on the GPU (pt_mesh_tessellate). Hand either to TriangleMesh::from_obj.
+    static Mesh grid(Vec3 q, Vec3 u, Vec3 v, uint32_t nu, uint32_t nv) {
+        const double a[3] = {q.x, q.y, q.z}, b[3] = {u.x, u.y, u.z}, c[3] = {v.x, v.y, v.z};
+        float *pos, *nrm, *uv;
+        uint32_t *idx, np, ni;
+        if (pt_mesh_grid(a, b, c, nu, nv, &pos, &np, &idx, &ni, &nrm, &uv) != 0) panic("Mesh::grid");
+        return take(pos, np, idx, ni, nrm, uv);
+    }
+    Mesh tessellated(pt_ctx* ctx, const pt_tess_opts& opts) const {
+        float *pos, *nrm, *uv;
+        uint32_t *idx, np, ni;
+        if (pt_mesh_tessellate(ctx, &opts, (uint32_t)(positions.size() / 3), positions.data(), (uint32_t)indices.size(), indices.data(), (uint32_t)(normals.size() / 3),
+                               normals.data(), (uint32_t)(texcoords.size() / 2), texcoords.data(), &pos, &np, &idx, &ni, &nrm, &uv) != 0)
+            panic("Mesh::tessellated");
+        return take(pos, np, idx, ni, nrm, uv);
+    }
+
+private:
+    static Mesh take(float* pos, uint32_t np, uint32_t* idx, uint32_t ni, float* nrm, float* uv) {
+        Mesh m;
+        m.positions.assign(pos, pos + 3 * (size_t)np);
+        m.indices.assign(idx, idx + ni);
+        if (nrm) m.normals.assign(nrm, nrm + 3 * (size_t)np);
+        if (uv) m.texcoords.assign(uv, uv + 2 * (size_t)np);
+        pt_free(pos); pt_free(idx); pt_free(nrm); pt_free(uv);
+        return m;
+    }
 };
 namespace tobj {
 struct Model { Mesh mesh; };
@@ -601,6 +630,9 @@ struct World {
     // this build's options (motion blur of instances): the camera shutter (pt_scene_set_shutter), and a second key applied to every Instance a
     // scene script makes: tr1 = tr0 + motion[0..2], angle1 = angle0 + motion[3] radians (pt_render --motion)
     double shutter[2] = {0.0, 1.0};
+    // this build's option: meshes of at least this many triangles get the GPU's LBVH builder (pt_world_set_device_bvh_threshold; 0 = always the
+    // host's binned-SAH builder, -1 = the library's default)
+    long long device_bvh_threshold = -1;
     bool instance_motion = false;
     double motion[4] = {0.0, 0.0, 0.0, 0.0};
     void build_bvh(pt_ctx* ctx, std::shared_ptr<ImageTexture> env = nullptr) {
@@ -613,6 +645,7 @@ struct World {
         if (light_sampling != 0 && pt_scene_set_light_sampling(s, light_sampling) != 0) panic("set_light_sampling");
         if (projection != 0 && pt_scene_set_projection(s, projection) != 0) panic("set_projection");
         if ((shutter[0] != 0.0 || shutter[1] != 1.0) && pt_scene_set_shutter(s, shutter[0], shutter[1]) != 0) panic("set_shutter");
+        if (device_bvh_threshold >= 0 && pt_world_set_device_bvh_threshold(s, (uint32_t)device_bvh_threshold) != 0) panic("set_device_bvh_threshold");
         emit_into(s, env);
     }
     void release() {
