@@ -67,9 +67,17 @@ typedef struct pt_render_stats {
        `samples` and `segments` as well; the other samples of those tiles (hard_samples) are the path pool's; the HIP-event time of the pass's
        kernel (profile=1). All zero when the pass is off. (In front of the sky pass's fields, which stay the structure's last: a caller built
        against the header before these four must be rebuilt, the sky fields' offsets having moved by 32 bytes.)
-       Device memory: the pass keeps a list sized for EVERY sample of the tiles it takes (4 bytes each, 8 where tile, pixel and sample do not
-       fit in 32 bits), capped at the bytes of the path pool's records — scene 6 at 1920x1080 @ 4000 spp: 7.9 GB beside a 27 GB pool; where the
+       Device memory: the pass keeps a list sized for EVERY sample of the tiles it takes by proof (4 bytes each, 8 where tile, pixel and sample do not
+       fit in 32 bits; the tiles taken by yield add what short_list_bytes says), capped at the bytes of the path pool's records — scene 6 at 1920x1080 @ 4000 spp: 7.9 GB beside a 27 GB pool; where the
        cap binds the pass takes fewer tiles. PT_EXPERIMENT=1 PT_SHORT_CAP_BYTES=n lowers the cap for a host with less memory. */
+    /* the pass's yield pilot: on a sample range of 256 samples per pixel or more the pass first renders 8 samples of every tile
+       of the path pool's, counting only, and takes the tiles it finishes half of as well. pilot_tiles: the tiles taken that way (counted in
+       short_tiles too); short_fallback: 1 when the pass found more hard samples than its list held and ran again with the proven tiles alone
+       (pilot_tiles is then 0); short_list_bytes: the bytes of the hard list — every sample of the proven tiles, and of the taken tiles 1.5
+       times the pilot's projection and 64 entries per tile; short_pixels: the pixels of the short tiles that lie inside the image
+       (short_samples + hard_samples = short_pixels x the samples per pixel); ms_pilot: the HIP-event time of the pilot's kernel (profile=1). */
+    uint64_t pilot_tiles, short_fallback, short_list_bytes, short_pixels;
+    double ms_pilot;
     uint64_t short_tiles, short_samples, hard_samples;
     double ms_short;
     uint64_t sky_tiles, sky_samples;

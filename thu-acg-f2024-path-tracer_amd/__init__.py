@@ -79,6 +79,11 @@ class RenderStats(C.Structure):
         ("blocks_shade", C.c_uint32),
         ("compactions", C.c_uint32),
         ("n_alloc_end", C.c_uint32),
+        ("pilot_tiles", C.c_uint64),
+        ("short_fallback", C.c_uint64),
+        ("short_list_bytes", C.c_uint64),
+        ("short_pixels", C.c_uint64),
+        ("ms_pilot", C.c_double),
         ("short_tiles", C.c_uint64),
         ("short_samples", C.c_uint64),
         ("hard_samples", C.c_uint64),

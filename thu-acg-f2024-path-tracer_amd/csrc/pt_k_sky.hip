@@ -20,14 +20,15 @@ __global__ __launch_bounds__(BLOCK) void k_sky_classify(SkyCam cam, uint32_t n_b
 // Thread i ranks the tiles [i * per, (i + 1) * per): the three lists come out in tile order. Of the SHORT tiles the first max_short (in
 // tile order) go to short_list; the others stay the wavefront's (the hard list's cap). counts[0] = active tiles, [1] =
 // sure-sky tiles, [2] = the pixels of the sure-sky tiles that lie inside the image, [3] = short tiles taken, [4] = their pixels inside the
-// image, [5] = short tiles found.
+// image, [5] = short tiles found (proven ones: SKY_TILE_SHORT). A tile k_short_select took by its pilot yield (SKY_TILE_TAKEN)
+// is listed with the proven ones, in tile order, and counted in [3] and [4]; [6] = those tiles alone, [7] = their pixels inside the image.
 __global__ __launch_bounds__(BLOCK) void k_sky_scan(const uint8_t* flags, uint32_t n_tiles, uint32_t width, uint32_t height, uint32_t max_short, uint32_t* tile_map,
                                                      uint32_t* sky_list, uint32_t* short_list, uint32_t* counts) {
-    __shared__ uint32_t s_sky[BLOCK], s_short[BLOCK], s_pixels, s_short_pixels;
+    __shared__ uint32_t s_sky[BLOCK], s_short[BLOCK], s_pixels, s_short_pixels, s_proven, s_taken, s_taken_pixels;
     const uint32_t tiles_x = (width + 7u) / 8u;
     const uint32_t per = (n_tiles + BLOCK - 1) / BLOCK, t0 = threadIdx.x * per, t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
-    uint32_t mine = 0, mine_short = 0, pixels = 0;
-    if (threadIdx.x == 0) s_pixels = s_short_pixels = 0;
+    uint32_t mine = 0, mine_short = 0, pixels = 0, proven = 0;
+    if (threadIdx.x == 0) s_pixels = s_short_pixels = s_proven = s_taken = s_taken_pixels = 0;
     auto tile_pixels = [&](uint32_t t) {
         uint32_t ty, tx;
         divmod_u31(t, tiles_x, ty, tx);
@@ -38,14 +39,16 @@ __global__ __launch_bounds__(BLOCK) void k_sky_scan(const uint8_t* flags, uint32
         if (flags[t] == SKY_TILE_SKY) {
             ++mine;
             pixels += tile_pixels(t);
-        } else if (flags[t] == SKY_TILE_SHORT) {
+        } else if (flags[t] == SKY_TILE_SHORT || flags[t] == SKY_TILE_TAKEN) {
             ++mine_short;
+            if (flags[t] == SKY_TILE_SHORT) ++proven;
         }
     }
     s_sky[threadIdx.x] = mine;
     s_short[threadIdx.x] = mine_short;
     __syncthreads();
     if (pixels) atomicAdd(&s_pixels, pixels);
+    if (proven) atomicAdd(&s_proven, proven);
     for (uint32_t d = 1; d < BLOCK; d <<= 1) {   // inclusive scans of the threads' sky and short counts
         const uint32_t v = threadIdx.x >= d ? s_sky[threadIdx.x - d] : 0u, u = threadIdx.x >= d ? s_short[threadIdx.x - d] : 0u;
         __syncthreads();
@@ -55,18 +58,26 @@ __global__ __launch_bounds__(BLOCK) void k_sky_scan(const uint8_t* flags, uint32
     }
     uint32_t sky_at = s_sky[threadIdx.x] - mine, short_at = s_short[threadIdx.x] - mine_short;
     uint32_t act_at = (t0 < n_tiles ? t0 : n_tiles) - sky_at - (short_at < max_short ? short_at : max_short);
-    uint32_t short_pixels = 0;
+    uint32_t short_pixels = 0, by_yield = 0, by_yield_pixels = 0;
     for (uint32_t t = t0; t < t1; ++t) {
         if (flags[t] == SKY_TILE_SKY) {
             sky_list[sky_at++] = t;
-        } else if (flags[t] == SKY_TILE_SHORT && short_at++ < max_short) {
+        } else if ((flags[t] == SKY_TILE_SHORT || flags[t] == SKY_TILE_TAKEN) && short_at++ < max_short) {
             short_list[short_at - 1u] = t;
             short_pixels += tile_pixels(t);
+            if (flags[t] == SKY_TILE_TAKEN) {
+                ++by_yield;
+                by_yield_pixels += tile_pixels(t);
+            }
         } else {
             tile_map[act_at++] = t;
         }
     }
     if (short_pixels) atomicAdd(&s_short_pixels, short_pixels);
+    if (by_yield) {
+        atomicAdd(&s_taken, by_yield);
+        atomicAdd(&s_taken_pixels, by_yield_pixels);
+    }
     __syncthreads();
     if (threadIdx.x == BLOCK - 1) {
         const uint32_t n_short = s_short[BLOCK - 1], taken = n_short < max_short ? n_short : max_short;
@@ -75,7 +86,9 @@ __global__ __launch_bounds__(BLOCK) void k_sky_scan(const uint8_t* flags, uint32
         counts[2] = s_pixels;
         counts[3] = taken;
         counts[4] = s_short_pixels;
-        counts[5] = n_short;
+        counts[5] = s_proven;
+        counts[6] = s_taken;
+        counts[7] = s_taken_pixels;
     }
 }
 
@@ -128,6 +141,11 @@ void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxe
                          uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, hipStream_t st) {
     hipLaunchKernelGGL(k_sky_classify, dim3((n_tiles + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, cam, n_boxes, boxes6, shadeable, (cam.width + 7u) / 8u, n_tiles, flags);
     hipLaunchKernelGGL(k_sky_scan, dim3(1), dim3(BLOCK), 0, st, flags, n_tiles, cam.width, cam.height, max_short, tile_map, sky_list, short_list, counts);
+}
+// the scan alone, over flags k_short_select has changed
+void launch_sky_scan(uint32_t width, uint32_t height, uint32_t max_short, uint32_t n_tiles, const uint8_t* flags, uint32_t* tile_map, uint32_t* sky_list,
+                     uint32_t* short_list, uint32_t* counts, hipStream_t st) {
+    hipLaunchKernelGGL(k_sky_scan, dim3(1), dim3(BLOCK), 0, st, flags, n_tiles, width, height, max_short, tile_map, sky_list, short_list, counts);
 }
 void launch_sky(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, const uint32_t* sky_list, uint32_t n_sky, uint32_t chunk,
                 hipStream_t st) {

@@ -71,7 +71,11 @@ void launch_detile(const PoolD& pool, double* accum, int max_blocks, hipStream_t
 struct SkyCam;
 void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, uint32_t max_short, uint32_t n_tiles, uint8_t* flags,
                          uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, hipStream_t st);
+void launch_sky_scan(uint32_t width, uint32_t height, uint32_t max_short, uint32_t n_tiles, const uint8_t* flags, uint32_t* tile_map, uint32_t* sky_list,
+                     uint32_t* short_list, uint32_t* counts, hipStream_t st);   // (the scan of launch_sky_classify alone; counts: 8 words)
 void launch_short(const SceneD& sc, const CamD& cam, const PoolD& pool, uint64_t seed, const ShortArgsD& a, hipStream_t st);
+// the pilot's selection (pt_k_short.hip k_short_select): flags of the piloted wavefront tiles -> SKY_TILE_TAKEN where the yield bin >= min_bin; hist: 3 * SHORT_YIELD_BINS words
+void launch_short_select(uint8_t* flags, uint32_t n_tiles, const uint32_t* pilot, uint32_t min_bin, uint32_t* hist, hipStream_t st);
 void launch_sky(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, const uint32_t* sky_list, uint32_t n_sky, uint32_t chunk,
                 hipStream_t st);
 // pt_adaptive.hip: the adaptive render's per-round kernels (see there)

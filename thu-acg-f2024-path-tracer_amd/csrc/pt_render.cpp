@@ -173,8 +173,8 @@ struct EventTimer {   // per-launch HIP-event timing, drained at the polling syn
     };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_list;
-    double ms[5] = {0, 0, 0, 0, 0};   // K2, K3, the small kernels, k_sky, k_short
-    uint64_t launches[5] = {0, 0, 0, 0, 0};
+    double ms[6] = {0, 0, 0, 0, 0, 0};   // K2, K3, the small kernels, k_sky, k_short, k_short's pilot
+    uint64_t launches[6] = {0, 0, 0, 0, 0, 0};
     bool enabled = false;
     hipEvent_t get() {
         if (!free_list.empty()) {
@@ -394,10 +394,21 @@ struct Job {
     const uint32_t* shade_prims = nullptr;
     unsigned long long* short_words = nullptr;   // k_short's three device words (ShortArgsD::n_hard)
     ShortHdrD short_hdr;   // the record behind the tile map (run_short)
+    // the yield pilot (DESIGN.md §23 "Taking tiles by yield"; classify_sky, select_by_yield): it ran; the tiles it added to the short list and
+    // their pixels inside the image; the entries the hard list holds (the proven tiles' worst case + the taken tiles' projection with its
+    // margin); the pass overflowed that list and ran again with the proven tiles alone; the miss proof's stack budget; the classification's
+    // device buffers, which the fallback selects from once more
+    bool pilot_ran = false, short_fallback = false;
+    uint32_t n_pilot_tiles = 0, n_pilot_pixels = 0, walk_cap = SHORT_WALK_STACK, n_tiles = 0;
+    uint64_t short_cap_entries = 0;
+    uint8_t* d_flags = nullptr;
+    uint32_t *d_counts = nullptr, *d_pilot = nullptr, *d_hist = nullptr, *d_tile_map = nullptr, *d_sky_list = nullptr, *d_short_list = nullptr;
     ShadeForm form;   // the form of K1 / K3 this render launches (render_core; classify_sky and choose_kernels both read this one)
 };
 
 // Every experiment switch of a render (exp_env: read under PT_EXPERIMENT=1 only), read once. An explicit option wins over its switch.
+constexpr uint32_t PILOT_SAMPLES = 8, PILOT_MIN = 256;   // the yield pilot's samples per pixel; the shortest sample range it runs on
+constexpr double PILOT_THETA = 0.5;                      // the pilot yield from which a tile is taken
 struct Switches {
     uint32_t slots_per_pixel = 0;   // opts.slots_per_pixel, else PT_SLOTS_PER_PIXEL
     bool pool_slots_set = false;    // PT_POOL_SLOTS: the dynamic pool's size (plan_pool refuses 0)
@@ -409,6 +420,14 @@ struct Switches {
     bool pool_in_place = false, no_defer_regen = false, no_compact_records = false, init_shuffle = false, accum_linear = false, no_compact_pool = false,
          prof = false, no_sky_pass = false, no_short_pass = false;   // no_sky_pass: PT_SKY_PASS=0; no_short_pass: PT_SHORT_PASS=0
     uint64_t short_cap_bytes = 0;   // PT_SHORT_CAP_BYTES: the hard list's byte cap in place of the pool's bytes (0: not set)
+    // the yield pilot of the short-path pass: PT_SHORT_PILOT=0 turns it off (the A/B switch inside one library);
+    // PT_PILOT_ANY_RANGE=1 lets it run on a sample range shorter than PILOT_MIN; PT_PILOT_THETA=x: tiles are taken from a pilot yield of x
+    // (read in sixteenths, rounded up); PT_PILOT_MARGIN=x: the taken tiles' part of the hard list is x times the projection and nothing
+    // more (default: 1.5 times and 64 entries per tile); PT_PILOT_STACK=n: the miss proof's stack budget, 0 .. SHORT_WALK_STACK entries;
+    // PT_PILOT_NARROW=1: no more tiles than 4-byte list entries address
+    bool no_pilot = false, pilot_any_range = false, pilot_margin_set = false, pilot_narrow = false;
+    double pilot_theta = PILOT_THETA, pilot_margin = 1.5;
+    uint32_t walk_cap = SHORT_WALK_STACK;
     int grid_mult = 1;   // persistent grids: resident blocks per CU x CUs x this
     uint32_t wide_window_min = 16;
     int ext2 = 0;        // PT_EXT2 = stack*10 + blocks per CU picks the two-phase K2's instantiation (0: not set)
@@ -442,6 +461,12 @@ Switches read_switches(const pt_render_opts& opts) {
     if (const char* e = exp_env("PT_SKY_PASS")) sw.no_sky_pass = atoi(e) == 0;
     if (const char* e = exp_env("PT_SHORT_PASS")) sw.no_short_pass = atoi(e) == 0;
     if (const char* e = exp_env("PT_SHORT_CAP_BYTES")) sw.short_cap_bytes = strtoull(e, nullptr, 10);
+    if (const char* e = exp_env("PT_SHORT_PILOT")) sw.no_pilot = atoi(e) == 0;
+    if (const char* e = exp_env("PT_PILOT_ANY_RANGE")) sw.pilot_any_range = atoi(e) != 0;
+    if (const char* e = exp_env("PT_PILOT_THETA")) sw.pilot_theta = atof(e);
+    if (const char* e = exp_env("PT_PILOT_MARGIN")) { sw.pilot_margin_set = true; sw.pilot_margin = std::max(0.0, atof(e)); }
+    if (const char* e = exp_env("PT_PILOT_STACK")) sw.walk_cap = (uint32_t)std::min<int>(SHORT_WALK_STACK, std::max(0, atoi(e)));
+    if (const char* e = exp_env("PT_PILOT_NARROW")) sw.pilot_narrow = atoi(e) != 0;
     return sw;
 }
 
@@ -452,6 +477,75 @@ Switches read_switches(const pt_render_opts& opts) {
 size_t tiled_accum_bytes(size_t n_tile_pixels) { return n_tile_pixels * 3 * sizeof(double) + ((n_tile_pixels / 64 + 1) & ~(size_t)1) * sizeof(uint32_t) + sizeof(ShortHdrD); }
 uint32_t* tile_map_behind(double* accum, size_t n_tile_pixels) { return reinterpret_cast<uint32_t*>(accum + 3 * n_tile_pixels); }
 ShortHdrD* short_hdr_behind(double* accum, size_t n_tile_pixels) { return reinterpret_cast<ShortHdrD*>(tile_map_behind(accum, n_tile_pixels) + ((n_tile_pixels / 64 + 1) & ~(size_t)1)); }
+
+// The short-path pass's helpers. short_entries_wide: a hard-list entry of a list of n_listed tiles needs 8 bytes.
+// short_pool / short_args: what k_short and its pilot read of the pool — the frame, its tiling, the sample range, the tiled planes — and
+// the arguments the two launches share. adopt_tile_counts: the job's view of k_sky_scan's counts, and the samples one wave takes.
+bool short_entries_wide(const Job& job, uint64_t n_listed) {
+    uint32_t ord_bits = 1u;
+    while ((1ull << ord_bits) < n_listed) ++ord_bits;
+    return ord_bits + 6u + job.short_sample_bits > 32u;
+}
+PoolD short_pool(pt_scene* s, const Job& job) {
+    PoolD pool;
+    memset(&pool, 0, sizeof pool);
+    pool.accum = s->tile_accum.as<double>();
+    pool.accum_tiled = 1u;
+    pool.width = job.dc.width;
+    pool.height = job.dc.height;
+    pool.tiles_x = (job.dc.width + 7) / 8;
+    pool.n_tile_pixels = (uint32_t)((size_t)pool.tiles_x * ((job.dc.height + 7) / 8) * 64);
+    pool.spp_begin = job.spp_begin;
+    pool.spp_end = job.spp_end;
+    return pool;
+}
+ShortArgsD short_args(const pt_scene* s, const Job& job) {
+    ShortArgsD a;
+    memset(&a, 0, sizeof a);
+    a.shade_prims = job.shade_prims;
+    a.n_shade = (uint32_t)s->shade_prims.size();
+    a.n_hard = job.short_words;
+    a.sample_bits = job.short_sample_bits;
+    a.walk_cap = job.walk_cap;
+    return a;
+}
+void adopt_tile_counts(const pt_scene* s, Job& job, const uint32_t counts[8]) {
+    job.n_active_tiles = counts[0];
+    job.n_sky_tiles = counts[1];
+    job.n_sky_pixels = counts[2];
+    job.n_short_tiles = counts[3];
+    job.n_short_pixels = counts[4];
+    job.n_pilot_tiles = counts[6];
+    job.n_pilot_pixels = counts[7];
+    job.short_wide = short_entries_wide(job, (uint64_t)counts[5] + counts[6]);
+    // one wave renders `chunk` samples of a tile: enough waves to fill the machine four times over, at least 32 samples each
+    const uint64_t target = (uint64_t)std::max(1, s->ctx->n_cus) * 4 * 8 * 4;
+    auto chunk_for = [&](uint32_t n_tiles_of) {
+        const uint64_t per_tile = std::max<uint64_t>(1, target / std::max(1u, n_tiles_of));
+        uint32_t chunk = (uint32_t)std::max<uint64_t>(32, (job.spp + per_tile - 1) / per_tile);
+        while ((uint64_t)n_tiles_of * ((job.spp + chunk - 1) / chunk) > 0x7FFFFFFFull) chunk *= 2;   // (the kernels' wave index)
+        return chunk;
+    };
+    job.sky_chunk = chunk_for(counts[1]);
+    job.short_chunk = chunk_for(counts[3]);
+}
+// The pilot's selection: k_short_select flags the piloted tiles whose yield bin is at least min_bin, k_sky_scan lists them with the proven
+// short tiles and takes them out of the wavefront's map; the counts and the histogram of the yields come back (one small synchronisation).
+int select_by_yield(pt_scene* s, Job& job, EventTimer& timer, uint32_t min_bin, uint32_t counts[8], uint32_t* hist) {
+    (void)s;
+    timer.begin(2, job.st);
+    launch_short_select(job.d_flags, job.n_tiles, job.d_pilot, min_bin, job.d_hist, job.st);
+    launch_sky_scan(job.dc.width, job.dc.height, 0xFFFFFFFFu, job.n_tiles, job.d_flags, job.d_tile_map, job.d_sky_list, job.d_short_list, job.d_counts, job.st);
+    timer.end(job.st);
+    if (!hip_ok(hipGetLastError(), "yield selection") ||
+        !hip_ok(hipMemcpyAsync(counts, job.d_counts, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, job.st), "hipMemcpy(sky counts)") ||
+        !hip_ok(hipMemcpyAsync(hist, job.d_hist, 3 * SHORT_YIELD_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, job.st), "hipMemcpy(pilot histogram)") ||
+        !hip_ok(hipStreamSynchronize(job.st), "hipStreamSynchronize(yield selection)"))
+        return -1;
+    timer.drain();
+    if ((uint64_t)counts[0] + counts[1] + counts[3] != job.n_tiles) return set_error("pt_render: the sky pass's tile counts do not add up (internal error)");
+    return 0;
+}
 
 // The sky pass, per render: the tiles whose camera rays provably enter no box of the world are classified on the device
 // (pt_sky_tiles.h; one thread per tile, then a one-block scan), the host reads the three counts back — the one small synchronisation — and
@@ -488,7 +582,9 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     // sky_mem: the counts and k_short's three words (64 B), the boxes, the sure-sky tile list, the short tile list, the shadeable primitives'
     // ids, the tiles' flags; the tile map lies behind the tiled accumulator's planes
     const size_t box_bytes = (size_t)SKY_MAX_BOXES * 6 * sizeof(double), prim_bytes = (size_t)SKY_MAX_BOXES * sizeof(uint32_t);
-    if (!s->sky_mem.reserve(64 + box_bytes + prim_bytes + (size_t)n_tiles * (2 * sizeof(uint32_t) + 1), "hipMalloc(sky pass)")) return -1;
+    // ... and behind the flags, at the next 8-byte boundary, the yield pilot's two words per tile and its histogram
+    const size_t pilot_at = (64 + box_bytes + prim_bytes + (size_t)n_tiles * (2 * sizeof(uint32_t) + 1) + 7) & ~(size_t)7;
+    if (!s->sky_mem.reserve(pilot_at + ((size_t)n_tiles * 2 + 3 * SHORT_YIELD_BINS) * sizeof(uint32_t), "hipMalloc(sky pass)")) return -1;
     if (!s->tile_accum.reserve(tiled_accum_bytes((size_t)n_tiles * 64), "hipMalloc(tiled accumulator)")) return -1;
     char* m = s->sky_mem.as<char>();
     uint32_t* d_counts = (uint32_t*)m;
@@ -498,7 +594,18 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     uint32_t* d_short_list = d_sky_list + n_tiles;
     uint8_t* d_flags = (uint8_t*)(d_short_list + n_tiles);
     uint32_t* d_tile_map = tile_map_behind(s->tile_accum.as<double>(), (size_t)n_tiles * 64);
-    uint32_t counts[6] = {0, 0, 0, 0, 0, 0};
+    uint32_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    job.n_tiles = n_tiles;
+    job.d_flags = d_flags;
+    job.d_counts = d_counts;
+    job.d_pilot = (uint32_t*)(m + pilot_at);
+    job.d_hist = job.d_pilot + (size_t)n_tiles * 2;
+    job.d_tile_map = d_tile_map;
+    job.d_sky_list = d_sky_list;
+    job.d_short_list = d_short_list;
+    job.shade_prims = d_prims;
+    job.short_words = (unsigned long long*)(m + 32);
+    job.walk_cap = sw.walk_cap;
     // (`boxes` and `counts` are this function's: both copies are done at its synchronise, below)
     if (n_boxes && !hip_ok(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice, job.st), "hipMemcpy(sky boxes)")) return -1;
     if (short_on && !hip_ok(hipMemcpyAsync(d_prims, s->shade_prims.data(), s->shade_prims.size() * sizeof(uint32_t), hipMemcpyHostToDevice, job.st), "hipMemcpy(shadeable ids)")) return -1;
@@ -515,82 +622,108 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
         return 0;
     };
     if (classify(0xFFFFFFFFu) != 0) return -1;
+    job.short_sample_bits = 1u;
+    while ((1ull << job.short_sample_bits) < (uint64_t)job.spp) ++job.short_sample_bits;
+    const uint64_t cap_bytes = !short_on ? 0 : sw.short_cap_bytes ? sw.short_cap_bytes : pool_bytes_for_cap(sw, job, s->ctx->n_cus);
     if (counts[3] != 0) {
-        // The hard list holds, at worst, every sample of the tiles taken; its bytes are capped at the pool's (or PT_SHORT_CAP_BYTES). Where the cap
+        // The hard list holds, at worst, every sample of the proven tiles; its bytes are capped at the pool's (or PT_SHORT_CAP_BYTES). Where the cap
         // binds the pass takes the first max_short short tiles in tile order and the rest stay the wavefront's: the classification runs once more
         // with that bound. One tile at least stays the wavefront's, whose forms read the hard list only when PoolD::n_work_pixels is not 0.
-        job.short_sample_bits = 1u;
-        while ((1ull << job.short_sample_bits) < (uint64_t)job.spp) ++job.short_sample_bits;
-        uint32_t ord_bits = 1u;
-        while ((1ull << ord_bits) < (uint64_t)counts[5]) ++ord_bits;
-        job.short_wide = ord_bits + 6u + job.short_sample_bits > 32u;
-        const uint64_t entry_bytes = job.short_wide ? 8 : 4, cap_bytes = sw.short_cap_bytes ? sw.short_cap_bytes : pool_bytes_for_cap(sw, job, s->ctx->n_cus);
+        const uint64_t entry_bytes = short_entries_wide(job, counts[5]) ? 8 : 4;
         uint64_t max_short = cap_bytes / entry_bytes / ((uint64_t)64 * job.spp);
         if (counts[0] == 0 && max_short >= counts[5]) max_short = counts[5] - 1u;
         if (max_short < counts[3] && classify((uint32_t)max_short) != 0) return -1;
     }
+    // The yield pilot (DESIGN.md §23 "Taking tiles by yield"): where the short-path pass may run, the range is long enough to pay for it and
+    // the cap has not already bound on the proven tiles, k_short's counting form renders the first PILOT_SAMPLES samples of every tile of the
+    // wavefront's map, and the tiles it finishes at least theta of go to the short list too (select_by_yield). The histogram of the yields says
+    // what the selection costs: where the list's bytes, the 4-byte entries (PT_PILOT_NARROW) or the rule that one tile stays the wavefront's
+    // do not allow it, the threshold moves up bin by bin — the lowest yields are dropped first — and the selection runs once more.
+    if (short_on && !sw.no_pilot && (job.spp >= PILOT_MIN || sw.pilot_any_range) && counts[3] == counts[5] && counts[0] > 1u) {
+        const uint32_t n_active = counts[0], n_proven = counts[5], proven_pixels = counts[4], p_eff = std::min(PILOT_SAMPLES, job.spp);
+        if (!hip_ok(hipMemsetAsync(job.d_pilot, 0, (size_t)n_tiles * 2 * sizeof(uint32_t), job.st), "hipMemset(pilot counts)")) return -1;
+        PoolD pool = short_pool(s, job);
+        pool.spp_end = job.spp_begin + p_eff;
+        ShortArgsD a = short_args(s, job);
+        a.short_list = d_tile_map;
+        a.n_short = n_active;
+        a.chunk = p_eff;
+        a.n_chunks = 1u;
+        a.pilot = job.d_pilot;
+        timer.begin(5, job.st);
+        launch_short(s->dev.view, job.dc, pool, job.seed, a, job.st);
+        timer.end(job.st);
+        uint32_t hist[3 * SHORT_YIELD_BINS];
+        const uint32_t bin0 = (uint32_t)std::min(17.0, std::max(0.0, std::ceil(sw.pilot_theta * 16.0)));
+        if (select_by_yield(s, job, timer, bin0, counts, hist) != 0) return -1;
+        uint64_t cap_entries = 0;
+        auto fits = [&](uint32_t bin) {
+            uint64_t tiles = 0, seen = 0, unfinished = 0;
+            for (uint32_t k = bin; k < SHORT_YIELD_BINS; ++k) {
+                tiles += hist[3 * k];
+                seen += hist[3 * k + 1];
+                unfinished += hist[3 * k + 2];
+            }
+            // the taken tiles' part of the list: their projected hard samples with the margin, at most every sample of theirs
+            const uint64_t projected = (unfinished * job.spp + p_eff - 1) / p_eff;
+            const uint64_t with_margin = sw.pilot_margin_set ? (uint64_t)std::ceil(sw.pilot_margin * (double)projected) : projected + projected / 2 + 64 * tiles;
+            cap_entries = (uint64_t)proven_pixels * job.spp + std::min<uint64_t>(with_margin, seen / p_eff * job.spp);
+            const bool wide = short_entries_wide(job, n_proven + tiles);
+            return tiles < n_active && !(wide && sw.pilot_narrow) && cap_entries * (wide ? 8 : 4) <= cap_bytes;
+        };
+        uint32_t bin = bin0;
+        while (bin < SHORT_YIELD_BINS && !fits(bin)) ++bin;
+        if (bin != bin0 && select_by_yield(s, job, timer, bin, counts, hist) != 0) return -1;
+        (void)fits(bin);   // (bin = SHORT_YIELD_BINS takes nothing: the proven tiles' worst case, which fits)
+        uint64_t tiles = 0;
+        for (uint32_t k = bin; k < SHORT_YIELD_BINS; ++k) tiles += hist[3 * k];
+        if (counts[6] != tiles || counts[5] != n_proven) return set_error("pt_render: the yield pilot's tile counts do not add up (internal error)");
+        job.pilot_ran = true;
+        job.short_cap_entries = cap_entries;
+        if (sw.prof) {
+            fprintf(stderr, "[pt prof] PILOT  tiles piloted %u, proven %u, threshold bin %u/16 (asked %u/16), taken %u; list entries %llu; bins (tiles, seen, unfinished):", n_active,
+                    n_proven, bin, bin0, counts[6], (unsigned long long)cap_entries);
+            for (uint32_t k = 0; k < SHORT_YIELD_BINS; ++k) fprintf(stderr, " %u:(%u,%u,%u)", k, hist[3 * k], hist[3 * k + 1], hist[3 * k + 2]);
+            fprintf(stderr, "\n");
+        }
+    }
     if (counts[1] == 0 && counts[3] == 0) return 0;   // neither a sure-sky nor a short tile: the render is the wavefront's, its kernel arguments what they are without the passes
     job.sky = true;
     job.tile_map = d_tile_map;
-    job.n_active_tiles = counts[0];
-    job.n_sky_tiles = counts[1];
-    job.n_sky_pixels = counts[2];
     job.sky_list = d_sky_list;
-    job.n_short_tiles = counts[3];
-    job.n_short_pixels = counts[4];
     job.short_list = d_short_list;
-    job.shade_prims = d_prims;
-    job.short_words = (unsigned long long*)(m + 32);
-    // one wave renders `chunk` samples of a tile: enough waves to fill the machine four times over, at least 32 samples each
-    const uint64_t target = (uint64_t)std::max(1, s->ctx->n_cus) * 4 * 8 * 4;
-    auto chunk_for = [&](uint32_t n_tiles_of) {
-        const uint64_t per_tile = std::max<uint64_t>(1, target / std::max(1u, n_tiles_of));
-        uint32_t chunk = (uint32_t)std::max<uint64_t>(32, (job.spp + per_tile - 1) / per_tile);
-        while ((uint64_t)n_tiles_of * ((job.spp + chunk - 1) / chunk) > 0x7FFFFFFFull) chunk *= 2;   // (the kernels' wave index)
-        return chunk;
-    };
-    job.sky_chunk = chunk_for(counts[1]);
-    job.short_chunk = chunk_for(counts[3]);
+    adopt_tile_counts(s, job, counts);
+    if (!job.pilot_ran) job.short_cap_entries = (uint64_t)job.n_short_pixels * job.spp;   // every sample of the tiles taken (their pixels inside the image)
     return 0;
 }
 
 // The short-path pass itself, between the classification and the pool's plan: k_short renders the short tiles' samples into
 // the tiled accumulator — cleared here, not by tiled_accum — and appends the hard ones to the scene's list; the host reads back their number
 // and the pass's sample and segment counts (one more small synchronisation ahead of k_init) and writes the record K1 / K3 find the list by.
+// The list holds every sample of the proven tiles and, of the tiles the pilot took, the projected hard samples with a margin
+// (Job::short_cap_entries). k_short checks every store against that size and counts on: when the count read back is larger than the list, the
+// planes are cleared again, the selection is undone (select_by_yield with a threshold no tile reaches) and the pass runs once more over the
+// proven tiles alone, whose worst case the list holds.
 int run_short(pt_scene* s, Job& job, EventTimer& timer) {
     if (!job.sky) return 0;
     const size_t n_tile_pixels = (size_t)((job.dc.width + 7) / 8) * ((job.dc.height + 7) / 8) * 64;
     double* planes = s->tile_accum.as<double>();
     ShortHdrD& hdr = job.short_hdr;   // (the job's: the copy below is asynchronous)
     memset(&hdr, 0, sizeof hdr);
-    if (job.n_short_tiles != 0) {
-        const uint64_t cap = (uint64_t)job.n_short_pixels * job.spp;   // every sample of the tiles taken (their pixels inside the image)
+    for (int pass = 0; job.n_short_tiles != 0; ++pass) {
+        const uint64_t cap = job.short_cap_entries, all = (uint64_t)job.n_short_pixels * job.spp;
         if (!s->short_mem.reserve((size_t)cap * (job.short_wide ? 8 : 4), "hipMalloc(hard list)")) return -1;
         if (!hip_ok(hipMemsetAsync(planes, 0, n_tile_pixels * 3 * sizeof(double), job.st), "hipMemset(tiled accumulator)")) return -1;
         if (!hip_ok(hipMemsetAsync(job.short_words, 0, 3 * sizeof(unsigned long long), job.st), "hipMemset(short pass counts)")) return -1;
-        PoolD pool;   // what k_short reads of it: the frame, its tiling, the sample range, the tiled planes
-        memset(&pool, 0, sizeof pool);
-        pool.accum = planes;
-        pool.accum_tiled = 1u;
-        pool.width = job.dc.width;
-        pool.height = job.dc.height;
-        pool.tiles_x = (job.dc.width + 7) / 8;
-        pool.n_tile_pixels = (uint32_t)n_tile_pixels;
-        pool.spp_begin = job.spp_begin;
-        pool.spp_end = job.spp_end;
-        ShortArgsD a;
-        memset(&a, 0, sizeof a);
+        const PoolD pool = short_pool(s, job);
+        ShortArgsD a = short_args(s, job);
         a.short_list = job.short_list;
         a.n_short = job.n_short_tiles;
         a.chunk = job.short_chunk;
         a.n_chunks = (job.spp + job.short_chunk - 1) / job.short_chunk;
-        a.shade_prims = job.shade_prims;
-        a.n_shade = (uint32_t)s->shade_prims.size();
         a.hard = s->short_mem.as<void>();
-        a.n_hard = job.short_words;
         a.cap = cap;
         a.wide = job.short_wide ? 1u : 0u;
-        a.sample_bits = job.short_sample_bits;
         unsigned long long words[3] = {0, 0, 0};
         timer.begin(4, job.st);
         launch_short(s->dev.view, job.dc, pool, job.seed, a, job.st);
@@ -600,7 +733,17 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
             !hip_ok(hipStreamSynchronize(job.st), "hipStreamSynchronize(short-path pass)"))
             return -1;
         timer.drain();
-        if (words[0] > cap || words[0] + words[1] != cap) return set_error("pt_render: the short-path pass's sample counts do not add up (internal error)");
+        if (words[0] > all || words[0] + words[1] != all) return set_error("pt_render: the short-path pass's sample counts do not add up (internal error)");
+        if (words[0] > cap) {   // more hard samples than the pilot projected, margin included: the proven tiles alone
+            if (pass != 0 || !job.pilot_ran) return set_error("pt_render: the short-path pass's hard list is too small (internal error)");
+            uint32_t counts[8], hist[3 * SHORT_YIELD_BINS];
+            if (select_by_yield(s, job, timer, SHORT_YIELD_BINS, counts, hist) != 0) return -1;
+            if (counts[6] != 0) return set_error("pt_render: the yield pilot's tile counts do not add up (internal error)");
+            adopt_tile_counts(s, job, counts);
+            job.short_cap_entries = (uint64_t)job.n_short_pixels * job.spp;
+            job.short_fallback = true;
+            continue;
+        }
         job.n_hard = words[0];
         job.short_samples = words[1];
         job.short_segments = words[2];
@@ -609,6 +752,7 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
         hdr.wide = a.wide;
         hdr.sample_bits = a.sample_bits;
         hdr.n_hard = job.n_hard;
+        break;
     }
     return hip_ok(hipMemcpyAsync(short_hdr_behind(planes, n_tile_pixels), &hdr, sizeof hdr, hipMemcpyHostToDevice, job.st), "hipMemcpy(hard list record)") ? 0 : -1;
 }
@@ -974,6 +1118,11 @@ void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kern
     stats->blocks_shade = (uint32_t)kn.grid_shade;
     stats->compactions = r.compactions;
     stats->n_alloc_end = pool.n_alloc;
+    stats->pilot_tiles = job.n_pilot_tiles;
+    stats->short_fallback = job.short_fallback ? 1u : 0u;
+    stats->short_list_bytes = job.n_short_tiles ? job.short_cap_entries * (job.short_wide ? 8 : 4) : 0u;
+    stats->short_pixels = job.n_short_pixels;
+    stats->ms_pilot = timer.ms[5];
     stats->short_tiles = job.n_short_tiles;
     stats->short_samples = job.short_samples;
     stats->hard_samples = job.n_hard;
@@ -1000,6 +1149,11 @@ void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
     sum.blocks_shade = ps.blocks_shade;
     sum.compactions += ps.compactions;
     sum.n_alloc_end = ps.n_alloc_end;
+    sum.pilot_tiles = std::max(sum.pilot_tiles, ps.pilot_tiles);
+    sum.short_fallback += ps.short_fallback;
+    sum.short_list_bytes = std::max(sum.short_list_bytes, ps.short_list_bytes);
+    sum.short_pixels = std::max(sum.short_pixels, ps.short_pixels);
+    sum.ms_pilot += ps.ms_pilot;
     sum.short_tiles = std::max(sum.short_tiles, ps.short_tiles);
     sum.short_samples += ps.short_samples;
     sum.hard_samples += ps.hard_samples;

@@ -146,7 +146,8 @@ PT_SKY_HD bool sky_tile_is_clear(const SkyCam& c, uint32_t ty, uint32_t tx, uint
 // (bit b = box b: the box of an entry the short-path pass can shade, pt_scene.cpp) — a camera ray of the tile hits such an entry or nothing.
 // WAVEFRONT: everything else, and every tile about which nothing can be said (a tile outside the image, more boxes than the cap, a NaN or an
 // infinity among the boxes or in the camera: sky_extent is then not finite). Only where the pass pays depends on this; no result does.
-enum SkyTileClass : uint8_t { SKY_TILE_WAVEFRONT = 0, SKY_TILE_SKY = 1, SKY_TILE_SHORT = 2 };
+enum SkyTileClass : uint8_t { SKY_TILE_WAVEFRONT = 0, SKY_TILE_SKY = 1, SKY_TILE_SHORT = 2,
+                              SKY_TILE_TAKEN = 3 };   // TAKEN: never this test's answer: a wavefront tile the short-path pass takes by its measured yield (k_short_select)
 PT_SKY_HD uint8_t sky_tile_class(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable) {
     if (n_boxes > SKY_MAX_BOXES || ty * 8u >= c.height || tx * 8u >= c.width) return SKY_TILE_WAVEFRONT;
     const unsigned long long todo = sky_tile_uncleared(c, ty, tx, n_boxes, boxes6);

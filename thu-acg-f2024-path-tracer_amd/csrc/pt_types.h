@@ -418,7 +418,11 @@ struct ShortArgsD {
     unsigned long long* n_hard;
     unsigned long long cap;
     uint32_t wide, sample_bits;
+    uint32_t* pilot;      // not null: the counting form runs (k_short<true>) and writes {finished, seen} at pilot[2 * tile]
+    uint32_t walk_cap;    // the miss proof's stack budget in entries per lane (<= SHORT_WALK_STACK)
 };
+constexpr uint32_t SHORT_WALK_STACK = 16;   // the miss proof's stack per lane in LDS (16 KB per block)
+constexpr uint32_t SHORT_YIELD_BINS = 17;   // pilot yields in sixteenths: bin = floor(16 finished / seen), 0 .. 16
 
 // The work counter of the dynamic mode is SHARDED: one word saturates at ~88 dequeues/us on this
 // chip (MI355X_MICROARCH.md, row "dequeue") and a frame needs one dequeue per wave per iteration
