@@ -76,6 +76,11 @@ typedef struct pt_render_stats {
        (pilot_tiles is then 0); short_list_bytes: the bytes of the hard list — every sample of the proven tiles, and of the taken tiles 1.5
        times the pilot's projection and 64 entries per tile; short_pixels: the pixels of the short tiles that lie inside the image
        (short_samples + hard_samples = short_pixels x the samples per pixel); ms_pilot: the HIP-event time of the pilot's kernel (profile=1). */
+    /* the pass's deferred miss proofs: a bounce ray that enters a mesh's box waits, with up to 63 others of its wave, for a
+       pass in which every lane proves one ray's miss. short_walks: the rays that waited; short_walk_passes: the passes that walked them
+       (their mean fill is short_walks / (64 x short_walk_passes)). Zero with PT_EXPERIMENT=1 PT_SHORT_DEFER=0. (In front of the pilot's
+       fields: a caller built against the header before these two must be rebuilt.) */
+    uint64_t short_walks, short_walk_passes;
     uint64_t pilot_tiles, short_fallback, short_list_bytes, short_pixels;
     double ms_pilot;
     uint64_t short_tiles, short_samples, hard_samples;

@@ -79,6 +79,8 @@ class RenderStats(C.Structure):
         ("blocks_shade", C.c_uint32),
         ("compactions", C.c_uint32),
         ("n_alloc_end", C.c_uint32),
+        ("short_walks", C.c_uint64),
+        ("short_walk_passes", C.c_uint64),
         ("pilot_tiles", C.c_uint64),
         ("short_fallback", C.c_uint64),
         ("short_list_bytes", C.c_uint64),

@@ -400,6 +400,10 @@ struct Job {
     // device buffers, which the fallback selects from once more
     bool pilot_ran = false, short_fallback = false;
     uint32_t n_pilot_tiles = 0, n_pilot_pixels = 0, walk_cap = SHORT_WALK_STACK, n_tiles = 0;
+    // the bounces' miss proofs run in dense passes; the records they walked and the passes; the short pass's waves per tile x this
+    bool short_defer = true, prof = false;   // (prof: PT_PROF, for the diagnostic build's print)
+    uint64_t short_walks = 0, short_walk_passes = 0;
+    uint32_t short_chunk_mult = 4;
     uint64_t short_cap_entries = 0;
     uint8_t* d_flags = nullptr;
     uint32_t *d_counts = nullptr, *d_pilot = nullptr, *d_hist = nullptr, *d_tile_map = nullptr, *d_sky_list = nullptr, *d_short_list = nullptr;
@@ -407,6 +411,7 @@ struct Job {
 };
 
 // Every experiment switch of a render (exp_env: read under PT_EXPERIMENT=1 only), read once. An explicit option wins over its switch.
+constexpr size_t SKY_HDR_BYTES = 32 + SHORT_WORDS * sizeof(unsigned long long);   // classify_sky's eight counts, then k_short's words
 constexpr uint32_t PILOT_SAMPLES = 8, PILOT_MIN = 256;   // the yield pilot's samples per pixel; the shortest sample range it runs on
 constexpr double PILOT_THETA = 0.5;                      // the pilot yield from which a tile is taken
 struct Switches {
@@ -428,6 +433,12 @@ struct Switches {
     bool no_pilot = false, pilot_any_range = false, pilot_margin_set = false, pilot_narrow = false;
     double pilot_theta = PILOT_THETA, pilot_margin = 1.5;
     uint32_t walk_cap = SHORT_WALK_STACK;
+    // PT_SHORT_DEFER=0: k_short walks for a bounce where it enters a mesh's box (the A/B switch of DESIGN.md §23.2 inside one library);
+    // PT_SHORT_CHUNK_MULT=n: the short pass cuts its tiles' samples into n times as many waves as k_sky's rule would (k_sky's chunks stay).
+    // Default 4: k_short's waves differ a lot in cost and the kernel's end ran underfilled — headline ms_short 327.8 / 316.5 / 310.8 / 308.2
+    // at 1 / 2 / 4 / 8, spreads under 1 ms (profiles/r25_short_defer.md); 8 was not taken: its last 2.6 ms put chunks at the 32-sample floor from 500 spp down
+    bool no_short_defer = false;
+    uint32_t short_chunk_mult = 4;
     int grid_mult = 1;   // persistent grids: resident blocks per CU x CUs x this
     uint32_t wide_window_min = 16;
     int ext2 = 0;        // PT_EXT2 = stack*10 + blocks per CU picks the two-phase K2's instantiation (0: not set)
@@ -467,6 +478,8 @@ Switches read_switches(const pt_render_opts& opts) {
     if (const char* e = exp_env("PT_PILOT_MARGIN")) { sw.pilot_margin_set = true; sw.pilot_margin = std::max(0.0, atof(e)); }
     if (const char* e = exp_env("PT_PILOT_STACK")) sw.walk_cap = (uint32_t)std::min<int>(SHORT_WALK_STACK, std::max(0, atoi(e)));
     if (const char* e = exp_env("PT_PILOT_NARROW")) sw.pilot_narrow = atoi(e) != 0;
+    if (const char* e = exp_env("PT_SHORT_DEFER")) sw.no_short_defer = atoi(e) == 0;
+    if (const char* e = exp_env("PT_SHORT_CHUNK_MULT")) sw.short_chunk_mult = (uint32_t)std::min(64, std::max(1, atoi(e)));
     return sw;
 }
 
@@ -507,6 +520,7 @@ ShortArgsD short_args(const pt_scene* s, const Job& job) {
     a.n_hard = job.short_words;
     a.sample_bits = job.short_sample_bits;
     a.walk_cap = job.walk_cap;
+    a.defer = job.short_defer ? 1u : 0u;
     return a;
 }
 void adopt_tile_counts(const pt_scene* s, Job& job, const uint32_t counts[8]) {
@@ -520,14 +534,14 @@ void adopt_tile_counts(const pt_scene* s, Job& job, const uint32_t counts[8]) {
     job.short_wide = short_entries_wide(job, (uint64_t)counts[5] + counts[6]);
     // one wave renders `chunk` samples of a tile: enough waves to fill the machine four times over, at least 32 samples each
     const uint64_t target = (uint64_t)std::max(1, s->ctx->n_cus) * 4 * 8 * 4;
-    auto chunk_for = [&](uint32_t n_tiles_of) {
-        const uint64_t per_tile = std::max<uint64_t>(1, target / std::max(1u, n_tiles_of));
+    auto chunk_for = [&](uint32_t n_tiles_of, uint32_t mult) {
+        const uint64_t per_tile = std::max<uint64_t>(1, target * mult / std::max(1u, n_tiles_of));
         uint32_t chunk = (uint32_t)std::max<uint64_t>(32, (job.spp + per_tile - 1) / per_tile);
         while ((uint64_t)n_tiles_of * ((job.spp + chunk - 1) / chunk) > 0x7FFFFFFFull) chunk *= 2;   // (the kernels' wave index)
         return chunk;
     };
-    job.sky_chunk = chunk_for(counts[1]);
-    job.short_chunk = chunk_for(counts[3]);
+    job.sky_chunk = chunk_for(counts[1], 1u);
+    job.short_chunk = chunk_for(counts[3], job.short_chunk_mult);
 }
 // The pilot's selection: k_short_select flags the piloted tiles whose yield bin is at least min_bin, k_sky_scan lists them with the proven
 // short tiles and takes them out of the wavefront's map; the counts and the histogram of the yields come back (one small synchronisation).
@@ -574,23 +588,23 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     // scene has no lights list (the selector draw then only moves the counter), some entry is shadeable (pt_scene.cpp; every entry has its own
     // box here: more than SKY_MAX_BOXES would be walked as their union) and a path may have two segments.
     unsigned long long shadeable = 0ull;
-    const bool short_on = !sw.no_short_pass && s->dev.view.tlas_flat != 0u && s->dev.view.n_lights == 0u && !s->shade_prims.empty() && dc.max_depth >= 2u &&
+    const bool short_on = !sw.no_short_pass && s->dev.view.tlas_flat != 0u && s->dev.view.n_lights == 0u && !s->shade_prims.empty() && dc.max_depth >= 2u && job.spp <= (1u << 26) /* k_short packs pixel << sample_bits | sample in 32 bits */ &&
                           s->entry_shadeable.size() == (size_t)n_boxes && s->entry_boxes.size() / 6 == (size_t)n_boxes;
     if (short_on)
         for (uint32_t i = 0; i < n_boxes; ++i)
             if (s->entry_shadeable[i]) shadeable |= 1ull << i;
-    // sky_mem: the counts and k_short's three words (64 B), the boxes, the sure-sky tile list, the short tile list, the shadeable primitives'
+    // sky_mem: the counts and k_short's words (SKY_HDR_BYTES), the boxes, the sure-sky tile list, the short tile list, the shadeable primitives'
     // ids, the tiles' flags; the tile map lies behind the tiled accumulator's planes
     const size_t box_bytes = (size_t)SKY_MAX_BOXES * 6 * sizeof(double), prim_bytes = (size_t)SKY_MAX_BOXES * sizeof(uint32_t);
     // ... and behind the flags, at the next 8-byte boundary, the yield pilot's two words per tile and its histogram
-    const size_t pilot_at = (64 + box_bytes + prim_bytes + (size_t)n_tiles * (2 * sizeof(uint32_t) + 1) + 7) & ~(size_t)7;
+    const size_t pilot_at = (SKY_HDR_BYTES + box_bytes + prim_bytes + (size_t)n_tiles * (2 * sizeof(uint32_t) + 1) + 7) & ~(size_t)7;
     if (!s->sky_mem.reserve(pilot_at + ((size_t)n_tiles * 2 + 3 * SHORT_YIELD_BINS) * sizeof(uint32_t), "hipMalloc(sky pass)")) return -1;
     if (!s->tile_accum.reserve(tiled_accum_bytes((size_t)n_tiles * 64), "hipMalloc(tiled accumulator)")) return -1;
     char* m = s->sky_mem.as<char>();
     uint32_t* d_counts = (uint32_t*)m;
-    double* d_boxes = (double*)(m + 64);
-    uint32_t* d_prims = (uint32_t*)(m + 64 + box_bytes);
-    uint32_t* d_sky_list = (uint32_t*)(m + 64 + box_bytes + prim_bytes);
+    double* d_boxes = (double*)(m + SKY_HDR_BYTES);
+    uint32_t* d_prims = (uint32_t*)(m + SKY_HDR_BYTES + box_bytes);
+    uint32_t* d_sky_list = (uint32_t*)(m + SKY_HDR_BYTES + box_bytes + prim_bytes);
     uint32_t* d_short_list = d_sky_list + n_tiles;
     uint8_t* d_flags = (uint8_t*)(d_short_list + n_tiles);
     uint32_t* d_tile_map = tile_map_behind(s->tile_accum.as<double>(), (size_t)n_tiles * 64);
@@ -606,6 +620,9 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     job.shade_prims = d_prims;
     job.short_words = (unsigned long long*)(m + 32);
     job.walk_cap = sw.walk_cap;
+    job.short_defer = !sw.no_short_defer;
+    job.prof = sw.prof;
+    job.short_chunk_mult = sw.short_chunk_mult;
     // (`boxes` and `counts` are this function's: both copies are done at its synchronise, below)
     if (n_boxes && !hip_ok(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice, job.st), "hipMemcpy(sky boxes)")) return -1;
     if (short_on && !hip_ok(hipMemcpyAsync(d_prims, s->shade_prims.data(), s->shade_prims.size() * sizeof(uint32_t), hipMemcpyHostToDevice, job.st), "hipMemcpy(shadeable ids)")) return -1;
@@ -704,6 +721,22 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
 // (Job::short_cap_entries). k_short checks every store against that size and counts on: when the count read back is larger than the list, the
 // planes are cleared again, the selection is undone (select_by_yield with a threshold no tile reaches) and the pass runs once more over the
 // proven tiles alone, whose worst case the list holds.
+// PT_PROF, diagnostic builds (-DPT_STAMPS): k_short's wave cycles per phase and its walks' counts (pt_k_short.hip)
+void short_prof(const Job& job, const unsigned long long* words) {
+#ifdef PT_STAMPS
+    if (!job.prof) return;
+    const unsigned long long* p = words + SHORT_PROF_AT;
+    unsigned long long all = 0;
+    for (int i = 0; i < 8; ++i) all += p[i];
+    fprintf(stderr, "[pt prof] SHORT  defer %d, chunk %u; wave cycles: rng+ray %llu, camera top level %llu, camera walks %llu, shade %llu, bounce top level %llu, bounce walks %llu, environment %llu, rings %llu; sum %llu\n",
+            job.short_defer ? 1 : 0, job.short_chunk, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], all);
+    for (int w = 0; w < 2; ++w)
+        fprintf(stderr, "[pt prof] SHORT  %s walks: wave-samples (passes) %llu, lanes %llu, lane-steps %llu, longest-lane steps %llu, skipped as outcome-neutral %llu\n", w ? "bounce" : "camera",
+                p[8 + 8 * w], p[9 + 8 * w], p[10 + 8 * w], p[11 + 8 * w], p[12 + 8 * w]);
+#else
+    (void)job; (void)words;
+#endif
+}
 int run_short(pt_scene* s, Job& job, EventTimer& timer) {
     if (!job.sky) return 0;
     const size_t n_tile_pixels = (size_t)((job.dc.width + 7) / 8) * ((job.dc.height + 7) / 8) * 64;
@@ -714,7 +747,7 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
         const uint64_t cap = job.short_cap_entries, all = (uint64_t)job.n_short_pixels * job.spp;
         if (!s->short_mem.reserve((size_t)cap * (job.short_wide ? 8 : 4), "hipMalloc(hard list)")) return -1;
         if (!hip_ok(hipMemsetAsync(planes, 0, n_tile_pixels * 3 * sizeof(double), job.st), "hipMemset(tiled accumulator)")) return -1;
-        if (!hip_ok(hipMemsetAsync(job.short_words, 0, 3 * sizeof(unsigned long long), job.st), "hipMemset(short pass counts)")) return -1;
+        if (!hip_ok(hipMemsetAsync(job.short_words, 0, SHORT_WORDS * sizeof(unsigned long long), job.st), "hipMemset(short pass counts)")) return -1;
         const PoolD pool = short_pool(s, job);
         ShortArgsD a = short_args(s, job);
         a.short_list = job.short_list;
@@ -724,7 +757,7 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
         a.hard = s->short_mem.as<void>();
         a.cap = cap;
         a.wide = job.short_wide ? 1u : 0u;
-        unsigned long long words[3] = {0, 0, 0};
+        unsigned long long words[SHORT_WORDS] = {};
         timer.begin(4, job.st);
         launch_short(s->dev.view, job.dc, pool, job.seed, a, job.st);
         timer.end(job.st);
@@ -747,6 +780,9 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
         job.n_hard = words[0];
         job.short_samples = words[1];
         job.short_segments = words[2];
+        job.short_walks = words[3];
+        job.short_walk_passes = words[4];
+        short_prof(job, words);
         hdr.hard = s->short_mem.as<void>();
         hdr.short_list = job.short_list;
         hdr.wide = a.wide;
@@ -1122,6 +1158,8 @@ void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kern
     stats->short_fallback = job.short_fallback ? 1u : 0u;
     stats->short_list_bytes = job.n_short_tiles ? job.short_cap_entries * (job.short_wide ? 8 : 4) : 0u;
     stats->short_pixels = job.n_short_pixels;
+    stats->short_walks = job.short_walks;
+    stats->short_walk_passes = job.short_walk_passes;
     stats->ms_pilot = timer.ms[5];
     stats->short_tiles = job.n_short_tiles;
     stats->short_samples = job.short_samples;
@@ -1153,6 +1191,8 @@ void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
     sum.short_fallback += ps.short_fallback;
     sum.short_list_bytes = std::max(sum.short_list_bytes, ps.short_list_bytes);
     sum.short_pixels = std::max(sum.short_pixels, ps.short_pixels);
+    sum.short_walks += ps.short_walks;
+    sum.short_walk_passes += ps.short_walk_passes;
     sum.ms_pilot += ps.ms_pilot;
     sum.short_tiles = std::max(sum.short_tiles, ps.short_tiles);
     sum.short_samples += ps.short_samples;

@@ -420,7 +420,11 @@ struct ShortArgsD {
     uint32_t wide, sample_bits;
     uint32_t* pilot;      // not null: the counting form runs (k_short<true>) and writes {finished, seen} at pilot[2 * tile]
     uint32_t walk_cap;    // the miss proof's stack budget in entries per lane (<= SHORT_WALK_STACK)
+    uint32_t defer;       // the bounces' miss proofs run in dense passes (0: where the ray enters the box, PT_SHORT_DEFER=0)
 };
+// ShortArgsD::n_hard's device words: the three above, [3] the deferred records walked, [4] the passes that walked them (the render's pass, not
+// the pilot's); a diagnostic build (-DPT_STAMPS) sums k_short's wave cycles and walk counts from word SHORT_PROF_AT on (pt_k_short.hip).
+constexpr uint32_t SHORT_WORDS = 40, SHORT_PROF_AT = 8;
 constexpr uint32_t SHORT_WALK_STACK = 16;   // the miss proof's stack per lane in LDS (16 KB per block)
 constexpr uint32_t SHORT_YIELD_BINS = 17;   // pilot yields in sixteenths: bin = floor(16 finished / seen), 0 .. 16
 
