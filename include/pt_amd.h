@@ -893,6 +893,69 @@ int pt_mesh_grid(const double q[3], const double u[3], const double v[3], uint32
 /* host only: w x h RGB8 -> w x h heights ((0.2126 r + 0.7152 g) + 0.0722 b) / 255, f64 rounded to f32 */
 int pt_height_from_rgb8(uint32_t w, uint32_t h, const uint8_t* rgb, float* out);
 
+/* ---- Loop subdivision surfaces: creases, corners, limit projection (not in the reference, opt-in) ----
+ * A stage of its own in front of pt_mesh, and in front of pt_mesh_tessellate when displacement follows: a coarse control cage in, a
+ * rounder fine mesh out. No render kernel knows of it. pt_mesh_subdivide runs on the GPU (csrc/pt_subdiv.hip), pt_mesh_subdivide_host
+ * is its host twin; the two return the same bytes.
+ * Input: f32 positions, u32 index triples, optional f32 texcoords indexed by the position index (brought to n = n_pos entries first:
+ *  entries past n_pos dropped, missing ones zero), optional crease flags: n_idx bytes, crease[3f + k] != 0 marks edge k of face f as
+ *  sharp, edges numbered as in section 27: e0 = (a, b), e1 = (b, c), e2 = (c, a). Flags are read as 0 or 1.
+ * Arithmetic: f64 on the f32 values widened, in the order written here, no fused operation; each written vertex attribute is rounded to
+ *  f32 once per level. sqrt is the IEEE operation. dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z. No trigonometry anywhere: the caller
+ *  turns angles into cosines.
+ * Topology of a level is section 27's: the same edge keys, the E distinct keys in ascending order, the midpoint of the key of rank r
+ *  is vertex n + r, the same four children in the same order: n' = n + E, F' = 4F, and out_idx is what pt_mesh_tessellate writes.
+ * An edge's run: the slots 3f + k that carry its key, in ascending order. An edge is sharp when its run's length is not 2 (boundary and
+ *  non-manifold edges), or its endpoints are equal (a == b), or any slot of its run is flagged.
+ * Creasing by angle, once, on the input mesh, before the first level (and before the limit projection when levels = 0): an edge of
+ *  run length 2 with a != b, whose slots lie in the faces f0 and f1, c_i = (p1 - p0) x (p2 - p0) of face f_i (section 27's cross
+ *  product): all of its slots are flagged when dot(c0, c1) < crease_cos * sqrt(dot(c0, c0) * dot(c1, c1)). False for NaN. Faces of
+ *  opposed winding across an edge therefore read as a fold: that is data, not an error.
+ * Child flags travel with the slots: with e_k = 1 when any slot of the run of the parent's edge k is flagged (the parent's own slot
+ *  is one of them), else 0: child 4f = (a, ab, ca) has the flags (e0, 0, e2), 4f + 1 = (ab, b, bc) has (e0, e1, 0), 4f + 2 =
+ *  (ca, bc, c) has (0, e1, e2), 4f + 3 = (ab, bc, ca) has (0, 0, 0). A crease flagged on one side only is then carried by both.
+ * Odd vertices: the midpoint of key (A, B), A the smaller index: sharp edge: (A + B) * 0.5; otherwise (A + B) * 0.375 + (C + D) * 0.125
+ *  with C, D the vertices opposite the edge in the first and the second slot of its run: for slot 3f + k that is idx[3f + (k + 2) % 3].
+ * Neighbours of v: one entry per distinct key with a != b that contains v, in ascending order of the other endpoint's index; k is
+ *  their number, s the number of them that are sharp. Self-edges give no neighbour.
+ * Even vertices: k = 0: the vertex keeps its value. s >= 3: a corner, kept. s == 2, the sharp neighbours w0 < w1: d0 = P[w0] - P[v],
+ *  d1 = P[w1] - P[v]; a corner, kept, when dot(d0, d1) > corner_cos * sqrt(dot(d0, d0) * dot(d1, d1)) (false for NaN); otherwise the
+ *  crease rule P[v] * 0.75 + (P[w0] + P[w1]) * 0.125. s <= 1: Warren's weights: beta = 0.1875 for k == 3, else 0.375 / (double)k;
+ *  S = 0, then S += P[w] over the neighbours in ascending order; the value is P[v] * (1.0 - (double)k * beta) + S * beta.
+ *  All masks read the level's input values. Unreferenced vertices stay.
+ * Texcoords go through the same masks (the same edge classes, the same w0, w1, k, beta) as positions; classification uses positions only.
+ * Limit projection (limit = 1): once, after the last level, on the last mesh's own edges and flags, the same classification:
+ *  s <= 1: chi = 0.2 for k == 3, else 0.5 / (double)k: P[v] * (1.0 - (double)k * chi) + S * chi; crease: P[v] * (2.0 / 3.0) +
+ *  (P[w0] + P[w1]) * (1.0 / 6.0); corners and k = 0: kept. It reads the unprojected values and writes new ones; texcoords go with it.
+ * Normals (`normals`): 0 smooth: section 27's smooth normals of the final positions, (0, 1, 0) where the sum is unusable; 1 none.
+ * out_crease (when wanted): the flags of the output mesh, 0 or 1 per slot: subdividing the output again with them continues the same
+ *  surface. With levels = 0 they are the input's flags after creasing by angle.
+ * Refused with -1 before any device work: a NULL output pointer (out_crease alone may be NULL: not wanted) or a NULL array with a count
+ *  above 0; n_idx % 3 != 0; an index out of range for positions or for given texcoords; levels > 12; 4^levels F > 0x07FFFFFF;
+ *  n + (4^levels - 1) F > 2^32 - 1; crease_cos or corner_cos NaN; an unknown limit or normals value. NULL options mean the defaults.
+ *  NaN and infinite coordinates are data. Outputs are malloc'd: free them with pt_free; *out_nrm / *out_uv are NULL where there is none.
+ * Device memory, per level of F faces, n vertices and E edges: the two meshes (20 B a vertex with texcoords, 15 B a face, old and new),
+ *  108 B a face of edge keys, slots, flags, ranks and midpoint indices, 48 B an edge of neighbour pairs, 2 B an edge of classes,
+ *  4 B a vertex of run starts, and the radix sort's own buffer.
+ * A mesh whose vertices are duplicated along texcoord seams (pt_load_obj_single_index) turns its seams into creases: boundary edges on
+ *  both sides. They stay closed (both copies compute the same crease positions) but are visible. Welding is not done here. */
+typedef struct pt_subdiv_opts {
+    uint32_t levels;      /* 0..12. Default 1 */
+    double crease_cos;    /* default -2: no edge is creased by angle */
+    double corner_cos;    /* default  2: no vertex is a corner by angle */
+    int limit;            /* 0 (default); 1: push the last level's vertices to their limit positions */
+    int normals;          /* 0 smooth (default): the area-weighted rule of section 27 on the final positions; 1 none */
+} pt_subdiv_opts;
+int pt_subdiv_opts_default(pt_subdiv_opts*);
+int pt_mesh_subdivide(pt_ctx*, const pt_subdiv_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                      uint32_t n_uv, const float* uv, const uint8_t* crease /* n_idx bytes or NULL */,
+                      float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx,
+                      float** out_nrm, float** out_uv, uint8_t** out_crease /* may be NULL: not wanted */);
+int pt_mesh_subdivide_host(const pt_subdiv_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                           uint32_t n_uv, const float* uv, const uint8_t* crease,
+                           float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx,
+                           float** out_nrm, float** out_uv, uint8_t** out_crease);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

@@ -12,6 +12,7 @@ Because the directory name contains hyphens, import it with
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -195,6 +196,30 @@ class TessOpts(C.Structure):
             super().__init__(levels, self._height.shape[1], self._height.shape[0], self._height.ctypes.data, scale, midlevel, wrap, normals)
 
 
+SUBDIV_NORMALS = {"smooth": 0, "none": 1}   # pt_subdiv_opts.normals
+
+
+def _cos_deg(deg, default):
+    """The cosine pt_subdiv_opts wants for an angle in degrees (None: `default`, the value that switches the test off)"""
+    return default if deg is None else math.cos(math.radians(float(deg)))
+
+
+class SubdivOpts(C.Structure):
+    """pt_subdiv_opts: Loop subdivision levels, the two angle thresholds as cosines, limit projection, which normals are written
+    (include/pt_amd.h has the rule). A fresh instance holds the defaults: one level, no angle test, no projection, smooth normals."""
+
+    _fields_ = [
+        ("levels", C.c_uint32),
+        ("crease_cos", C.c_double),
+        ("corner_cos", C.c_double),
+        ("limit", C.c_int),
+        ("normals", C.c_int),
+    ]
+
+    def __init__(self, levels=1, crease_cos=-2.0, corner_cos=2.0, limit=0, normals="smooth"):
+        super().__init__(levels, crease_cos, corner_cos, int(limit), SUBDIV_NORMALS.get(normals, normals))
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -226,6 +251,7 @@ ABI_SYMBOLS = [
     "pt_scene_set_punctual_selection", "pt_scene_punctual_selection", "pt_scene_set_punctual_grid", "pt_scene_punctual_grid", "pt_punctual_grid_row", "pt_punctual_grid_select",
     "pt_sky_opts_default", "pt_sky_opts_check", "pt_sky_eval", "pt_sky_sun_irradiance", "pt_sky_probe", "pt_sky_bake", "pt_tex_sky",
     "pt_tess_opts_default", "pt_mesh_tessellate", "pt_mesh_tessellate_host", "pt_mesh_grid", "pt_height_from_rgb8",
+    "pt_subdiv_opts_default", "pt_mesh_subdivide", "pt_mesh_subdivide_host",
 ]
 
 
@@ -398,6 +424,12 @@ def _load():
         lib.pt_mesh_tessellate_host.argtypes = [C.POINTER(TessOpts)] + mesh_in + mesh_out
         lib.pt_mesh_grid.argtypes = [d3, d3, d3, C.c_uint32, C.c_uint32] + mesh_out
         lib.pt_height_from_rgb8.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pt_mesh_subdivide"):          # (absent from an older build in an A/B run: PT_AMD_LIB)
+        fpp, upp, up = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)
+        sub_args = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, fpp, up, upp, up, fpp, fpp, C.POINTER(C.POINTER(C.c_uint8))]
+        lib.pt_subdiv_opts_default.argtypes = [C.POINTER(SubdivOpts)]
+        lib.pt_mesh_subdivide.argtypes = [C.c_void_p, C.POINTER(SubdivOpts)] + sub_args
+        lib.pt_mesh_subdivide_host.argtypes = [C.POINTER(SubdivOpts)] + sub_args
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -547,6 +579,13 @@ class Context:
         wrap: "clamp" / "repeat"; normals: "auto" / "keep" / "smooth" / "none" (include/pt_amd.h has the rule)."""
         return _tessellate(self.handle, pos, idx, nrm, uv, TessOpts(levels, height, scale, midlevel, wrap, normals))
 
+    def subdivide(self, pos, idx, uv=None, crease=None, levels=1, crease_deg=None, corner_deg=None, limit=False, normals="smooth"):
+        """pt_mesh_subdivide: `levels` levels of Loop subdivision of a triangle mesh on the GPU -> (pos, idx, nrm | None, uv | None, crease),
+        ready for Scene.mesh or Context.tessellate. crease: one flag per index, crease[3f + k] marks edge k of face f as sharp; crease_deg:
+        the angle between two faces' normals above which their edge is sharp; corner_deg: the angle between a crease vertex's two sharp edges
+        below which it is a corner; limit: push the vertices to the limit surface; normals: "smooth" / "none" (include/pt_amd.h has the rule)."""
+        return _subdivide(self.handle, pos, idx, uv, crease, SubdivOpts(levels, _cos_deg(crease_deg, -2.0), _cos_deg(corner_deg, 2.0), limit, normals))
+
     def sky_probe(self, dirs: np.ndarray, **opts) -> np.ndarray:
         """pt_sky_probe: sky_eval by the bake kernel's device function: (n, 3) unit directions -> (n, 3) radiance, no disc."""
         dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
@@ -606,6 +645,36 @@ def _tessellate(ctx, pos, idx, nrm, uv, opts):
 def tessellate_host(pos, idx, nrm=None, uv=None, levels=1, height=None, scale=1.0, midlevel=0.5, wrap="clamp", normals="auto"):
     """pt_mesh_tessellate_host: Context.tessellate on the host, the same bytes (no context needed)."""
     return _tessellate(None, pos, idx, nrm, uv, TessOpts(levels, height, scale, midlevel, wrap, normals))
+
+
+def _subdivide(ctx, pos, idx, uv, crease, opts):
+    args, keep = _mesh_in(pos, idx, None, uv)
+    args = args[:4] + args[6:]                       # (no normals go in)
+    if crease is not None:
+        crease = np.ascontiguousarray(crease, dtype=np.uint8).reshape(-1)
+        if len(crease) != args[2]:
+            raise ValueError("crease must hold one flag per index")
+    out, flags = _MeshOut(), C.POINTER(C.c_uint8)()
+    tail = (None if crease is None else crease.ctypes.data, *out.refs(), C.byref(flags))
+    if ctx is None:
+        rc = lib.pt_mesh_subdivide_host(C.byref(opts), *args, *tail)
+    else:
+        rc = lib.pt_mesh_subdivide(ctx, C.byref(opts), *args, *tail)
+    name = "pt_mesh_subdivide_host" if ctx is None else "pt_mesh_subdivide"
+    if rc < 0:
+        out.free()
+        if flags:
+            lib.pt_free(flags)
+    _check(rc, name)
+    m = out.n_idx.value
+    cr = np.ctypeslib.as_array(flags, (m,)).copy() if m else np.zeros(0, np.uint8)
+    lib.pt_free(flags)
+    return (*out.take(), cr)
+
+
+def subdivide_host(pos, idx, uv=None, crease=None, levels=1, crease_deg=None, corner_deg=None, limit=False, normals="smooth"):
+    """pt_mesh_subdivide_host: Context.subdivide on the host, the same bytes (no context needed)."""
+    return _subdivide(None, pos, idx, uv, crease, SubdivOpts(levels, _cos_deg(crease_deg, -2.0), _cos_deg(corner_deg, 2.0), limit, normals))
 
 
 def mesh_grid(q, u, v, nu: int, nv: int):

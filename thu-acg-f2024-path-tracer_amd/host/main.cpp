@@ -201,6 +201,35 @@ static void displace_brick_wall(World& world, pt_ctx* ctx, const std::string& fi
     throw std::runtime_error("--displace: the scene has no wall with a normal-mapped material");
 }
 
+// --subdivide: the three OBJ meshes of scene 6 (bunny, spot, cow: coarse control cages) become Loop subdivision surfaces: LEVELS levels on the
+// GPU, pushed to the limit surface, with smooth normals. v = LEVELS[, CREASE_DEG[, CORNER_DEG]].
+static const char* const SUBDIVIDE_FILES[3] = {"bunny.obj", "spot.obj", "cow.obj"};
+static const uint64_t SUBDIVIDE_MAX_FACES = 1ull << 19;   // the default device-BVH threshold: from there on the LBVH can be too deep
+
+static pt_subdiv_opts subdivide_opts(const std::vector<double>& v) {
+    pt_subdiv_opts o;
+    pt_subdiv_opts_default(&o);
+    const double rad = 3.14159265358979323846 / 180.0;
+    o.levels = (uint32_t)v[0];
+    if (v.size() > 1) o.crease_cos = std::cos(v[1] * rad);
+    if (v.size() > 2) o.corner_cos = std::cos(v[2] * rad);
+    o.limit = 1;
+    return o;
+}
+
+static void subdivide_meshes(World& world, pt_ctx* ctx, const std::vector<double>& v) {
+    const pt_subdiv_opts o = subdivide_opts(v);
+    size_t done = 0;
+    for (auto& obj : world.objects) {
+        auto inst = std::dynamic_pointer_cast<Instance>(obj);
+        auto mesh = inst ? std::dynamic_pointer_cast<TriangleMesh>(inst->object) : nullptr;
+        if (!mesh) continue;
+        inst->object = TriangleMesh::from_obj(mesh->scale, mesh->mesh.subdivided(ctx, o), mesh->material);
+        ++done;
+    }
+    if (done != 3) throw std::runtime_error("--subdivide: the scene does not hold its three meshes");
+}
+
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
@@ -235,6 +264,8 @@ int main(int argc, char** argv) {
     bool displace = false;                   // --displace FILE,SCALE[,LEVELS[,MIDLEVEL]]
     std::string displace_file;
     std::vector<double> displace_v;
+    bool subdivide = false;                  // --subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]
+    std::vector<double> subdivide_v;
     uint64_t seed = 1;
     std::string out, assets = "assets";
     for (int i = 1; i < argc; ++i) {
@@ -390,12 +421,25 @@ int main(int argc, char** argv) {
             }
             displace = true;
         }
+        else if (a == "--subdivide") {
+            if (!parse_numbers(next(), 1, 3, subdivide_v) || subdivide_v[0] < 0.0 || subdivide_v[0] > 12.0 || subdivide_v[0] != std::floor(subdivide_v[0])) {
+                std::cerr << "--subdivide must be LEVELS[,CREASE_DEG[,CORNER_DEG]]: finite numbers, LEVELS a whole one in 0..12\n";
+                return 2;
+            }
+            if (subdivide_v.size() > 1 && !(subdivide_v[1] >= 0.0 && subdivide_v[1] <= 180.0)) { std::cerr << "--subdivide: CREASE_DEG must lie in 0..180\n"; return 2; }
+            if (subdivide_v.size() > 2 && !(subdivide_v[2] >= 0.0 && subdivide_v[2] <= 180.0)) { std::cerr << "--subdivide: CORNER_DEG must lie in 0..180\n"; return 2; }
+            subdivide = true;
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]] [--subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]]\n"
+                         "  --subdivide: scene 6 only: bunny, spot and cow, coarse control cages, become Loop subdivision surfaces: LEVELS levels on the GPU (each makes\n"
+                         "           four triangles of one; at most 2^19 a mesh), the vertices pushed to the limit surface, smooth normals. An edge whose two faces'\n"
+                         "           normals differ by more than CREASE_DEG stays sharp (default: none does; 0 keeps every edge, the cage itself); a crease vertex whose\n"
+                         "           two sharp edges meet at less than CORNER_DEG stays a corner (default: none does). Boundary edges are always sharp\n"
                          "  --displace: scene 7 only: the wall that carries the normal-mapped bricks becomes a 64 x 64 grid mesh, subdivided LEVELS times (default 2) on\n"
                          "           the GPU and pushed along its normal by SCALE * (luminance of the PNG or JPEG image FILE - MIDLEVEL) (MIDLEVEL default 0.5): real relief\n"
                          "           with a silhouette and shadows; the wall keeps the brick colours and drops the normal map\n"
@@ -469,6 +513,20 @@ int main(int argc, char** argv) {
         }
     }
     if (displace && scene != 7) { std::cerr << "--displace works on scene 7 only (the wall with the normal-mapped bricks)\n"; return 2; }
+    if (subdivide && scene != 6) { std::cerr << "--subdivide works on scene 6 only (bunny, spot and cow)\n"; return 2; }
+    if (subdivide) {   // the size of the result, from the files alone: before a context is made
+        const uint64_t grow = 1ull << (2 * (uint32_t)subdivide_v[0]);
+        for (const char* file : SUBDIVIDE_FILES) {
+            float *pos, *uv;
+            uint32_t *idx, np, ni, nuv;
+            if (pt_load_obj((assets + "/" + file).c_str(), &pos, &np, &idx, &ni, &uv, &nuv) != 0) { std::cerr << "--subdivide: " << pt_last_error() << "\n"; return 2; }
+            pt_free(pos); pt_free(idx); pt_free(uv);
+            if ((uint64_t)(ni / 3) * grow > SUBDIVIDE_MAX_FACES) {
+                std::cerr << "--subdivide: LEVELS " << (uint32_t)subdivide_v[0] << " takes " << file << " (" << ni / 3 << " triangles) past 2^19 triangles\n";
+                return 2;
+            }
+        }
+    }
     pt_sky_opts sky_opts;
     uint32_t sky_width = 2048;
     pt_sky_opts_default(&sky_opts);
@@ -512,6 +570,7 @@ int main(int argc, char** argv) {
             // scene's other entries can pass the traversal stack
             setup.world.device_bvh_threshold = 0;
         }
+        if (subdivide) subdivide_meshes(setup.world, ctx, subdivide_v);
         if (sky) setup.camera.environment = EnvironmentType::Map(Sky::new_(sky_opts, sky_width, sky_width / 2));
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;

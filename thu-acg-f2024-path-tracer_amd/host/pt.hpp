@@ -359,6 +359,21 @@ struct Mesh {
             panic("Mesh::tessellated");
         return take(pos, np, idx, ni, nrm, uv);
     }
+    // not in the reference: Loop subdivision on the GPU (pt_mesh_subdivide; include/pt_amd.h has the rule): the cage's
+    // positions and texcoords in (its normals are not read), a rounder mesh with smooth normals out. crease: one flag per index, or NULL;
+    // out_crease: the flags of the result, for a further call. Hand the result to TriangleMesh::from_obj, or to tessellated() to displace it.
+    Mesh subdivided(pt_ctx* ctx, const pt_subdiv_opts& opts, const std::vector<uint8_t>* crease = nullptr, std::vector<uint8_t>* out_crease = nullptr) const {
+        float *pos, *nrm, *uv;
+        uint32_t *idx, np, ni;
+        uint8_t* flags = nullptr;
+        if (crease && crease->size() != indices.size()) panic("Mesh::subdivided: one crease flag per index");
+        if (pt_mesh_subdivide(ctx, &opts, (uint32_t)(positions.size() / 3), positions.data(), (uint32_t)indices.size(), indices.data(), (uint32_t)(texcoords.size() / 2),
+                              texcoords.data(), crease ? crease->data() : nullptr, &pos, &np, &idx, &ni, &nrm, &uv, out_crease ? &flags : nullptr) != 0)
+            panic("Mesh::subdivided");
+        if (out_crease) out_crease->assign(flags, flags + ni);
+        pt_free(flags);
+        return take(pos, np, idx, ni, nrm, uv);
+    }
 
 private:
     static Mesh take(float* pos, uint32_t np, uint32_t* idx, uint32_t ni, float* nrm, float* uv) {
