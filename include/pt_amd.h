@@ -80,6 +80,12 @@ typedef struct pt_render_stats {
        pass in which every lane proves one ray's miss. short_walks: the rays that waited; short_walk_passes: the passes that walked them
        (their mean fill is short_walks / (64 x short_walk_passes)). Zero with PT_EXPERIMENT=1 PT_SHORT_DEFER=0. (In front of the pilot's
        fields: a caller built against the header before these two must be rebuilt.) */
+    /* the pass's reach masks (pt_tile_reach below). short_direct_tiles: the tiles of the pass whose mask names one shadeable entry
+       and nothing else, whose camera rays are tested against that primitive alone; short_self_prims: the shadeable quads a bounce that left them
+       does not test again (the numbers of quad and camera keep the proof's bound). Under PT_EXPERIMENT=1: short_direct_tiles is zero with
+       PT_SHORT_REACH=0 or PT_SHORT_DIRECT=0; short_self_prims is zero with PT_SHORT_SELF=0 (PT_SHORT_REACH=0 leaves it as it is). (In front of the deferred proofs' fields: a caller built against the header
+       before these two must be rebuilt.) */
+    uint64_t short_direct_tiles, short_self_prims;
     uint64_t short_walks, short_walk_passes;
     uint64_t pilot_tiles, short_fallback, short_list_bytes, short_pixels;
     double ms_pilot;
@@ -460,6 +466,13 @@ int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, u
    short tiles' samples ahead of the path pool where their path is camera -> miss or camera -> one hit of a shadeable entry (a still world-level
    sphere or quad, diffuse, no normal map, no instance) -> miss; sums and counts are what they are without (PT_SHORT_PASS=0 under PT_EXPERIMENT=1). */
 int pt_short_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, uint8_t* out_tiles);
+/* Host only, no context needed. The same test, its answer per box (csrc/pt_sky_tiles.h sky_tile_reach): bit b of out_masks[ty * tiles_x + tx] is 0 when NO
+   camera ray of the tile can enter box b (a proof, as above) and 1 when the test could not clear it. The mask is 0 exactly where pt_sky_tiles says 1.
+   All ones (every one of the 64 bits) wherever the test says nothing: a NaN or an infinity among the boxes or in the camera, the lens's centre or a
+   corner of it inside or on a box, and, with more than 64 boxes, every tile whose union of boxes is not cleared. A render that runs the short-path pass
+   keeps these masks on the device and its pass tests, per tile, only the entries a camera ray can reach (PT_SHORT_REACH=0,
+   PT_SHORT_DIRECT=0 and PT_SHORT_SELF=0 under PT_EXPERIMENT=1 switch its steps off): sums and counts are what they are without. */
+int pt_tile_reach(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, uint64_t* out_masks);
 int pt_motion_swept_box(const double box[6], const double axis[3], double angle0, double angle1, const double tr0[3], const double tr1[3], double out[6]);
 /* test probe: the f64 world box (lo.xyz, hi.xyz) of world entry `entry` (lights list first, then objects), before the f32 rounding */
 int pt_world_entry_box(pt_scene*, uint32_t entry, double out[6]);

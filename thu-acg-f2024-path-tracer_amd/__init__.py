@@ -80,6 +80,8 @@ class RenderStats(C.Structure):
         ("blocks_shade", C.c_uint32),
         ("compactions", C.c_uint32),
         ("n_alloc_end", C.c_uint32),
+        ("short_direct_tiles", C.c_uint64),
+        ("short_self_prims", C.c_uint64),
         ("short_walks", C.c_uint64),
         ("short_walk_passes", C.c_uint64),
         ("pilot_tiles", C.c_uint64),
@@ -245,7 +247,7 @@ ABI_SYMBOLS = [
     "pt_mat_glass_set_dispersion", "pt_mat_glass_dispersion", "pt_dispersion_probe",
     "pt_scene_set_projection", "pt_scene_projection", "pt_camera_probe",
     "pt_instance_moving", "pt_scene_set_shutter", "pt_scene_shutter", "pt_scene_motion", "pt_motion_pose", "pt_motion_swept_box", "pt_world_entry_box",
-    "pt_sky_tiles", "pt_short_tiles",
+    "pt_sky_tiles", "pt_short_tiles", "pt_tile_reach",
     "pt_light_point", "pt_light_spot", "pt_light_directional", "pt_scene_clear_punctual_lights", "pt_scene_punctual_count", "pt_scene_punctual_light",
     "pt_scene_set_punctual_fraction", "pt_scene_punctual_fraction", "pt_punctual_probe", "pt_punctual_eval", "pt_scene_set_punctual_media", "pt_scene_punctual_media",
     "pt_scene_set_punctual_selection", "pt_scene_punctual_selection", "pt_scene_set_punctual_grid", "pt_scene_punctual_grid", "pt_punctual_grid_row", "pt_punctual_grid_select",
@@ -346,6 +348,8 @@ def _load():
         lib.pt_sky_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p]
     if hasattr(lib, "pt_short_tiles"):             # (absent from an older build in an A/B run: PT_AMD_LIB)
         lib.pt_short_tiles.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pt_tile_reach"):
+        lib.pt_tile_reach.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_void_p, C.c_void_p]
     lib.pt_load_hdr_rgbf32.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.pt_mat_diffuse.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.pt_mat_metal.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1267,6 +1271,16 @@ def short_tiles(cam: Camera, boxes, shadeable) -> np.ndarray:
     out = np.zeros((tiles_y, tiles_x), dtype=np.uint8)
     _check(lib.pt_short_tiles(C.byref(cam), len(boxes), boxes.ctypes.data if len(boxes) else None, flags.ctypes.data if len(boxes) else None, out.ctypes.data),
            "pt_short_tiles")
+    return out
+
+
+def tile_reach(cam: Camera, boxes) -> np.ndarray:
+    """The tile test's answer per box (pt_tile_reach; host only): boxes (n, 6) -> (tiles_y, tiles_x) uint64, bit b = 0: no camera ray of the tile
+    enters box b; all ones where the test says nothing."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.float64).reshape(-1, 6)
+    tiles_y, tiles_x = (image_height(cam) + 7) // 8, (cam.image_width + 7) // 8
+    out = np.zeros((tiles_y, tiles_x), dtype=np.uint64)
+    _check(lib.pt_tile_reach(C.byref(cam), len(boxes), boxes.ctypes.data if len(boxes) else None, out.ctypes.data), "pt_tile_reach")
     return out
 
 

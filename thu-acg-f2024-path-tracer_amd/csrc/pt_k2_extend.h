@@ -94,9 +94,11 @@ PT_PAIR_PASS_ATTR void pair_pass(const SceneD& sc, const RayD& r, double t_min, 
 // PAIRS: cuboids few rays of the chunk enter go through the pair passes (L must be valid); false: everything on the spot.
 // CULL: compile the cuboid face culling in (the instantiation for scenes without cuboids leaves it out: its registers spilled there).
 // MOT: instances are posed at each lane's ray time (inst_at); face culling and the pair passes use the per-lane local ray they compute anyway.
-template <bool PAIRS, bool CULL, bool MOT = false, class OnMesh>
+// MASKED (k_short): the loop visits the entries whose bit is set in `reach` (bit k = SceneD::entry_box[k], wave-uniform,
+// no bit at or above n_entries), in the same ascending order; an entry whose bit is 0 costs not even its box's load. false: every entry.
+template <bool PAIRS, bool CULL, bool MOT = false, bool MASKED = false, class OnMesh>
 PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const RayF& f, double t_min, float t_min_f, int lane, const PairLds& L,
-                              OnMesh&& on_mesh) {
+                              OnMesh&& on_mesh, uint32_t reach = 0xFFFFFFFFu) {
     if constexpr (PAIRS) {
         ((volatile unsigned long long*)L.bt)[lane] = (unsigned long long)__double_as_longlong(D_INF);
         ((volatile uint32_t*)L.bid)[lane] = HIT_NONE;
@@ -115,7 +117,11 @@ PT_DEV Closest flat_top_level(const SceneD& sc, bool alive, const RayD& r, const
         }
         pairs_open = false;
     };
-    for (uint32_t k = 0; k < sc.n_entries; ++k) {                    // SceneD::entry_box: non-mesh entries first
+    for (uint32_t k = 0; MASKED ? reach != 0u : k < sc.n_entries; ++k) {   // SceneD::entry_box: non-mesh entries first
+        if constexpr (MASKED) {                                      // the lowest set bit is this turn's entry
+            k = (uint32_t)__builtin_ctz(reach);
+            reach &= reach - 1u;
+        }
         const EntryBox bx = ldu(&sc.entry_box[k]);
         if (PAIRS && pairs_open && bx.kind == ENTRY_MESH) close_pairs();
         float tn;

@@ -128,6 +128,16 @@ __global__ __launch_bounds__(BLOCK, 4) void k_short(SceneD sc, CamD cam, PoolD p
     const bool in_image = col < pool.width && row < pool.height;
     const uint32_t pixel = row * pool.width + col;
     const uint32_t s0 = pool.spp_begin + ci * a.chunk, s1 = pool.spp_end - s0 < a.chunk ? pool.spp_end : s0 + a.chunk;
+    // DESIGN.md §23.3, all wave-uniform (scalar registers). reach: the entries a camera ray of this tile may enter, bit k = entry_box[k]; every
+    // other entry's box is entered by none (pt_sky_tiles.h), so its turn of the loop could only fail: it is not taken. direct_gid: the mask
+    // names ONE entry and that entry is a shadeable primitive — the loop's one exact test is the rebuild's, which runs anyway.
+    // (the host runs the pass on a top level of at most 32 entries, classify_sky: the masks name every entry there is)
+    const uint32_t all_entries = sc.n_entries >= 32u ? 0xFFFFFFFFu : (1u << sc.n_entries) - 1u;
+    const uint32_t reach = (a.reach ? ldu(&a.reach[tile]) : 0xFFFFFFFFu) & all_entries;
+    uint32_t direct_gid = HIT_NONE;
+    if (a.direct != 0u && a.shade_at && __popc(reach) == 1)
+        for (uint32_t j = 0; j < a.n_shade; ++j)
+            if ((ldu(&a.shade_at[j]) & 0xFFu) == (uint32_t)__builtin_ctz(reach)) direct_gid = ldu(&a.shade_prims[j]);
     const double t_min = 1e-3;                                     // camera.rs:171,179 (K2's)
     const float t_min_f = __double2float_rd(t_min);
     V3 sum{0.0, 0.0, 0.0};
@@ -197,7 +207,10 @@ __global__ __launch_bounds__(BLOCK, 4) void k_short(SceneD sc, CamD cam, PoolD p
             uint32_t w_steps = 0u, w_neutral = 0u;
             bool w_walked = false;
 #endif
-            const Closest c = flat_top_level<false, true, false>(sc, in_image, r, make_rayf(r.o, r.d, sc.tlas_extent), t_min, t_min_f, lane, PairLds{},
+            //  the direct hit: every in-image lane is a candidate of the tile's one primitive, and the rebuild below decides
+            Closest c{D_INF, direct_gid};
+            if (direct_gid == HIT_NONE)
+                c = flat_top_level<false, true, false, true>(sc, in_image, r, make_rayf(r.o, r.d, sc.tlas_extent), t_min, t_min_f, lane, PairLds{},
                                                                  [&](uint32_t, const Entry& e, Closest& best) {
                                                                      if (recorded) return;
                                                                      if (best.id != HIT_NONE) {
@@ -219,28 +232,32 @@ __global__ __launch_bounds__(BLOCK, 4) void k_short(SceneD sc, CamD cam, PoolD p
 #else
                                                                      recorded = !mesh_walk_misses(sc, r, e, t_min_f, best.t, stk, a.walk_cap);
 #endif
-                                                                 });
+                                                                 }, reach);
 #ifdef PT_STAMPS
             cam_walks.sample(w_walked, w_steps, w_neutral);
 #endif
             PT_STAMP(2);
             bool done = false;
             const bool clean = in_image && !recorded;
-            if (clean && c.id == HIT_NONE) {                       // K3: the ray left the scene (camera.rs:180-183)
-                if constexpr (!PILOT) add(V3{1.0, 1.0, 1.0} * sample_environment(sc, cam, r.d));
-                ++n_one;
-                done = true;
-            }
+            bool miss = clean && c.id == HIT_NONE;                 // K3: the ray left the scene (camera.rs:180-183), finished below
             // K3 at a shadeable primitive: phase A, B1, B2 of shade_slot for a diffuse material at bounce 0 without a lights list
             bool have_dir = false;
             V3 thr{1.0, 1.0, 1.0};
+            uint32_t n_left = 0u, left_at = 0u;                    // wave-uniform: the shadeable primitives bounces of this wave leave, the last one's shade_at
             for (uint32_t j = 0; j < a.n_shade; ++j) {
                 const uint32_t gid = ldu(&a.shade_prims[j]);
                 const bool mine = clean && c.id == gid;
                 if (__ballot(mine) == 0ull) continue;
                 const PrimRef pr0 = ldu(&sc.prims[gid]);
                 HitD hit{};
-                if (mine && reconstruct_hit_prim<false, true, false>(sc, r, pr0, 1e-3, hit)) {
+                // (the direct hit: the walk would have reported this primitive iff the same test on the same ray succeeds here; else it is a miss)
+                const bool hit_ok = mine && reconstruct_hit_prim<false, true, false>(sc, r, pr0, 1e-3, hit);
+                miss = miss || (mine && !hit_ok && direct_gid != HIT_NONE);
+                if (__ballot(hit_ok) != 0ull) {
+                    ++n_left;
+                    left_at = a.shade_at ? ldu(&a.shade_at[j]) : 0u;
+                }
+                if (hit_ok) {
                     const MatD* um = &sc.mats[pr0.mat];
                     const TexVals tv = fetch_tex<true>(sc, *um, hit);
                     const LocalFrame lf = make_local_frame(MAT_DIFFUSE, hit, -r.d);
@@ -259,6 +276,11 @@ __global__ __launch_bounds__(BLOCK, 4) void k_short(SceneD sc, CamD cam, PoolD p
                     have_dir = true;
                 }
             }
+            if (miss) {
+                if constexpr (!PILOT) add(V3{1.0, 1.0, 1.0} * sample_environment(sc, cam, r.d));
+                ++n_one;
+                done = true;
+            }
             PT_STAMP(3);
 #ifdef PT_STAMPS
             unsigned long long t_4 = t_3, t_5 = t_3;
@@ -270,7 +292,10 @@ __global__ __launch_bounds__(BLOCK, 4) void k_short(SceneD sc, CamD cam, PoolD p
                 w_steps = w_neutral = 0u;
                 w_walked = false;
 #endif
-                const Closest c2 = flat_top_level<false, true, false>(sc, have_dir, r2, make_rayf(r2.o, r2.d, sc.tlas_extent), t_min, t_min_f, lane, PairLds{},
+                //  every bounce of the wave left ONE quad the host has flagged: its exact test has t < 0 (the proof there), so
+                // its entry is not tested
+                const uint32_t reach2 = n_left == 1u && (left_at & SHADE_AT_SELF_OK) != 0u ? all_entries & ~(1u << (left_at & 31u)) : all_entries;
+                const Closest c2 = flat_top_level<false, true, false, true>(sc, have_dir, r2, make_rayf(r2.o, r2.d, sc.tlas_extent), t_min, t_min_f, lane, PairLds{},
                                                                       [&](uint32_t ei, const Entry& e, Closest& best) {
                                                                           if (best.id != HIT_NONE) {
 #ifdef PT_STAMPS
@@ -292,7 +317,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_short(SceneD sc, CamD cam, PoolD p
                                                                               recorded2 = !mesh_walk_misses(sc, r2, e, t_min_f, best.t, stk, a.walk_cap);
 #endif
                                                                           }
-                                                                      });
+                                                                      }, reach2);
 #ifdef PT_STAMPS
                 if constexpr (!DEFER) bounce_walks.sample(w_walked, w_steps, w_neutral);
                 else bounce_walks.sample(false, 0u, w_neutral);
@@ -436,6 +461,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_short(SceneD sc, CamD cam, PoolD p
         atomicAdd(&a.n_hard[1], one + two);                        // (the host adds them to the render's counts: ShortArgsD)
         atomicAdd(&a.n_hard[2], one + 2ull * two);
     }
+    if (lane == 0 && ci == 0u && direct_gid != HIT_NONE) atomicAdd(&a.n_hard[5], 1ull);   // (the tiles of the direct hit)
     if (lane == 0 && n_passes != 0u) {
         atomicAdd(&a.n_hard[3], (unsigned long long)n_walks);
         atomicAdd(&a.n_hard[4], (unsigned long long)n_passes);

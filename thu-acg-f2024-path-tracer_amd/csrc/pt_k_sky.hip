@@ -8,13 +8,26 @@
 
 namespace pt {
 
+// reach (null: not wanted): the tile's reach mask (pt_sky_tiles.h sky_tile_reach) for the short-path pass, DESIGN.md §23.3, one word per tile —
+// every tile, whatever its class — with box b's bit at position order.at[b]: the place of entry b in SceneD::entry_box, the order
+// flat_top_level's loop runs in (the host only asks for it when every entry has its own box and there are at most TLAS_FLAT_MAX of them).
 __global__ __launch_bounds__(BLOCK) void k_sky_classify(SkyCam cam, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, uint32_t tiles_x,
-                                                         uint32_t n_tiles, uint8_t* flags) {
+                                                         uint32_t n_tiles, uint8_t* flags, uint32_t* reach, ReachOrder order) {
     const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
     if (t >= n_tiles) return;
     uint32_t ty, tx;
     divmod_u31(t, tiles_x, ty, tx);
-    flags[t] = sky_tile_class(cam, ty, tx, n_boxes, boxes6, shadeable);   // (shadeable = 0: sure sky or wavefront, the sky pass's two kinds)
+    const unsigned long long todo = sky_tile_uncleared(cam, ty, tx, n_boxes, boxes6);
+    flags[t] = sky_tile_class_of(cam, ty, tx, n_boxes, boxes6, shadeable, todo);   // (shadeable = 0: sure sky or wavefront, the sky pass's two kinds)
+    if (reach) {
+        uint32_t m = 0xFFFFFFFFu;
+        if (n_boxes <= 32u && !sky_tile_says_nothing(cam, ty, tx, n_boxes, boxes6)) {
+            m = 0u;
+            for (uint32_t b = 0; b < n_boxes; ++b)
+                if ((todo >> b) & 1ull) m |= 1u << (order.at[b] & 31u);
+        }
+        reach[t] = m;
+    }
 }
 
 // Thread i ranks the tiles [i * per, (i + 1) * per): the three lists come out in tile order. Of the SHORT tiles the first max_short (in
@@ -138,8 +151,8 @@ __global__ __launch_bounds__(BLOCK) void k_sky(SceneD sc, CamD cam, PoolD pool, 
 }
 
 void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, uint32_t max_short, uint32_t n_tiles, uint8_t* flags,
-                         uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, hipStream_t st) {
-    hipLaunchKernelGGL(k_sky_classify, dim3((n_tiles + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, cam, n_boxes, boxes6, shadeable, (cam.width + 7u) / 8u, n_tiles, flags);
+                         uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, uint32_t* reach, const ReachOrder& order, hipStream_t st) {
+    hipLaunchKernelGGL(k_sky_classify, dim3((n_tiles + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, cam, n_boxes, boxes6, shadeable, (cam.width + 7u) / 8u, n_tiles, flags, reach, order);
     hipLaunchKernelGGL(k_sky_scan, dim3(1), dim3(BLOCK), 0, st, flags, n_tiles, cam.width, cam.height, max_short, tile_map, sky_list, short_list, counts);
 }
 // the scan alone, over flags k_short_select has changed

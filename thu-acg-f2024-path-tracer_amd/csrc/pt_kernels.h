@@ -69,8 +69,9 @@ void launch_detile(const PoolD& pool, double* accum, int max_blocks, hipStream_t
 // samples [spp_begin, spp_end) of every pixel of the short tiles, finished where the path is camera -> (miss | shadeable hit -> miss), else
 // appended to the hard list (pt_types.h ShortArgsD).
 struct SkyCam;
+struct ReachOrder;
 void launch_sky_classify(const SkyCam& cam, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, uint32_t max_short, uint32_t n_tiles, uint8_t* flags,
-                         uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, hipStream_t st);
+                         uint32_t* tile_map, uint32_t* sky_list, uint32_t* short_list, uint32_t* counts, uint32_t* reach, const ReachOrder& order, hipStream_t st);   // (reach: null, or the tiles' reach masks in `order`)
 void launch_sky_scan(uint32_t width, uint32_t height, uint32_t max_short, uint32_t n_tiles, const uint8_t* flags, uint32_t* tile_map, uint32_t* sky_list,
                      uint32_t* short_list, uint32_t* counts, hipStream_t st);   // (the scan of launch_sky_classify alone; counts: 8 words)
 void launch_short(const SceneD& sc, const CamD& cam, const PoolD& pool, uint64_t seed, const ShortArgsD& a, hipStream_t st);

@@ -135,16 +135,22 @@ std::vector<double> sky_boxes(uint32_t n_boxes, const double* boxes6) {
     return u;
 }
 }  // namespace
-static int tiles_of(const char* who, const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, bool classes, uint8_t* out_tiles);
+static int tiles_of(const char* who, const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, bool classes, uint8_t* out_tiles,
+                    uint64_t* out_reach = nullptr);
+extern "C" int pt_tile_reach(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, uint64_t* out_masks) {
+    return tiles_of("pt_tile_reach", cam, n_boxes, boxes6, nullptr, false, nullptr, out_masks);
+}
 extern "C" int pt_sky_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, uint8_t* out_tiles) {
     return tiles_of("pt_sky_tiles", cam, n_boxes, boxes6, nullptr, false, out_tiles);
 }
 extern "C" int pt_short_tiles(const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, uint8_t* out_tiles) {
     return tiles_of("pt_short_tiles", cam, n_boxes, boxes6, shadeable, true, out_tiles);
 }
-// classes: the three kinds of tile (sky_tile_class), with the shadeable boxes flagged; else 1 = sure sky, 0 = not (sky_tile_is_clear)
-static int tiles_of(const char* who, const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, bool classes, uint8_t* out_tiles) {
-    if (!cam || !out_tiles || (n_boxes && !boxes6)) return set_error(std::string(who) + ": bad arguments");
+// classes: the three kinds of tile (sky_tile_class), with the shadeable boxes flagged; else 1 = sure sky, 0 = not (sky_tile_is_clear).
+// out_reach: the tiles' reach masks instead (sky_tile_reach, bit b = box b; more boxes than the cap: all ones unless their union is cleared)
+static int tiles_of(const char* who, const pt_camera* cam, uint32_t n_boxes, const double* boxes6, const uint8_t* shadeable, bool classes, uint8_t* out_tiles,
+                    uint64_t* out_reach) {
+    if (!cam || (!out_tiles && !out_reach) || (n_boxes && !boxes6)) return set_error(std::string(who) + ": bad arguments");
     CamDerived d;
     if (derive_camera(cam, d) != 0) return -1;
     const double lens_radius = std::tan((cam->defocus_angle / 2.0) * (PI / 180.0)) * cam->focal_length;   // (make_camd's)
@@ -161,7 +167,11 @@ static int tiles_of(const char* who, const pt_camera* cam, uint32_t n_boxes, con
     const uint32_t tiles_x = (c.width + 7) / 8, tiles_y = (c.height + 7) / 8;
     for (uint32_t ty = 0; ty < tiles_y; ++ty)
         for (uint32_t tx = 0; tx < tiles_x; ++tx)
-            out_tiles[(size_t)ty * tiles_x + tx] = classes ? sky_tile_class(c, ty, tx, nb, boxes.data(), mask) : sky_tile_is_clear(c, ty, tx, nb, boxes.data()) ? 1 : 0;
+            if (out_reach) {
+                const unsigned long long m = sky_tile_reach(c, ty, tx, nb, boxes.data());
+                out_reach[(size_t)ty * tiles_x + tx] = nb != n_boxes && m != 0ull ? ~0ull : m;
+            } else
+                out_tiles[(size_t)ty * tiles_x + tx] = classes ? sky_tile_class(c, ty, tx, nb, boxes.data(), mask) : sky_tile_is_clear(c, ty, tx, nb, boxes.data()) ? 1 : 0;
     return 0;
 }
 
@@ -392,7 +402,10 @@ struct Job {
     uint32_t short_chunk = 0, short_sample_bits = 0;
     bool short_wide = false;
     const uint32_t* shade_prims = nullptr;
-    unsigned long long* short_words = nullptr;   // k_short's three device words (ShortArgsD::n_hard)
+    // the tiles' reach masks, the shadeable primitives' places in the top level's loop (ShortArgsD), the direct hit is on
+    const uint32_t *reach = nullptr, *shade_at = nullptr;
+    bool short_direct = false;
+    unsigned long long* short_words = nullptr;   // k_short's device words (ShortArgsD::n_hard, SHORT_WORDS of them; pt_types.h says which is which)
     ShortHdrD short_hdr;   // the record behind the tile map (run_short)
     // the yield pilot (DESIGN.md §23 "Taking tiles by yield"; classify_sky, select_by_yield): it ran; the tiles it added to the short list and
     // their pixels inside the image; the entries the hard list holds (the proven tiles' worst case + the taken tiles' projection with its
@@ -402,7 +415,7 @@ struct Job {
     uint32_t n_pilot_tiles = 0, n_pilot_pixels = 0, walk_cap = SHORT_WALK_STACK, n_tiles = 0;
     // the bounces' miss proofs run in dense passes; the records they walked and the passes; the short pass's waves per tile x this
     bool short_defer = true, prof = false;   // (prof: PT_PROF, for the diagnostic build's print)
-    uint64_t short_walks = 0, short_walk_passes = 0;
+    uint64_t short_walks = 0, short_walk_passes = 0, short_direct_tiles = 0, short_self_prims = 0;
     uint32_t short_chunk_mult = 4;
     uint64_t short_cap_entries = 0;
     uint8_t* d_flags = nullptr;
@@ -439,6 +452,10 @@ struct Switches {
     // at 1 / 2 / 4 / 8, spreads under 1 ms (profiles/r25_short_defer.md); 8 was not taken: its last 2.6 ms put chunks at the 32-sample floor from 500 spp down
     bool no_short_defer = false;
     uint32_t short_chunk_mult = 4;
+    // DESIGN.md §23.3, each the A/B switch of its step inside one library: PT_SHORT_REACH=0: k_short's camera rays test every entry (the masks
+    // are all ones); PT_SHORT_DIRECT=0: a tile whose mask names one shadeable entry walks the top level like any other; PT_SHORT_SELF=0: a bounce
+    // tests the quad it left
+    bool no_short_reach = false, no_short_direct = false, no_short_self = false;
     int grid_mult = 1;   // persistent grids: resident blocks per CU x CUs x this
     uint32_t wide_window_min = 16;
     int ext2 = 0;        // PT_EXT2 = stack*10 + blocks per CU picks the two-phase K2's instantiation (0: not set)
@@ -479,6 +496,9 @@ Switches read_switches(const pt_render_opts& opts) {
     if (const char* e = exp_env("PT_PILOT_STACK")) sw.walk_cap = (uint32_t)std::min<int>(SHORT_WALK_STACK, std::max(0, atoi(e)));
     if (const char* e = exp_env("PT_PILOT_NARROW")) sw.pilot_narrow = atoi(e) != 0;
     if (const char* e = exp_env("PT_SHORT_DEFER")) sw.no_short_defer = atoi(e) == 0;
+    if (const char* e = exp_env("PT_SHORT_REACH")) sw.no_short_reach = atoi(e) == 0;
+    if (const char* e = exp_env("PT_SHORT_DIRECT")) sw.no_short_direct = atoi(e) == 0;
+    if (const char* e = exp_env("PT_SHORT_SELF")) sw.no_short_self = atoi(e) == 0;
     if (const char* e = exp_env("PT_SHORT_CHUNK_MULT")) sw.short_chunk_mult = (uint32_t)std::min(64, std::max(1, atoi(e)));
     return sw;
 }
@@ -521,6 +541,9 @@ ShortArgsD short_args(const pt_scene* s, const Job& job) {
     a.sample_bits = job.short_sample_bits;
     a.walk_cap = job.walk_cap;
     a.defer = job.short_defer ? 1u : 0u;
+    a.reach = job.reach;
+    a.shade_at = job.shade_at;
+    a.direct = job.short_direct ? 1u : 0u;
     return a;
 }
 void adopt_tile_counts(const pt_scene* s, Job& job, const uint32_t counts[8]) {
@@ -589,7 +612,8 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     // box here: more than SKY_MAX_BOXES would be walked as their union) and a path may have two segments.
     unsigned long long shadeable = 0ull;
     const bool short_on = !sw.no_short_pass && s->dev.view.tlas_flat != 0u && s->dev.view.n_lights == 0u && !s->shade_prims.empty() && dc.max_depth >= 2u && job.spp <= (1u << 26) /* k_short packs pixel << sample_bits | sample in 32 bits */ &&
-                          s->entry_shadeable.size() == (size_t)n_boxes && s->entry_boxes.size() / 6 == (size_t)n_boxes;
+                          s->entry_shadeable.size() == (size_t)n_boxes && s->entry_boxes.size() / 6 == (size_t)n_boxes &&
+                          n_boxes <= 32u /* k_short walks the top level by a 32-bit mask of entries; a flat top level of more (PT_FLAT_MAX) keeps the wavefront */;
     if (short_on)
         for (uint32_t i = 0; i < n_boxes; ++i)
             if (s->entry_shadeable[i]) shadeable |= 1ull << i;
@@ -598,7 +622,9 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     const size_t box_bytes = (size_t)SKY_MAX_BOXES * 6 * sizeof(double), prim_bytes = (size_t)SKY_MAX_BOXES * sizeof(uint32_t);
     // ... and behind the flags, at the next 8-byte boundary, the yield pilot's two words per tile and its histogram
     const size_t pilot_at = (SKY_HDR_BYTES + box_bytes + prim_bytes + (size_t)n_tiles * (2 * sizeof(uint32_t) + 1) + 7) & ~(size_t)7;
-    if (!s->sky_mem.reserve(pilot_at + ((size_t)n_tiles * 2 + 3 * SHORT_YIELD_BINS) * sizeof(uint32_t), "hipMalloc(sky pass)")) return -1;
+    // ... and behind those the tiles' reach masks, one word per tile
+    const size_t reach_at = pilot_at + ((size_t)n_tiles * 2 + 3 * SHORT_YIELD_BINS) * sizeof(uint32_t);
+    if (!s->sky_mem.reserve(reach_at + (size_t)n_tiles * sizeof(uint32_t), "hipMalloc(sky pass)")) return -1;
     if (!s->tile_accum.reserve(tiled_accum_bytes((size_t)n_tiles * 64), "hipMalloc(tiled accumulator)")) return -1;
     char* m = s->sky_mem.as<char>();
     uint32_t* d_counts = (uint32_t*)m;
@@ -618,6 +644,26 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     job.d_sky_list = d_sky_list;
     job.d_short_list = d_short_list;
     job.shade_prims = d_prims;
+    // (the shadeable ids take at most TLAS_FLAT_MAX of the SKY_MAX_BOXES words: their places in the loop lie in the second half)
+    uint32_t* d_shade_at = d_prims + SKY_MAX_BOXES / 2;
+    uint32_t* d_reach = (uint32_t*)(m + reach_at);
+    ReachOrder order;
+    memset(&order, 0, sizeof order);
+    std::vector<uint32_t> shade_at;
+    const bool reach_on = short_on && s->entry_at.size() == (size_t)n_boxes && n_boxes <= TLAS_FLAT_MAX && s->shade_prims.size() <= SKY_MAX_BOXES / 2 &&
+                          s->shade_entry.size() == s->shade_prims.size() && s->shade_self_ok.size() == s->shade_prims.size();
+    if (reach_on) {
+        for (uint32_t i = 0; i < n_boxes; ++i) order.at[i] = (uint8_t)s->entry_at[i];
+        // step 3's bound on the camera rays' origins (the proof): the lens within 1e6 of the origin
+        bool cam_ok = true;
+        for (int i = 0; i < 3; ++i) cam_ok = cam_ok && std::fabs(dc.center[i]) + std::fabs(dc.dof_right[i]) + std::fabs(dc.dof_up[i]) <= 1e6;
+        for (size_t j = 0; j < s->shade_prims.size(); ++j)
+            shade_at.push_back(s->entry_at[s->shade_entry[j]] | (s->shade_self_ok[j] && cam_ok && !sw.no_short_self ? SHADE_AT_SELF_OK : 0u));
+        job.shade_at = d_shade_at;
+        for (uint32_t v : shade_at) job.short_self_prims += (v & SHADE_AT_SELF_OK) ? 1u : 0u;
+        job.reach = sw.no_short_reach ? nullptr : d_reach;
+        job.short_direct = !sw.no_short_reach && !sw.no_short_direct;
+    }
     job.short_words = (unsigned long long*)(m + 32);
     job.walk_cap = sw.walk_cap;
     job.short_defer = !sw.no_short_defer;
@@ -626,9 +672,10 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     // (`boxes` and `counts` are this function's: both copies are done at its synchronise, below)
     if (n_boxes && !hip_ok(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(double), hipMemcpyHostToDevice, job.st), "hipMemcpy(sky boxes)")) return -1;
     if (short_on && !hip_ok(hipMemcpyAsync(d_prims, s->shade_prims.data(), s->shade_prims.size() * sizeof(uint32_t), hipMemcpyHostToDevice, job.st), "hipMemcpy(shadeable ids)")) return -1;
+    if (reach_on && !hip_ok(hipMemcpyAsync(d_shade_at, shade_at.data(), shade_at.size() * sizeof(uint32_t), hipMemcpyHostToDevice, job.st), "hipMemcpy(shadeable places)")) return -1;
     auto classify = [&](uint32_t max_short) -> int {
         timer.begin(2, job.st);
-        launch_sky_classify(cam, n_boxes, d_boxes, shadeable, max_short, n_tiles, d_flags, d_tile_map, d_sky_list, d_short_list, d_counts, job.st);
+        launch_sky_classify(cam, n_boxes, d_boxes, shadeable, max_short, n_tiles, d_flags, d_tile_map, d_sky_list, d_short_list, d_counts, job.reach ? d_reach : nullptr, order, job.st);
         timer.end(job.st);
         if (!hip_ok(hipGetLastError(), "sky classification") ||
             !hip_ok(hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, job.st), "hipMemcpy(sky counts)") ||
@@ -782,6 +829,7 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
         job.short_segments = words[2];
         job.short_walks = words[3];
         job.short_walk_passes = words[4];
+        job.short_direct_tiles = words[5];
         short_prof(job, words);
         hdr.hard = s->short_mem.as<void>();
         hdr.short_list = job.short_list;
@@ -1158,6 +1206,8 @@ void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kern
     stats->short_fallback = job.short_fallback ? 1u : 0u;
     stats->short_list_bytes = job.n_short_tiles ? job.short_cap_entries * (job.short_wide ? 8 : 4) : 0u;
     stats->short_pixels = job.n_short_pixels;
+    stats->short_direct_tiles = job.short_direct_tiles;
+    stats->short_self_prims = job.n_short_tiles ? job.short_self_prims : 0u;
     stats->short_walks = job.short_walks;
     stats->short_walk_passes = job.short_walk_passes;
     stats->ms_pilot = timer.ms[5];
@@ -1191,6 +1241,8 @@ void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
     sum.short_fallback += ps.short_fallback;
     sum.short_list_bytes = std::max(sum.short_list_bytes, ps.short_list_bytes);
     sum.short_pixels = std::max(sum.short_pixels, ps.short_pixels);
+    sum.short_direct_tiles = std::max(sum.short_direct_tiles, ps.short_direct_tiles);
+    sum.short_self_prims = std::max(sum.short_self_prims, ps.short_self_prims);
     sum.short_walks += ps.short_walks;
     sum.short_walk_passes += ps.short_walk_passes;
     sum.ms_pilot += ps.ms_pilot;

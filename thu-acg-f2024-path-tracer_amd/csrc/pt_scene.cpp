@@ -1312,6 +1312,8 @@ int pt::scene_build(pt_scene* s) {
     // chain, still, a diffuse material without a normal map (fetch_tex looks up whatever colour texture it has)
     s->entry_shadeable.assign(entries.size(), 0);
     s->shade_prims.clear();
+    s->shade_self_ok.clear();
+    s->shade_entry.clear();
     for (size_t i = 0; i < entries.size(); ++i) {
         const Entry& e = entries[i];
         if ((e.kind != ENTRY_SPHERE && e.kind != ENTRY_QUAD) || e.inst >= 0 || e.n_prims != 1u) continue;
@@ -1324,6 +1326,25 @@ int pt::scene_build(pt_scene* s) {
         } else if ((pr.kind & 0xFFu) != PRIM_QUAD) continue;
         s->entry_shadeable[i] = 1;
         s->shade_prims.push_back(e.first_prim);
+        s->shade_entry.push_back((uint32_t)i);
+        //  a quad whose numbers keep the proof's bound: finite, |coordinates| <= 1e6, the stored normal of unit length
+        bool self_ok = (pr.kind & 0xFFu) == PRIM_QUAD;
+        if (self_ok) {
+            const QuadD& q = quads[pr.index];
+            for (int a = 0; a < 3; ++a)
+                for (double x : {q.q[a], q.q[a] + q.u[a], q.q[a] + q.v[a], q.q[a] + q.u[a] + q.v[a], q.n[a]}) self_ok = self_ok && std::fabs(x) <= 1e6;
+            const double n2 = (q.n[0] * q.n[0] + q.n[1] * q.n[1]) + q.n[2] * q.n[2];
+            self_ok = self_ok && std::fabs(q.d) <= 2e6 && std::fabs(n2 - 1.0) <= 1e-9;   // (a NaN fails every comparison)
+        }
+        s->shade_self_ok.push_back(self_ok ? 1 : 0);
+    }
+    // the place of every entry in SceneD::entry_box, the order the flat top level's loop runs in (below: non-mesh entries first, each kind in entry order)
+    s->entry_at.assign(entries.size(), 0);
+    {
+        uint32_t at = 0;
+        for (int pass = 0; pass < 2; ++pass)
+            for (size_t i = 0; i < entries.size(); ++i)
+                if ((entries[i].kind == ENTRY_MESH) == (pass == 1)) s->entry_at[i] = at++;
     }
     std::vector<Box> entry_boxes(tlas_items.size());
     for (const BuildItem& it : tlas_items) entry_boxes[it.ref_payload] = it.box;

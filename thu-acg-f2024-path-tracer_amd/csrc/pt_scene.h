@@ -88,6 +88,10 @@ struct pt_scene {
     // an instance chain that does not move, its material diffuse without a normal map — and the global primitive ids of the flagged entries
     std::vector<uint8_t> entry_shadeable;
     std::vector<uint32_t> shade_prims;
+    //  entry_at: the place of entry i in SceneD::entry_box; shade_entry: the entry of shade_prims[j]; shade_self_ok[j]: a quad
+    // whose numbers keep the bound under which a bounce that left it cannot hit it again (k_short then does not test it)
+    std::vector<uint32_t> entry_at, shade_entry;
+    std::vector<uint8_t> shade_self_ok;
     bool motion_on() const {       // "in effect": the kernels' MOT forms run
         return has_moving_instance || ((shutter_open != 0.0 || shutter_close != 1.0) && !motionless);
     }

@@ -58,6 +58,11 @@ struct SkyCam {
     uint32_t width, height;
 };
 
+// Where box b's bit stands in a reach mask the device keeps (k_sky_classify): the place of entry b in the flat top level's loop
+struct ReachOrder {
+    uint8_t at[SKY_MAX_BOXES];
+};
+
 PT_SKY_HD double sky_abs(double x) { return x < 0.0 ? -x : x; }
 PT_SKY_HD double sky_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
@@ -142,21 +147,47 @@ PT_SKY_HD unsigned long long sky_tile_uncleared(const SkyCam& c, uint32_t ty, ui
 PT_SKY_HD bool sky_tile_is_clear(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6) {
     return sky_tile_uncleared(c, ty, tx, n_boxes, boxes6) == 0ull;
 }
+// The REACH mask of a tile: sky_tile_uncleared's answer, or all ones wherever the test says nothing — a tile outside the
+// image, more boxes than the cap, a NaN or an infinity among the boxes or in the camera (sky_extent is then not finite), the lens's centre or a corner of it inside
+// or on a box (point 6 above: that box is never cleared; the mask then names every box, so that a reader sees at once that nothing was
+// said). A 0 bit is the proof above: no camera ray of the tile enters that box. The mask is 0 exactly for the sure-sky tiles.
+PT_SKY_HD bool sky_tile_says_nothing(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6) {
+    if (n_boxes > SKY_MAX_BOXES || ty * 8u >= c.height || tx * 8u >= c.width || !(c.extent < 1.7976931348623157e308)) return true;
+    for (uint32_t i = 0; i < 6 * n_boxes; ++i)
+        if (!(boxes6[i] - boxes6[i] == 0.0)) return true;   // (sky_extent may have lost a NaN behind a later, finite coordinate)
+    for (int k = 0; k < 5; ++k) {   // the lens's centre and its four corners
+        double o[3];
+        for (int a = 0; a < 3; ++a) o[a] = k == 4 ? c.center[a] : c.center[a] + (c.dof_right[a] * ((k & 1) ? 1.0 : -1.0) + c.dof_up[a] * ((k & 2) ? 1.0 : -1.0));
+        for (uint32_t b = 0; b < n_boxes; ++b) {
+            const double* bx = boxes6 + 6 * (size_t)b;
+            if (bx[0] <= o[0] && o[0] <= bx[3] && bx[1] <= o[1] && o[1] <= bx[4] && bx[2] <= o[2] && o[2] <= bx[5]) return true;
+        }
+    }
+    return false;
+}
+PT_SKY_HD unsigned long long sky_tile_reach(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6) {
+    if (n_boxes == 0u) return 0ull;
+    return sky_tile_says_nothing(c, ty, tx, n_boxes, boxes6) ? ~0ull : sky_tile_uncleared(c, ty, tx, n_boxes, boxes6);
+}
 // The three kinds of tile. SURE SKY: every box is cleared. SHORT: every box that is NOT cleared is flagged in `shadeable`
 // (bit b = box b: the box of an entry the short-path pass can shade, pt_scene.cpp) — a camera ray of the tile hits such an entry or nothing.
 // WAVEFRONT: everything else, and every tile about which nothing can be said (a tile outside the image, more boxes than the cap, a NaN or an
 // infinity among the boxes or in the camera: sky_extent is then not finite). Only where the pass pays depends on this; no result does.
 enum SkyTileClass : uint8_t { SKY_TILE_WAVEFRONT = 0, SKY_TILE_SKY = 1, SKY_TILE_SHORT = 2,
                               SKY_TILE_TAKEN = 3 };   // TAKEN: never this test's answer: a wavefront tile the short-path pass takes by its measured yield (k_short_select)
-PT_SKY_HD uint8_t sky_tile_class(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable) {
+// (`todo`: sky_tile_uncleared's answer for the tile, which the caller has)
+PT_SKY_HD uint8_t sky_tile_class_of(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable, unsigned long long todo) {
     if (n_boxes > SKY_MAX_BOXES || ty * 8u >= c.height || tx * 8u >= c.width) return SKY_TILE_WAVEFRONT;
-    const unsigned long long todo = sky_tile_uncleared(c, ty, tx, n_boxes, boxes6);
     if (todo == 0ull) return SKY_TILE_SKY;
     if (!(c.extent < 1.7976931348623157e308) || (todo & ~shadeable) != 0ull) return SKY_TILE_WAVEFRONT;
     for (uint32_t b = 0; b < n_boxes; ++b)   // (a box with a NaN or an infinity is never cleared: flagged or not, it makes no tile short)
         for (int i = 0; i < 6 && ((todo >> b) & 1ull); ++i)
             if (!(boxes6[6 * (size_t)b + i] - boxes6[6 * (size_t)b + i] == 0.0)) return SKY_TILE_WAVEFRONT;
     return SKY_TILE_SHORT;
+}
+PT_SKY_HD uint8_t sky_tile_class(const SkyCam& c, uint32_t ty, uint32_t tx, uint32_t n_boxes, const double* boxes6, unsigned long long shadeable) {
+    if (n_boxes > SKY_MAX_BOXES || ty * 8u >= c.height || tx * 8u >= c.width) return SKY_TILE_WAVEFRONT;
+    return sky_tile_class_of(c, ty, tx, n_boxes, boxes6, shadeable, sky_tile_uncleared(c, ty, tx, n_boxes, boxes6));
 }
 
 }  // namespace pt

@@ -421,9 +421,17 @@ struct ShortArgsD {
     uint32_t* pilot;      // not null: the counting form runs (k_short<true>) and writes {finished, seen} at pilot[2 * tile]
     uint32_t walk_cap;    // the miss proof's stack budget in entries per lane (<= SHORT_WALK_STACK)
     uint32_t defer;       // the bounces' miss proofs run in dense passes (0: where the ray enters the box, PT_SHORT_DEFER=0)
+    // DESIGN.md §23.3. reach: per tile of the frame, the entries a camera ray of the tile may enter, bit k = SceneD::entry_box[k] (k_sky_classify;
+    // null: all ones, PT_SHORT_REACH=0). shade_at: parallel to shade_prims, the entry's place k in entry_box, | SHADE_AT_SELF_OK for a quad a
+    // bounce that left it need not test again (null bit: it tests it; PT_SHORT_SELF=0 clears them all). direct: a tile whose mask names one
+    // shadeable entry rebuilds the hit without the top level's loop (0: PT_SHORT_DIRECT=0)
+    const uint32_t* reach;
+    const uint32_t* shade_at;
+    uint32_t direct;
 };
+constexpr uint32_t SHADE_AT_SELF_OK = 0x100u;
 // ShortArgsD::n_hard's device words: the three above, [3] the deferred records walked, [4] the passes that walked them (the render's pass, not
-// the pilot's); a diagnostic build (-DPT_STAMPS) sums k_short's wave cycles and walk counts from word SHORT_PROF_AT on (pt_k_short.hip).
+// the pilot's), [5] the tiles rendered by the direct hit; a diagnostic build (-DPT_STAMPS) sums k_short's wave cycles and walk counts from word SHORT_PROF_AT on (pt_k_short.hip).
 constexpr uint32_t SHORT_WORDS = 40, SHORT_PROF_AT = 8;
 constexpr uint32_t SHORT_WALK_STACK = 16;   // the miss proof's stack per lane in LDS (16 KB per block)
 constexpr uint32_t SHORT_YIELD_BINS = 17;   // pilot yields in sixteenths: bin = floor(16 finished / seen), 0 .. 16
