@@ -969,6 +969,68 @@ int pt_mesh_subdivide_host(const pt_subdiv_opts*, uint32_t n_pos, const float* p
                            float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx,
                            float** out_nrm, float** out_uv, uint8_t** out_crease);
 
+/* ---- isosurface extraction: density grids and signed distance fields to meshes (not in the reference, opt-in) ----
+ * A stage of its own in front of pt_mesh (and of pt_mesh_subdivide / pt_mesh_tessellate when rounding or displacement follows): a 3-D
+ * grid of samples in, the triangle mesh of one of its level sets out. No render kernel knows of it. pt_mesh_isosurface runs on the GPU
+ * (csrc/pt_iso.hip), pt_mesh_isosurface_host is its host twin; the two return the same bytes.
+ * Arithmetic: f64 on the f32 samples widened, in the order written here, no fused operation; each written attribute is rounded to f32
+ *  once. sqrt is the IEEE operation.
+ * Grid: pt_mat_medium_grid's: values[(k ny + j) nx + i] is the sample at the centre of cell (i, j, k) of the box, so with
+ *  h_a = (hi_a - lo_a) / (double)n_a the point of grid index i_a lies at lo_a + ((double)i_a + 0.5) * h_a per axis. A grid made for a
+ *  medium meshes where the medium's density crosses `iso`.
+ * Lattice: the sample centres. closed = 1 adds one layer on every side: grid indices -1 .. n_a per axis, the added points read
+ *  `outside`, their positions continue the spacing ((double)(-1) + 0.5 = -0.5). NX x NY x NZ points, N_a = n_a + 2 closed; primed
+ *  indices count from the first lattice layer; the linear index of a point is (k' NY + j') NX + i'.
+ * A point is inside when its value >= iso.
+ * Marching tetrahedra. A lattice cube is anchored at its corner of lowest indices (every point with i' < NX - 1, j' < NY - 1,
+ *  k' < NZ - 1 anchors one; its linear index is the anchor's); its corners are numbered c = x + 2y + 4z. It is cut into the six
+ *  tetrahedra of the Kuhn split around the diagonal 0-7, in this order, corners (v0, v1, v2, v3):
+ *    0 (0,1,3,7)   1 (0,1,5,7)   2 (0,2,3,7)   3 (0,2,6,7)   4 (0,4,5,7)   5 (0,4,6,7)
+ *  so neighbouring cubes agree on every face diagonal. Tetrahedra 0, 3 and 4 are positive (det(v1 - v0, v2 - v0, v3 - v0) = +1 in
+ *  lattice coordinates), 1, 2 and 5 negative.
+ * Edges: a lattice edge runs from point A to B = A + d, d one of the seven offsets with d = dx + 2dy + 4dz in 1..7 (axes, face
+ *  diagonals, the cube diagonal): every edge of every tetrahedron is one, from the corner with the lower number. An edge crosses when
+ *  exactly one endpoint is inside. The crossing edges in ascending order of (A's linear index, B's linear index), which for one A is
+ *  ascending d: the edge of rank r gives vertex r, shared by every tetrahedron around it.
+ * Vertex: a, b the values at A, B: t = (iso - a) / (b - a) (always from A), P = PA + (PB - PA) * t per component.
+ * Triangles, in ascending order of (cube, tetrahedron 0..5, triangle 0..1). Case m of a tetrahedron: bit l set when v_l is inside. Its
+ *  edges: 0 = (v0,v1) 1 = (v0,v2) 2 = (v0,v3) 3 = (v1,v2) 4 = (v1,v3) 5 = (v2,v3). One corner a alone on its side, the others b < c < d:
+ *  the triangle of the edges (ab, ac, ad). Two inside a < b, two outside c < d: the quad (ac, ad, bd, bc) split by its diagonal ac-bd
+ *  into (ac, ad, bd) and (ac, bd, bc). The second and third vertex are then swapped where needed so that, with lattice coordinates for
+ *  the corners and edge midpoints for the vertices, (p1 - p0) x (p2 - p0) has a positive dot product with (mean of the outside corners -
+ *  mean of the inside corners): normals point towards lower values. For a positive tetrahedron that gives, per case m = 0 .. 15:
+ *    0000 -                 0001 (0,1,2)           0010 (0,4,3)           0011 (1,2,4) (1,4,3)
+ *    0100 (1,3,5)           0101 (0,5,2) (0,3,5)   0110 (0,4,5) (0,5,1)   0111 (2,4,5)
+ *    1000 (2,5,4)           1001 (0,1,5) (0,5,4)   1010 (0,5,3) (0,2,5)   1011 (1,5,3)
+ *    1100 (1,3,4) (1,4,2)   1101 (0,3,4)           1110 (0,2,1)           1111 -
+ *  (m written v3 v2 v1 v0); a negative tetrahedron swaps the second and third vertex of each triangle. A sample equal to iso makes
+ *  several edges meet in one point (t = 0): the zero-area triangles that follow are data, as section 27 keeps a == b edges.
+ * Normals (`normals`): 0 gradient: at a lattice point g_a = (v+ - v-) / (2.0 * h_a) per axis, v+ and v- the neighbours along the axis;
+ *  where one of them is not in the lattice, the one-sided difference over h_a with the point's own value in its place. At a vertex
+ *  G = gA + (gB - gA) * t per component, N = -G, L = sqrt((N.x N.x + N.y N.y) + N.z N.z); N / L when L is finite and > 0, else
+ *  (0, 1, 0). 1 smooth: section 27's smooth normals of the finished mesh, (0, 1, 0) where the sum is unusable. 2 none: *out_nrm = NULL.
+ * Refused with -1 before any device work: a NULL output pointer, values or box; some n_a < 2; nx ny nz > 2^28; more than 2^29 lattice
+ *  points after padding (7 x points then fits 32 bits); a value, iso, outside or a box coordinate that is not finite; lo_a >= hi_a; an
+ *  unknown closed or normals value. NULL options mean the defaults. Refused with -1 after the counting pass, with nothing held: more than
+ *  0x07FFFFFF triangles (pt_mesh's cap). A grid with no crossing returns 0 and an empty mesh (counts 0). Outputs are malloc'd: free
+ *  them with pt_free.
+ * Device memory: 13 B a lattice point (the sample, the mask byte, the first vertex, the first triangle), the scan's own buffer, and the
+ *  mesh: 12 B a vertex (24 with normals), 12 B a triangle; smooth normals add section 27's 28 B a corner. */
+typedef struct pt_iso_opts {
+    double iso;       /* the level. Default 0.5 */
+    int closed;       /* 0 open (default): the surface ends at the hull of the sample centres; 1: one layer of samples of value
+                         `outside` is added on every side, so the surface closes */
+    float outside;    /* default 0 */
+    int normals;      /* 0 gradient (default), 1 smooth (section 27's rule on the final mesh), 2 none */
+} pt_iso_opts;
+int pt_iso_opts_default(pt_iso_opts*);
+int pt_mesh_isosurface(pt_ctx*, const pt_iso_opts*, uint32_t nx, uint32_t ny, uint32_t nz, const float* values,
+                       const double box_lo[3], const double box_hi[3],
+                       float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx, float** out_nrm);
+int pt_mesh_isosurface_host(const pt_iso_opts*, uint32_t nx, uint32_t ny, uint32_t nz, const float* values,
+                            const double box_lo[3], const double box_hi[3],
+                            float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx, float** out_nrm);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

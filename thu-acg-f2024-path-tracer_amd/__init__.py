@@ -222,6 +222,24 @@ class SubdivOpts(C.Structure):
         super().__init__(levels, crease_cos, corner_cos, int(limit), SUBDIV_NORMALS.get(normals, normals))
 
 
+ISO_NORMALS = {"gradient": 0, "smooth": 1, "none": 2}   # pt_iso_opts.normals
+
+
+class IsoOpts(C.Structure):
+    """pt_iso_opts: the level, whether the surface is closed by a layer of `outside` samples, which normals are written
+    (include/pt_amd.h has the rule). A fresh instance holds the defaults: level 0.5, open, gradient normals."""
+
+    _fields_ = [
+        ("iso", C.c_double),
+        ("closed", C.c_int),
+        ("outside", C.c_float),
+        ("normals", C.c_int),
+    ]
+
+    def __init__(self, iso=0.5, closed=0, outside=0.0, normals="gradient"):
+        super().__init__(iso, int(closed), outside, ISO_NORMALS.get(normals, normals))
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -254,6 +272,7 @@ ABI_SYMBOLS = [
     "pt_sky_opts_default", "pt_sky_opts_check", "pt_sky_eval", "pt_sky_sun_irradiance", "pt_sky_probe", "pt_sky_bake", "pt_tex_sky",
     "pt_tess_opts_default", "pt_mesh_tessellate", "pt_mesh_tessellate_host", "pt_mesh_grid", "pt_height_from_rgb8",
     "pt_subdiv_opts_default", "pt_mesh_subdivide", "pt_mesh_subdivide_host",
+    "pt_iso_opts_default", "pt_mesh_isosurface", "pt_mesh_isosurface_host",
 ]
 
 
@@ -434,6 +453,12 @@ def _load():
         lib.pt_subdiv_opts_default.argtypes = [C.POINTER(SubdivOpts)]
         lib.pt_mesh_subdivide.argtypes = [C.c_void_p, C.POINTER(SubdivOpts)] + sub_args
         lib.pt_mesh_subdivide_host.argtypes = [C.POINTER(SubdivOpts)] + sub_args
+    if hasattr(lib, "pt_mesh_isosurface"):         # (absent from an older build in an A/B run: PT_AMD_LIB)
+        fpp, upp, up = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)
+        iso_args = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, fpp, up, upp, up, fpp]
+        lib.pt_iso_opts_default.argtypes = [C.POINTER(IsoOpts)]
+        lib.pt_mesh_isosurface.argtypes = [C.c_void_p, C.POINTER(IsoOpts)] + iso_args
+        lib.pt_mesh_isosurface_host.argtypes = [C.POINTER(IsoOpts)] + iso_args
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -590,6 +615,13 @@ class Context:
         below which it is a corner; limit: push the vertices to the limit surface; normals: "smooth" / "none" (include/pt_amd.h has the rule)."""
         return _subdivide(self.handle, pos, idx, uv, crease, SubdivOpts(levels, _cos_deg(crease_deg, -2.0), _cos_deg(corner_deg, 2.0), limit, normals))
 
+    def isosurface(self, values, box_lo, box_hi, iso=0.5, closed=False, outside=0.0, normals="gradient"):
+        """pt_mesh_isosurface: the level set `iso` of a (nz, ny, nx) float32 grid (pt_mat_medium_grid's layout: the samples sit at the
+        cell centres of the box) as a triangle mesh, by marching tetrahedra on the GPU -> (pos, idx, nrm | None), ready for Scene.mesh,
+        Context.subdivide or Context.tessellate. closed: a layer of `outside` samples around the grid closes the surface; normals:
+        "gradient" / "smooth" / "none" (include/pt_amd.h has the rule)."""
+        return _isosurface(self.handle, values, box_lo, box_hi, IsoOpts(iso, closed, outside, normals))
+
     def sky_probe(self, dirs: np.ndarray, **opts) -> np.ndarray:
         """pt_sky_probe: sky_eval by the bake kernel's device function: (n, 3) unit directions -> (n, 3) radiance, no disc."""
         dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
@@ -679,6 +711,30 @@ def _subdivide(ctx, pos, idx, uv, crease, opts):
 def subdivide_host(pos, idx, uv=None, crease=None, levels=1, crease_deg=None, corner_deg=None, limit=False, normals="smooth"):
     """pt_mesh_subdivide_host: Context.subdivide on the host, the same bytes (no context needed)."""
     return _subdivide(None, pos, idx, uv, crease, SubdivOpts(levels, _cos_deg(crease_deg, -2.0), _cos_deg(corner_deg, 2.0), limit, normals))
+
+
+def _isosurface(ctx, values, box_lo, box_hi, opts):
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    if values.ndim != 3:
+        raise ValueError("values must be a (nz, ny, nx) grid")
+    nz, ny, nx = values.shape
+    lo, hi = np.ascontiguousarray(box_lo, dtype=np.float64).reshape(3), np.ascontiguousarray(box_hi, dtype=np.float64).reshape(3)
+    out = _MeshOut()
+    refs = out.refs()[:5]                            # (no texcoords come out)
+    args = (nx, ny, nz, values.ctypes.data, lo.ctypes.data, hi.ctypes.data)
+    if ctx is None:
+        rc = lib.pt_mesh_isosurface_host(C.byref(opts), *args, *refs)
+    else:
+        rc = lib.pt_mesh_isosurface(ctx, C.byref(opts), *args, *refs)
+    if rc < 0:
+        out.free()
+    _check(rc, "pt_mesh_isosurface_host" if ctx is None else "pt_mesh_isosurface")
+    return out.take()[:3]
+
+
+def isosurface_host(values, box_lo, box_hi, iso=0.5, closed=False, outside=0.0, normals="gradient"):
+    """pt_mesh_isosurface_host: Context.isosurface on the host, the same bytes (no context needed)."""
+    return _isosurface(None, values, box_lo, box_hi, IsoOpts(iso, closed, outside, normals))
 
 
 def mesh_grid(q, u, v, nu: int, nv: int):

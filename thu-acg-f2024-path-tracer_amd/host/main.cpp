@@ -8,6 +8,8 @@
 // albedo (default 1,1,1) and Henyey-Greenstein g (default 0); the camera starts inside it when look_from lies inside),
 // --smoke SCALE[,R,G,B[,G]] (a fixed closed-form plume, smoke_plume below, sampled into a 64^3 grid over the box --fog would build, as an
 // unbounded grid-density camera medium of extinction SCALE * V),
+// --isosurface ISO[,GRID_N] (the same plume sampled into GRID_N^3 cells over the same box and meshed on the GPU where it crosses ISO:
+// pt_mesh_isosurface),
 // --interior DENSITY[,R,G,B[,G[,AR,AG,AB]]] (every glass material of the scene script is filled with a homogeneous medium of that density,
 // albedo, g and absorption per channel; density 0 with an absorption > 0 is a clear tinted body),
 // --dispersion ABBE (every glass material of the scene script disperses: its ior is n_d, ABBE > 0 its Abbe number V_d),
@@ -230,6 +232,23 @@ static void subdivide_meshes(World& world, pt_ctx* ctx, const std::vector<double
     if (done != 3) throw std::runtime_error("--subdivide: the scene does not hold its three meshes");
 }
 
+// --isosurface ISO[,GRID_N]: the plume of --smoke, sampled into GRID_N^3 cells over the box --fog would fill, meshed on the GPU where it
+// crosses ISO (closed, gradient normals) and added to the world as a white diffuse body.
+static void add_isosurface(World& world, pt_ctx* ctx, const std::vector<double>& v, Vec3 lo, Vec3 hi) {
+    const uint32_t N = v.size() > 1 ? (uint32_t)v[1] : 64u;
+    std::vector<float> f((size_t)N * N * N);
+    for (uint32_t k = 0; k < N; ++k)
+        for (uint32_t j = 0; j < N; ++j)
+            for (uint32_t i = 0; i < N; ++i) f[((size_t)k * N + j) * N + i] = (float)smoke_plume((i + 0.5) / N, (j + 0.5) / N, (k + 0.5) / N);
+    pt_iso_opts o;
+    pt_iso_opts_default(&o);
+    o.iso = v[0];
+    o.closed = 1;
+    const Mesh m = Mesh::isosurface(ctx, o, N, N, N, f, lo, hi);
+    if (m.indices.empty()) throw std::runtime_error("--isosurface: the plume does not cross that level");
+    world.add_object(TriangleMesh::from_obj(1.0, m, DiffuseBRDF::from_rgb(Vec3{0.73, 0.73, 0.73})));
+}
+
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
@@ -266,6 +285,8 @@ int main(int argc, char** argv) {
     std::vector<double> displace_v;
     bool subdivide = false;                  // --subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]
     std::vector<double> subdivide_v;
+    bool isosurface = false;                 // --isosurface ISO[,GRID_N]
+    std::vector<double> isosurface_v;
     uint64_t seed = 1;
     std::string out, assets = "assets";
     for (int i = 1; i < argc; ++i) {
@@ -430,12 +451,22 @@ int main(int argc, char** argv) {
             if (subdivide_v.size() > 2 && !(subdivide_v[2] >= 0.0 && subdivide_v[2] <= 180.0)) { std::cerr << "--subdivide: CORNER_DEG must lie in 0..180\n"; return 2; }
             subdivide = true;
         }
+        else if (a == "--isosurface") {
+            if (!parse_numbers(next(), 1, 2, isosurface_v) || (isosurface_v.size() > 1 && (isosurface_v[1] < 2.0 || isosurface_v[1] > 512.0 || isosurface_v[1] != std::floor(isosurface_v[1])))) {
+                std::cerr << "--isosurface must be ISO[,GRID_N]: finite numbers, GRID_N a whole one in 2..512\n";
+                return 2;
+            }
+            isosurface = true;
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]] [--subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]] [--subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]] [--isosurface ISO[,GRID_N]]\n"
+                         "  --isosurface: the plume of --smoke as a surface: V is sampled at the centres of GRID_N^3 cells (default 64) over the box --fog would fill,\n"
+                         "           meshed on the GPU by marching tetrahedra where it crosses ISO (0 < ISO < 1; closed where it leaves the box) and added to the\n"
+                         "           scene as a white diffuse body. Not with --smoke or --fog\n"
                          "  --subdivide: scene 6 only: bunny, spot and cow, coarse control cages, become Loop subdivision surfaces: LEVELS levels on the GPU (each makes\n"
                          "           four triangles of one; at most 2^19 a mesh), the vertices pushed to the limit surface, smooth normals. An edge whose two faces'\n"
                          "           normals differ by more than CREASE_DEG stays sharp (default: none does; 0 keeps every edge, the cage itself); a crease vertex whose\n"
@@ -486,6 +517,7 @@ int main(int argc, char** argv) {
     if (fog && env_sampling > 0.0) { std::cerr << "--fog and --env-sampling cannot be combined\n"; return 2; }
     if (smoke && env_sampling > 0.0) { std::cerr << "--smoke and --env-sampling cannot be combined\n"; return 2; }
     if (smoke && fog) { std::cerr << "--smoke and --fog cannot be combined\n"; return 2; }
+    if (isosurface && (smoke || fog)) { std::cerr << "--isosurface cannot be combined with --smoke or --fog\n"; return 2; }
     if (interior && env_sampling > 0.0) { std::cerr << "--interior and --env-sampling cannot be combined\n"; return 2; }
     if (interior && (fog || smoke)) { std::cerr << "--interior cannot be combined with --fog or --smoke (that would nest media)\n"; return 2; }
     if (mesh_light && (env_sampling > 0.0 || fog || smoke || interior)) {
@@ -594,14 +626,16 @@ int main(int argc, char** argv) {
             setup.world.add_object(ball);
             setup.world.add_light(ball);
         }
-        if (fog || smoke) {
+        if (fog || smoke || isosurface) {
             const double inf = std::numeric_limits<double>::infinity();
             Vec3 lo{inf, inf, inf}, hi{-inf, -inf, -inf};
             setup.world.bounds(lo, hi);
             const Vec3 grow{0.005 * (hi.x - lo.x), 0.005 * (hi.y - lo.y), 0.005 * (hi.z - lo.z)};   // 1 % larger, about its centre
             lo = Vec3{lo.x - grow.x, lo.y - grow.y, lo.z - grow.z};
             hi = Vec3{hi.x + grow.x, hi.y + grow.y, hi.z + grow.z};
-            if (fog) {
+            if (isosurface) {
+                add_isosurface(setup.world, ctx, isosurface_v, lo, hi);
+            } else if (fog) {
                 auto vol = HomogeneousVolume::from_albedo(Cuboid::new_(lo, hi, nullptr), fog_v[0], Vec3{fog_v[1], fog_v[2], fog_v[3]}, fog_v[4]);
                 setup.world.add_object(vol);
                 const Vec3 c = setup.camera.look_from;

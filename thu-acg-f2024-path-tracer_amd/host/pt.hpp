@@ -374,6 +374,17 @@ struct Mesh {
         pt_free(flags);
         return take(pos, np, idx, ni, nrm, uv);
     }
+    // not in the reference: the level set of a grid of samples as a mesh, on the GPU (pt_mesh_isosurface; include/pt_amd.h has the rule;
+    // DESIGN.md section 29). values: nx * ny * nz samples at the cell centres of the box (HeterogeneousVolume::from_grid's layout). Hand the
+    // result to TriangleMesh::from_obj, or to subdivided() / tessellated() first.
+    static Mesh isosurface(pt_ctx* ctx, const pt_iso_opts& opts, uint32_t nx, uint32_t ny, uint32_t nz, const std::vector<float>& values, Vec3 lo, Vec3 hi) {
+        const double a[3] = {lo.x, lo.y, lo.z}, b[3] = {hi.x, hi.y, hi.z};
+        float *pos, *nrm;
+        uint32_t *idx, np, ni;
+        if (values.size() != (size_t)nx * ny * nz) panic("Mesh::isosurface: one value per cell");
+        if (pt_mesh_isosurface(ctx, &opts, nx, ny, nz, values.data(), a, b, &pos, &np, &idx, &ni, &nrm) != 0) panic("Mesh::isosurface");
+        return take(pos, np, idx, ni, nrm, nullptr);
+    }
 
 private:
     static Mesh take(float* pos, uint32_t np, uint32_t* idx, uint32_t ni, float* nrm, float* uv) {
