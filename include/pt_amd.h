@@ -85,6 +85,13 @@ typedef struct pt_render_stats {
        does not test again (the numbers of quad and camera keep the proof's bound). Under PT_EXPERIMENT=1: short_direct_tiles is zero with
        PT_SHORT_REACH=0 or PT_SHORT_DIRECT=0; short_self_prims is zero with PT_SHORT_SELF=0 (PT_SHORT_REACH=0 leaves it as it is). (In front of the deferred proofs' fields: a caller built against the header
        before these two must be rebuilt.) */
+    /* K2's rounds: the two-phase kernel k_extend2 collects the rays of a window that enter mesh boxes in a list and walks the
+       meshes in a second phase; a ray that finds the list full is walked where it was found, which is slow. k2_overflow_rays: those rays, over
+       all launches. A full window whose first half has filled more than half of the list runs the second phase there and again at its end:
+       k2_split_windows counts them. Under PT_EXPERIMENT=1, PT_K2_SPLIT=0 splits no window and PT_K2_SPLIT=2 runs the second phase after any
+       chunk that leaves less than a chunk of room (k2_split_windows then counts those rounds); PT_K2_BLOCKS=n launches K2 on n blocks. Both zero
+       for the batch kernel. (In front of the short pass's fields: a caller built against the header before these two must be rebuilt.) */
+    uint64_t k2_split_windows, k2_overflow_rays;
     uint64_t short_direct_tiles, short_self_prims;
     uint64_t short_walks, short_walk_passes;
     uint64_t pilot_tiles, short_fallback, short_list_bytes, short_pixels;

@@ -80,6 +80,8 @@ class RenderStats(C.Structure):
         ("blocks_shade", C.c_uint32),
         ("compactions", C.c_uint32),
         ("n_alloc_end", C.c_uint32),
+        ("k2_split_windows", C.c_uint64),
+        ("k2_overflow_rays", C.c_uint64),
         ("short_direct_tiles", C.c_uint64),
         ("short_self_prims", C.c_uint64),
         ("short_walks", C.c_uint64),

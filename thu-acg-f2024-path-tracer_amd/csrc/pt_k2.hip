@@ -4,7 +4,8 @@
 namespace pt {
 
 typedef void (*extend_fn)(SceneD, PoolD, CountersD*);
-static extend_fn pick_extend2(int code) {   // code = stack entries * 10 + min blocks per CU
+typedef void (*extend2_fn)(SceneD, PoolD, CountersD*, uint32_t);
+static extend2_fn pick_extend2(int code) {   // code = stack entries * 10 + min blocks per CU
     switch (code) {
     case 163: return k_extend2<16, 3>;
     case 164: return k_extend2<16, 4>;
@@ -18,7 +19,7 @@ static extend_fn pick_extend2(int code) {   // code = stack entries * 10 + min b
     }
 }
 // the MOT forms (motion in effect, pt_amd.h): the default codes only — any other code becomes the default one for its stack
-static extend_fn pick_extend2_mot(int code) {
+static extend2_fn pick_extend2_mot(int code) {
     const int stack = (code % 1000) / 10;
     if (stack <= 16) return k_extend2<16, 4, 128, true>;
     if (stack <= 20) return k_extend2<20, 4, BLOCK, true>;
@@ -32,11 +33,11 @@ static extend_fn pick_extend_batch(uint32_t flat, uint32_t pairs, bool motion = 
     if (motion) return !flat ? k_extend<false, false, true> : pairs ? k_extend<true, true, true> : k_extend<true, false, true>;
     return !flat ? k_extend<false, false> : pairs ? k_extend<true, true> : k_extend<true, false>;
 }
-void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st, bool motion) {   // code: pt_render.cpp extend_code
+void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st, bool motion, uint32_t split) {   // code: pt_render.cpp extend_code
     if (code <= -100) {
         const int kb = motion ? extend2_threads_mot(-code) : extend2_threads(-code);
         const uint32_t blocks = clamp_blocks(pool.n_alloc / (uint32_t)(EXT_WINDOW / BLOCK * kb), max_blocks);   // one per window at most
-        hipLaunchKernelGGL(motion ? pick_extend2_mot(-code) : pick_extend2(-code), dim3(blocks), dim3((uint32_t)kb), 0, st, sc, pool, cnt);
+        hipLaunchKernelGGL(motion ? pick_extend2_mot(-code) : pick_extend2(-code), dim3(blocks), dim3((uint32_t)kb), 0, st, sc, pool, cnt, split);
     }
     else hipLaunchKernelGGL(pick_extend_batch(sc.tlas_flat, sc.flat_pairs, motion), grid_for(pool.n_alloc, max_blocks), dim3(BLOCK), 0, st, sc, pool, cnt);
 }

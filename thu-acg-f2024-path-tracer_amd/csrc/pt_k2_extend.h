@@ -304,21 +304,35 @@ constexpr uint32_t REFILL_MIN = PT_REFILL_MIN;   // idle lanes that trigger a re
 // inside the divergent top-level code — expensive: scene 6, 128-thread blocks: 512 entries K2 +8.6 %, 768 (37.5 % of the window, the
 // round-1 choice) the reference, 1024 -2.3 %. The 128-thread form has the LDS for 1024 (19.5 KB per block, eight blocks per CU); the
 // 256-thread forms with their deeper stacks stay at 768.
+// [r27] Those figures are of a pool nearly half sky and ground rays. Since the sky and short-path passes took those away, 17.6 % of the headline
+// frame's candidates found the list full; a full window now hands a list that fills early to phase B in mid-window (k_extend2, "rounds of a window").
 constexpr int EXT_CAND = PT_EXT_CAND, EXT_CAND_SMALL = PT_EXT_CAND_SMALL;
 static_assert(EXT_WINDOW % BLOCK == 0 && EXT_WINDOW <= 65536, "k_extend2: s_cand_sl holds 16-bit slot offsets inside the window");
 static_assert(EXT_WINDOW == SORT_WINDOW_SLOTS, "the pool is allocated in whole windows of this size (pt_render.cpp rounds n_alloc to 2048)");
 
+#ifdef PT_STAMPS   // diagnostic build: the cycles since the last lap go to `acc` (k_extend2's phases, summed over a window's rounds)
+#define K2_LAP(acc) do { const unsigned long long t_now = stamp(); acc += t_now - t_lap; t_lap = t_now; } while (0)
+#else
+#define K2_LAP(acc)
+#endif
+constexpr uint32_t K2_SPLIT_OFF = 0, K2_SPLIT_HALF = 1, K2_SPLIT_DRAIN = 2;   // k_extend2's `split` (PT_K2_SPLIT; pt_render.cpp Switches::k2_split)
 // KB: threads per block (256; [r3] other sizes for A/B — the window and the candidate list scale with it; MINB = waves per SIMD, which is what hipcc's launch bound means)
 // MOT: as in k_extend
+// split ("rounds of a window"): K2_SPLIT_OFF / K2_SPLIT_HALF / K2_SPLIT_DRAIN — whether a full window's phase A may stop at a
+// chunk boundary and hand the list it has to phase B (wave-uniform: a kernel argument)
 template <int EXT_STACK, int MINB, int KB = BLOCK, bool MOT = false>
-__global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, CountersD* cnt) {
+__global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, CountersD* cnt, uint32_t split) {
     constexpr int WIN = EXT_WINDOW / BLOCK * KB, CAND = (KB <= 128 ? EXT_CAND_SMALL : EXT_CAND) / BLOCK * KB;
+    constexpr int NSEG = WIN / KB + 1;                             // a window's phase A has at most one segment per chunk
     __shared__ uint32_t stack[EXT_STACK * KB];
     __shared__ uint32_t s_best_id[WIN];                            //  8 KB  closest primitive of every slot of the window
     __shared__ double s_cand_t[CAND];                              //  6 KB  candidates (rays that entered mesh boxes): phase-A best t,
     __shared__ uint32_t s_cand_items[CAND];                        //  3 KB  recorded mesh entries, 8 bit each, 0xFF = none,
     __shared__ uint16_t s_cand_sl[CAND];                           //        slot inside the window
-    __shared__ uint32_t s_nrays, s_next, s_win;
+    // s_seg[g]: the candidates phase A found in SEGMENT g of the window — the chunks between two of its barriers. A segment's appends count
+    // into a word of their own, so the words of the segments before it are final from their barrier to the window's end: every thread
+    // reads the same number from them however late it reads (a single counter would already hold the next segment's first appends).
+    __shared__ uint32_t s_seg[NSEG], s_next, s_win, s_stat[2];     // s_stat: this block's {mid-window rounds, overflow rays}, thread 0's
     uint32_t* stk = &stack[threadIdx.x];
     const int lane = (int)(threadIdx.x & 63u);
     const double t_min = 1e-3;                                     // camera.rs:171,179
@@ -336,10 +350,11 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
     if (blockIdx.x == 0 && threadIdx.x == 0) cnt->win_shade = 0;
     if (ldu(&cnt->alive) == 0ull) return;   // (see k_extend)
 #ifdef PT_STAMPS
-    if (threadIdx.x < 8) g_prof[CLASS_DEAD][threadIdx.x] = 0ull;
+    if (threadIdx.x < PROF_COLS) g_prof[CLASS_DEAD][threadIdx.x] = 0ull;
 #endif
     // (the next window's index is drawn before the barrier that ends a window and published by it: see k_shade)
-    if (threadIdx.x == 0) { s_win = (uint32_t)atomicAdd(&cnt->win_extend, 1ull); s_nrays = 0; s_next = 0; }
+    if (threadIdx.x == 0) { s_win = (uint32_t)atomicAdd(&cnt->win_extend, 1ull); s_next = 0; s_stat[0] = 0; s_stat[1] = 0; }
+    if (threadIdx.x < (uint32_t)NSEG) s_seg[threadIdx.x] = 0;
     __syncthreads();
     for (;;) {
         const uint32_t q = s_win;
@@ -349,7 +364,100 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
         // [r3] K2 walks the pool from its END, k_shade from its beginning: each kernel starts on the windows the other touched last,
         // i.e. on what the 256 MB memory-side cache still holds of the 3-5 GB the previous launch streamed (PT_K2_REVERSE=0: A/B)
         const uint32_t wbase = (PT_K2_REVERSE ? n_windows - 1u - win : win) * WIN;
-        PT_STAMP(e0);
+        // ---- rounds of a window ------------------------------------------------------------------------
+        // A window that is mostly mesh fills the list before phase A ends, and what does not fit is walked where it is found (below): in
+        // divergent code, without refill. So a FULL window (tail rounds are half windows already) may hand the list to phase B early:
+        //   K2_SPLIT_HALF   after half of its chunks, when the list holds more than CAND / 2 rays. In the 128-thread form half a window is
+        //                   CAND slots: neither round of a split window can overflow, and each holds more than CAND / 2 rays. A window
+        //                   whose first half stays at or below CAND / 2 is not split and may still overflow in its second half.
+        //   K2_SPLIT_DRAIN  after every chunk from chunk CAND / KB on, when the list holds more than CAND - KB rays: no full window overflows
+        //                   (a tail round of the 256-thread forms — 1024 slots, a list of 768 — still can, under every rule).
+        // Invariants. (1) The decision is block-uniform: it is n_list, the sum of the s_seg words of the segments that have ended, each read
+        // behind the barrier that ended it and written by nobody until the window's end — so every thread takes the same barriers.
+        // (2) A round's list is reused only behind a barrier that follows its phase B. (3) s_best_id covers the whole window; a round's
+        // phase B writes the slots of its own candidates only. (4) A ray's tests keep their order — non-mesh entries, then its meshes in
+        // item order — whichever round walks it, so every hit word keeps its bits.
+        const int j_rule = q >= n_full || split == K2_SPLIT_OFF ? j_hi : split == K2_SPLIT_HALF ? j_lo + (j_hi - j_lo) / 2 : CAND / KB;
+        const uint32_t n_rule = split == K2_SPLIT_HALF ? (uint32_t)CAND / 2u : (uint32_t)(CAND - KB);
+        uint32_t n_list = 0, seg = 0;                                // block-uniform: the list's rays at the last barrier, the current segment
+#ifdef PT_STAMPS
+        unsigned long long t_lap = stamp(), p_a = 0, p_wa = 0, p_b = 0, p_wb = 0, p_over = 0;
+        uint32_t n_walked = 0, n_window = 0;
+#endif
+        // ---- phase B: mesh traversals, 64 rays per pull ------------------------------------------------
+        auto phase_b = [&](const uint32_t n_rays) {
+            // Lanes are refilled: a lane whose ray is done does not wait for the longest ray of a fixed group of 64 —
+            // when at least REFILL_MIN lanes of the wave are idle they draw the next candidates from the list (one
+            // LDS atomic per wave) and the wave goes on with every lane at its own ray. s_next counts RAYS here.
+            bool busy = false, exhausted = false;                   // exhausted: wave-uniform, the list has run out
+            uint32_t sl = 0, items = 0, item_k = 0, cur = REF_EMPTY, first_prim = 0;
+            int sp = 0;
+            RayD wr{}, r{};
+            RayF f{};
+            Closest best{D_INF, HIT_NONE};
+            float t_max_f = 0.0f;
+            auto start_item = [&]() -> bool {                       // enters mesh number item_k of this lane's ray, if any
+                const uint32_t ei = item_k < 4u ? (items >> (8u * item_k)) & 0xFFu : 0xFFu;
+                if (ei == 0xFFu) return false;
+                const Entry e = sc.entries[ei];
+                r = ray_to_local_chain<false, MOT>(sc, e.inst, wr);
+                first_prim = e.first_prim;
+                f = make_rayf(r.o, r.d, e.extent);
+                t_max_f = t_max_f32(best.t);
+                cur = e.blas_root;
+                sp = 0;
+                return true;
+            };
+            for (;;) {
+                const unsigned long long idle = __ballot(!busy);
+                const uint32_t n_idle = (uint32_t)__popcll(idle);
+                if (!exhausted && (n_idle >= REFILL_MIN || n_idle == 64u)) {
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(&s_next, n_idle);
+                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                    exhausted = base + n_idle >= n_rays;
+                    if (!busy) {
+                        const uint32_t idx = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+                        if (idx < n_rays) {
+                            sl = s_cand_sl[idx];
+                            items = s_cand_items[idx];
+                            wr = load_ray(pool, wbase + sl);
+                            best = Closest{s_cand_t[idx], s_best_id[sl]};
+                            item_k = 0;
+                            busy = start_item();                    // a candidate always has at least one item
+                        }
+                    }
+                }
+                if (__ballot(busy) == 0ull) {
+                    if (exhausted) break;
+                    continue;                                       // everybody idle: the refill above was forced, go again
+                }
+                // descend until every busy lane holds a triangle leaf or has run out of nodes in this mesh
+                while (busy && (cur & REF_TYPE_MASK) == REF_NODE) {
+                    uint32_t c0, c1;
+                    const int n = visit_node(&sc.nodes[cur], f, t_min_f, t_max_f, c0, c1);
+                    if (n == 2 && sp < EXT_STACK) stk[(sp++) * KB] = c1;
+                    if (n > 0) cur = c0;
+                    else if (sp > 0) cur = stk[(--sp) * KB];
+                    else cur = REF_EMPTY;
+                }
+                if (busy) {
+                    if ((cur & REF_TYPE_MASK) == REF_TRIS) {
+                        const uint32_t first = cur & 0x07FFFFFFu, count = ((cur >> 27) & 7u) + 1u;
+                        test_leaf(sc, first, count, r, t_min, first_prim, best);
+                        t_max_f = t_max_f32(best.t);
+                        cur = sp > 0 ? stk[(--sp) * KB] : REF_EMPTY;
+                    }
+                    if (cur == REF_EMPTY) {                         // this mesh is done: the ray's next mesh, or the ray is done
+                        ++item_k;
+                        if (!start_item()) {
+                            s_best_id[sl] = best.id;
+                            busy = false;
+                        }
+                    }
+                }
+            }
+        };
         // ---- phase A: top level only ---------------------------------------------------------------
         // (PT_K2_PREFETCH: the ray of the NEXT chunk requested before this chunk's traversal starts)
 #if PT_K2_PREFETCH
@@ -433,8 +541,12 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
             if (m) {
                 const int leader = __ffsll((long long)m) - 1;
                 uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(&s_nrays, (uint32_t)__popcll(m));
-                base = (uint32_t)__shfl((int)base, leader);
+                if (lane == leader) base = atomicAdd(&s_seg[seg], (uint32_t)__popcll(m));
+                base = n_list + (uint32_t)__shfl((int)base, leader);
+#ifdef PT_STAMPS
+                const bool walks = __ballot(n_my > 0 && base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)) >= (uint32_t)CAND) != 0ull;
+                const unsigned long long t_walk = walks ? stamp() : 0ull;
+#endif
                 if (n_my > 0) {
                     const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
                     if (pos < (uint32_t)CAND) {
@@ -445,98 +557,55 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
                         for (uint32_t k = 0; k < n_my; ++k) blas_pass<KB, MOT>(sc, r, sc.entries[(items >> (8u * k)) & 0xFFu], t_min, t_min_f, stk, EXT_STACK, best);
                     }
                 }
+#ifdef PT_STAMPS
+                if (walks) p_over += stamp() - t_walk;
+#endif
             }
             s_best_id[sl] = alive ? best.id : dead_or_idle(state);
-        }
-        PT_STAMP(e1);
-        __syncthreads();
-        PT_STAMP(e2);
-        // ---- phase B: mesh traversals, 64 rays per pull ------------------------------------------------
-        const uint32_t n_rays = s_nrays < (uint32_t)CAND ? s_nrays : (uint32_t)CAND;
-        {
-            // Lanes are refilled: a lane whose ray is done does not wait for the longest ray of a fixed group of 64 —
-            // when at least REFILL_MIN lanes of the wave are idle they draw the next candidates from the list (one
-            // LDS atomic per wave) and the wave goes on with every lane at its own ray. s_next counts RAYS here.
-            bool busy = false, exhausted = false;                   // exhausted: wave-uniform, the list has run out
-            uint32_t sl = 0, items = 0, item_k = 0, cur = REF_EMPTY, first_prim = 0;
-            int sp = 0;
-            RayD wr{}, r{};
-            RayF f{};
-            Closest best{D_INF, HIT_NONE};
-            float t_max_f = 0.0f;
-            auto start_item = [&]() -> bool {                       // enters mesh number item_k of this lane's ray, if any
-                const uint32_t ei = item_k < 4u ? (items >> (8u * item_k)) & 0xFFu : 0xFFu;
-                if (ei == 0xFFu) return false;
-                const Entry e = sc.entries[ei];
-                r = ray_to_local_chain<false, MOT>(sc, e.inst, wr);
-                first_prim = e.first_prim;
-                f = make_rayf(r.o, r.d, e.extent);
-                t_max_f = t_max_f32(best.t);
-                cur = e.blas_root;
-                sp = 0;
-                return true;
-            };
-            for (;;) {
-                const unsigned long long idle = __ballot(!busy);
-                const uint32_t n_idle = (uint32_t)__popcll(idle);
-                if (!exhausted && (n_idle >= REFILL_MIN || n_idle == 64u)) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(&s_next, n_idle);
-                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                    exhausted = base + n_idle >= n_rays;
-                    if (!busy) {
-                        const uint32_t idx = base + (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-                        if (idx < n_rays) {
-                            sl = s_cand_sl[idx];
-                            items = s_cand_items[idx];
-                            wr = load_ray(pool, wbase + sl);
-                            best = Closest{s_cand_t[idx], s_best_id[sl]};
-                            item_k = 0;
-                            busy = start_item();                    // a candidate always has at least one item
-                        }
-                    }
-                }
-                if (__ballot(busy) == 0ull) {
-                    if (exhausted) break;
-                    continue;                                       // everybody idle: the refill above was forced, go again
-                }
-                // descend until every busy lane holds a triangle leaf or has run out of nodes in this mesh
-                while (busy && (cur & REF_TYPE_MASK) == REF_NODE) {
-                    uint32_t c0, c1;
-                    const int n = visit_node(&sc.nodes[cur], f, t_min_f, t_max_f, c0, c1);
-                    if (n == 2 && sp < EXT_STACK) stk[(sp++) * KB] = c1;
-                    if (n > 0) cur = c0;
-                    else if (sp > 0) cur = stk[(--sp) * KB];
-                    else cur = REF_EMPTY;
-                }
-                if (busy) {
-                    if ((cur & REF_TYPE_MASK) == REF_TRIS) {
-                        const uint32_t first = cur & 0x07FFFFFFu, count = ((cur >> 27) & 7u) + 1u;
-                        test_leaf(sc, first, count, r, t_min, first_prim, best);
-                        t_max_f = t_max_f32(best.t);
-                        cur = sp > 0 ? stk[(--sp) * KB] : REF_EMPTY;
-                    }
-                    if (cur == REF_EMPTY) {                         // this mesh is done: the ray's next mesh, or the ray is done
-                        ++item_k;
-                        if (!start_item()) {
-                            s_best_id[sl] = best.id;
-                            busy = false;
-                        }
-                    }
-                }
-            }
-        }
-        PT_STAMP(e3);
-        __syncthreads();
-        PT_STAMP(e4);
+            // ---- the segment's end: the window's last chunk, or a chunk boundary at which the rule is applied (see "rounds of a window")
+            const int jn = j + 1;
+            const bool last = jn == j_hi;
+            if (!last && !(split == K2_SPLIT_DRAIN ? jn >= j_rule : jn == j_rule)) continue;
+            K2_LAP(p_a);
+            __syncthreads();
+            K2_LAP(p_wa);
+            n_list += (uint32_t)__builtin_amdgcn_readfirstlane((int)s_seg[seg]);
+            ++seg;
+            if (!last && n_list <= n_rule) continue;             // the window goes on unsplit: one barrier was all it cost
+            const uint32_t n_over = n_list > (uint32_t)CAND ? n_list - (uint32_t)CAND : 0u;   // the rays phase A walked for want of room
+            if (threadIdx.x == 0) { s_stat[0] += last ? 0u : 1u; s_stat[1] += n_over; }
 #ifdef PT_STAMPS
-        if (lane == 0) {   // K2's row of the profile: CLASS_DEAD (k_shade never runs a group of that class)
+            n_walked += n_over;
+            n_window += n_list;
+#endif
+            phase_b(n_list - n_over);
+            K2_LAP(p_b);
+            if (last) break;
+            __syncthreads();                                       // every wave has left this round's list
+            K2_LAP(p_wb);
+            if (threadIdx.x == 0) s_next = 0;                      // (read again behind the barrier that ends the next segment)
+            n_list = 0;
+        }
+        __syncthreads();
+        K2_LAP(p_wb);
+#ifdef PT_STAMPS
+        // K2's row of the profile: CLASS_DEAD (k_shade never runs a group of that class). Per wave: [0] windows, [1] phase A, [2] its barriers,
+        // [3] phase B, [4] its barriers, [5] rays phase B walked, [7] cycles of the chunks' ends in which a lane walked for want of room
+        // (inside [1]). Per block: [6] the rays walked so, [8 + b / 2] the full windows whose candidates fill b eighths of the window
+        // (b = 0 .. 8; even b in the low 32 bits, odd b in the high)
+        if (lane == 0) {
             atomicAdd(&g_prof[CLASS_DEAD][0], 1ull);
-            atomicAdd(&g_prof[CLASS_DEAD][1], t_e1 - t_e0);   // phase A
-            atomicAdd(&g_prof[CLASS_DEAD][2], t_e2 - t_e1);   // barrier
-            atomicAdd(&g_prof[CLASS_DEAD][3], t_e3 - t_e2);   // phase B
-            atomicAdd(&g_prof[CLASS_DEAD][4], t_e4 - t_e3);   // barrier
-            atomicAdd(&g_prof[CLASS_DEAD][5], (unsigned long long)n_rays);
+            atomicAdd(&g_prof[CLASS_DEAD][1], p_a);
+            atomicAdd(&g_prof[CLASS_DEAD][2], p_wa);
+            atomicAdd(&g_prof[CLASS_DEAD][3], p_b);
+            atomicAdd(&g_prof[CLASS_DEAD][4], p_wb);
+            atomicAdd(&g_prof[CLASS_DEAD][5], (unsigned long long)(n_window - n_walked));
+            atomicAdd(&g_prof[CLASS_DEAD][7], p_over);
+        }
+        if (threadIdx.x == 0) {
+            atomicAdd(&g_prof[CLASS_DEAD][6], (unsigned long long)n_walked);
+            const uint32_t bin = n_window * 8u / (uint32_t)WIN;
+            if (q < n_full) atomicAdd(&g_prof[CLASS_DEAD][8 + bin / 2u], 1ull << (32u * (bin & 1u)));
         }
 #endif
         {   // the window's result: one coalesced 4-byte store per slot; the eight PrimRef gathers (material class) go out together
@@ -546,14 +615,19 @@ __global__ __launch_bounds__(KB, MINB) void k_extend2(SceneD sc, PoolD pool, Cou
 #pragma unroll
             for (int j = 0; j < WIN / KB; ++j) if (j >= j_lo && j < j_hi) stnt(&pool.hit_prim[wbase + (uint32_t)j * KB + threadIdx.x], word[j]);
         }
-        if (threadIdx.x == 0) { s_win = (uint32_t)atomicAdd(&cnt->win_extend, 1ull); s_nrays = 0; s_next = 0; }   // all of this window's uses are behind the barrier above
+        if (threadIdx.x == 0) { s_win = (uint32_t)atomicAdd(&cnt->win_extend, 1ull); s_next = 0; }   // all of this window's uses are behind the barrier above
+        if (threadIdx.x < (uint32_t)NSEG) s_seg[threadIdx.x] = 0;
         __syncthreads();   // LDS lists are reused by the next window
     }
     nseg = wave_sum(nseg);
     if (nseg && (threadIdx.x & 63u) == 0u) atomicAdd(&cnt->segments, nseg);
+    if (threadIdx.x == 0) {                                         // pt_render_stats::k2_split_windows, k2_overflow_rays
+        if (s_stat[0]) atomicAdd(&cnt->k2_split_windows, (unsigned long long)s_stat[0]);
+        if (s_stat[1]) atomicAdd(&cnt->k2_overflow_rays, (unsigned long long)s_stat[1]);
+    }
 #ifdef PT_STAMPS
     __syncthreads();
-    if (threadIdx.x < 8 && g_prof[CLASS_DEAD][threadIdx.x]) atomicAdd(&cnt->prof[CLASS_DEAD][threadIdx.x], g_prof[CLASS_DEAD][threadIdx.x]);
+    if (threadIdx.x < PROF_COLS && g_prof[CLASS_DEAD][threadIdx.x]) atomicAdd(&cnt->prof[CLASS_DEAD][threadIdx.x], g_prof[CLASS_DEAD][threadIdx.x]);
 #endif
 }
 

@@ -24,7 +24,8 @@ bool launch_init(const CamD& cam, const PoolD& pool, uint64_t seed, int max_bloc
 // flat-top-level instantiation without / with pair passes), -(stack*10 + blocks) = two-phase kernel k_extend2<stack, blocks> for stack in {16, 20, 24}.
 // motion: the MOT forms (instances posed at each ray's time). They exist for the batch kernel and the default two-phase codes; another
 // two-phase code becomes the default one for its stack.
-void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st, bool motion = false);
+// split: the two-phase kernel's rule for mid-window rounds (pt_k2_extend.h K2_SPLIT_*; 0: none, 1: at half a window, 2: drain); the batch kernel has none.
+void launch_extend(const SceneD& sc, const PoolD& pool, CountersD* cnt, int max_blocks, int code, hipStream_t st, bool motion = false, uint32_t split = 1);
 // wide_window_min (variant 42): 8192-slot windows while the pool holds at least that many of them per block launched, 4096-slot ones below
 // env: the table argument of a mode that has one (pt_types.h mode_has_table) — the ENV forms' tables; the DSP forms' weight table (device, DSP_BINS x 3) in `col` — else null
 bool launch_shade(const SceneD& sc, const CamD& cam, const PoolD& pool, CountersD* cnt, uint64_t seed, int max_blocks, const ShadeForm& form, hipStream_t st,

@@ -459,6 +459,12 @@ struct Switches {
     int grid_mult = 1;   // persistent grids: resident blocks per CU x CUs x this
     uint32_t wide_window_min = 16;
     int ext2 = 0;        // PT_EXT2 = stack*10 + blocks per CU picks the two-phase K2's instantiation (0: not set)
+    // k_extend2's mid-window rounds (pt_k2_extend.h "rounds of a window"): PT_K2_SPLIT=0: none (the A/B switch inside one library), 1: a full
+    // window whose first half fills more than half of the candidate list runs phase B there, 2: the drain form. PT_K2_BLOCKS=n: K2's
+    // persistent grid is n blocks — with the product grid every window of a pool under 2 M slots is a tail window, so a test of a full
+    // window's code has to ask for fewer.
+    uint32_t k2_split = 1;
+    int k2_blocks = 0;
     enum { K2_AUTO, K2_BATCH, K2_TWOPHASE } k2 = K2_AUTO;   // PT_K2=batch forces the batch kernel, twophase the two-phase one where it can run
     uint64_t compact_num = 1, compact_den = 2;   // compact when live <= num/den of the slots still covered (25 % .. 85 % measured level: within 0.5 %)
     uint32_t poll_cap = 8;
@@ -480,6 +486,8 @@ Switches read_switches(const pt_render_opts& opts) {
     if (const char* e = exp_env("PT_GRID_MULT")) sw.grid_mult = std::max(1, atoi(e));
     if (const char* e = exp_env("PT_WIDE_WINDOW_MIN")) sw.wide_window_min = (uint32_t)std::max(1, atoi(e));
     if (const char* e = exp_env("PT_EXT2")) sw.ext2 = atoi(e);
+    if (const char* e = exp_env("PT_K2_SPLIT")) sw.k2_split = (uint32_t)std::min(2, std::max(0, atoi(e)));
+    if (const char* e = exp_env("PT_K2_BLOCKS")) sw.k2_blocks = std::max(0, atoi(e));
     if (const char* e = exp_env("PT_K2")) sw.k2 = !strcmp(e, "batch") ? Switches::K2_BATCH : !strcmp(e, "twophase") ? Switches::K2_TWOPHASE : Switches::K2_AUTO;
     sw.accum_linear = exp_env("PT_ACCUM_LINEAR") != nullptr;
     sw.no_compact_pool = exp_env("PT_NO_COMPACT_POOL") != nullptr;
@@ -953,7 +961,7 @@ Kernels choose_kernels(const Switches& sw, const pt_scene* s, const Job& job, co
     else if (sw.k2 == Switches::K2_TWOPHASE && two_phase != 0) kn.extend_code = -two_phase;
     const int blocks_extend = extend_occupancy_blocks(kn.extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : kn.extend_code, kn.form.motion);
     kn.blocks_shade = shade_occupancy_blocks(kn.form);
-    kn.grid_extend = s->ctx->n_cus * blocks_extend * sw.grid_mult;
+    kn.grid_extend = sw.k2_blocks ? sw.k2_blocks : s->ctx->n_cus * blocks_extend * sw.grid_mult;
     kn.grid_shade = s->ctx->n_cus * kn.blocks_shade * sw.grid_mult;
     return kn;
 }
@@ -1101,7 +1109,7 @@ int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPla
     while (alive) {
         for (uint32_t i = 0; i < poll_every; ++i) {
             timer.begin(0, st);
-            launch_extend(s->dev.view, pool, s->d_counters, kn.grid_extend, kn.extend_code, st, kn.form.motion);
+            launch_extend(s->dev.view, pool, s->d_counters, kn.grid_extend, kn.extend_code, st, kn.form.motion, sw.k2_split);
             timer.end(st);
             timer.begin(1, st);
             if (!launch_shade(s->dev.view, dc, pool, s->d_counters, job.seed, kn.grid_shade, kn.form, st, sw.wide_window_min, mode_has_table(job.mode) ? &job.env : nullptr))
@@ -1165,7 +1173,15 @@ void print_prof(const CountersD* cnt) {
         const unsigned long long* p = cnt->prof[c];
         if (p[0] && c == CLASS_DEAD)
             fprintf(stderr, "[pt prof] K2 window  n %10llu  phase A %8.0f  barrier %8.0f  phase B %8.0f  barrier %8.0f  candidates %6.1f (cycles per window and wave)\n", p[0],
-                    (double)p[1] / p[0], (double)p[2] / p[0], (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0]);
+                    (double)p[1] / p[0], (double)p[2] / p[0], (double)p[3] / p[0], (double)p[4] / p[0], (double)p[5] / p[0])
+#ifdef PT_STAMPS
+            // the list's overflow (pt_k2_extend.h "rounds of a window"): sums over the frame, and the full windows by eighths of candidates
+            , fprintf(stderr, "[pt prof] K2 overflow  wave cycles: phase A %llu (of it chunk ends with a walk %llu)  barriers %llu  phase B %llu  barriers %llu; rays: phase B %llu (per wave-window sums: x waves per block)  walked in phase A %llu\n",
+                      p[1], p[7], p[2], p[3], p[4], p[5], p[6]),
+              fprintf(stderr, "[pt prof] K2 full windows by candidates in eighths of the window, 0 .. 8: %llu %llu %llu %llu %llu %llu %llu %llu %llu\n", p[8] & 0xFFFFFFFFull,
+                      p[8] >> 32, p[9] & 0xFFFFFFFFull, p[9] >> 32, p[10] & 0xFFFFFFFFull, p[10] >> 32, p[11] & 0xFFFFFFFFull, p[11] >> 32, p[12] & 0xFFFFFFFFull)
+#endif
+            ;
         else if (p[0] && c < N_CLASSES)
             fprintf(stderr, "[pt prof] %-10s n %10llu  body %8.0f = hit %7.0f + env/tex %7.0f + direction %7.0f + pdf/eval/ray %7.0f  dequeue %8.0f  regen+store %8.0f  whole %8.0f (cycles per wave-group)\n",
                     names[c], p[0], (double)p[2] / p[0], (double)p[1] / p[0], (double)p[6] / p[0], (double)p[7] / p[0], (double)(p[2] - p[1] - p[6] - p[7]) / p[0],
@@ -1202,6 +1218,8 @@ void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kern
     stats->blocks_shade = (uint32_t)kn.grid_shade;
     stats->compactions = r.compactions;
     stats->n_alloc_end = pool.n_alloc;
+    stats->k2_split_windows = s->h_counters->k2_split_windows;
+    stats->k2_overflow_rays = s->h_counters->k2_overflow_rays;
     stats->pilot_tiles = job.n_pilot_tiles;
     stats->short_fallback = job.short_fallback ? 1u : 0u;
     stats->short_list_bytes = job.n_short_tiles ? job.short_cap_entries * (job.short_wide ? 8 : 4) : 0u;
@@ -1237,6 +1255,8 @@ void add_stats(pt_render_stats& sum, const pt_render_stats& ps) {
     sum.blocks_shade = ps.blocks_shade;
     sum.compactions += ps.compactions;
     sum.n_alloc_end = ps.n_alloc_end;
+    sum.k2_split_windows += ps.k2_split_windows;
+    sum.k2_overflow_rays += ps.k2_overflow_rays;
     sum.pilot_tiles = std::max(sum.pilot_tiles, ps.pilot_tiles);
     sum.short_fallback += ps.short_fallback;
     sum.short_list_bytes = std::max(sum.short_list_bytes, ps.short_list_bytes);

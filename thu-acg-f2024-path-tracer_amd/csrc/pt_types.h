@@ -454,7 +454,10 @@ struct CountersD {
     // of striding over it (window costs differ by an order of magnitude between sky and mesh tiles). Each
     // kernel zeroes the OTHER kernel's queue; the two alternate on one stream.
     unsigned long long win_extend, win_shade;
-    unsigned long long pad[11];
+    // k_extend2's rounds (pt_k2_extend.h "rounds of a window"): the mid-window rounds it ran, and the rays phase A walked itself because the
+    // candidate list was full. In what was padding: no field moves.
+    unsigned long long k2_split_windows, k2_overflow_rays;
+    unsigned long long pad[9];
     // diagnostic builds only (-DPT_STAMPS, tools/build_variant.sh): wave-cycle sums per k_shade class
     // [class][0 groups, 1 record-load wait, 2 body, 3 work dequeue, 4 regeneration + stores, 5 whole, .., 12 groups whose surface lanes hit one
     // primitive, 13 those whose primitive is no triangle], [N_CLASSES][..] = window phases
