@@ -1038,6 +1038,78 @@ int pt_mesh_isosurface_host(const pt_iso_opts*, uint32_t nx, uint32_t ny, uint32
                             const double box_lo[3], const double box_hi[3],
                             float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx, float** out_nrm);
 
+/* ---- mesh voxelisation: signed distance, occupancy and density grids of a triangle mesh (not in the reference, opt-in) ----
+ * The direction isosurface extraction lacks: a triangle mesh in, a 3-D grid of samples out, in the layout pt_mat_medium_grid and
+ * pt_mesh_isosurface read. No render kernel knows of it. pt_mesh_sdf runs on the GPU (csrc/pt_sdf.hip), pt_mesh_sdf_host is its host
+ * twin; the two write the same bytes. out_values is the caller's: nx ny nz floats.
+ * Arithmetic: f64 on the f32 positions widened, in the order written here, no fused operation; sqrt is the IEEE operation; each output
+ *  is rounded to f32 once.
+ * Grid: values[(k ny + j) nx + i] is the sample at the centre of cell (i, j, k): x_i = lo_x + ((double)i + 0.5) * h_x, with
+ *  h_a = (hi_a - lo_a) / (double)n_a, and so for y_j, z_k.
+ * POSITIVE INSIDE is the default: depth = +d inside, -d outside. With pt_mesh_isosurface (inside: value >= iso, normals towards lower
+ *  values) iso = 0 gives outward normals, iso = -r grows the body by r, iso = +r shrinks it, and a density is the depth clamped.
+ * Sign (skipped for what = 1). The winding number of a sample is the signed count of the surface's crossings of the ray from the sample
+ *  towards +x, taken per column (j, k) so that it is an integer and watertight. P = (y_j, z_k). A triangle (A, B, C) is projected to the
+ *  (y, z) plane; only a column with min(A.y, B.y, C.y) <= P.y <= max(..) and the same in z (exact comparisons) can cross it. For each
+ *  directed edge U -> V of (A -> B, B -> C, C -> A):
+ *   1. if (V.y, V.z) < (U.y, U.z) lexicographically, swap U and V and remember `swapped`;
+ *   2. dy = V.y - U.y, dz = V.z - U.z, e = dy * (P.z - U.z) - dz * (P.y - U.y);
+ *   3. s = +1 when e > 0, or when e == 0 and (dz < 0, or dz == 0 and dy > 0); else s = -1. The tie is P moved by (+eps, +eps^2); an
+ *      edge that projects to a point (dy == dz == 0) gets -1;
+ *   4. the directed edge's side is swapped ? -s : s, its value swapped ? -e : e.
+ *  The two triangles on an edge evaluate the same bits, so exactly one of them owns a column that lies on it. The column crosses the
+ *  triangle when the three sides are equal; that value o is the crossing's orientation (+1: the projection is counter-clockwise, the
+ *  normal has +x, the ray leaves the body). With wa, wb, wc the directed values of B -> C, C -> A, A -> B:
+ *   x* = ((wa * A.x + wb * B.x) + wc * C.x) / ((wa + wb) + wc); a crossing with a zero denominator or a non-finite x* is dropped;
+ *   m = the number of i in 0 .. nx - 1 with x_i < x* (by the x_i formula, not a rounded division); the crossing adds o to the winding of
+ *   every sample i < m of the column. A sample is inside when its winding is non-zero (fill = 0) or odd (fill = 1).
+ *  A degenerate projection never has three equal sides with a non-zero denominator. An open mesh (assets/bunny.obj has 42 boundary
+ *  edges) gets a sign that is defined but not meaningful: use what = 1. A face that lies exactly on sample centres makes the body
+ *  half-open there: an axis-aligned cube [c0, c1]^3 on sample centres is inside on [c0, c1) per axis.
+ * Distance (skipped for what = 2). A triangle with a repeated index, or with n.n == 0 for ab = B - A, ac = C - A (per component, f64),
+ *  n = (ab.y ac.z - ab.z ac.y, ab.z ac.x - ab.x ac.z, ab.x ac.y - ab.y ac.x), is dropped from this pass; dot(u, v) =
+ *  (u.x v.x + u.y v.y) + u.z v.z throughout. D = the minimum over the other triangles of the squared distance from the sample centre
+ *  P to the triangle, by the Voronoi region of the closest point, the first that applies:
+ *   ap = P - A; d1 = dot(ab, ap); d2 = dot(ac, ap);               d1 <= 0 and d2 <= 0: dot(ap, ap)                      (vertex A)
+ *   bp = ap - ab; d3 = dot(ab, bp); d4 = dot(ac, bp);             d3 >= 0 and d4 <= d3: dot(bp, bp)                     (vertex B)
+ *   vc = d1 * d4 - d3 * d2;          vc <= 0, d1 >= 0, d3 <= 0: v = d1 / (d1 - d3), q = ap - ab * v, dot(q, q)          (edge AB)
+ *   cp = ap - ac; d5 = dot(ab, cp); d6 = dot(ac, cp);             d6 >= 0 and d5 <= d6: dot(cp, cp)                     (vertex C)
+ *   vb = d5 * d2 - d1 * d6;          vb <= 0, d2 >= 0, d6 <= 0: w = d2 / (d2 - d6), q = ap - ac * w, dot(q, q)          (edge AC)
+ *   va = d3 * d6 - d5 * d4;          va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)),
+ *                                                                         q = bp - (ac - ab) * w, dot(q, q)             (edge BC)
+ *   else den = (va + vb) + vc; v = vb / den; w = vc / den; q = ap - (ab * v + ac * w), dot(q, q)                        (the face)
+ *  (vector operations per component). The minimum of f64 values does not depend on the order of the triangles, nor on leaving out
+ *  triangles that cannot hold it: the GPU stage culls, the twin does not cull by brick, and the bytes are the same.
+ * Outputs: d = sqrt(D), and d = band where band > 0 and not d < band; depth = inside ? d : -d. what = 0: (float)depth, (float)(-depth)
+ *  with negate; what = 1: (float)d; what = 2: 1.0f inside, 0.0f outside; what = 3: (float)(min(d, ramp) / ramp) inside, 0.0f outside.
+ * Refused with -1, nothing written, before any device work: a NULL pointer (NULL options mean the defaults); n_idx that is 0 or not a
+ *  multiple of 3; more than 0x07FFFFFF triangles; an index >= n_pos; a position or box coordinate that is not finite; lo_a >= hi_a; some
+ *  n_a < 2; nx ny nz > 2^28; an unknown what or fill; a band that is negative or not finite; what = 3 with a ramp that is not finite or
+ *  not > 0; for what != 2, no triangle left after the degenerate ones are dropped.
+ * Limits: coordinates whose products overflow or underflow f64 are the caller's problem (f32 positions and a box of their size never do).
+ * Device memory: 96 B a triangle (the 72-B record A, ab, ac and the 24-B f32 box), 4 B x (nx + 1) ny nz for the deltas, which the inside
+ *  flags then replace, 4 B a sample for the output, and the mesh as uploaded (12 B a position, 4 B an index).
+ * pt_mesh_fit_grid (host only) gives cubic cells around a mesh: lo_a / hi_a the bounds of the positions (widened to f64),
+ *  ext_a = hi_a - lo_a, E = the largest ext_a, h = E / ((double)n_longest - 2.0 * margin_cells),
+ *  n_a = max(2, ceil(ext_a / h + 2.0 * margin_cells)), c_a = lo_a + 0.5 * ext_a, half_a = 0.5 * ((double)n_a * h),
+ *  out_lo_a = c_a - half_a, out_hi_a = c_a + half_a. Refused with -1: a NULL pointer, no positions, a position that is not finite, a
+ *  margin that is negative or not finite, n_longest <= 2 margin_cells + 1, E == 0, nx ny nz > 2^28. */
+typedef struct pt_sdf_opts {
+    int what;      /* 0 depth: signed distance, POSITIVE INSIDE (default); 1 distance (unsigned; no sign pass, open meshes welcome);
+                      2 occupancy: 1.0f inside, 0.0f outside (no distance pass); 3 density: a ramp for pt_mat_medium_grid */
+    int fill;      /* which winding numbers are inside: 0 non-zero (default), 1 odd */
+    int negate;    /* what = 0 only: 1 writes -depth (the usual "negative inside" convention) */
+    double band;   /* > 0: distances are capped at band (what 0, 1); 0 (default): exact everywhere */
+    double ramp;   /* what = 3: density = min(d, ramp) / ramp inside, 0 outside; must be given, > 0 (no default) */
+} pt_sdf_opts;
+int pt_sdf_opts_default(pt_sdf_opts*);
+int pt_mesh_sdf(pt_ctx*, const pt_sdf_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                uint32_t nx, uint32_t ny, uint32_t nz, const double box_lo[3], const double box_hi[3], float* out_values);
+int pt_mesh_sdf_host(const pt_sdf_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                     uint32_t nx, uint32_t ny, uint32_t nz, const double box_lo[3], const double box_hi[3], float* out_values);
+int pt_mesh_fit_grid(uint32_t n_pos, const float* pos, uint32_t n_longest, double margin_cells,
+                     uint32_t out_dims[3], double out_lo[3], double out_hi[3]);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

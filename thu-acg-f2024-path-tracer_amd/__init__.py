@@ -242,6 +242,26 @@ class IsoOpts(C.Structure):
         super().__init__(iso, int(closed), outside, ISO_NORMALS.get(normals, normals))
 
 
+SDF_WHAT = {"depth": 0, "distance": 1, "occupancy": 2, "density": 3}   # pt_sdf_opts.what
+SDF_FILL = {"nonzero": 0, "odd": 1}                                    # pt_sdf_opts.fill
+
+
+class SdfOpts(C.Structure):
+    """pt_sdf_opts: what is written (depth, positive inside / distance / occupancy / density), which winding numbers are inside, the
+    band distances are capped at and the density's ramp (include/pt_amd.h has the rule). A fresh instance holds the defaults."""
+
+    _fields_ = [
+        ("what", C.c_int),
+        ("fill", C.c_int),
+        ("negate", C.c_int),
+        ("band", C.c_double),
+        ("ramp", C.c_double),
+    ]
+
+    def __init__(self, what="depth", fill="nonzero", negate=False, band=0.0, ramp=None):
+        super().__init__(SDF_WHAT.get(what, what), SDF_FILL.get(fill, fill), int(negate), band, 0.0 if ramp is None else ramp)
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -275,6 +295,7 @@ ABI_SYMBOLS = [
     "pt_tess_opts_default", "pt_mesh_tessellate", "pt_mesh_tessellate_host", "pt_mesh_grid", "pt_height_from_rgb8",
     "pt_subdiv_opts_default", "pt_mesh_subdivide", "pt_mesh_subdivide_host",
     "pt_iso_opts_default", "pt_mesh_isosurface", "pt_mesh_isosurface_host",
+    "pt_sdf_opts_default", "pt_mesh_sdf", "pt_mesh_sdf_host", "pt_mesh_fit_grid",
 ]
 
 
@@ -461,6 +482,12 @@ def _load():
         lib.pt_iso_opts_default.argtypes = [C.POINTER(IsoOpts)]
         lib.pt_mesh_isosurface.argtypes = [C.c_void_p, C.POINTER(IsoOpts)] + iso_args
         lib.pt_mesh_isosurface_host.argtypes = [C.POINTER(IsoOpts)] + iso_args
+    if hasattr(lib, "pt_mesh_sdf"):                # (absent from an older build in an A/B run: PT_AMD_LIB)
+        sdf_args = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pt_sdf_opts_default.argtypes = [C.POINTER(SdfOpts)]
+        lib.pt_mesh_sdf.argtypes = [C.c_void_p, C.POINTER(SdfOpts)] + sdf_args
+        lib.pt_mesh_sdf_host.argtypes = [C.POINTER(SdfOpts)] + sdf_args
+        lib.pt_mesh_fit_grid.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -624,6 +651,13 @@ class Context:
         "gradient" / "smooth" / "none" (include/pt_amd.h has the rule)."""
         return _isosurface(self.handle, values, box_lo, box_hi, IsoOpts(iso, closed, outside, normals))
 
+    def mesh_sdf(self, pos, idx, dims, box_lo, box_hi, what="depth", fill="nonzero", negate=False, band=0.0, ramp=None):
+        """pt_mesh_sdf: a triangle mesh sampled at the cell centres of an (nx, ny, nz) = dims grid over the box, on the GPU -> a (nz, ny, nx)
+        float32 array in Scene.mat_medium_grid's and Context.isosurface's layout. what: "depth" (signed distance, positive inside) /
+        "distance" (unsigned, open meshes welcome) / "occupancy" / "density" (min(d, ramp) / ramp inside, 0 outside); fill: "nonzero" /
+        "odd"; band > 0 caps the distances (include/pt_amd.h has the rule)."""
+        return _mesh_sdf(self.handle, pos, idx, dims, box_lo, box_hi, SdfOpts(what, fill, negate, band, ramp))
+
     def sky_probe(self, dirs: np.ndarray, **opts) -> np.ndarray:
         """pt_sky_probe: sky_eval by the bake kernel's device function: (n, 3) unit directions -> (n, 3) radiance, no disc."""
         dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
@@ -737,6 +771,38 @@ def _isosurface(ctx, values, box_lo, box_hi, opts):
 def isosurface_host(values, box_lo, box_hi, iso=0.5, closed=False, outside=0.0, normals="gradient"):
     """pt_mesh_isosurface_host: Context.isosurface on the host, the same bytes (no context needed)."""
     return _isosurface(None, values, box_lo, box_hi, IsoOpts(iso, closed, outside, normals))
+
+
+def _mesh_sdf(ctx, pos, idx, dims, box_lo, box_hi, opts):
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+    nx, ny, nz = (int(n) for n in dims)
+    if min(nx, ny, nz) < 0 or max(nx, ny, nz) >= 2**32:
+        raise ValueError("dims must be three 32-bit unsigned integers")
+    lo, hi = np.ascontiguousarray(box_lo, dtype=np.float64).reshape(3), np.ascontiguousarray(box_hi, dtype=np.float64).reshape(3)
+    big = nx * ny * nz > 2**28 or min(nx, ny, nz) < 2                       # (refused by the library: no array of that size is made first)
+    out = np.zeros(1 if big else (nz, ny, nx), dtype=np.float32)
+    args = (len(pos), pos.ctypes.data, len(idx), idx.ctypes.data, nx, ny, nz, lo.ctypes.data, hi.ctypes.data, out.ctypes.data)
+    if ctx is None:
+        rc = lib.pt_mesh_sdf_host(C.byref(opts), *args)
+    else:
+        rc = lib.pt_mesh_sdf(ctx, C.byref(opts), *args)
+    _check(rc, "pt_mesh_sdf_host" if ctx is None else "pt_mesh_sdf")
+    return out
+
+
+def mesh_sdf_host(pos, idx, dims, box_lo, box_hi, what="depth", fill="nonzero", negate=False, band=0.0, ramp=None):
+    """pt_mesh_sdf_host: Context.mesh_sdf on the host, the same bytes (no context needed)."""
+    return _mesh_sdf(None, pos, idx, dims, box_lo, box_hi, SdfOpts(what, fill, negate, band, ramp))
+
+
+def mesh_fit_grid(pos, n_longest: int, margin_cells: float = 2.0):
+    """pt_mesh_fit_grid: cubic cells around a mesh, n_longest of them along its longest extent, margin_cells of them free on either side
+    -> ((nx, ny, nz), box_lo, box_hi) for mesh_sdf."""
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+    dims, lo, hi = np.zeros(3, np.uint32), np.zeros(3, np.float64), np.zeros(3, np.float64)
+    _check(lib.pt_mesh_fit_grid(len(pos), pos.ctypes.data, int(n_longest), float(margin_cells), dims.ctypes.data, lo.ctypes.data, hi.ctypes.data), "pt_mesh_fit_grid")
+    return (int(dims[0]), int(dims[1]), int(dims[2])), lo, hi
 
 
 def mesh_grid(q, u, v, nu: int, nv: int):

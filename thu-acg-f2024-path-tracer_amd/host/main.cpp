@@ -10,6 +10,9 @@
 // unbounded grid-density camera medium of extinction SCALE * V),
 // --isosurface ISO[,GRID_N] (the same plume sampled into GRID_N^3 cells over the same box and meshed on the GPU where it crosses ISO:
 // pt_mesh_isosurface),
+// --mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]] (scene 6: spot, sampled on the GPU into a density grid of its shape, replaces its surface as an
+// unbounded camera medium: pt_mesh_sdf), --remesh OFFSET[,GRID_N] (scene 6: spot and cow go through a signed distance grid and
+// come back as the level set OFFSET * E outside their surface: pt_mesh_sdf, then pt_mesh_isosurface),
 // --interior DENSITY[,R,G,B[,G[,AR,AG,AB]]] (every glass material of the scene script is filled with a homogeneous medium of that density,
 // albedo, g and absorption per channel; density 0 with an absorption > 0 is a clear tinted body),
 // --dispersion ABBE (every glass material of the scene script disperses: its ior is n_d, ABBE > 0 its Abbe number V_d),
@@ -249,6 +252,82 @@ static void add_isosurface(World& world, pt_ctx* ctx, const std::vector<double>&
     world.add_object(TriangleMesh::from_obj(1.0, m, DiffuseBRDF::from_rgb(Vec3{0.73, 0.73, 0.73})));
 }
 
+// --mesh-smoke and --remesh work on the OBJ meshes of scene 6, which the scene adds in the order of SUBDIVIDE_FILES: bunny, spot, cow
+static std::vector<std::shared_ptr<Instance>> obj_instances(World& world, const char* flag) {
+    std::vector<std::shared_ptr<Instance>> out;
+    for (auto& obj : world.objects) {
+        auto inst = std::dynamic_pointer_cast<Instance>(obj);
+        if (inst && std::dynamic_pointer_cast<TriangleMesh>(inst->object)) out.push_back(inst);
+    }
+    if (out.size() != 3) throw std::runtime_error(std::string(flag) + ": the scene does not hold its three meshes");
+    return out;
+}
+
+// The mesh of an instance where the scene puts it: scaled, turned about the instance's axis (Rodrigues, as Instance::bounds), translated
+static Mesh placed_mesh(const Instance& inst) {
+    const auto tm = std::dynamic_pointer_cast<TriangleMesh>(inst.object);
+    Mesh m;
+    m.indices = tm->mesh.indices;
+    m.positions.resize(tm->mesh.positions.size());
+    const double c = std::cos(inst.angle), s = std::sin(inst.angle);
+    const Vec3 a = inst.axis, t = inst.translation;
+    for (size_t i = 0; i + 2 < m.positions.size(); i += 3) {
+        const Vec3 p{tm->mesh.positions[i] * tm->scale, tm->mesh.positions[i + 1] * tm->scale, tm->mesh.positions[i + 2] * tm->scale};
+        const double d = a.x * p.x + a.y * p.y + a.z * p.z;
+        const Vec3 x{a.y * p.z - a.z * p.y, a.z * p.x - a.x * p.z, a.x * p.y - a.y * p.x};
+        m.positions[i] = (float)(p.x * c + x.x * s + a.x * d * (1.0 - c) + t.x);
+        m.positions[i + 1] = (float)(p.y * c + x.y * s + a.y * d * (1.0 - c) + t.y);
+        m.positions[i + 2] = (float)(p.z * c + x.z * s + a.z * d * (1.0 - c) + t.z);
+    }
+    return m;
+}
+
+// --mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]]: spot leaves the scene as a surface and comes back as a cloud of its shape: its mesh, where the
+// scene puts it, sampled on the GPU into a density that rises from 0 at the surface to 1 RAMP_CELLS cells inside (pt_mesh_sdf, what = 3;
+// DESIGN.md section 30) over cubic cells fitted around it, GRID_N along its longest extent; the grid is the camera's unbounded medium, as --smoke's is.
+static void mesh_smoke_cloud(World& world, pt_ctx* ctx, const std::vector<double>& v) {
+    const auto spot = obj_instances(world, "--mesh-smoke")[1];
+    const Mesh m = placed_mesh(*spot);
+    const Grid shape = Grid::fit(m, v.size() > 1 ? (uint32_t)v[1] : 64u, 2.0);
+    pt_sdf_opts o;
+    pt_sdf_opts_default(&o);
+    o.what = 3;
+    o.ramp = (v.size() > 2 ? v[2] : 2.0) * shape.cell();
+    Grid g = Grid::from_mesh(ctx, o, m, shape);
+    for (size_t i = 0; i < world.objects.size(); ++i)
+        if (world.objects[i] == spot) {
+            world.objects.erase(world.objects.begin() + (std::ptrdiff_t)i);
+            break;
+        }
+    world.camera_medium = HeterogeneousVolume::from_grid(nullptr, v[0], Vec3{1.0, 1.0, 1.0}, 0.0, g.nx, g.ny, g.nz, std::move(g.values), g.lo, g.hi);
+}
+
+// --remesh OFFSET[,GRID_N]: spot and cow are sampled into signed distance grids (pt_mesh_sdf, what = 0, GRID_N cubic cells along the longest
+// extent E) and meshed again where the depth is -OFFSET * E (pt_mesh_isosurface, closed): the body grown by OFFSET * E (shrunk when negative),
+// uniformly tessellated, with its material and placement. The bunny is an open mesh, whose sign means nothing, and stays as it is.
+static void remesh_meshes(World& world, pt_ctx* ctx, const std::vector<double>& v) {
+    const auto inst = obj_instances(world, "--remesh");
+    const double N = v.size() > 1 ? v[1] : 64.0, grow = std::fabs(v[0]);
+    const double margin = std::ceil((grow * N + 2.0) / (1.0 + 2.0 * grow));   // cells: two past the grown body on either side
+    for (size_t k = 1; k < 3; ++k) {
+        const auto tm = std::dynamic_pointer_cast<TriangleMesh>(inst[k]->object);
+        const Grid shape = Grid::fit(tm->mesh, (uint32_t)N, margin);
+        const double h = shape.cell(), E = h * (N - 2.0 * margin);
+        pt_sdf_opts o;
+        pt_sdf_opts_default(&o);
+        o.band = grow * E + 4.0 * h;
+        const Grid g = Grid::from_mesh(ctx, o, tm->mesh, shape);
+        pt_iso_opts io;
+        pt_iso_opts_default(&io);
+        io.iso = -v[0] * E;
+        io.closed = 1;
+        io.outside = (float)-o.band;
+        const Mesh r = Mesh::isosurface(ctx, io, g.nx, g.ny, g.nz, g.values, g.lo, g.hi);
+        if (r.indices.empty()) throw std::runtime_error("--remesh: nothing is left of a mesh at that offset");
+        inst[k]->object = TriangleMesh::from_obj(tm->scale, r, tm->material);
+    }
+}
+
 int main(int argc, char** argv) {
     bool quality = false, float_hdr = false;
     int scene = 1, device = 0;
@@ -287,6 +366,10 @@ int main(int argc, char** argv) {
     std::vector<double> subdivide_v;
     bool isosurface = false;                 // --isosurface ISO[,GRID_N]
     std::vector<double> isosurface_v;
+    bool mesh_smoke = false;                 // --mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]]
+    std::vector<double> mesh_smoke_v;
+    bool remesh = false;                     // --remesh OFFSET[,GRID_N]
+    std::vector<double> remesh_v;
     uint64_t seed = 1;
     std::string out, assets = "assets";
     for (int i = 1; i < argc; ++i) {
@@ -458,12 +541,36 @@ int main(int argc, char** argv) {
             }
             isosurface = true;
         }
+        else if (a == "--mesh-smoke") {
+            const auto grid_n = [](double n) { return n >= 8.0 && n <= 256.0 && n == std::floor(n); };
+            if (!parse_numbers(next(), 1, 3, mesh_smoke_v) || !(mesh_smoke_v[0] > 0.0) || (mesh_smoke_v.size() > 1 && !grid_n(mesh_smoke_v[1])) ||
+                (mesh_smoke_v.size() > 2 && !(mesh_smoke_v[2] > 0.0))) {
+                std::cerr << "--mesh-smoke must be SCALE[,GRID_N[,RAMP_CELLS]]: finite numbers, SCALE > 0, GRID_N a whole one in 8..256, RAMP_CELLS > 0\n";
+                return 2;
+            }
+            mesh_smoke = true;
+        }
+        else if (a == "--remesh") {
+            if (!parse_numbers(next(), 1, 2, remesh_v) || !(std::fabs(remesh_v[0]) <= 0.25) ||
+                (remesh_v.size() > 1 && !(remesh_v[1] >= 8.0 && remesh_v[1] <= 256.0 && remesh_v[1] == std::floor(remesh_v[1])))) {
+                std::cerr << "--remesh must be OFFSET[,GRID_N]: finite numbers, OFFSET in -0.25..0.25, GRID_N a whole one in 8..256\n";
+                return 2;
+            }
+            remesh = true;
+        }
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]] [--subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]] [--isosurface ISO[,GRID_N]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]] [--subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]] [--isosurface ISO[,GRID_N]] [--mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]]] [--remesh OFFSET[,GRID_N]]\n"
+                         "  --mesh-smoke: scene 6 only: spot leaves the scene as a surface and comes back as a cloud of its shape: an unbounded grid-density camera\n"
+                         "           medium of extinction SCALE * V, as --smoke's, V the density pt_mesh_sdf samples on the GPU over cubic cells fitted around spot (GRID_N\n"
+                         "           along its longest extent, default 64, two cells of margin): 0 outside, rising to 1 RAMP_CELLS cells (default 2) below the surface.\n"
+                         "           White, isotropic. Not with whatever --smoke is refused with, nor with --smoke, --isosurface, --subdivide or --remesh\n"
+                         "  --remesh: scene 6 only: spot and cow are sampled into signed distance grids on the GPU (GRID_N cubic cells along the longest extent E, default\n"
+                         "           64) and meshed again by --isosurface's marching tetrahedra at the distance OFFSET * E outside the surface (inside when negative):\n"
+                         "           grown, shrunk or (0) merely tessellated evenly; material and placement stay. The bunny is open and stays. Not with --subdivide\n"
                          "  --isosurface: the plume of --smoke as a surface: V is sampled at the centres of GRID_N^3 cells (default 64) over the box --fog would fill,\n"
                          "           meshed on the GPU by marching tetrahedra where it crosses ISO (0 < ISO < 1; closed where it leaves the box) and added to the\n"
                          "           scene as a white diffuse body. Not with --smoke or --fog\n"
@@ -518,6 +625,14 @@ int main(int argc, char** argv) {
     if (smoke && env_sampling > 0.0) { std::cerr << "--smoke and --env-sampling cannot be combined\n"; return 2; }
     if (smoke && fog) { std::cerr << "--smoke and --fog cannot be combined\n"; return 2; }
     if (isosurface && (smoke || fog)) { std::cerr << "--isosurface cannot be combined with --smoke or --fog\n"; return 2; }
+    if (mesh_smoke && (smoke || fog || isosurface || env_sampling > 0.0 || interior || mesh_light || dispersion > 0.0 || motion ||
+                       ((!point_lights.empty() || !spot_lights.empty() || !suns.empty()) && !light_shafts))) {
+        std::cerr << "--mesh-smoke cannot be combined with --smoke, --fog, --isosurface, --env-sampling, --interior, --mesh-light, --dispersion, --motion, "
+                     "or --point-light, --spot-light and --sun without --light-shafts (whatever --smoke is refused with)\n";
+        return 2;
+    }
+    if ((mesh_smoke || remesh) && subdivide) { std::cerr << (mesh_smoke ? "--mesh-smoke" : "--remesh") << " and --subdivide cannot be combined\n"; return 2; }
+    if (mesh_smoke && remesh) { std::cerr << "--mesh-smoke and --remesh cannot be combined\n"; return 2; }
     if (interior && env_sampling > 0.0) { std::cerr << "--interior and --env-sampling cannot be combined\n"; return 2; }
     if (interior && (fog || smoke)) { std::cerr << "--interior cannot be combined with --fog or --smoke (that would nest media)\n"; return 2; }
     if (mesh_light && (env_sampling > 0.0 || fog || smoke || interior)) {
@@ -545,6 +660,8 @@ int main(int argc, char** argv) {
         }
     }
     if (displace && scene != 7) { std::cerr << "--displace works on scene 7 only (the wall with the normal-mapped bricks)\n"; return 2; }
+    if (mesh_smoke && scene != 6) { std::cerr << "--mesh-smoke works on scene 6 only (spot)\n"; return 2; }
+    if (remesh && scene != 6) { std::cerr << "--remesh works on scene 6 only (spot and cow)\n"; return 2; }
     if (subdivide && scene != 6) { std::cerr << "--subdivide works on scene 6 only (bunny, spot and cow)\n"; return 2; }
     if (subdivide) {   // the size of the result, from the files alone: before a context is made
         const uint64_t grow = 1ull << (2 * (uint32_t)subdivide_v[0]);
@@ -603,6 +720,8 @@ int main(int argc, char** argv) {
             setup.world.device_bvh_threshold = 0;
         }
         if (subdivide) subdivide_meshes(setup.world, ctx, subdivide_v);
+        if (remesh) remesh_meshes(setup.world, ctx, remesh_v);
+        if (mesh_smoke) mesh_smoke_cloud(setup.world, ctx, mesh_smoke_v);
         if (sky) setup.camera.environment = EnvironmentType::Map(Sky::new_(sky_opts, sky_width, sky_width / 2));
         setup.world.env_sampling = env_sampling;
         setup.world.sampler = sampler;

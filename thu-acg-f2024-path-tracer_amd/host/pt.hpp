@@ -397,6 +397,34 @@ private:
         return m;
     }
 };
+// not in the reference: a mesh sampled into a 3-D grid on the GPU (pt_mesh_sdf; include/pt_amd.h has the rule): the
+// signed distance (positive inside), the distance, the occupancy or a density ramp at the cell centres of a box, in the layout
+// HeterogeneousVolume::from_grid and Mesh::isosurface read. fit: cubic cells around the mesh (pt_mesh_fit_grid).
+struct Grid {
+    uint32_t nx = 0, ny = 0, nz = 0;
+    Vec3 lo, hi;
+    std::vector<float> values;
+    double cell() const { return (hi.x - lo.x) / (double)nx; }   // (of a fitted grid: its cells are cubes)
+    static Grid fit(const Mesh& mesh, uint32_t n_longest, double margin_cells) {
+        Grid g;
+        uint32_t n[3];
+        double a[3], b[3];
+        if (pt_mesh_fit_grid((uint32_t)(mesh.positions.size() / 3), mesh.positions.data(), n_longest, margin_cells, n, a, b) != 0) panic("Grid::fit");
+        g.nx = n[0]; g.ny = n[1]; g.nz = n[2];
+        g.lo = Vec3{a[0], a[1], a[2]}; g.hi = Vec3{b[0], b[1], b[2]};
+        return g;
+    }
+    // the samples of `mesh` at the cells of `shape` (its dimensions and box; its values are not read)
+    static Grid from_mesh(pt_ctx* ctx, const pt_sdf_opts& opts, const Mesh& mesh, const Grid& shape) {
+        Grid g = shape;
+        const double a[3] = {g.lo.x, g.lo.y, g.lo.z}, b[3] = {g.hi.x, g.hi.y, g.hi.z};
+        g.values.assign((size_t)g.nx * g.ny * g.nz, 0.0f);
+        if (pt_mesh_sdf(ctx, &opts, (uint32_t)(mesh.positions.size() / 3), mesh.positions.data(), (uint32_t)mesh.indices.size(), mesh.indices.data(), g.nx, g.ny, g.nz, a, b,
+                        g.values.data()) != 0)
+            panic("Grid::from_mesh");
+        return g;
+    }
+};
 namespace tobj {
 struct Model { Mesh mesh; };
 // tobj::load_obj(path, &OFFLINE_RENDERING_LOAD_OPTIONS).unwrap() — main.rs:408
