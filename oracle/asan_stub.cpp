@@ -1,5 +1,5 @@
 // Sanitizer build only (oracle/Makefile, target `asan`): csrc/pt_assets.cpp reports errors through pt::set_error / pt::last_error,
-// which live in pt_scene.cpp together with the HIP-dependent scene flattener. This file provides just those two so that the
+// which live in csrc/pt_error.cpp (host-only, like the scene flattener). This file provides just those two so that the
 // file parsers can be built and run under AddressSanitizer / UBSan on the CPU, without a device.
 #include <string>
 

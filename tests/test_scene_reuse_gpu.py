@@ -93,3 +93,29 @@ def test_reused_scene_equals_fresh_scenes(pt, ctx, sid, dyn_width, dyn_spp):
     probes(gs)
     _same(small(gs, cam), want_small)
     gs.close()                              # 8: teardown with every buffer kind live
+
+
+def test_refused_build_then_corrected_equals_a_fresh_scene(pt, ctx):
+    """A build refused half-way — the light grid's table over 2^25 entries: after the placements and the derived flags, before the top
+    level and any upload — leaves a scene that, rebuilt with the setting corrected, renders what a fresh scene with that setting does."""
+    import test_light_grid_gpu as LG
+
+    lights = LG.many_points(129)            # 64^3 cells x 129 lights: just over 2^25
+    quads = [LG.FLOOR, LG.OCCLUDER, LG.CEILING]
+    fresh, cam, _ = LG.grid_scene(pt, ctx, quads, lights, dims=(4, 4, 4))
+    cam = _resized(pt, cam, 32)             # (aspect 1: 32 x 32)
+    assert pt.image_height(cam) == 32
+    want = fresh.render(cam, SEED, 0, 4, slots_per_pixel=1)
+    fresh.close()
+    gs, _, _ = LG.TP.make_scene(pt, ctx, quads, lights)   # built once, uniform selection
+    gs.set_punctual_selection("grid")
+    gs.set_punctual_grid(64, 64, 64)
+    with pytest.raises(pt.PtError, match="2\\^25"):
+        gs.world_build()
+    with pytest.raises(pt.PtError):
+        gs.render(cam, SEED, 0, 4, slots_per_pixel=1)     # (a refused build leaves the world unbuilt)
+    gs.set_punctual_grid(4, 4, 4)
+    gs.world_build()
+    assert gs.punctual_grid()[0] == (4, 4, 4)
+    _same(gs.render(cam, SEED, 0, 4, slots_per_pixel=1), want)
+    gs.close()

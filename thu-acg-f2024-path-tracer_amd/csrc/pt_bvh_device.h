@@ -2,17 +2,9 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
-#include <vector>
-
-#include "pt_types.h"
+#include "pt_flatten.h"   // DeviceBlas: what the builder hands back
 
 namespace pt {
-struct DeviceBlas {
-    std::vector<BvhNode> nodes;     // node 0 = root; child references are LOCAL: REF_NODE | index into `nodes`,
-                                    // REF_TRIS | (count-1) << 27 | first position in `order`
-    std::vector<uint32_t> order;    // BLAS (leaf) order: position -> face index of the mesh
-    int depth = 0;                  // deepest leaf, counted like the host builder's depth_reached
-};
 // false: nothing built (too few triangles, a tree deeper than max_depth, or a HIP error) — build on the host instead
 // median_below: subtrees of at most this many triangles are split in the middle of their (Morton-sorted) run instead of at the
 // code's highest differing bit — balanced bottoms leave the depth budget to the upper levels, where the Morton splits matter

@@ -1,5 +1,5 @@
 // GPU-side BVH builder for triangle meshes (the reference's builder is the O(n^2) sweep SAH of
-// bvh.rs:24-121, the default builder here a host binned SAH — pt_scene.cpp). LBVH after Karras 2012: 63-bit Morton codes
+// bvh.rs:24-121, the default builder here a host binned SAH — pt_flatten.cpp). LBVH after Karras 2012: 63-bit Morton codes
 // of the triangle centroids, one radix sort, the radix tree built in parallel (one thread per internal node), boxes
 // fitted bottom-up with one atomic arrival counter per node, then subtrees of <= leaf_max triangles collapsed into the
 // triangle leaves of pt_types.h and the remaining internal nodes compacted into BvhNode records.
@@ -119,7 +119,7 @@ __global__ void k_split_level(const uint64_t* keys, uint32_t level_first, uint32
         }
     }
 }
-// conservative f32 box of a padded f64 box: Builder::store_box of pt_scene.cpp
+// conservative f32 box of a padded f64 box: Builder::store_box of pt_flatten.cpp
 __device__ inline void store_box(const Box64& b, float* lo, float* hi) {
     double m = 1e-3;
     for (int k = 0; k < 3; ++k) m = fmax(m, fmax(fabs(b.lo[k]), fabs(b.hi[k])));

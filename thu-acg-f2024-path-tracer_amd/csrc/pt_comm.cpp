@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 
 using namespace pt;
 

@@ -18,7 +18,7 @@ PT_DEV RayD ray_to_local(const InstD& m, const RayD& r) {
     return make_ray(xform_point(m.i0, m.i1, m.i2, m.it, r.o), xform_vector(m.i0, m.i1, m.i2, r.d), r.time);
 }
 
-// The pose of a moving instance at `time` (pt_instance_moving's rule, pt_amd.h): pt_instance's operation sequence (pt_scene.cpp
+// The pose of a moving instance at `time` (pt_instance_moving's rule, pt_amd.h): pt_instance's operation sequence (pt_graph.cpp
 // make_pose) on angle0 + dangle * time and tr0 + dtr * time, so the record equals the static instance's of those two values bit for
 // bit. A key pair that does not spin keeps the stored rotation columns and makes no sincos call.
 PT_DEV void pose_at(const InstMotionD& k, double time, InstD& m) {

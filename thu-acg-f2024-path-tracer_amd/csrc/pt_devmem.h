@@ -9,7 +9,7 @@
 
 namespace pt {
 
-bool hip_ok(hipError_t e, const char* what);   // pt_scene.cpp
+bool hip_ok(hipError_t e, const char* what);   // pt_scene_upload.cpp
 
 class DevMem {
     void* p_ = nullptr;

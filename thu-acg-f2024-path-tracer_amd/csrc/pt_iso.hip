@@ -19,7 +19,7 @@
 #include <string>
 
 #include "../../include/pt_amd.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 #include "pt_iso.h"
 #define PT_MESH_STAGE "isosurface"
 #include "pt_tess_dev.h"

@@ -13,7 +13,7 @@
 
 namespace pt {
 
-int set_error(const std::string& msg);   // pt_scene.cpp; returns -1
+int set_error(const std::string& msg);   // pt_error.cpp; returns -1
 
 int iso_check(const char* who, const void* opts_, uint32_t nx, uint32_t ny, uint32_t nz, const float* values, const double* box_lo, const double* box_hi,
               const IsoOut& out, IsoPlan& plan) {

@@ -39,7 +39,7 @@ namespace pt {
 #define PT_PAIR_SINGLE 1            // 0: only cuboids (six faces behind one transform) go through the pair passes
 #endif
 constexpr int PAIR_CAP = 128;       // ring of waiting pairs per wave (a pass runs as soon as 64 wait, an append adds <= 64)
-// pair word = id << 6 | lane: the host (pt_scene.cpp) only sets tlas_flat when the ids of spheres / quads / cuboid faces are below 2^26
+// pair word = id << 6 | lane: the host (pt_flatten.cpp) only sets tlas_flat when the ids of spheres / quads / cuboid faces are below 2^26
 struct PairLds {                    // per wave
     unsigned long long* bt;         // [64] bits of the closest t so far of every ray of the chunk (+inf: none)
     uint32_t* bid;                  // [64] its primitive id

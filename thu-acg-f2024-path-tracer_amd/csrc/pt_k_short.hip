@@ -1,5 +1,5 @@
 // The short-path pass: the tiles whose camera rays can enter only boxes of SHADEABLE entries (pt_sky_tiles.h sky_tile_class;
-// pt_scene.cpp marks the entries: still spheres and quads of the world, a diffuse material without a normal map) are rendered here, ahead of
+// pt_flatten.cpp marks the entries: still spheres and quads of the world, a diffuse material without a normal map) are rendered here, ahead of
 // the wavefront, as far as their paths are camera -> miss or camera -> one diffuse hit -> miss. Every other sample of those tiles — the HARD
 // ones — is appended to a list and rendered by the wavefront from its first draw (pt_k_common.h work_to_pixel).
 //   k_short<false, DEFER>   one wave per (short tile, chunk of samples), lane = pixel of the tile

@@ -9,7 +9,7 @@
 
 #include "../../include/pt_amd.h"
 #include "pt_kernels.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 
 using namespace pt;
 

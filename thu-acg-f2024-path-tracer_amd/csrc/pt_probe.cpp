@@ -9,7 +9,7 @@
 
 #include "../../include/pt_amd.h"
 #include "pt_kernels.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 
 using namespace pt;
 
@@ -40,7 +40,7 @@ int pt::run_probe(pt_ctx* ctx, std::initializer_list<ProbeIn> in, void* out, siz
 extern "C" int pt_intersect(pt_scene* s, const double* rays, uint32_t n, double* out) {
     if (!s || !s->built) return set_error("pt_intersect: world not built");
     return run_probe(s->ctx, {{rays, (size_t)n * 7 * sizeof(double)}}, out, (size_t)n * 15 * sizeof(double), [&](void* const* d_in, void* d_out) {
-        launch_probe(s->dev.view, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
+        launch_probe(s->gpu->dev.view, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
     });
 }
 
@@ -56,12 +56,12 @@ extern "C" int pt_env_probe(pt_scene* s, const pt_camera* cam, int which, const 
     if (env_tables(s, dc, ctx->stream, e) != 0) return -1;
     if (!(e.z > 0.0)) return set_error("pt_env_probe: the environment map has no weight (Z = 0)");
     TexD T;
-    if (!hip_ok(hipMemcpyAsync(&T, s->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") ||
+    if (!hip_ok(hipMemcpyAsync(&T, s->gpu->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, ctx->stream), "hipMemcpy") ||
         !hip_ok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize"))
         return -1;
     const size_t n_in = (size_t)n * (which == 0 ? 2 : 3), n_out = (size_t)n * (which == 0 ? 4 : 1);
     return run_probe(ctx, {{in, n_in * sizeof(double)}}, out, n_out * sizeof(double), [&](void* const* d_in, void* d_out) {
-        launch_env_probe(s->dev.view, T, e, which, (const double*)d_in[0], n, (double*)d_out, ctx->stream);
+        launch_env_probe(s->gpu->dev.view, T, e, which, (const double*)d_in[0], n, (double*)d_out, ctx->stream);
     });
 }
 
@@ -102,7 +102,7 @@ extern "C" int pt_medium_probe(pt_scene* s, int mat, int which, const double* in
 extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t n, double* out) {
     if (!s || !s->built) return set_error("pt_light_probe: world not built");
     if (which != 0 && which != 1) return set_error("pt_light_probe: which must be 0 or 1");
-    if (s->dev.view.n_lights == 0u) return set_error("pt_light_probe: the world has no lights list");
+    if (s->gpu->dev.view.n_lights == 0u) return set_error("pt_light_probe: the world has no lights list");
     const bool exact = s->light_sampling == 1;
     // (pt_render's refusal: the exact functions' chain walks read the stored poses, so they would answer for the scene at time 0)
     if (exact && s->has_moving_instance) return set_error("pt_light_probe: motion together with exact light sampling is not supported (set light sampling to 0, or take the moving instances out)");
@@ -112,16 +112,16 @@ extern "C" int pt_light_probe(pt_scene* s, int which, const double* in, uint32_t
     if (!in || !out) return set_error("pt_light_probe: null buffer");
     const size_t n_in = (size_t)n * (which == 0 ? 4 : 7), n_out = (size_t)n * (which == 0 ? 6 : 1);
     return run_probe(s->ctx, {{in, n_in * sizeof(double)}}, out, n_out * sizeof(double), [&](void* const* d_in, void* d_out) {
-        launch_light_probe(s->dev.view, exact, which, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
+        launch_light_probe(s->gpu->dev.view, exact, which, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
     });
 }
 
 extern "C" int pt_punctual_probe(pt_scene* s, int which, const double* in, uint32_t n, double* out) {
     if (!s || !s->built) return set_error("pt_punctual_probe: world not built");
     if (which < 0 || which > 3) return set_error("pt_punctual_probe: which must be 0, 1, 2 or 3");
-    const uint32_t n_lights = s->dev.view.n_punctual;
+    const uint32_t n_lights = s->gpu->dev.view.n_punctual;
     if (n_lights == 0u) return set_error("pt_punctual_probe: the world was built without punctual lights");
-    if (which >= 2 && !s->dev.view.punctual_cdf) return set_error("pt_punctual_probe: which 2 and 3 need the light grid in effect (pt_scene_set_punctual_selection, then pt_world_build)");
+    if (which >= 2 && !s->gpu->dev.view.punctual_cdf) return set_error("pt_punctual_probe: which 2 and 3 need the light grid in effect (pt_scene_set_punctual_selection, then pt_world_build)");
     if (n == 0) return 0;
     if (!in || !out) return set_error("pt_punctual_probe: null buffer");
     if (which == 1)
@@ -138,7 +138,7 @@ extern "C" int pt_punctual_probe(pt_scene* s, int which, const double* in, uint3
     static const size_t IN_COLS[4] = {3, 4, 3, 2}, OUT_COLS[4] = {9, 7, 11, 1};
     const size_t n_in = (size_t)n * IN_COLS[which], n_out = (size_t)n * OUT_COLS[which];
     return run_probe(s->ctx, {{in, n_in * sizeof(double)}}, out, n_out * sizeof(double), [&](void* const* d_in, void* d_out) {
-        launch_punctual_probe(s->dev.view, which, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
+        launch_punctual_probe(s->gpu->dev.view, which, (const double*)d_in[0], n, (double*)d_out, s->ctx->stream);
     });
 }
 

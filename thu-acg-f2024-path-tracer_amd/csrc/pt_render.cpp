@@ -15,14 +15,11 @@
 
 #include "../../include/pt_amd.h"
 #include "pt_kernels.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 #include "pt_sky_tiles.h"
 
 using namespace pt;
 using namespace pt::host;
-
-extern "C" const char* pt_last_error(void) { return pt::last_error(); }
-extern "C" int pt_set_error_message(const char* msg) { return set_error(msg); }
 
 extern "C" int pt_ctx_create(int device, pt_ctx** out) {
     *out = nullptr;
@@ -62,14 +59,14 @@ extern "C" pt_scene* pt_scene_create(pt_ctx* c) {
     }
     pt_scene* s = new pt_scene();
     s->ctx = c;
+    s->gpu = new SceneGpu();
     return s;
 }
-extern "C" void pt_scene_destroy(pt_scene* s) { delete s; }
-extern "C" pt_ctx* pt_scene_ctx(pt_scene* s) { return s ? s->ctx : nullptr; }
-extern "C" int pt_find_registered_image(pt_scene* s, const char* name) {
-    auto it = s->images.find(name);
-    return it == s->images.end() ? -1 : it->second;
+extern "C" void pt_scene_destroy(pt_scene* s) {
+    if (s) delete s->gpu;   // (its members free what they hold: pt_scene_gpu.h)
+    delete s;
 }
+extern "C" pt_ctx* pt_scene_ctx(pt_scene* s) { return s ? s->ctx : nullptr; }
 
 // Camera::init camera.rs:51-77 (host, once per render)
 namespace {
@@ -246,7 +243,7 @@ int pt::make_camd(pt_scene* s, const pt_camera* cam, CamD& dc) {
     dc.max_depth = cam->max_depth;
     dc.env_is_map = cam->env_is_map ? 1u : 0u;
     dc.env_tex = cam->env_tex;
-    dc.n_lights = s->dev.view.n_lights;
+    dc.n_lights = s->gpu->dev.view.n_lights;
     dc.medium = s->camera_medium >= 0 ? (uint32_t)s->camera_medium + 1u : 0u;
     {   // camera.rs:159-163 with radius 0: origin = center + 0 * px + 0 * py = center bit for bit (px, py are finite), unless a
         // component of center is -0.0 (then -0 + +0 = +0): only then must the products be formed
@@ -288,19 +285,19 @@ int pt::env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e) {
     memset(&e, 0, sizeof e);
     if (s->env_tab_tex != dc.env_tex) {
         TexD T;
-        if (!hip_ok(hipMemcpyAsync(&T, s->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, st), "hipMemcpy(env texture)") ||
+        if (!hip_ok(hipMemcpyAsync(&T, s->gpu->dev.view.tex + dc.env_tex, sizeof T, hipMemcpyDeviceToHost, st), "hipMemcpy(env texture)") ||
             !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(env texture)"))
             return -1;
-        s->env_tab.release();   // the tables are forgotten before they are rebuilt: a failed rebuild leaves none
+        s->gpu->env_tab.release();   // the tables are forgotten before they are rebuilt: a failed rebuild leaves none
         s->env_tab_tex = -1;
         s->env_tab_w = T.w;
         s->env_tab_h = T.h;
         s->env_tab_z = 0.0;
         if (T.w != 0 && T.h != 0) {
             const size_t n_col = (size_t)T.h * (T.w + 1), bytes = (n_col + T.h + 1) * sizeof(double);
-            if (!s->env_tab.reserve(bytes, "hipMalloc(env tables)")) return -1;
-            double* tab = s->env_tab.as<double>();
-            launch_env_tables(s->dev.view, T, tab, tab + n_col, st);
+            if (!s->gpu->env_tab.reserve(bytes, "hipMalloc(env tables)")) return -1;
+            double* tab = s->gpu->env_tab.as<double>();
+            launch_env_tables(s->gpu->dev.view, T, tab, tab + n_col, st);
             if (!hip_ok(hipGetLastError(), "env tables") ||
                 !hip_ok(hipMemcpyAsync(&s->env_tab_z, tab + n_col + T.h, sizeof(double), hipMemcpyDeviceToHost, st), "hipMemcpy(env Z)") ||
                 !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(env tables)"))
@@ -311,8 +308,8 @@ int pt::env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e) {
     e.w = s->env_tab_w;
     e.h = s->env_tab_h;
     e.f = s->env_f;
-    if (s->env_tab && std::isfinite(s->env_tab_z) && s->env_tab_z > 0.0) {
-        e.col = s->env_tab.as<double>();
+    if (s->gpu->env_tab && std::isfinite(s->env_tab_z) && s->env_tab_z > 0.0) {
+        e.col = s->gpu->env_tab.as<double>();
         e.row = e.col + (size_t)e.h * (e.w + 1);
         e.z = s->env_tab_z;
     }
@@ -530,7 +527,7 @@ bool short_entries_wide(const Job& job, uint64_t n_listed) {
 PoolD short_pool(pt_scene* s, const Job& job) {
     PoolD pool;
     memset(&pool, 0, sizeof pool);
-    pool.accum = s->tile_accum.as<double>();
+    pool.accum = s->gpu->tile_accum.as<double>();
     pool.accum_tiled = 1u;
     pool.width = job.dc.width;
     pool.height = job.dc.height;
@@ -616,10 +613,10 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     SkyCam cam = sky_camera(dc.center, dc.forward, dc.pixel00, dc.pixel_du, dc.pixel_dv, dc.dof_right, dc.dof_up, dc.blur_strength, dc.width, dc.height);
     cam.extent = sky_extent(cam, n_boxes, boxes.data());
     // The short-path pass is on where the sky pass is, and only when K2 walks the top level flat (k_short calls that walk), the
-    // scene has no lights list (the selector draw then only moves the counter), some entry is shadeable (pt_scene.cpp; every entry has its own
+    // scene has no lights list (the selector draw then only moves the counter), some entry is shadeable (pt_flatten.cpp; every entry has its own
     // box here: more than SKY_MAX_BOXES would be walked as their union) and a path may have two segments.
     unsigned long long shadeable = 0ull;
-    const bool short_on = !sw.no_short_pass && s->dev.view.tlas_flat != 0u && s->dev.view.n_lights == 0u && !s->shade_prims.empty() && dc.max_depth >= 2u && job.spp <= (1u << 26) /* k_short packs pixel << sample_bits | sample in 32 bits */ &&
+    const bool short_on = !sw.no_short_pass && s->gpu->dev.view.tlas_flat != 0u && s->gpu->dev.view.n_lights == 0u && !s->shade_prims.empty() && dc.max_depth >= 2u && job.spp <= (1u << 26) /* k_short packs pixel << sample_bits | sample in 32 bits */ &&
                           s->entry_shadeable.size() == (size_t)n_boxes && s->entry_boxes.size() / 6 == (size_t)n_boxes &&
                           n_boxes <= 32u /* k_short walks the top level by a 32-bit mask of entries; a flat top level of more (PT_FLAT_MAX) keeps the wavefront */;
     if (short_on)
@@ -632,16 +629,16 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
     const size_t pilot_at = (SKY_HDR_BYTES + box_bytes + prim_bytes + (size_t)n_tiles * (2 * sizeof(uint32_t) + 1) + 7) & ~(size_t)7;
     // ... and behind those the tiles' reach masks, one word per tile
     const size_t reach_at = pilot_at + ((size_t)n_tiles * 2 + 3 * SHORT_YIELD_BINS) * sizeof(uint32_t);
-    if (!s->sky_mem.reserve(reach_at + (size_t)n_tiles * sizeof(uint32_t), "hipMalloc(sky pass)")) return -1;
-    if (!s->tile_accum.reserve(tiled_accum_bytes((size_t)n_tiles * 64), "hipMalloc(tiled accumulator)")) return -1;
-    char* m = s->sky_mem.as<char>();
+    if (!s->gpu->sky_mem.reserve(reach_at + (size_t)n_tiles * sizeof(uint32_t), "hipMalloc(sky pass)")) return -1;
+    if (!s->gpu->tile_accum.reserve(tiled_accum_bytes((size_t)n_tiles * 64), "hipMalloc(tiled accumulator)")) return -1;
+    char* m = s->gpu->sky_mem.as<char>();
     uint32_t* d_counts = (uint32_t*)m;
     double* d_boxes = (double*)(m + SKY_HDR_BYTES);
     uint32_t* d_prims = (uint32_t*)(m + SKY_HDR_BYTES + box_bytes);
     uint32_t* d_sky_list = (uint32_t*)(m + SKY_HDR_BYTES + box_bytes + prim_bytes);
     uint32_t* d_short_list = d_sky_list + n_tiles;
     uint8_t* d_flags = (uint8_t*)(d_short_list + n_tiles);
-    uint32_t* d_tile_map = tile_map_behind(s->tile_accum.as<double>(), (size_t)n_tiles * 64);
+    uint32_t* d_tile_map = tile_map_behind(s->gpu->tile_accum.as<double>(), (size_t)n_tiles * 64);
     uint32_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     job.n_tiles = n_tiles;
     job.d_flags = d_flags;
@@ -723,7 +720,7 @@ int classify_sky(pt_scene* s, const Switches& sw, Job& job, EventTimer& timer) {
         a.n_chunks = 1u;
         a.pilot = job.d_pilot;
         timer.begin(5, job.st);
-        launch_short(s->dev.view, job.dc, pool, job.seed, a, job.st);
+        launch_short(s->gpu->dev.view, job.dc, pool, job.seed, a, job.st);
         timer.end(job.st);
         uint32_t hist[3 * SHORT_YIELD_BINS];
         const uint32_t bin0 = (uint32_t)std::min(17.0, std::max(0.0, std::ceil(sw.pilot_theta * 16.0)));
@@ -795,12 +792,12 @@ void short_prof(const Job& job, const unsigned long long* words) {
 int run_short(pt_scene* s, Job& job, EventTimer& timer) {
     if (!job.sky) return 0;
     const size_t n_tile_pixels = (size_t)((job.dc.width + 7) / 8) * ((job.dc.height + 7) / 8) * 64;
-    double* planes = s->tile_accum.as<double>();
+    double* planes = s->gpu->tile_accum.as<double>();
     ShortHdrD& hdr = job.short_hdr;   // (the job's: the copy below is asynchronous)
     memset(&hdr, 0, sizeof hdr);
     for (int pass = 0; job.n_short_tiles != 0; ++pass) {
         const uint64_t cap = job.short_cap_entries, all = (uint64_t)job.n_short_pixels * job.spp;
-        if (!s->short_mem.reserve((size_t)cap * (job.short_wide ? 8 : 4), "hipMalloc(hard list)")) return -1;
+        if (!s->gpu->short_mem.reserve((size_t)cap * (job.short_wide ? 8 : 4), "hipMalloc(hard list)")) return -1;
         if (!hip_ok(hipMemsetAsync(planes, 0, n_tile_pixels * 3 * sizeof(double), job.st), "hipMemset(tiled accumulator)")) return -1;
         if (!hip_ok(hipMemsetAsync(job.short_words, 0, SHORT_WORDS * sizeof(unsigned long long), job.st), "hipMemset(short pass counts)")) return -1;
         const PoolD pool = short_pool(s, job);
@@ -809,12 +806,12 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
         a.n_short = job.n_short_tiles;
         a.chunk = job.short_chunk;
         a.n_chunks = (job.spp + job.short_chunk - 1) / job.short_chunk;
-        a.hard = s->short_mem.as<void>();
+        a.hard = s->gpu->short_mem.as<void>();
         a.cap = cap;
         a.wide = job.short_wide ? 1u : 0u;
         unsigned long long words[SHORT_WORDS] = {};
         timer.begin(4, job.st);
-        launch_short(s->dev.view, job.dc, pool, job.seed, a, job.st);
+        launch_short(s->gpu->dev.view, job.dc, pool, job.seed, a, job.st);
         timer.end(job.st);
         if (!hip_ok(hipGetLastError(), "short-path pass") ||
             !hip_ok(hipMemcpyAsync(words, job.short_words, sizeof words, hipMemcpyDeviceToHost, job.st), "hipMemcpy(short pass counts)") ||
@@ -839,7 +836,7 @@ int run_short(pt_scene* s, Job& job, EventTimer& timer) {
         job.short_walk_passes = words[4];
         job.short_direct_tiles = words[5];
         short_prof(job, words);
-        hdr.hard = s->short_mem.as<void>();
+        hdr.hard = s->gpu->short_mem.as<void>();
         hdr.short_list = job.short_list;
         hdr.wide = a.wide;
         hdr.sample_bits = a.sample_bits;
@@ -959,7 +956,7 @@ Kernels choose_kernels(const Switches& sw, const pt_scene* s, const Job& job, co
     kn.extend_code = (s->n_mesh_entries > 0 && two_phase != 0) ? -two_phase : -1;
     if (sw.k2 == Switches::K2_BATCH) kn.extend_code = -1;
     else if (sw.k2 == Switches::K2_TWOPHASE && two_phase != 0) kn.extend_code = -two_phase;
-    const int blocks_extend = extend_occupancy_blocks(kn.extend_code == -1 && s->dev.view.tlas_flat ? (s->dev.view.flat_pairs ? -3 : -2) : kn.extend_code, kn.form.motion);
+    const int blocks_extend = extend_occupancy_blocks(kn.extend_code == -1 && s->gpu->dev.view.tlas_flat ? (s->gpu->dev.view.flat_pairs ? -3 : -2) : kn.extend_code, kn.form.motion);
     kn.blocks_shade = shade_occupancy_blocks(kn.form);
     kn.grid_extend = sw.k2_blocks ? sw.k2_blocks : s->ctx->n_cus * blocks_extend * sw.grid_mult;
     kn.grid_shade = s->ctx->n_cus * kn.blocks_shade * sw.grid_mult;
@@ -974,14 +971,14 @@ int bind_pool(pt_scene* s, const Switches& sw, const Job& job, const PoolPlan& p
     const size_t n_f64 = p.dynamic ? 0 : 6;   // the per-slot sample sums and radiances exist in the static mode only (the dynamic mode adds into the frame)
     const size_t bytes = n_al * (sizeof(RayRec) + sizeof(PathRec) + n_f64 * sizeof(double) + 2 * sizeof(uint32_t)) +
                          (kn.ordered ? n_al * (sizeof(RayRec) + sizeof(PathRec) + sizeof(uint32_t)) : 0);
-    if (!s->pool_mem.reserve(bytes, "hipMalloc(path pool)")) return -1;
-    if (!s->d_counters) {
-        if (!hip_ok(hipMalloc((void**)&s->d_counters, sizeof(CountersD)), "hipMalloc(counters)")) return -1;
-        if (!hip_ok(hipHostMalloc((void**)&s->h_counters, sizeof(CountersD), hipHostMallocDefault), "hipHostMalloc(counters)")) return -1;
+    if (!s->gpu->pool_mem.reserve(bytes, "hipMalloc(path pool)")) return -1;
+    if (!s->gpu->counters()) {
+        if (!s->gpu->d_counters.alloc(sizeof(CountersD), "hipMalloc(counters)")) return -1;
+        if (!s->gpu->h_counters.reserve(sizeof(CountersD), "hipHostMalloc(counters)")) return -1;
     }
     memset(&pool, 0, sizeof pool);
     {
-        char* m = s->pool_mem.as<char>();   // hipMalloc memory is 256-B aligned; records first (64-B aligned)
+        char* m = s->gpu->pool_mem.as<char>();   // hipMalloc memory is 256-B aligned; records first (64-B aligned)
         pool.ray = (RayRec*)m; m += n_al * sizeof(RayRec);
         pool.path = (PathRec*)m; m += n_al * sizeof(PathRec);
         double* d = (double*)m;
@@ -1044,10 +1041,10 @@ double* device_accum(const Job& job, double* accum, DevMem& own) {
 // (tiled_accum_bytes, above: the tile map behind the planes is written by classify_sky and never cleared here)
 int tiled_accum(pt_scene* s, const Job& job, PoolD& pool) {
     const size_t tb = (size_t)pool.n_tile_pixels * 3 * sizeof(double);
-    if (!s->tile_accum.reserve(tiled_accum_bytes(pool.n_tile_pixels), "hipMalloc(tiled accumulator)")) return -1;
+    if (!s->gpu->tile_accum.reserve(tiled_accum_bytes(pool.n_tile_pixels), "hipMalloc(tiled accumulator)")) return -1;
     // (the short-path pass has cleared the planes ahead of its kernel, whose sums they hold by now: run_short)
-    if (job.n_short_tiles == 0 && !hip_ok(hipMemsetAsync(s->tile_accum.as<double>(), 0, tb, job.st), "hipMemset(tiled accumulator)")) return -1;
-    pool.accum = s->tile_accum.as<double>();
+    if (job.n_short_tiles == 0 && !hip_ok(hipMemsetAsync(s->gpu->tile_accum.as<double>(), 0, tb, job.st), "hipMemset(tiled accumulator)")) return -1;
+    pool.accum = s->gpu->tile_accum.as<double>();
     pool.accum_tiled = 1u;
     // the kernels find the map behind THIS accumulator's planes (pool_tile_map): the buffer classify_sky wrote into may not have moved
     if (job.sky && tile_map_behind(pool.accum, pool.n_tile_pixels) != job.tile_map) return set_error("pt_render: the sky pass's tile map is not behind the tiled accumulator (internal error)");
@@ -1062,7 +1059,7 @@ int start_counters(pt_scene* s, const Job& job, uint32_t n_slots, CountersD& ini
         const uint64_t part = rem > (uint64_t)sh * 64 ? std::min<uint64_t>(rem - (uint64_t)sh * 64, 64) : 0;
         init_cnt.work[sh].next = rows * 64 + part;
     }
-    return hip_ok(hipMemcpyAsync(s->d_counters, &init_cnt, sizeof init_cnt, hipMemcpyHostToDevice, job.st), "hipMemcpy(counters)") ? 0 : -1;
+    return hip_ok(hipMemcpyAsync(s->gpu->counters(), &init_cnt, sizeof init_cnt, hipMemcpyHostToDevice, job.st), "hipMemcpy(counters)") ? 0 : -1;
 }
 
 // the frame's end: once half of the slots still covered are dead the survivors move to the front and the launches shrink with them
@@ -1070,8 +1067,8 @@ int start_counters(pt_scene* s, const Job& job, uint32_t n_slots, CountersD& ini
 int compact_pool(pt_scene* s, hipStream_t st, uint64_t n_alive, PoolD& pool, EventTimer& timer) {
     const uint32_t new_end = (uint32_t)((n_alive + 8191) & ~(uint64_t)8191);
     const uint32_t cap = new_end;                                  // holes and movers are both at most the live count
-    if (!s->compact_scratch.reserve((2 * (size_t)cap + 2) * sizeof(uint32_t), "hipMalloc(compaction lists)")) return -1;
-    uint32_t* scratch = s->compact_scratch.as<uint32_t>();
+    if (!s->gpu->compact_scratch.reserve((2 * (size_t)cap + 2) * sizeof(uint32_t), "hipMalloc(compaction lists)")) return -1;
+    uint32_t* scratch = s->gpu->compact_scratch.as<uint32_t>();
     timer.begin(2, st);
     launch_compact(pool, new_end, scratch, scratch + cap, scratch + 2 * (size_t)cap, cap, s->ctx->n_cus * 8, st);
     timer.end(st);
@@ -1091,7 +1088,7 @@ int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPla
 
     if (job.sky && job.n_sky_tiles != 0 && job.spp != 0) {   // the sure-sky tiles' samples, ahead of the wavefront
         timer.begin(3, st);
-        launch_sky(s->dev.view, dc, pool, s->d_counters, job.seed, job.sky_list, job.n_sky_tiles, job.sky_chunk, st);
+        launch_sky(s->gpu->dev.view, dc, pool, s->gpu->counters(), job.seed, job.sky_list, job.n_sky_tiles, job.sky_chunk, st);
         timer.end(st);
     }
     const bool wavefront = !(job.sky && job.n_active_tiles == 0);   // a frame that is all sky has none
@@ -1109,10 +1106,10 @@ int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPla
     while (alive) {
         for (uint32_t i = 0; i < poll_every; ++i) {
             timer.begin(0, st);
-            launch_extend(s->dev.view, pool, s->d_counters, kn.grid_extend, kn.extend_code, st, kn.form.motion, sw.k2_split);
+            launch_extend(s->gpu->dev.view, pool, s->gpu->counters(), kn.grid_extend, kn.extend_code, st, kn.form.motion, sw.k2_split);
             timer.end(st);
             timer.begin(1, st);
-            if (!launch_shade(s->dev.view, dc, pool, s->d_counters, job.seed, kn.grid_shade, kn.form, st, sw.wide_window_min, mode_has_table(job.mode) ? &job.env : nullptr))
+            if (!launch_shade(s->gpu->dev.view, dc, pool, s->gpu->counters(), job.seed, kn.grid_shade, kn.form, st, sw.wide_window_min, mode_has_table(job.mode) ? &job.env : nullptr))
                 return set_error("pt_render: no k_shade form for this render");
             timer.end(st);
             if (kn.ordered) {   // what K3 wrote is the pool K2, the compaction and the next K3 read
@@ -1122,10 +1119,10 @@ int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPla
             }
             ++r.iterations;
         }
-        if (!hip_ok(hipMemcpyAsync(s->h_counters, s->d_counters, sizeof(CountersD), hipMemcpyDeviceToHost, st), "hipMemcpy(counters)")) return -1;
+        if (!hip_ok(hipMemcpyAsync(s->gpu->host_counters(), s->gpu->counters(), sizeof(CountersD), hipMemcpyDeviceToHost, st), "hipMemcpy(counters)")) return -1;
         if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(render)")) return -1;
         timer.drain();
-        const uint64_t n_alive = s->h_counters->alive;
+        const uint64_t n_alive = s->gpu->host_counters()->alive;
         alive = n_alive != 0;
         if (alive && r.iterations > max_iterations + 128) return set_error("pt_render: iteration bound exceeded (internal error)");
         if (poll_every < sw.poll_cap) poll_every *= 2;     // (a poll is a pipeline drain of some tens of microseconds: every 8 iterations costs <= 0.5 %)
@@ -1140,7 +1137,7 @@ int run_wavefront(pt_scene* s, const Switches& sw, const Job& job, const PoolPla
         else launch_resolve(pool, d_accum, s->ctx->n_cus * 8, st);
         timer.end(st);
     }
-    if (!hip_ok(hipMemcpyAsync(s->h_counters, s->d_counters, sizeof(CountersD), hipMemcpyDeviceToHost, st), "hipMemcpy(counters)")) return -1;
+    if (!hip_ok(hipMemcpyAsync(s->gpu->host_counters(), s->gpu->counters(), sizeof(CountersD), hipMemcpyDeviceToHost, st), "hipMemcpy(counters)")) return -1;
     if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize(resolve)")) return -1;
     timer.drain();
     r.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1201,8 +1198,8 @@ void print_prof(const CountersD* cnt) {
 
 void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kernels& kn, const PoolD& pool, const EventTimer& timer, const RunResult& r, pt_render_stats* stats) {
     memset(stats, 0, sizeof *stats);
-    stats->samples = s->h_counters->samples + job.short_samples;   // (k_short counts into words of its own: the counters start after it)
-    stats->segments = s->h_counters->segments + job.short_segments;
+    stats->samples = s->gpu->host_counters()->samples + job.short_samples;   // (k_short counts into words of its own: the counters start after it)
+    stats->segments = s->gpu->host_counters()->segments + job.short_segments;
     stats->iterations = r.iterations;
     stats->n_slots = p.n_slots;
     stats->slots_per_pixel = p.dynamic ? 0u : p.k;
@@ -1218,8 +1215,8 @@ void fill_stats(const pt_scene* s, const Job& job, const PoolPlan& p, const Kern
     stats->blocks_shade = (uint32_t)kn.grid_shade;
     stats->compactions = r.compactions;
     stats->n_alloc_end = pool.n_alloc;
-    stats->k2_split_windows = s->h_counters->k2_split_windows;
-    stats->k2_overflow_rays = s->h_counters->k2_overflow_rays;
+    stats->k2_split_windows = s->gpu->host_counters()->k2_split_windows;
+    stats->k2_overflow_rays = s->gpu->host_counters()->k2_overflow_rays;
     stats->pilot_tiles = job.n_pilot_tiles;
     stats->short_fallback = job.short_fallback ? 1u : 0u;
     stats->short_list_bytes = job.n_short_tiles ? job.short_cap_entries * (job.short_wide ? 8 : 4) : 0u;
@@ -1301,7 +1298,7 @@ int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_b
     if (render_mode(s, job.dc, job.st, job.mode, job.env) != 0) return -1;
 
     const Switches sw = read_switches(job.opts);
-    job.form = shade_form(ShadeForm{sw.shade_variant, s->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode, s->motion_on(), s->punctual_on()});
+    job.form = shade_form(ShadeForm{sw.shade_variant, s->gpu->dev.view.n_lights != 0u, job.list, s->sampler == 1 /* the Sobol sampler: DESIGN.md §11 */, job.mode, s->motion_on(), s->punctual_on()});
     EventTimer timer;
     timer.enabled = job.opts.profile != 0;
     if (classify_sky(s, sw, job, timer) != 0) return -1;
@@ -1324,7 +1321,7 @@ int render_core(pt_scene* s, const pt_camera* cam, uint64_t seed, uint32_t spp_b
     RunResult run;
     if (run_wavefront(s, sw, job, plan, kn, pool, d_accum, timer, run) != 0) return -1;
     if (copy_back(job, d_accum, accum) != 0) return -1;
-    if (sw.prof) print_prof(s->h_counters);
+    if (sw.prof) print_prof(s->gpu->host_counters());
     if (stats) fill_stats(s, job, plan, kn, pool, timer, run, stats);
     return 0;
 }
@@ -1365,9 +1362,9 @@ extern "C" int pt_render_pixels(pt_scene* s, const pt_camera* cam, uint64_t seed
     std::vector<uint32_t> sorted(pixels, pixels + n);
     std::sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return tiled_key(a, width, tiles_x) < tiled_key(b, width, tiles_x); });
     if (!hip_ok(hipSetDevice(s->ctx->device), "hipSetDevice")) return -1;
-    if (!s->pixel_list.reserve((size_t)n * sizeof(uint32_t), "hipMalloc(pixel list)")) return -1;   // (re-used like the pool)
-    if (!hip_ok(hipMemcpy(s->pixel_list.as<uint32_t>(), sorted.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(pixel list)")) return -1;
-    return render_core(s, cam, seed, spp_begin, spp_end, accum, opts, stats, s->pixel_list.as<uint32_t>(), sorted.data(), n);
+    if (!s->gpu->pixel_list.reserve((size_t)n * sizeof(uint32_t), "hipMalloc(pixel list)")) return -1;   // (re-used like the pool)
+    if (!hip_ok(hipMemcpy(s->gpu->pixel_list.as<uint32_t>(), sorted.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(pixel list)")) return -1;
+    return render_core(s, cam, seed, spp_begin, spp_end, accum, opts, stats, s->gpu->pixel_list.as<uint32_t>(), sorted.data(), n);
 }
 
 extern "C" int pt_adaptive_schedule(uint32_t min_spp, uint32_t max_spp, uint32_t* bounds, uint32_t cap) {
@@ -1503,7 +1500,7 @@ extern "C" int pt_render_aovs(pt_scene* s, const pt_camera* cam, uint64_t seed, 
     ShadeForm aov_form;   // of a form, the AOV walk looks at the sampler only
     aov_form.qmc = s->sampler == 1;
     aov_form.motion = s->motion_on();   // moving instances are posed at each sample's time, taken through the shutter
-    if (!launch_aov(s->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, aov_form))
+    if (!launch_aov(s->gpu->dev.view, dc, seed, spp_begin, spp_end, d_aov, opts.overwrite != 0, ctx->n_cus * 8, st, aov_form))
         return set_error("pt_render_aovs: no k_aov form for this sampler");
     if (!hip_ok(hipGetLastError(), "kernel launch")) return -1;
     if (!opts.accum_on_device && !hip_ok(hipMemcpyAsync(aov, d_aov, bytes, hipMemcpyDeviceToHost, st), "hipMemcpy(aov)")) return -1;

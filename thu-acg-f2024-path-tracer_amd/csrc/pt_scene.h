@@ -1,32 +1,25 @@
-// Host scene graph (the builder side of World / Hittable / BxDFMaterial / Texture) and its
-// flattening into the device tables of pt_types.h.
+// Host scene graph (the builder side of World / Hittable / BxDFMaterial / Texture): plain host data, no HIP type. pt_graph.cpp edits it,
+// pt_flatten.cpp turns it into the tables of pt_types.h, pt_scene_upload.cpp puts those on the device; what lives there hangs off
+// pt_scene::gpu (pt_scene_gpu.h).
 #pragma once
-#include <hip/hip_runtime_api.h>
-
 #include <functional>
 #include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
 
-#include "pt_devmem.h"
 #include "pt_host_math.h"
 #include "pt_types.h"
 
 struct pt_camera;   // include/pt_amd.h
 
-struct pt_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int n_cus = 0;
-    std::string name;
-};
+struct pt_ctx;      // pt_scene_gpu.h
 
 namespace pt {
+struct SceneGpu;    // pt_scene_gpu.h
 
 int set_error(const std::string& msg);   // returns -1
 const char* last_error();
-bool hip_ok(hipError_t e, const char* what);   // (declared in pt_devmem.h too)
 // Experiment switches (PT_POOL_SLOTS, PT_SHADE_VARIANT, ...) are read only when PT_EXPERIMENT=1 is set: a release
 // library's behaviour does not depend on stray environment variables, and an explicit option always wins over them.
 const char* exp_env(const char* name);
@@ -59,16 +52,11 @@ struct HostGrid {                   // one grid-density medium (pt_mat_medium_gr
     std::vector<float> vals;
 };
 
-struct DeviceBuffers {
-    std::vector<void*> allocs;
-    SceneD view{};
-    void release();
-};
-
 }  // namespace pt
 
 struct pt_scene {
     pt_ctx* ctx = nullptr;
+    pt::SceneGpu* gpu = nullptr;   // the device side (pt_scene_create / pt_scene_destroy); null in a scene that is only flattened on the host
     std::vector<pt::HostTex> tex;
     std::vector<pt::MatD> mats;
     std::vector<pt::HostObj> objs;
@@ -99,20 +87,10 @@ struct pt_scene {
     uint32_t device_bvh_min_tris = 1u << 19;   // meshes with at least this many triangles get their BVH built on the GPU (0 = never)
     uint32_t n_device_blas = 0, device_blas_depth = 0;   // meshes of the last build that the GPU builder handled, deepest of them
     uint32_t stack_need_extend2 = 0;   // ... for k_extend2, whose top-level walk is stackless when the entry list is walked flat
-    pt::DeviceBuffers dev;
-    // buffers cached across calls (pt_devmem.h GrowBuf: grown on demand, freed with the scene). A call sizes what it carves out of one
-    // from its own needs, never from the cached capacity.
-    pt::GrowBuf pool_mem;          // the path pool of a render (pt_render.cpp bind_pool)
-    pt::GrowBuf tile_accum;        // dynamic mode: the frame accumulator in tile order (PoolD::accum_tiled)
-    pt::GrowBuf compact_scratch;   // the end-of-frame compaction's hole / mover lists + counters (pt_render.cpp)
-    pt::GrowBuf pixel_list;        // pt_render_pixels: the device pixel list (tiled order)
-    pt::GrowBuf sky_mem;           // the sky pass: counts, boxes, tile flags, the sure-sky tile list (pt_render.cpp classify_sky; the tile map is in tile_accum)
-    pt::GrowBuf short_mem;         // the short-path pass's hard list (pt_render.cpp run_short; its tile list and the shadeable ids are in sky_mem)
     // environment importance sampling (pt_scene_set_env_sampling): the mixture weight, and the f64 tables of ONE
-    // environment texture, built at the first render or probe that needs them (pt_render.cpp env_tables) and kept until destroy
+    // environment texture (SceneGpu::env_tab), built at the first render or probe that needs them (pt_render.cpp env_tables) and kept until destroy
     double env_f = 0.0;
-    int env_tab_tex = -1;          // texture the tables below belong to (-1: none built)
-    pt::GrowBuf env_tab;           // H * (W + 1) row prefix sums, then H + 1 row-total prefix sums (EnvTabD), doubles
+    int env_tab_tex = -1;          // texture the tables belong to (-1: none built)
     uint32_t env_tab_w = 0, env_tab_h = 0;
     double env_tab_z = 0.0;
     // participating media (pt_mat_medium). camera_medium: the medium material camera rays start in, -1 = none.
@@ -142,12 +120,11 @@ struct pt_scene {
     bool light_sampling_on() const { return light_sampling == 1 && lights_have_mesh_or_sphere; }   // "in effect"
     // spectral dispersion (pt_mat_glass_set_dispersion): MatD::p[1..3] of a glass = the Cauchy b, inv2(0.58756) and its Abbe
     // number (0 = off). world_has_dispersion (set by scene_build): some world object's material is a glass with an Abbe number > 0.
-    // disp_w: the weight table W[DSP_BINS][3] on the device, uploaded at the first render or probe that needs it and kept until destroy.
+    // (the weight table W[DSP_BINS][3] on the device: SceneGpu::disp_w)
     bool world_has_dispersion = false;
     bool dispersion_on() const { return world_has_dispersion; }   // "in effect": the kernels' DSP forms run
-    double* disp_w = nullptr;
     // punctual lights (pt_light_point / pt_light_spot / pt_light_directional): the list as the calls formed it, the selector's
-    // share of the punctual branch, and the number of lights of the last build (the device list: DeviceBuffers::view.punctual)
+    // share of the punctual branch, and the number of lights of the last build (the device list: SceneD::punctual)
     std::vector<pt::PunctualD> punctual;
     double punctual_f = 0.5;
     uint32_t n_punctual_built = 0;
@@ -155,7 +132,7 @@ struct pt_scene {
     // light shafts (pt_scene_set_punctual_media): the option that lets punctual lights and participating media be in effect together
     int punctual_media = 0;
     // the light grid (pt_scene_set_punctual_selection / pt_scene_set_punctual_grid): the settings wait for the next build like
-    // the list; grid_built: what the last build used (cells = 0: the grid is not in effect; the table: DeviceBuffers::view.punctual_cdf)
+    // the list; grid_built: what the last build used (cells = 0: the grid is not in effect; the table: SceneD::punctual_cdf)
     int punctual_selection = 0;    // 0 uniform, 1 the light grid
     uint32_t grid_dims_set[3] = {0u, 0u, 0u};   // all 0: automatic
     bool grid_box_given = false;
@@ -164,19 +141,20 @@ struct pt_scene {
     double grid_build_ms = 0.0;    // the table kernel's time at the last build (PT_VERBOSE prints it)
     int projection = 0;            // pt_scene_set_projection: 0 perspective, 1 orthographic, 2 fisheye, 3 panorama (CamD::projection)
     int sampler = 0;               // pt_scene_set_sampler: 0 independent (Philox), 1 Owen-scrambled Sobol (the kernels' QMC forms)
-    pt::CountersD* d_counters = nullptr;
-    pt::CountersD* h_counters = nullptr;   // pinned
-    ~pt_scene();
 };
 
 namespace pt {
-int scene_build(pt_scene* s);   // flatten + BVH + upload
+int scene_build(pt_scene* s);   // flatten + BVH + upload (pt_scene_upload.cpp)
+// pt_graph.cpp: the record constructors the entry points share with the flattener and the upload
+void pose_of_keys(const InstMotionD& k, double time, InstD& xf);      // the pose of a moving instance's keys at `time`
+host::Box xform_box(const host::Box& b, const InstD& m);              // box of the transformed box
+host::Box swept_box(const host::Box& b, const InstMotionD& k);        // ... under a moving instance over every time in [0, 1]
+bool grid_box_ok(const double b[6]);                                  // a light grid's box: finite, hi >= lo
+PunctualGridD grid_descriptor(const double box[6], const uint32_t dims[3], uint32_t n);
 void dispersion_weights(double w[DSP_BINS][3]);   // the weight table of pt_mat_glass_set_dispersion's rule (host, f64)
 double dispersion_ior(const MatD& glass, double lambda_nm);   // n(lambda) of a dispersive glass as the device computes it
-double* dispersion_table(pt_scene* s, hipStream_t st);   // pt_scene::disp_w, uploaded if need be; null (error set) when that fails
-// pt_render.cpp, shared with the probes (pt_probe.cpp): the device camera of a render, and the environment-sampling tables of its map
+// pt_render.cpp, shared with the probes (pt_probe.cpp): the device camera of a render
 int make_camd(pt_scene* s, const pt_camera* cam, CamD& dc);
-int env_tables(pt_scene* s, const CamD& dc, hipStream_t st, EnvTabD& e);
 // pt_probe.cpp: the one path of the probes and the u8 resolves. Host inputs go to the device, `launch` enqueues its kernel on the
 // context's stream given the device pointers (inputs in the order listed), the launch error is checked, `out_bytes` come back and the
 // stream is synchronised. 0, or -1 with the error set. An empty output (n == 0) is no device work at all.

@@ -21,7 +21,7 @@
 #include <string>
 
 #include "../../include/pt_amd.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 #include "pt_sdf.h"
 
 using namespace pt;

@@ -14,7 +14,7 @@
 
 namespace pt {
 
-int set_error(const std::string& msg);   // pt_scene.cpp; returns -1
+int set_error(const std::string& msg);   // pt_error.cpp; returns -1
 
 int sdf_check(const char* who, const void* opts_, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx, uint32_t nx, uint32_t ny, uint32_t nz,
               const double* box_lo, const double* box_hi, const float* out_values, SdfGrid& g) {

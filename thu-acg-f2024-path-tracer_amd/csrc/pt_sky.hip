@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 #include "pt_sky.h"
 
 using namespace pt;

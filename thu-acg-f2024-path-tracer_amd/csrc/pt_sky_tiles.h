@@ -170,7 +170,7 @@ PT_SKY_HD unsigned long long sky_tile_reach(const SkyCam& c, uint32_t ty, uint32
     return sky_tile_says_nothing(c, ty, tx, n_boxes, boxes6) ? ~0ull : sky_tile_uncleared(c, ty, tx, n_boxes, boxes6);
 }
 // The three kinds of tile. SURE SKY: every box is cleared. SHORT: every box that is NOT cleared is flagged in `shadeable`
-// (bit b = box b: the box of an entry the short-path pass can shade, pt_scene.cpp) — a camera ray of the tile hits such an entry or nothing.
+// (bit b = box b: the box of an entry the short-path pass can shade, pt_flatten.cpp) — a camera ray of the tile hits such an entry or nothing.
 // WAVEFRONT: everything else, and every tile about which nothing can be said (a tile outside the image, more boxes than the cap, a NaN or an
 // infinity among the boxes or in the camera: sky_extent is then not finite). Only where the pass pays depends on this; no result does.
 enum SkyTileClass : uint8_t { SKY_TILE_WAVEFRONT = 0, SKY_TILE_SKY = 1, SKY_TILE_SHORT = 2,

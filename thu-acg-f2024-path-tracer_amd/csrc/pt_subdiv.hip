@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 #include "pt_subdiv.h"
 #define PT_MESH_STAGE "subdivision"
 #include "pt_tess_dev.h"

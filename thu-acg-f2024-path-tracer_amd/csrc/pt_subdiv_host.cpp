@@ -13,7 +13,7 @@
 
 namespace pt {
 
-int set_error(const std::string& msg);   // pt_scene.cpp; returns -1
+int set_error(const std::string& msg);   // pt_error.cpp; returns -1
 
 int subdiv_check(const char* who, const void* opts_, const SubdivIn& in, const SubdivOut& out, SubdivPlan& plan) {
     const std::string p = std::string(who) + ": ";

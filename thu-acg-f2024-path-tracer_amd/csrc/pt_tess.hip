@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "../../include/pt_amd.h"
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 #include "pt_tess.h"
 #define PT_MESH_STAGE "tessellation"
 #include "pt_tess_dev.h"

@@ -8,7 +8,7 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "pt_scene.h"
+#include "pt_scene_gpu.h"
 #include "pt_tess.h"
 
 // The including unit names its stage: the word the error labels below carry ("hipMalloc(tessellation)", "hipMalloc(subdivision)")

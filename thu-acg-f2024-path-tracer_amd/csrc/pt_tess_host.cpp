@@ -13,7 +13,7 @@
 
 namespace pt {
 
-int set_error(const std::string& msg);   // pt_scene.cpp; returns -1
+int set_error(const std::string& msg);   // pt_error.cpp; returns -1
 
 int tess_check(const char* who, const void* opts_, const TessIn& in, const TessOut& out, TessPlan& plan) {
     const std::string p = std::string(who) + ": ";

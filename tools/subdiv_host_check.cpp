@@ -15,7 +15,7 @@
 
 namespace pt {
 static std::string g_err;
-int set_error(const std::string& msg) { g_err = msg; return -1; }   // the library's is in pt_scene.cpp
+int set_error(const std::string& msg) { g_err = msg; return -1; }   // the library's is in pt_error.cpp
 }  // namespace pt
 
 struct Shape {
