@@ -1110,6 +1110,80 @@ int pt_mesh_sdf_host(const pt_sdf_opts*, uint32_t n_pos, const float* pos, uint3
 int pt_mesh_fit_grid(uint32_t n_pos, const float* pos, uint32_t n_longest, double margin_cells,
                      uint32_t out_dims[3], double out_lo[3], double out_hi[3]);
 
+/* ---- mesh welding and simplification: quadric vertex clustering (not in the reference, opt-in) ----
+ * The stage that makes a mesh smaller, and the welding sections 27 and 28 leave out: vertices are grouped (by equal position, or by
+ * the cubic cell they lie in), each group becomes one vertex, faces that lose a corner go. A stage of its own in front of pt_mesh,
+ * pt_mesh_subdivide, pt_mesh_tessellate and pt_mesh_sdf; no render kernel knows of it. pt_mesh_simplify runs on the GPU
+ * (csrc/pt_simplify.hip), pt_mesh_simplify_host is its host twin; the two return the same bytes.
+ * Input: f32 positions, u32 index triples, optional f32 texcoords indexed by the position index (brought to n = n_pos entries first:
+ *  entries past n_pos dropped, missing ones zero).
+ * Arithmetic: f64 on the f32 values widened, in the order written here, no fused operation; each written attribute is rounded to f32
+ *  once. floor is the IEEE operation; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z and the cross product are section 27's.
+ * TSUM(t_0 .. t_{L-1}), L >= 1, the only summation order used: tile j holds t_{16j} .. t_{16j+15}, missing entries read +0.0. A tile's
+ *  value is the balanced pairwise tree s0_i = t_i, s(l+1)_i = s(l)_{2i} + s(l)_{2i+1}, l = 0 .. 3, taken at s4_0. TSUM is tile 0's
+ *  value, then += tile 1's, tile 2's, ... in order. (Sixteen lanes take a tile in four xor-butterfly steps: f64 addition is
+ *  commutative bit for bit. A run of L terms then costs L / 16 sequential additions.)
+ * 1. Referenced vertices: only vertices some index names take part; the others are ignored and dropped.
+ * 2. Keys. mode 0 (weld): two vertices are equal when their three components compare equal as floats (-0 equals +0). mode 1
+ *  (cluster): lo_a = the minimum of the referenced positions per axis, hi_a the maximum, ext_a = hi_a - lo_a, E the largest ext_a;
+ *  cell = `cell` when that is > 0, else E / (double)grid_n; c_a = floor(((double)p_a - lo_a) / cell); two vertices are equal when
+ *  their (c_x, c_y, c_z) are (key = (c_z << 42) | (c_y << 21) | c_x).
+ * 3. Clusters: a cluster is the set of referenced vertices of one key, its members in ascending vertex index, its head the lowest
+ *  member. Cluster ids ascend with the head's vertex index. Welding an already welded, fully referenced mesh is the identity.
+ * 4. Triangles: face (a, b, c) maps to the cluster ids (A, B, C), rotation kept; it is dropped when two ids are equal. With `dedup`
+ *  the surviving faces are grouped by vertex set {A, B, C}. In a group, in ascending face index, e faces are even permutations of the
+ *  sorted triple and o are odd: e > o: the first e - o even faces survive; o > e: the first o - e odd faces; e = o: none. Survivors
+ *  are written in ascending input face index. Every directed edge of the output is then as often used as its reverse when that held
+ *  for the input: a closed input gives a closed output with the same winding numbers. It need NOT be manifold: a thin wall that
+ *  collapses into one layer of cells cancels, a handle narrower than a cell pinches into a shared edge or vertex.
+ * 5. Output vertices: the clusters a surviving face names, in cluster-id order. out_map[v] (when wanted; n_pos entries) is the output
+ *  vertex of input vertex v, 0xFFFFFFFF for an unreferenced vertex and for one whose cluster was dropped.
+ * 6. Placement. mode 0: the head's position bits and the head's texcoord. mode 1, per cluster of `count` members:
+ *  o_a = lo_a + ((double)c_a + 0.5) * cell; m_a = TSUM over the members of ((double)p_a - o_a) / (double)count; texcoord: per
+ *  component (float)(TSUM over the members / (double)count). placement 1 (mean): x = m. placement 0 (quadric): the cluster's corners
+ *  are the slots 3f + k of the input index array that name a member, in ascending order (a face with two corners in the cluster counts
+ *  twice; dropped faces count). Each corner gives nine terms from face f's vertices in index order, o subtracted from each
+ *  (p' = (double)p - o per component): e1 = p1' - p0', e2 = p2' - p0', n = e1 x e2, d = dot(n, p0'); the terms n.x n.x, n.x n.y,
+ *  n.x n.z, n.y n.y, n.y n.z, n.z n.z, n.x d, n.y d, n.z d. The TSUM of each over the corners: a00 a01 a02 a11 a12 a22 b0 b1 b2.
+ *  T = (a00 + a11) + a22; T not finite or not > 0: x = m. Otherwise lambda = reg * T; a00, a11, a22 each + lambda;
+ *  r_a = b_a + lambda * m_a;
+ *   c00 = a11 a22 - a12 a12   c01 = a02 a12 - a01 a22   c02 = a01 a12 - a02 a11
+ *   c11 = a00 a22 - a02 a02   c12 = a01 a02 - a00 a12   c22 = a00 a11 - a01 a01
+ *   det = (a00 c00 + a01 c01) + a02 c02
+ *   x0 = ((c00 r0 + c01 r1) + c02 r2) / det   x1 = ((c01 r0 + c11 r1) + c12 r2) / det   x2 = ((c02 r0 + c12 r1) + c22 r2) / det
+ *  accepted when det > 0, every x_a is finite and |x_a| <= cell (the optimum may leave its cell by half a cell); otherwise x = m.
+ *  Position = (float)(o_a + x_a). reg is bounded because Cramer's rule in f64 loses the in-plane block of a flat cluster below about 1e-8.
+ * Normals (`normals`): 0 smooth: section 27's smooth normals of the result, (0, 1, 0) where the sum is unusable; 1 none.
+ * Refused with -1 before any device work: a NULL output pointer (out_map alone may be NULL: not wanted) or a NULL array with a count
+ *  above 0; n_idx that is 0 or not a multiple of 3; more than 0x07FFFFFF faces; an index out of range for positions or for given
+ *  texcoords; a position that is not finite (texcoords are data); an unknown mode, placement, dedup or normals value; mode 1 with a
+ *  cell that is negative or not finite, with cell == 0 and grid_n == 0, with E == 0, with floor(ext_a / cell) >= 2^21 on some axis,
+ *  or with reg outside [1e-6, 1] or NaN. NULL options mean the defaults. pt_mesh_simplify alone also refuses n_pos above 2^31 - 2
+ *  (its sorts count in 31 bits). A mesh that collapses entirely returns 0 and an empty mesh (counts 0). Outputs are malloc'd: free
+ *  them with pt_free; *out_nrm / *out_uv are NULL where there is none. A failed device allocation returns -1 with nothing held.
+ * Device memory: the mesh as uploaded (12 B a vertex, 8 more with texcoords, 12 B a face); 48 B a vertex of flags, keys, sorted
+ *  vertices, ranks and cluster ids (mode 0: 12 more during its first sort); quadric placement 48 B a face of (cluster, corner) pairs;
+ *  8 B a face of survivor flags and ranks, with dedup 45 B a face more of group keys and sorted faces; 32 B a cluster (40 with
+ *  texcoords); the result, section 27's 28 B a corner of it for smooth normals, and the radix sorts' own buffers. */
+typedef struct pt_simplify_opts {
+    int mode;          /* 0 weld: merge vertices of equal position; 1 cluster (default) */
+    double cell;       /* mode 1: edge of the cubic cells; > 0 wins over grid_n. Default 0 */
+    uint32_t grid_n;   /* mode 1, cell == 0: cell = E / (double)grid_n, E the longest extent. Default 64 */
+    int placement;     /* mode 1: 0 quadric (default), 1 mean */
+    double reg;        /* quadric: Tikhonov weight towards the mean, in [1e-6, 1]. Default 1e-3 */
+    int dedup;         /* 1 (default): coincident triangles cancel by orientation; 0: only degenerate ones go */
+    int normals;       /* 0 smooth (section 27's rule on the result, (0, 1, 0) where unusable; default), 1 none */
+} pt_simplify_opts;
+int pt_simplify_opts_default(pt_simplify_opts*);
+int pt_mesh_simplify(pt_ctx*, const pt_simplify_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                     uint32_t n_uv, const float* uv,
+                     float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx,
+                     float** out_nrm, float** out_uv, uint32_t** out_map /* may be NULL: not wanted */);
+int pt_mesh_simplify_host(const pt_simplify_opts*, uint32_t n_pos, const float* pos, uint32_t n_idx, const uint32_t* idx,
+                          uint32_t n_uv, const float* uv,
+                          float** out_pos, uint32_t* out_n_pos, uint32_t** out_idx, uint32_t* out_n_idx,
+                          float** out_nrm, float** out_uv, uint32_t** out_map);
+
 /* ---- multi-GPU: one process per GPU, spp sharding, ONE RCCL reduce over xGMI --------------------------------------
  * The reference is a single process (rayon over pixels, camera.rs:102); samples of a pixel are only summed
  * (camera.rs:106-108), so rank r of N renders the sample range pt_shard_range(spp, r, N) of every pixel and one

@@ -262,6 +262,30 @@ class SdfOpts(C.Structure):
         super().__init__(SDF_WHAT.get(what, what), SDF_FILL.get(fill, fill), int(negate), band, 0.0 if ramp is None else ramp)
 
 
+SIMPLIFY_MODES = {"weld": 0, "cluster": 1}       # pt_simplify_opts.mode
+SIMPLIFY_PLACEMENTS = {"quadric": 0, "mean": 1}   # pt_simplify_opts.placement
+
+
+class SimplifyOpts(C.Structure):
+    """pt_simplify_opts: weld or cluster, the cell (or the cells along the longest extent), where a cluster's vertex is placed, whether
+    coincident triangles cancel, which normals are written (include/pt_amd.h has the rule). A fresh instance holds the defaults:
+    clustering at 64 cells, quadric placement with reg 1e-3, dedup, smooth normals."""
+
+    _fields_ = [
+        ("mode", C.c_int),
+        ("cell", C.c_double),
+        ("grid_n", C.c_uint32),
+        ("placement", C.c_int),
+        ("reg", C.c_double),
+        ("dedup", C.c_int),
+        ("normals", C.c_int),
+    ]
+
+    def __init__(self, mode="cluster", cell=0.0, grid_n=64, placement="quadric", reg=1e-3, dedup=True, normals="smooth"):
+        super().__init__(SIMPLIFY_MODES.get(mode, mode), cell, grid_n, SIMPLIFY_PLACEMENTS.get(placement, placement), reg, int(dedup),
+                         SUBDIV_NORMALS.get(normals, normals))
+
+
 # every symbol include/pt_amd.h declares (the not-gpu test checks the library exports them all)
 ABI_SYMBOLS = [
     "pt_last_error", "pt_set_error_message", "pt_ctx_create", "pt_ctx_destroy", "pt_device_name",
@@ -296,6 +320,7 @@ ABI_SYMBOLS = [
     "pt_subdiv_opts_default", "pt_mesh_subdivide", "pt_mesh_subdivide_host",
     "pt_iso_opts_default", "pt_mesh_isosurface", "pt_mesh_isosurface_host",
     "pt_sdf_opts_default", "pt_mesh_sdf", "pt_mesh_sdf_host", "pt_mesh_fit_grid",
+    "pt_simplify_opts_default", "pt_mesh_simplify", "pt_mesh_simplify_host",
 ]
 
 
@@ -488,6 +513,12 @@ def _load():
         lib.pt_mesh_sdf.argtypes = [C.c_void_p, C.POINTER(SdfOpts)] + sdf_args
         lib.pt_mesh_sdf_host.argtypes = [C.POINTER(SdfOpts)] + sdf_args
         lib.pt_mesh_fit_grid.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pt_mesh_simplify"):           # (absent from an older build in an A/B run: PT_AMD_LIB)
+        fpp, upp, up = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)
+        simp_args = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, fpp, up, upp, up, fpp, fpp, upp]
+        lib.pt_simplify_opts_default.argtypes = [C.POINTER(SimplifyOpts)]
+        lib.pt_mesh_simplify.argtypes = [C.c_void_p, C.POINTER(SimplifyOpts)] + simp_args
+        lib.pt_mesh_simplify_host.argtypes = [C.POINTER(SimplifyOpts)] + simp_args
     if os.environ.get("PT_AMD_LIB") and not hasattr(lib, "pt_shard_range"):
         return lib                                   # A/B run against a build that predates the multi-GPU entry points
     lib.pt_shard_range.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -658,6 +689,14 @@ class Context:
         "odd"; band > 0 caps the distances (include/pt_amd.h has the rule)."""
         return _mesh_sdf(self.handle, pos, idx, dims, box_lo, box_hi, SdfOpts(what, fill, negate, band, ramp))
 
+    def simplify(self, pos, idx, uv=None, mode="cluster", cell=0.0, grid_n=64, placement="quadric", reg=1e-3, dedup=True, normals="smooth"):
+        """pt_mesh_simplify: a triangle mesh welded (mode "weld": vertices of equal position become one) or simplified (mode "cluster":
+        the vertices of each cubic cell become one, placed by the cell's quadric or at their mean) on the GPU -> (pos, idx, nrm | None,
+        uv | None, map), ready for Scene.mesh, Context.subdivide, Context.tessellate or Context.mesh_sdf. cell: the cells' edge, or 0:
+        the longest extent / grid_n; dedup: coincident triangles cancel by orientation; map[v]: the output vertex of input vertex v or
+        0xFFFFFFFF (include/pt_amd.h has the rule)."""
+        return _simplify(self.handle, pos, idx, uv, SimplifyOpts(mode, cell, grid_n, placement, reg, dedup, normals))
+
     def sky_probe(self, dirs: np.ndarray, **opts) -> np.ndarray:
         """pt_sky_probe: sky_eval by the bake kernel's device function: (n, 3) unit directions -> (n, 3) radiance, no disc."""
         dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
@@ -771,6 +810,30 @@ def _isosurface(ctx, values, box_lo, box_hi, opts):
 def isosurface_host(values, box_lo, box_hi, iso=0.5, closed=False, outside=0.0, normals="gradient"):
     """pt_mesh_isosurface_host: Context.isosurface on the host, the same bytes (no context needed)."""
     return _isosurface(None, values, box_lo, box_hi, IsoOpts(iso, closed, outside, normals))
+
+
+def _simplify(ctx, pos, idx, uv, opts):
+    args, keep = _mesh_in(pos, idx, None, uv)
+    args = args[:4] + args[6:]                       # (no normals go in)
+    out, vmap = _MeshOut(), C.POINTER(C.c_uint32)()
+    if ctx is None:
+        rc = lib.pt_mesh_simplify_host(C.byref(opts), *args, *out.refs(), C.byref(vmap))
+    else:
+        rc = lib.pt_mesh_simplify(ctx, C.byref(opts), *args, *out.refs(), C.byref(vmap))
+    if rc < 0:
+        out.free()
+        if vmap:
+            lib.pt_free(vmap)
+    _check(rc, "pt_mesh_simplify_host" if ctx is None else "pt_mesh_simplify")
+    n = args[0]
+    vm = np.ctypeslib.as_array(vmap, (n,)).copy() if n else np.zeros(0, np.uint32)
+    lib.pt_free(vmap)
+    return (*out.take(), vm)
+
+
+def simplify_host(pos, idx, uv=None, mode="cluster", cell=0.0, grid_n=64, placement="quadric", reg=1e-3, dedup=True, normals="smooth"):
+    """pt_mesh_simplify_host: Context.simplify on the host, the same bytes (no context needed)."""
+    return _simplify(None, pos, idx, uv, SimplifyOpts(mode, cell, grid_n, placement, reg, dedup, normals))
 
 
 def _mesh_sdf(ctx, pos, idx, dims, box_lo, box_hi, opts):

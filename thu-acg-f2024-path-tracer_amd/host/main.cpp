@@ -13,6 +13,8 @@
 // --mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]] (scene 6: spot, sampled on the GPU into a density grid of its shape, replaces its surface as an
 // unbounded camera medium: pt_mesh_sdf), --remesh OFFSET[,GRID_N] (scene 6: spot and cow go through a signed distance grid and
 // come back as the level set OFFSET * E outside their surface: pt_mesh_sdf, then pt_mesh_isosurface),
+// --simplify GRID_N[,quadric|mean] (scene 6's meshes and the surface of --isosurface clustered on the GPU into cubic cells, GRID_N along the
+// longest extent: pt_mesh_simplify) and --weld (vertices of equal position become one: the same stage's mode 0),
 // --interior DENSITY[,R,G,B[,G[,AR,AG,AB]]] (every glass material of the scene script is filled with a homogeneous medium of that density,
 // albedo, g and absorption per channel; density 0 with an absorption > 0 is a clear tinted body),
 // --dispersion ABBE (every glass material of the scene script disperses: its ior is n_d, ABBE > 0 its Abbe number V_d),
@@ -175,7 +177,7 @@ static Mesh icosphere(int level, Vec3 centre, double radius) {
 
 // --displace: the Quad of the scene whose material carries a normal map gives way to a tessellated, displaced grid mesh of the same q, u, v
 // with the same base colour and no normal map. v = SCALE[, LEVELS[, MIDLEVEL]].
-static void displace_brick_wall(World& world, pt_ctx* ctx, const std::string& file, const std::string& asset_dir, const std::vector<double>& v) {
+static void displace_brick_wall(World& world, pt_ctx* ctx, const std::string& file, const std::string& asset_dir, const std::vector<double>& v, bool weld) {
     std::string path = file;
     if (!std::ifstream(path)) {   // "assets/bricks/color.png" the way the scene scripts name their images: relative to --assets
         const std::string prefix = "assets/";
@@ -200,7 +202,14 @@ static void displace_brick_wall(World& world, pt_ctx* ctx, const std::string& fi
         auto quad = std::dynamic_pointer_cast<Quad>(obj);
         auto mat = quad ? std::dynamic_pointer_cast<DiffuseBRDF>(quad->material) : nullptr;
         if (!mat || !mat->normal_map) continue;
-        obj = TriangleMesh::from_obj(1.0, Mesh::grid(quad->q, quad->u, quad->v, 64, 64).tessellated(ctx, o), DiffuseBRDF::from_textures(mat->base_color, nullptr));
+        Mesh grid = Mesh::grid(quad->q, quad->u, quad->v, 64, 64);
+        if (weld) {   // (a grid shares its vertices already: the pass is the identity but for the normals, which it recomputes)
+            pt_simplify_opts wo;
+            pt_simplify_opts_default(&wo);
+            wo.mode = 0;
+            grid = grid.simplified(ctx, wo);
+        }
+        obj = TriangleMesh::from_obj(1.0, grid.tessellated(ctx, o), DiffuseBRDF::from_textures(mat->base_color, nullptr));
         return;
     }
     throw std::runtime_error("--displace: the scene has no wall with a normal-mapped material");
@@ -235,9 +244,32 @@ static void subdivide_meshes(World& world, pt_ctx* ctx, const std::vector<double
     if (done != 3) throw std::runtime_error("--subdivide: the scene does not hold its three meshes");
 }
 
+// --simplify GRID_N[,quadric|mean]: a mesh clustered on the GPU into cubic cells, GRID_N along its longest extent (pt_mesh_simplify,
+// DESIGN.md section 31). A mesh that came with normals gets smooth ones back, one without stays flat-shaded. --weld: mode 0 of the same
+// stage: vertices of equal position become one, so that a mesh whose vertices are duplicated along seams subdivides and displaces as one surface.
+static Mesh simplified_mesh(const Mesh& m, pt_ctx* ctx, uint32_t grid_n, int placement) {
+    pt_simplify_opts o;
+    pt_simplify_opts_default(&o);
+    o.grid_n = grid_n;
+    o.placement = placement;
+    o.normals = m.normals.empty() ? 1 : 0;
+    return m.simplified(ctx, o);
+}
+
+static void simplify_meshes(World& world, pt_ctx* ctx, uint32_t grid_n, int placement, bool weld) {
+    for (auto& obj : world.objects) {
+        auto inst = std::dynamic_pointer_cast<Instance>(obj);
+        auto mesh = inst ? std::dynamic_pointer_cast<TriangleMesh>(inst->object) : nullptr;
+        if (!mesh) continue;
+        const Mesh r = weld ? mesh->mesh.welded(ctx) : simplified_mesh(mesh->mesh, ctx, grid_n, placement);
+        if (r.indices.empty()) throw std::runtime_error("--simplify: nothing is left of a mesh at that GRID_N");
+        inst->object = TriangleMesh::from_obj(mesh->scale, r, mesh->material);
+    }
+}
+
 // --isosurface ISO[,GRID_N]: the plume of --smoke, sampled into GRID_N^3 cells over the box --fog would fill, meshed on the GPU where it
 // crosses ISO (closed, gradient normals) and added to the world as a white diffuse body.
-static void add_isosurface(World& world, pt_ctx* ctx, const std::vector<double>& v, Vec3 lo, Vec3 hi) {
+static void add_isosurface(World& world, pt_ctx* ctx, const std::vector<double>& v, Vec3 lo, Vec3 hi, uint32_t simplify_n, int placement) {
     const uint32_t N = v.size() > 1 ? (uint32_t)v[1] : 64u;
     std::vector<float> f((size_t)N * N * N);
     for (uint32_t k = 0; k < N; ++k)
@@ -247,8 +279,12 @@ static void add_isosurface(World& world, pt_ctx* ctx, const std::vector<double>&
     pt_iso_opts_default(&o);
     o.iso = v[0];
     o.closed = 1;
-    const Mesh m = Mesh::isosurface(ctx, o, N, N, N, f, lo, hi);
+    Mesh m = Mesh::isosurface(ctx, o, N, N, N, f, lo, hi);
     if (m.indices.empty()) throw std::runtime_error("--isosurface: the plume does not cross that level");
+    if (simplify_n) {
+        m = simplified_mesh(m, ctx, simplify_n, placement);
+        if (m.indices.empty()) throw std::runtime_error("--simplify: nothing is left of the isosurface at that GRID_N");
+    }
     world.add_object(TriangleMesh::from_obj(1.0, m, DiffuseBRDF::from_rgb(Vec3{0.73, 0.73, 0.73})));
 }
 
@@ -368,6 +404,9 @@ int main(int argc, char** argv) {
     std::vector<double> isosurface_v;
     bool mesh_smoke = false;                 // --mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]]
     std::vector<double> mesh_smoke_v;
+    bool simplify = false, weld = false;     // --simplify GRID_N[,quadric|mean]; --weld
+    uint32_t simplify_n = 0;
+    int simplify_placement = 0;
     bool remesh = false;                     // --remesh OFFSET[,GRID_N]
     std::vector<double> remesh_v;
     uint64_t seed = 1;
@@ -558,12 +597,30 @@ int main(int argc, char** argv) {
             }
             remesh = true;
         }
+        else if (a == "--simplify") {
+            const std::string v = next();
+            const size_t comma = v.find(',');
+            const std::string how = comma == std::string::npos ? "quadric" : v.substr(comma + 1);
+            std::vector<double> n;
+            if (!parse_numbers(v.substr(0, comma), 1, 1, n) || !(n[0] >= 1.0 && n[0] <= 4096.0 && n[0] == std::floor(n[0])) || (how != "quadric" && how != "mean")) {
+                std::cerr << "--simplify must be GRID_N[,quadric|mean]: GRID_N a whole number in 1..4096\n";
+                return 2;
+            }
+            simplify = true;
+            simplify_n = (uint32_t)n[0];
+            simplify_placement = how == "mean" ? 1 : 0;
+        }
+        else if (a == "--weld") weld = true;
         else if (a == "--adaptive") { adaptive = atof(next()); use_adaptive = true; }
         else if (a == "--min-spp") min_spp = atol(next());
         else if (a == "--denoise") use_denoise = true;
         else if (a == "--aov-spp") aov_spp = atol(next());
         else if (a == "-h" || a == "--help") {
-            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]] [--subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]] [--isosurface ISO[,GRID_N]] [--mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]]] [--remesh OFFSET[,GRID_N]]\n"
+            std::cout << "usage: pt_render [-q] [-s N] [--width W] [--spp S] [--seed K] [--out file.png] [--assets DIR] [--device D] [--float-hdr] [--env-sampling F] [--sampler independent|sobol] [--fog DENSITY[,R,G,B[,G]]] [--smoke SCALE[,R,G,B[,G]]] [--interior DENSITY[,R,G,B[,G[,AR,AG,AB]]]] [--dispersion ABBE] [--light-sampling reference|exact] [--mesh-light X,Y,Z,RADIUS[,R,G,B]] [--projection perspective|orthographic|fisheye|panorama] [--shutter OPEN,CLOSE] [--motion DX,DY,DZ[,DEGREES]] [--point-light X,Y,Z,R,G,B]... [--spot-light X,Y,Z,TX,TY,TZ,INNER,OUTER,R,G,B]... [--sun DX,DY,DZ,R,G,B]... [--punctual-fraction F] [--punctual-selection uniform|grid[,NX,NY,NZ]] [--light-shafts] [--stats] [--adaptive T [--min-spp M]] [--denoise [--aov-spp N]] [--exposure EV] [--tonemap reference|srgb|reinhard|aces] [--white W] [--bloom S[,THRESHOLD[,SIGMA[,LEVELS]]]] [--out-hdr file.hdr|file.pfm] [--sky ELEVATION_DEG,AZIMUTH_DEG[,TURBIDITY[,WIDTH]] [--sky-no-disc]] [--displace FILE,SCALE[,LEVELS[,MIDLEVEL]]] [--subdivide LEVELS[,CREASE_DEG[,CORNER_DEG]]] [--isosurface ISO[,GRID_N]] [--mesh-smoke SCALE[,GRID_N[,RAMP_CELLS]]] [--remesh OFFSET[,GRID_N]] [--simplify GRID_N[,quadric|mean]] [--weld]\n"
+                         "  --simplify: scene 6's meshes (after --remesh, before --subdivide) and the surface of --isosurface are clustered on the GPU into cubic cells,\n"
+                         "           GRID_N along the mesh's longest extent: the vertices of a cell become one, placed where the planes of the faces around them meet\n"
+                         "           (quadric, the default) or at their mean; faces that lose a corner go. Fewer triangles for the BVH and for K2\n"
+                         "  --weld: vertices of equal position become one, on the GPU: scene 6's meshes before --subdivide, the wall's grid before --displace\n"
                          "  --mesh-smoke: scene 6 only: spot leaves the scene as a surface and comes back as a cloud of its shape: an unbounded grid-density camera\n"
                          "           medium of extinction SCALE * V, as --smoke's, V the density pt_mesh_sdf samples on the GPU over cubic cells fitted around spot (GRID_N\n"
                          "           along its longest extent, default 64, two cells of margin): 0 outside, rising to 1 RAMP_CELLS cells (default 2) below the surface.\n"
@@ -659,6 +716,8 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (simplify && scene != 6 && !isosurface) { std::cerr << "--simplify works on scene 6 (bunny, spot and cow) and with --isosurface only\n"; return 2; }
+    if (weld && scene != 6 && !displace) { std::cerr << "--weld works on scene 6 (bunny, spot and cow) and with --displace only\n"; return 2; }
     if (displace && scene != 7) { std::cerr << "--displace works on scene 7 only (the wall with the normal-mapped bricks)\n"; return 2; }
     if (mesh_smoke && scene != 6) { std::cerr << "--mesh-smoke works on scene 6 only (spot)\n"; return 2; }
     if (remesh && scene != 6) { std::cerr << "--remesh works on scene 6 only (spot and cow)\n"; return 2; }
@@ -714,13 +773,15 @@ int main(int argc, char** argv) {
         SceneSetup setup = make_scene(scene, w, s, assets, 1);
         setup.world.float_hdr = float_hdr;
         if (displace) {
-            displace_brick_wall(setup.world, ctx, displace_file, assets, displace_v);
+            displace_brick_wall(setup.world, ctx, displace_file, assets, displace_v, weld);
             // the wall goes to the host's SAH builder at every size: from 2^19 triangles on it would get the device's LBVH, whose depth under the
             // scene's other entries can pass the traversal stack
             setup.world.device_bvh_threshold = 0;
         }
-        if (subdivide) subdivide_meshes(setup.world, ctx, subdivide_v);
         if (remesh) remesh_meshes(setup.world, ctx, remesh_v);
+        if (weld && scene == 6) simplify_meshes(setup.world, ctx, 0, 0, true);
+        if (simplify && scene == 6) simplify_meshes(setup.world, ctx, simplify_n, simplify_placement, false);
+        if (subdivide) subdivide_meshes(setup.world, ctx, subdivide_v);
         if (mesh_smoke) mesh_smoke_cloud(setup.world, ctx, mesh_smoke_v);
         if (sky) setup.camera.environment = EnvironmentType::Map(Sky::new_(sky_opts, sky_width, sky_width / 2));
         setup.world.env_sampling = env_sampling;
@@ -753,7 +814,7 @@ int main(int argc, char** argv) {
             lo = Vec3{lo.x - grow.x, lo.y - grow.y, lo.z - grow.z};
             hi = Vec3{hi.x + grow.x, hi.y + grow.y, hi.z + grow.z};
             if (isosurface) {
-                add_isosurface(setup.world, ctx, isosurface_v, lo, hi);
+                add_isosurface(setup.world, ctx, isosurface_v, lo, hi, simplify ? simplify_n : 0u, simplify_placement);
             } else if (fog) {
                 auto vol = HomogeneousVolume::from_albedo(Cuboid::new_(lo, hi, nullptr), fog_v[0], Vec3{fog_v[1], fog_v[2], fog_v[3]}, fog_v[4]);
                 setup.world.add_object(vol);

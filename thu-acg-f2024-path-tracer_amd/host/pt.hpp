@@ -385,6 +385,26 @@ struct Mesh {
         if (pt_mesh_isosurface(ctx, &opts, nx, ny, nz, values.data(), a, b, &pos, &np, &idx, &ni, &nrm) != 0) panic("Mesh::isosurface");
         return take(pos, np, idx, ni, nrm, nullptr);
     }
+    // not in the reference: welding and simplification by quadric vertex clustering on the GPU (pt_mesh_simplify; include/pt_amd.h has
+    // the rule): positions and texcoords in (normals are not read), a smaller mesh out. out_map: for every input
+    // vertex its vertex in the result, or 0xFFFFFFFF. welded(): vertices of equal position become one, nothing else changes.
+    Mesh simplified(pt_ctx* ctx, const pt_simplify_opts& opts, std::vector<uint32_t>* out_map = nullptr) const {
+        float *pos, *nrm, *uv;
+        uint32_t *idx, np, ni, *map = nullptr;
+        if (pt_mesh_simplify(ctx, &opts, (uint32_t)(positions.size() / 3), positions.data(), (uint32_t)indices.size(), indices.data(), (uint32_t)(texcoords.size() / 2),
+                             texcoords.data(), &pos, &np, &idx, &ni, &nrm, &uv, out_map ? &map : nullptr) != 0)
+            panic("Mesh::simplified");
+        if (out_map) out_map->assign(map, map + positions.size() / 3);
+        pt_free(map);
+        return take(pos, np, idx, ni, nrm, uv);
+    }
+    Mesh welded(pt_ctx* ctx) const {
+        pt_simplify_opts o;
+        pt_simplify_opts_default(&o);
+        o.mode = 0;
+        o.normals = normals.empty() ? 1 : 0;
+        return simplified(ctx, o);
+    }
 
 private:
     static Mesh take(float* pos, uint32_t np, uint32_t* idx, uint32_t ni, float* nrm, float* uv) {
